@@ -21,6 +21,14 @@ batch k-1 overlapped with the encoder of batch k on separate HIP streams.  One "
 
 Image-parallel: every rank runs its own replica, no collective on the data path (weak scaling); the only collective
 is the final int64 statistics all-reduce, outside the step.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps steps and prints the line (`value`, `ms_per_step` = milliseconds of one timed
+step).  --full adds everything else the line can carry: the in-situ roofline of the dominant kernel, the secondary legs
+(RLE-inclusive, PCIe-inclusive, the other operand-split mode, bf16, the all-split mode, the generation CLI, the reference's
+20-box chunks), the CPU / torch-eager baselines and the committed parity figures; in a plain run those keys are null.
+--dump-outputs DIR writes what the timed path handed its caller in the last timed step (rank 0) as DIR/<name>.npy
+(float32 / float64): seg_mask [tiles, H, W] (class ids, 255 = unlabeled; c2 / c3), areas and quality (concatenated over the
+tiles; quality for c4), boxes_per_tile and tile_index.  Inputs are seeded, so two builds can be compared file for file.
 """
 from __future__ import annotations
 
@@ -152,6 +160,32 @@ def _cpu_model() -> str:
     return "unknown"
 
 
+DUMP_BUDGET = 48 << 20           # bytes of seg_mask in float32 (the other arrays are a few KB)
+
+
+def dump_outputs(out_dir: str, results) -> None:
+    """--dump-outputs: the sink's copies of the last timed batch, (key, seg_mask, areas, quality) per tile, as .npy files.  A class-map
+    stack larger than DUMP_BUDGET (batches above 8 tiles of 1024^2) is written as a fixed sample: the pixels at flat positions drawn
+    once with numpy's default_rng(0), sorted, as seg_mask_sample.npy."""
+    assert results, "--dump-outputs: the timed region handed no batch to the sink"
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"tile_index": np.array([float(k) for k, _, _, _ in results]),
+              "boxes_per_tile": np.array([float(len(a)) for _, _, a, _ in results]),
+              "areas": np.concatenate([a for _, _, a, _ in results]).astype(np.float64)}
+    if all(q is not None for _, _, _, q in results):
+        arrays["quality"] = np.concatenate([q for _, _, _, q in results]).astype(np.float32)
+    if all(s is not None for _, s, _, _ in results) and len({s.shape for _, s, _, _ in results}) == 1:
+        seg = np.stack([s for _, s, _, _ in results]).astype(np.float32)
+        if seg.nbytes <= DUMP_BUDGET:
+            arrays["seg_mask"] = seg
+        else:
+            idx = np.sort(np.random.default_rng(0).choice(seg.size, DUMP_BUDGET // 4, replace=False))
+            arrays["seg_mask_sample"] = seg.reshape(-1)[idx]
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print(f"[bench] --dump-outputs: {', '.join(f'{k} {list(v.shape)}' for k, v in arrays.items())} -> {out_dir}", file=sys.stderr, flush=True)
+
+
 def _self_launch(n: int) -> None:
     """`python bench.py --gpus N` with N > 1 and no launcher around it: become the launcher.  Re-runs this same command line
     under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free>` (one
@@ -197,6 +231,11 @@ def main() -> None:
     ap.add_argument("--no-cli-leg", action="store_true", help="skip the end-to-end run of the generation CLI (PNG files in, files out)")
     ap.add_argument("--cli-tiles", type=int, default=320, help="tiles of the CLI leg")
     ap.add_argument("--no-rle-leg", action="store_true", help="skip the RLE-inclusive measurement (the reference's full output contract)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the dominant kernel's in-situ roofline, the secondary "
+                         "legs and baselines above (each --no-* flag still turns its own off) and the parity figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the timed path returned in its last timed step as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -275,6 +314,9 @@ def main() -> None:
         return sam, make_pipe(sam, device_inputs)
 
     counters = {"tiles": 0, "boxes": 0, "rle_bytes": 0}
+    # --dump-outputs: once armed, the sink keeps host copies of the results of the last batch (static queue: batch number `last`
+    # of this rank; the dynamic queue cannot know which batch is its last, so every batch is copied over the previous one)
+    capture = {"armed": False, "batches": 0, "last": None, "results": None}
 
     def sink(results, release):
         for r in results:
@@ -282,6 +324,11 @@ def main() -> None:
             if r.rle_table is not None:
                 counters["rle_bytes"] += int(r.rle_table[:, 1].sum())
         counters["tiles"] += len(results)
+        if capture["armed"]:
+            capture["batches"] += 1
+            if capture["last"] is None or capture["batches"] == capture["last"]:
+                capture["results"] = [(r.key, None if r.seg_mask is None else np.array(r.seg_mask), np.array(r.areas),
+                                       None if r.quality is None else np.array(r.quality)) for r in results]
         release()
 
     def run_steps(pipe, n_steps, tiles, first_index, shared_queue=False):
@@ -331,42 +378,55 @@ def main() -> None:
     sam, pipe = make_pipeline(args.dtype, device_inputs=True)
     eng = sam.engine
     eng_info = {k: eng.get_option(k) for k in ("outlier_cols", "outlier_blocks", "outlier_columns")}
-    # the engine brackets every launch of the dominant kernel (MLP lin1+GELU GEMM) with hipEvents on its
+    # --full: the engine brackets every launch of the dominant kernel (MLP lin1+GELU GEMM) with hipEvents on its
     # launch stream; warm-up launches are discarded, so the average below is over the timed region
-    eng.time_dominant_kernel(True)
-    dt, tiles_done, boxes_done = timed(pipe, dev_tiles, args.steps, args.warmup, after_warmup=eng.dominant_kernel_time,
-                                       shared_queue=shared_q)
-    gemm_ms, gemm_launches, N, K = eng.dominant_kernel_time()
-    eng.time_dominant_kernel(False)
+    if args.full:
+        eng.time_dominant_kernel(True)
+
+    def after_warmup():
+        if args.full:
+            eng.dominant_kernel_time()
+        if args.dump_outputs and rank == 0:
+            capture.update(armed=True, batches=0, last=None if (shared_q and world > 1) else args.steps)
+
+    dt, tiles_done, boxes_done = timed(pipe, dev_tiles, args.steps, args.warmup, after_warmup=after_warmup, shared_queue=shared_q)
+    capture["armed"] = False
+    if args.full:
+        gemm_ms, gemm_launches, N, K = eng.dominant_kernel_time()
+        eng.time_dominant_kernel(False)
     assert tiles_done == world * B * args.steps, (tiles_done, world, B, args.steps)
     value = tiles_done / dt
     boxes_per_tile = boxes_done / max(1, tiles_done)
     if rank == 0:
         print(f"[bench] {args.workload} {args.dtype}: {value:.2f} images/s over {world} GPU(s), {dt / args.steps * 1e3:.1f} ms/step, "
               f"{boxes_per_tile:.1f} boxes/tile", file=sys.stderr, flush=True)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, capture["results"])
     F = flops_per_image(cfg, boxes_per_tile)
 
     # ---- roofline of the dominant kernel: the MLP lin1+GELU GEMM (57.6 % of encoder FLOPs with lin2),
     # timed in situ over the timed region (see above) ----
-    M = B * cfg.grid ** 2
-    gemm_tflops = 2.0 * M * N * K / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
-    # HBM traffic of that kernel: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this same command
-    # (tools/gpu_round.sh pmc), corrected per MI355X_MICROARCH.md and committed under profiles/ together with the
-    # hash of the kernel source it was measured on -- a number taken on an older kernel is NOT reported.
-    traffic, traffic_note = None, "no PMC summary committed for this kernel source"
-    if args.model == "vit_h" and B == 8 and os.path.exists(PMC_FILE):
-        pmc = json.load(open(PMC_FILE))
-        if pmc.get("gemm_hip_sha16") == file_sha(os.path.join(ROOT, "samrs_amd", "csrc", "gemm.hip")):
-            traffic, traffic_note = pmc.get("traffic_bytes_per_launch"), pmc.get("source", "profiles/")
-        else:
-            traffic_note = "profiles/dominant_kernel_pmc.json was measured on an older gemm.hip: not reported"
-    roofline = {"bound": "mfma", "kernel": f"gemm_et<{args.dtype}> lin1+GELU M={M} N={N} K={K}",
-                "achieved": round(gemm_tflops, 1), "peak": PEAK_MFMA_TFLOPS, "unit": "TFLOP/s",
-                "frac": round(gemm_tflops / PEAK_MFMA_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_note,
-                "algorithmic_bytes": 2 * (M * K + N * K + M * N), "avg_launch_ms": round(gemm_ms, 4),
-                "launches_timed": gemm_launches, "algorithmic_flops_per_launch": 2.0 * M * N * K,
-                "whole_path_tflops": round(value / world * F / 1e12, 1),
-                "whole_path_frac": round(value / world * F / 1e12 / PEAK_MFMA_TFLOPS, 4)}
+    roofline = None
+    if args.full:
+        M = B * cfg.grid ** 2
+        gemm_tflops = 2.0 * M * N * K / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+        # HBM traffic of that kernel: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this same command
+        # (tools/gpu_round.sh pmc), corrected as profiles/README.md describes and committed under profiles/ together with the
+        # hash of the kernel source it was measured on -- a number taken on an older kernel is NOT reported.
+        traffic, traffic_note = None, "no PMC summary committed for this kernel source"
+        if args.model == "vit_h" and B == 8 and os.path.exists(PMC_FILE):
+            pmc = json.load(open(PMC_FILE))
+            if pmc.get("gemm_hip_sha16") == file_sha(os.path.join(ROOT, "samrs_amd", "csrc", "gemm.hip")):
+                traffic, traffic_note = pmc.get("traffic_bytes_per_launch"), pmc.get("source", "profiles/")
+            else:
+                traffic_note = "profiles/dominant_kernel_pmc.json was measured on an older gemm.hip: not reported"
+        roofline = {"bound": "mfma", "kernel": f"gemm_et<{args.dtype}> lin1+GELU M={M} N={N} K={K}",
+                    "achieved": round(gemm_tflops, 1), "peak": PEAK_MFMA_TFLOPS, "unit": "TFLOP/s",
+                    "frac": round(gemm_tflops / PEAK_MFMA_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_note,
+                    "algorithmic_bytes": 2 * (M * K + N * K + M * N), "avg_launch_ms": round(gemm_ms, 4),
+                    "launches_timed": gemm_launches, "algorithmic_flops_per_launch": 2.0 * M * N * K,
+                    "whole_path_tflops": round(value / world * F / 1e12, 1),
+                    "whole_path_frac": round(value / world * F / 1e12 / PEAK_MFMA_TFLOPS, 4)}
 
     # ---- the one collective of the path: class statistics all-reduce (outside the timed step) ----
     tot_pix, tot_ins = driver.reduce_statistics(pipe.class_pixels, pipe.class_instances)
@@ -386,7 +446,7 @@ def main() -> None:
     # and only they cross PCIe; the sink receives (offset, length) tables + the byte buffer.  NB: masks of random-init weights
     # are noise-like (~135 k runs per mask, ~140 KB per string; a real mask has a few thousand runs, a few KB).
     rle_leg = None
-    if rank == 0 and world == 1 and not args.no_rle_leg:
+    if args.full and rank == 0 and world == 1 and not args.no_rle_leg:
         pipe_r = make_pipe(sam, True, rle=True)
         n_r = max(2, args.steps)
         dtr, tr, br = timed(pipe_r, dev_tiles, n_r, 1, shared_queue=False)
@@ -398,7 +458,7 @@ def main() -> None:
 
     # ---- c3 only: the same stream in the reference's own 20-box chunks (main_sam_hbox_semantic.py:91,157-181) ----
     chunk_leg = None
-    if args.workload == "c3" and rank == 0 and world == 1 and box_batch != 20:
+    if args.full and args.workload == "c3" and rank == 0 and world == 1 and box_batch != 20:
         pipe_c = make_pipe(sam, True, chunk=20)
         n_c = max(2, args.steps)
         dtc, tc, _ = timed(pipe_c, dev_tiles, n_c, 1, shared_queue=False)
@@ -412,7 +472,7 @@ def main() -> None:
     # hi + lo operands: what holds IoU >= 0.999 on the C4 fixtures).  This leg runs the same loop in the mode the headline did NOT use. ----
     other_mode = None
     split_used = pipe.split_mode if pipe.split_mode is not None else eng.get_option("split")
-    if rank == 0 and world == 1 and not args.no_fast_leg and args.model == "vit_h":
+    if args.full and rank == 0 and world == 1 and not args.no_fast_leg and args.model == "vit_h":
         other = 79 if split_used == 15 else 15
         keep_mode, keep_allow = pipe.split_mode, pipe.allow_reduced
         try:
@@ -429,7 +489,7 @@ def main() -> None:
     # ---- PCIe-inclusive: the same product loop, tiles start in pinned host memory (3 MiB H2D per tile on its own
     # stream, prefetched one batch ahead); class maps + areas go back either way ----
     pcie = None
-    if rank == 0 and world == 1 and not args.no_pcie_leg:
+    if args.full and rank == 0 and world == 1 and not args.no_pcie_leg:
         del pipe
         pipe_h = make_pipe(sam, False)
         n_p = max(2, args.steps)
@@ -440,7 +500,7 @@ def main() -> None:
         del pipe_h
 
     alt = None
-    if not args.no_alt_dtype:
+    if args.full and not args.no_alt_dtype:
         other = "bf16" if args.dtype == "f16" else "f16"
         pipe = None
         del sam, eng
@@ -456,7 +516,7 @@ def main() -> None:
     # ---- the mode closest to the reference's own fp32 floor (VERDICT r05 "next round" 2): EVERY block GEMM on hi + lo operands (split 63,
     # MXFP4 lo terms).  Needs the lo copies of all block weights, i.e. an engine of its own; same loop, same tiles. ----
     all_split = None
-    if rank == 0 and world == 1 and not args.no_fast_leg and args.model == "vit_h" and args.workload == "c2" and args.dtype == "f16":
+    if args.full and rank == 0 and world == 1 and not args.no_fast_leg and args.model == "vit_h" and args.workload == "c2" and args.dtype == "f16":
         try:
             pipe = None
             torch.cuda.empty_cache()
@@ -478,7 +538,7 @@ def main() -> None:
     # TilePipeline with device RLE, writer pool) -> gray + color PNG + ins/*.pkl on disk.  The rate is that of generate's loop
     # (first read to last file written; its model build is outside).  Host-side work on this box's CPU slice is part of it. ----
     cli = None
-    if rank == 0 and world == 1 and not args.no_cli_leg and args.workload == "c2":
+    if args.full and rank == 0 and world == 1 and not args.no_cli_leg and args.workload == "c2":
         import argparse as _ap
         import shutil
         import tempfile
@@ -542,7 +602,7 @@ def main() -> None:
             cli = {"value": None, "note": f"failed: {type(ex).__name__}: {ex}"}
 
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # the oracle (a port of the reference's algorithm) on the host cores: 1 warm-up tile, then 2 timed tiles with
         # 32 boxes each as 20 + 12 chunks (main_sam_hbox_semantic.py:157-181)
         from oracle import sam_oracle as so
@@ -624,7 +684,8 @@ def main() -> None:
                        "accumulate": "f32", "operand_split": split_used},
             "flops_per_image": F, "roofline": roofline, "cpu_baseline": cpu_baseline, "alt_dtype": alt, "pcie_inclusive": pcie,
             "rle_inclusive": rle_leg, "cli_inclusive": cli, "other_precision_mode": other_mode, "all_split_mode": all_split,
-            "parity": parity_of_mode(int(split_used), args.workload, args.model), "reference_chunking": chunk_leg,
+            "parity": parity_of_mode(int(split_used), args.workload, args.model) if args.full else None, "reference_chunking": chunk_leg,
+            "full": args.full,
             "boxes_per_s": round(boxes_done / dt, 1),
             "stats_allreduce": {"total_pixels": int(tot_pix.sum().item()), "total_instances": int(tot_ins.sum().item()),
                                 "per_rank_local": [{"pixels": int(a), "instances": int(b)} for a, b in per_rank]},

@@ -215,7 +215,50 @@ def make_golden(path: str) -> None:
         print({k: v.shape for k, v in blob.items()})
 
 
+def ddp_worker(rank, world, port, root, out, use_reference=False):
+    """One gloo rank of `train_steps` over the sample dataset's train split, read by the restated reader or (use_reference) by the
+    reference's own SegmentationDataset.  Stores (losses, weight, drawn indices, label histogram) in out[rank]."""
+    import torch.distributed as dist
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    if use_reference:
+        ds = reference_dataset(root, "trn")
+    else:
+        ds = SegmentationDataset(root, os.path.join(root, "images"), os.path.join(root, "hbox_segs_init", "gray"), flag="trn")
+    losses, w, drawn, hist = train_steps(ds, SAMPLE_CLASSES, rank, world, steps=2, batch_size=2)
+    out[rank] = (losses, w.numpy().copy(), drawn, hist)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def make_golden_ddp(path: str) -> None:
+    """tests/golden/consumer_ref_ddp.npz: two DDP-gloo iterations of `train_steps` with the reference's OWN SegmentationDataset over the
+    sample dataset the product's writers wrote, per rank: losses, weight after the steps, drawn indices, label histogram.  Run where
+    the reference tree exists:
+        python -m oracle.consumer_check --ddp tests/golden/consumer_ref_ddp.npz"""
+    import socket
+    import tempfile
+    import torch.multiprocessing as mp
+    with tempfile.TemporaryDirectory() as root:
+        make_sample_dataset(root)
+        with socket.socket() as s:
+            s.bind(("127.0.0.1", 0))
+            port = s.getsockname()[1]
+        out = mp.Manager().dict()
+        mp.spawn(ddp_worker, args=(2, port, root, out, True), nprocs=2, join=True)
+        blob = {}
+        for r in range(2):
+            losses, w, drawn, hist = out[r]
+            blob.update({f"rank{r}_losses": np.asarray(losses, np.float64), f"rank{r}_w": w, f"rank{r}_drawn": np.asarray(drawn, np.int64),
+                         f"rank{r}_hist": hist})
+        np.savez_compressed(path, **blob)
+        print({k: v.shape for k, v in blob.items()})
+
+
 if __name__ == "__main__":
     import sys
-    make_golden(sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden",
-                                                                   "consumer_ref.npz"))
+    golden = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+    if sys.argv[1:2] == ["--ddp"]:
+        make_golden_ddp(sys.argv[2] if len(sys.argv) > 2 else os.path.join(golden, "consumer_ref_ddp.npz"))
+    else:
+        make_golden(sys.argv[1] if len(sys.argv) > 1 else os.path.join(golden, "consumer_ref.npz"))

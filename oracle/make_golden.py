@@ -6,6 +6,7 @@ Run in the authoring container (needs ``/root/reference``)::
     PYTHONDONTWRITEBYTECODE=1 python -m oracle.make_golden vit_b_c2c4 vit_h_c2c4      # C2 / C4 fixtures, margin weights
     PYTHONDONTWRITEBYTECODE=1 python -m oracle.make_golden vit_h_c2c4_v1              # a second, independent draw of the same
     PYTHONDONTWRITEBYTECODE=1 python -m oracle.make_golden vit_b_inst vit_h_inst      # the instance drivers' recipes as scripted
+    PYTHONDONTWRITEBYTECODE=1 python -m oracle.make_golden mask_to_rle_counts         # the reference's COCO RLE counts (JSON)
 
 Weights / images / prompts come from ``samrs_amd.synth`` (seeded, reproducible anywhere), the
 outputs come from the reference's own ``SamPredictor`` (Generate Dataset/segment_anything/
@@ -203,9 +204,46 @@ def instances(name: str, variant: int = 0) -> None:
     print("wrote", path, os.path.getsize(path) // 1024, "KiB", flush=True)
 
 
+def rle_pin_masks():
+    """Masks of the COCO RLE counts pin (tests/test_rle_and_writers.py): random, blob, all-zero, all-one and first-pixel-set
+    masks, square and ragged."""
+    rng = np.random.default_rng(11)
+    masks = []
+    for shape in [(64, 64), (37, 91), (128, 50)]:
+        for p in (0.0, 0.02, 0.5, 1.0):
+            m = rng.random(shape) < p
+            if p == 0.02:
+                m[shape[0] // 4: shape[0] // 2, 3:] = True
+            masks.append(m)
+        m = np.zeros(shape, bool); m[0, 0] = True; masks.append(m)
+        m = np.ones(shape, bool); m[-1, -1] = False; masks.append(m)
+    return masks
+
+
+def mask_to_rle_counts() -> None:
+    """``tests/golden/mask_to_rle_counts.json``: the REAL reference's ``mask_to_rle_pytorch`` (Generate Dataset/segment_anything/
+    utils/amg.py:107-135) on every mask of ``rle_pin_masks()``: its ``size`` and ``counts``, plus a packed copy of the mask."""
+    import json
+    ref_import.import_reference()
+    from segment_anything.utils.amg import mask_to_rle_pytorch            # the reference's
+    out = []
+    for m in rle_pin_masks():
+        r = mask_to_rle_pytorch(torch.from_numpy(m)[None])[0]
+        out.append({"size": [int(v) for v in r["size"]], "counts": [int(v) for v in r["counts"]],
+                    "mask_packed_hex": np.packbits(m.ravel()).tobytes().hex()})
+    path = os.path.join(GOLDEN_DIR, "mask_to_rle_counts.json")
+    with open(path, "w") as f:
+        json.dump({"source": "Generate Dataset/segment_anything/utils/amg.py mask_to_rle_pytorch, via oracle/make_golden.py "
+                             "mask_to_rle_counts", "masks": out}, f, separators=(",", ":"))
+    print("wrote", path, os.path.getsize(path) // 1024, "KiB", flush=True)
+
+
 def main(names):
     os.makedirs(GOLDEN_DIR, exist_ok=True)
     torch.set_num_threads(os.cpu_count() or 1)
+    if "mask_to_rle_counts" in names:
+        names = [n for n in names if n != "mask_to_rle_counts"]
+        mask_to_rle_counts()
     import re
     ext = [re.fullmatch(r"(.+)_(c2c4|inst)(?:_v(\d+))?", n) for n in names]
     names = [n for n, m in zip(names, ext) if m is None]

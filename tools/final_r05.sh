@@ -3,7 +3,7 @@
 # bench.py -> dominant-kernel summary pinned to gemm.hip -> the bench lines (c2 default, c3, c4) that read both.
 set -u
 mkdir -p gpurun_out; cd "${GRAFT_REPO_ROOT:-.}"; export PYTHONDONTWRITEBYTECODE=1
-BQ="--no-cpu-baseline --no-alt-dtype --no-pcie-leg --no-cli-leg --no-fast-leg --no-rle-leg"
+BQ="--full --no-cpu-baseline --no-alt-dtype --no-pcie-leg --no-cli-leg --no-fast-leg --no-rle-leg"
 timeout 2300 python -m pytest tests -m gpu -q -rs -p no:cacheprovider > gpurun_out/all_final.log 2>&1; tail -4 gpurun_out/all_final.log
 cp gpurun_out/parity_stats_test.json profiles/parity_stats.json
 cd /tmp; export TMPDIR=/tmp; cd - >/dev/null
@@ -17,6 +17,6 @@ timeout 400 rocprofv3 --pmc WRITE_SIZE SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VALU_
 python tools/pmc_summary.py gpurun_out gpurun_out/r05_pmc_per_kernel.json --dominant "gemm_et_w4x_kernel<1, false, 2, true" gpurun_out/dominant_kernel_pmc.json 2>&1 | tail -2
 cp gpurun_out/dominant_kernel_pmc.json profiles/dominant_kernel_pmc.json
 find gpurun_out -name "*kernel_trace.csv" -delete; find gpurun_out -name "*counter_collection.csv" -delete
-timeout 900 python bench.py > gpurun_out/bench_final.log 2> gpurun_out/bench_final.err; tail -1 gpurun_out/bench_final.log | cut -c1-400
+timeout 900 python bench.py --full | tail -1 | cut -c1-400
 timeout 400 python bench.py --workload c3 --steps 12 --warmup 2 $BQ > gpurun_out/c3.log 2>&1; tail -1 gpurun_out/c3.log | cut -c1-200
 timeout 400 python bench.py --workload c4 --steps 12 --warmup 2 $BQ > gpurun_out/c4.log 2>&1; tail -1 gpurun_out/c4.log | cut -c1-200

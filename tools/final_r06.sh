@@ -5,7 +5,7 @@
 # evidence files are copied into profiles/ ONLY from a green run of THIS call (stale files are removed first).
 set -u
 mkdir -p gpurun_out; cd "${GRAFT_REPO_ROOT:-.}"; export PYTHONDONTWRITEBYTECODE=1
-BQ="--no-cpu-baseline --no-alt-dtype --no-pcie-leg --no-cli-leg --no-fast-leg --no-rle-leg"
+BQ="--full --no-cpu-baseline --no-alt-dtype --no-pcie-leg --no-cli-leg --no-fast-leg --no-rle-leg"
 rm -f gpurun_out/parity_stats_test.json gpurun_out/heavy_tailed_parity.json
 timeout 2300 python -m pytest tests -m gpu -q -rs -p no:cacheprovider > gpurun_out/all_final.log 2>&1; RC=$?; tail -4 gpurun_out/all_final.log
 if [ $RC -eq 0 ] && [ -s gpurun_out/parity_stats_test.json ] && [ -s gpurun_out/heavy_tailed_parity.json ]; then
@@ -34,8 +34,7 @@ timeout 400 rocprofv3 --pmc WRITE_SIZE SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VALU_
 python tools/pmc_summary.py gpurun_out gpurun_out/r06_pmc_per_kernel.json --dominant "gemm_et_w4x_kernel<1, false, 2, true" gpurun_out/dominant_kernel_pmc.json 2>&1 | tail -2
 if [ -s gpurun_out/dominant_kernel_pmc.json ]; then cp gpurun_out/dominant_kernel_pmc.json profiles/dominant_kernel_pmc.json; cp gpurun_out/r06_pmc_per_kernel.json profiles/r06_pmc_per_kernel.json; fi
 find gpurun_out -name "*kernel_trace.csv" -delete; find gpurun_out -name "*counter_collection.csv" -delete
-timeout 900 python bench.py > gpurun_out/bench_final.log 2> gpurun_out/bench_final.err; tail -1 gpurun_out/bench_final.log | cut -c1-400
-tail -1 gpurun_out/bench_final.log > profiles/r06_bench.json
+timeout 900 python bench.py --full | tail -1 > profiles/r06_bench.json; cut -c1-400 profiles/r06_bench.json
 timeout 400 python bench.py --workload c3 --steps 12 --warmup 2 $BQ > gpurun_out/c3.log 2>&1; tail -1 gpurun_out/c3.log | cut -c1-200
 timeout 400 python bench.py --workload c4 --steps 12 --warmup 2 $BQ > gpurun_out/c4.log 2>&1; tail -1 gpurun_out/c4.log | cut -c1-200
 # the driver's N > 1 command form on this ONE-GPU box: bench.py launches its own ranks; both share cuda:0 over gloo

@@ -12,7 +12,7 @@ run() { local name=$1; shift; local t=$1; shift
   grep -E "passed|failed|error" "gpurun_out/$name.log" | tail -3 | tee -a gpurun_out/summary.txt; }
 : > gpurun_out/summary.txt
 PT="python -m pytest -m gpu -q -s -rA -p no:cacheprovider -x"
-BQ="--no-cpu-baseline --no-alt-dtype --no-pcie-leg --no-cli-leg --no-fast-leg --no-rle-leg"
+BQ="--full --no-cpu-baseline --no-alt-dtype --no-pcie-leg --no-cli-leg --no-fast-leg --no-rle-leg"
 prof_env() { cd /tmp; export TMPDIR=/tmp; cd - >/dev/null; }
 for step in "$@"; do
   case $step in
@@ -40,7 +40,7 @@ for step in "$@"; do
              SAMRS_LO_FORMAT=${LOF:-4} run profc4 900 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/profc4 -o c4 -- python bench.py --workload c4 --steps 3 --warmup 1 $BQ ;;
     pstats)  run pstats 1500 python tools/parity_stats.py --modes ${PS_MODES:-15,79,63} ${PS_ARGS:-} ;;
     benchq)  run benchq 900 python bench.py --steps ${BENCH_STEPS:-8} --warmup 2 $BQ ${BENCH_EXTRA:-} ;;
-    bench)   run bench 1500 python bench.py ${BENCH_ARGS:-} ;;
+    bench)   run bench 1500 python bench.py --full ${BENCH_ARGS:-} ;;
     ablib)   run ablib 1200 bash tools/ab_libs.sh ${AB_ROUNDS:-2} ${AB_LIB:-samrs_amd/csrc/libsamrs_hip_noskew.so} samrs_amd/csrc/libsamrs_hip.so ;;
     c3)      run c3 600 python bench.py --workload c3 --steps ${BENCH_STEPS:-6} --warmup 2 $BQ ;;
     c4)      run c4 600 python bench.py --workload c4 --steps ${BENCH_STEPS:-6} --warmup 2 $BQ ;;

@@ -12,7 +12,7 @@ run() { local name=$1; shift; local t=$1; shift
   grep -E "passed|failed|error" "gpurun_out/$name.log" | tail -3 | tee -a gpurun_out/summary.txt; }
 : > gpurun_out/summary.txt
 PT="python -m pytest -m gpu -q -s -rA -p no:cacheprovider -x"
-BQ="--no-cpu-baseline --no-alt-dtype --no-pcie-leg --no-cli-leg --no-fast-leg --no-rle-leg"
+BQ="--full --no-cpu-baseline --no-alt-dtype --no-pcie-leg --no-cli-leg --no-fast-leg --no-rle-leg"
 prof_env() { cd /tmp; export TMPDIR=/tmp; cd - >/dev/null; }
 for step in "$@"; do
   case $step in

@@ -2,7 +2,7 @@
 # What the outlier-column extension costs in the PRODUCT loop: bench.py --weights <w>, secondary legs off, arms alternated twice on one box
 # (profiles/r06_outlier_loop_cost.txt is this script's output + a reading).
 cd "${GRAFT_REPO_ROOT:-.}"
-BQ="--steps 20 --warmup 3 --no-cpu-baseline --no-alt-dtype --no-pcie-leg --no-cli-leg --no-fast-leg --no-rle-leg"
+BQ="--steps 20 --warmup 3 --full --no-cpu-baseline --no-alt-dtype --no-pcie-leg --no-cli-leg --no-fast-leg --no-rle-leg"
 row() { python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
