@@ -162,6 +162,15 @@ int samrs_paint(samrs_engine_t* e, const uint8_t* masks, const int32_t* labels, 
 int samrs_select_best(samrs_engine_t* e, const uint8_t* masks, const float* iou, int n, int n_sel, int h, int w,
                       uint8_t* best_out, float* quality_out, int64_t* areas_out, void* stream);
 
+/* -- HRSC instance evaluation (main_sam_rhbox_mask_instance.py:204-214, :222-238).
+ * masks uint8 [n][h][w] (non-zero = set; the kept masks of samrs_select_best), label_rgb uint8 [h][w][3],
+ * colors uint8 [n][3], all on the device.  Instance j's ground truth = the pixels whose RGB equals colors[j].
+ * inter_out[j] = |mask_j AND gt_j|, gt_area_out[j] = |gt_j| (int64, overwritten).  gt_masks_out uint8 [n][h][w] (0/1) or NULL.
+ * The union is pred_area + gt_area - inter with pred_area from samrs_select_best; gt_masks_out is what samrs_rle_encode takes
+ * for the ground truth's COCO RLE.  The label image is read once per call, not once per instance.  h * w < 2^30. */
+int samrs_gt_match(samrs_engine_t* e, const uint8_t* masks, int n, int h, int w, const uint8_t* label_rgb,
+                   const uint8_t* colors, int64_t* inter_out, int64_t* gt_area_out, uint8_t* gt_masks_out, void* stream);
+
 /* -- the reference's per-instance output: COCO RLE of every full-resolution mask (main_sam_hbox_semantic.py:201-202:
  * `maskUtils.encode(np.asfortranarray(mask))` + `.decode('ascii')`; counts half stated in-tree at utils/amg.py:107-135).
  * masks: uint8 [n][h][w] on device (non-zero = set; the C = 1 output of samrs_predict).  The n ASCII strings are packed into

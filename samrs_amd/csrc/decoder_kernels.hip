@@ -1014,6 +1014,95 @@ __global__ __launch_bounds__(256) void select_best_kernel(const uint8_t* __restr
     if ((threadIdx.x & 63) == 0 && c > 0.f) atomicAdd(&areas[j], (unsigned long long)c);
 }
 
+// ---- HRSC instance evaluation: ground truth of instance j = the label pixels whose RGB equals colors[j] ----------------------
+// main_sam_rhbox_mask_instance.py:204-214 decodes the label PNG and compares all H x W pixels once per instance.  Here a thread
+// owns 16 adjacent pixels: it reads their 48 label bytes ONCE, keeps them as 16 packed 0x00BBGGRR keys in registers and loops
+// over the n instances (16-byte mask loads where the row is aligned, byte loads at a ragged tail / misaligned row).  Per instance
+// it counts |gt| and |mask AND gt|; the two counts travel packed in one 32-bit word (a wave holds <= 1024 of each, a block
+// <= 4096: 16 bits each, integer sums, exact) through one wave reduction and one LDS counter, then one 64-bit atomic per block.
+// Pixels past hw get the key 0xFFFFFFFF, which no colour matches.
+constexpr int GM_CHUNK = 64;          // instances per LDS counter chunk
+__global__ __launch_bounds__(256) void gt_match_kernel(const uint8_t* __restrict__ masks, int n, long hw,
+                                                       const uint8_t* __restrict__ label_rgb, const uint8_t* __restrict__ colors,
+                                                       unsigned long long* __restrict__ inter, unsigned long long* __restrict__ gt_area,
+                                                       uint8_t* __restrict__ gt_masks) {
+    __shared__ unsigned int cnt_s[GM_CHUNK];
+    const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * 16;
+    const bool full = p0 + 16 <= hw;
+    uint32_t key[16];
+    if (full && (((uintptr_t)(label_rgb + p0 * 3)) & 15) == 0) {
+        const uint4* lp = reinterpret_cast<const uint4*>(label_rgb + p0 * 3);
+        const uint4 a = lp[0], b = lp[1], c = lp[2];
+        const uint32_t wv[12] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w};
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            uint32_t v = 0;
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                const int byte = 3 * k + ch;
+                v |= ((wv[byte >> 2] >> (8 * (byte & 3))) & 0xFFu) << (8 * ch);
+            }
+            key[k] = v;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const long p = p0 + k;
+            key[k] = p < hw ? (uint32_t)label_rgb[p * 3] | ((uint32_t)label_rgb[p * 3 + 1] << 8) | ((uint32_t)label_rgb[p * 3 + 2] << 16)
+                            : 0xFFFFFFFFu;
+        }
+    }
+    for (int jlo = 0; jlo < n; jlo += GM_CHUNK) {
+        const int jhi = jlo + GM_CHUNK < n ? jlo + GM_CHUNK : n;
+        if (threadIdx.x < GM_CHUNK) cnt_s[threadIdx.x] = 0u;
+        __syncthreads();
+        for (int j = jlo; j < jhi; ++j) {
+            const uint32_t want = (uint32_t)colors[3 * j] | ((uint32_t)colors[3 * j + 1] << 8) | ((uint32_t)colors[3 * j + 2] << 16);
+            uint32_t g[4] = {0u, 0u, 0u, 0u};                 // 0x01 in every byte whose pixel is ground truth
+#pragma unroll
+            for (int k = 0; k < 16; ++k) g[k >> 2] |= (key[k] == want ? 1u : 0u) << (8 * (k & 3));
+            const uint8_t* m = masks + (size_t)j * hw + p0;
+            uint32_t mw[4] = {0u, 0u, 0u, 0u};                // 0x80 in every byte whose mask pixel is set
+            const bool vec = full && (((uintptr_t)m) & 15) == 0;
+            if (vec) {
+                const uint4 v = *reinterpret_cast<const uint4*>(m);
+                mw[0] = nonzero_bytes(v.x); mw[1] = nonzero_bytes(v.y); mw[2] = nonzero_bytes(v.z); mw[3] = nonzero_bytes(v.w);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 16; ++k)
+                    if (p0 + k < hw && m[k]) mw[k >> 2] |= 0x80u << (8 * (k & 3));
+            }
+            uint32_t cg = 0, ci = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                cg += __popc(g[q]);
+                ci += __popc(mw[q] & (g[q] << 7));
+            }
+            if (gt_masks) {
+                uint8_t* o = gt_masks + (size_t)j * hw + p0;
+                if (full && (((uintptr_t)o) & 15) == 0) {
+                    *reinterpret_cast<uint4*>(o) = make_uint4(g[0], g[1], g[2], g[3]);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 16; ++k)
+                        if (p0 + k < hw) o[k] = (uint8_t)((g[k >> 2] >> (8 * (k & 3))) & 1u);
+                }
+            }
+            uint32_t packed = ci | (cg << 16);                // <= 16 each per thread
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) packed += __shfl_xor(packed, off, 64);
+            if ((threadIdx.x & 63) == 0 && packed) atomicAdd(&cnt_s[j - jlo], packed);
+        }
+        __syncthreads();
+        if (threadIdx.x < jhi - jlo) {
+            const uint32_t v = cnt_s[threadIdx.x];
+            if (v & 0xFFFFu) atomicAdd(&inter[jlo + threadIdx.x], (unsigned long long)(v & 0xFFFFu));
+            if (v >> 16) atomicAdd(&gt_area[jlo + threadIdx.x], (unsigned long long)(v >> 16));
+        }
+        __syncthreads();
+    }
+}
+
 __global__ void class_stats_kernel(const unsigned long long* __restrict__ areas, const int32_t* __restrict__ labels, int n,
                                    unsigned long long* __restrict__ cpix, unsigned long long* __restrict__ cins, int n_classes) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -1337,6 +1426,17 @@ hipError_t launch_select_best(const uint8_t* masks, const float* iou, int n, int
     int chunks = (int)((hw / 16 + 255) / 256);
     chunks = chunks < 1 ? 1 : (chunks > 64 ? 64 : chunks);
     select_best_kernel<<<dim3(chunks, n), 256, 0, s>>>(masks, iou, nsel, hw, out, quality, areas);
+    return hipGetLastError();
+}
+
+hipError_t launch_gt_match(const uint8_t* masks, int n, int h, int w, const uint8_t* label_rgb, const uint8_t* colors,
+                           unsigned long long* inter, unsigned long long* gt_area, uint8_t* gt_masks, hipStream_t s) {
+    const long hw = (long)h * w;
+    if (n < 1 || h < 1 || w < 1 || hw >= (1l << 30)) return hipErrorInvalidValue;
+    HIP_CHECK_RET(hipMemsetAsync(inter, 0, sizeof(unsigned long long) * n, s));
+    HIP_CHECK_RET(hipMemsetAsync(gt_area, 0, sizeof(unsigned long long) * n, s));
+    const int blocks = (int)(((hw + 15) / 16 + 255) / 256);     // one thread per 16 pixels
+    gt_match_kernel<<<blocks, 256, 0, s>>>(masks, n, hw, label_rgb, colors, inter, gt_area, gt_masks);
     return hipGetLastError();
 }
 

@@ -1540,6 +1540,16 @@ int samrs_select_best(samrs_engine_t* e, const uint8_t* masks, const float* iou,
     CK(e, launch_select_best(masks, iou, n, n_sel, h, w, best_out, quality_out, (unsigned long long*)areas_out, (hipStream_t)stream));
     return SAMRS_OK;
 }
+int samrs_gt_match(samrs_engine_t* e, const uint8_t* masks, int n, int h, int w, const uint8_t* label_rgb, const uint8_t* colors,
+                   int64_t* inter_out, int64_t* gt_area_out, uint8_t* gt_masks_out, void* stream) {
+    if (!e || !masks || !label_rgb || !colors || !inter_out || !gt_area_out || n < 1 || h < 1 || w < 1)
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_gt_match: bad argument");
+    if ((long long)h * w >= (1ll << 30)) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_gt_match: h * w = %lld must stay below 2^30", (long long)h * w);
+    ON_DEVICE(e);
+    CK(e, launch_gt_match(masks, n, h, w, label_rgb, colors, (unsigned long long*)inter_out, (unsigned long long*)gt_area_out, gt_masks_out,
+                          (hipStream_t)stream));
+    return SAMRS_OK;
+}
 
 // per-engine options (see the top of this file)
 int samrs_set_option(samrs_engine_t* e, const char* name, int value) {

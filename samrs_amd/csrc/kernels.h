@@ -168,6 +168,9 @@ hipError_t launch_paint(const uint8_t* masks, const int32_t* labels, int n, int 
 // best-of-nsel by predicted IoU (first maximum): out [n][h][w] = masks[j][argmax_c iou[j][c]], quality[j], areas[j] = pixels set
 hipError_t launch_select_best(const uint8_t* masks, const float* iou, int n, int nsel, int h, int w, uint8_t* out, float* quality,
                               unsigned long long* areas, hipStream_t s);
+// ground-truth matching: inter[j] = |mask j AND (label == colors[j])|, gt_area[j] = |label == colors[j]|; gt_masks [n][h][w] 0/1 or null
+hipError_t launch_gt_match(const uint8_t* masks, int n, int h, int w, const uint8_t* label_rgb, const uint8_t* colors,
+                           unsigned long long* inter, unsigned long long* gt_area, uint8_t* gt_masks, hipStream_t s);
 hipError_t launch_resample_pass(const uint8_t* in, uint8_t* out, const int32_t* bounds, const int32_t* coef, int ksize,
                                 int in_len, int out_len, int other, int horizontal, hipStream_t s);
 // rotated-box polygons (int32 [n][nv][2]) -> mask prompts [n][out][out] fp32 (main_sam_rbox_mask_instance.py:125-141)

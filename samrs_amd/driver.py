@@ -295,11 +295,14 @@ def gather_mask_sizes(local_sizes: Sequence[int], group=None) -> List[int]:
 @dataclass
 class WorkItem:
     """One image of the stream: uint8 HWC pixels (host numpy array, host tensor or device tensor), its boxes in
-    ORIGINAL-image pixels (xyxy) and their class labels; `key` travels to the sink untouched."""
+    ORIGINAL-image pixels (xyxy) and their class labels; `key` travels to the sink untouched.  `gt` (only read by
+    ``InstancePipeline(gt=True)``): ``(label_rgb, colors)``, the host label image uint8 [H, W, 3] and one colour uint8 [3] per
+    annotation -- instance j's ground truth is the label pixels of colour j (main_sam_rhbox_mask_instance.py:210-214)."""
     key: object
     image: object
     boxes: np.ndarray
     labels: np.ndarray
+    gt: Optional[Tuple[np.ndarray, np.ndarray]] = None
 
 
 @dataclass
@@ -314,12 +317,24 @@ class TileResult:
     rle_table: Optional[np.ndarray] = None  # int64 [n_boxes, 3] (offset, length, n_counts) into rle_data when rle=True
     rle_data: Optional[np.ndarray] = None   # uint8 view of the batch's pinned RLE byte buffer
     size: Optional[Tuple[int, int]] = None  # (H, W) of the tile
+    inter: Optional[np.ndarray] = None      # int64 [n_boxes] |mask AND ground truth| (InstancePipeline(gt=True))
+    gt_area: Optional[np.ndarray] = None    # int64 [n_boxes] |ground truth| (InstancePipeline(gt=True))
+    gt_rle_table: Optional[np.ndarray] = None   # like rle_table, for the ground-truth masks (gt=True, rle=True)
+    gt_rle_data: Optional[np.ndarray] = None
 
     def rle(self, j: int) -> dict:
         """COCO RLE of instance j exactly as the reference stores it (main_sam_hbox_semantic.py:201-202):
         ``{"size": [H, W], "counts": str}``; encoded on the device (samrs_rle_encode)."""
         off, n, _ = (int(v) for v in self.rle_table[j])
         return {"size": [int(self.size[0]), int(self.size[1])], "counts": self.rle_data[off:off + n].tobytes().decode("ascii")}
+
+    def gt_rle(self, j: int) -> Optional[dict]:
+        """COCO RLE of instance j's ground-truth mask (instance_to_json.py:44-45), encoded on the device; None unless the
+        pipeline ran with gt=True and rle=True."""
+        if self.gt_rle_table is None:
+            return None
+        off, n, _ = (int(v) for v in self.gt_rle_table[j])
+        return {"size": [int(self.size[0]), int(self.size[1])], "counts": self.gt_rle_data[off:off + n].tobytes().decode("ascii")}
 
 
 class _OutBuf:
@@ -562,22 +577,33 @@ class TilePipeline:
     def _extra_outputs(self, b: int, out: _OutBuf) -> None:
         pass
 
+    def _fetch_extra(self, b: int, out: _OutBuf, n_boxes: int):
+        return None
+
+    def _extra_result(self, r: TileResult, i: int, off: int, nb: int, out: _OutBuf, extra) -> None:
+        pass
+
     def _fetch_rle(self, b: int, out: _OutBuf, n_boxes: int):
         """The batch's RLE strings: the table and the byte count are on the host (out.done), so the strings can be copied
         with their exact size -- on a copy stream, while the GPU works on the batches already queued."""
-        total = int(out.rle_cur[0])
-        tab = out.rle_tab[:n_boxes].numpy()
+        tab, out.rle_bytes = self._fetch_strings(self.rle_dev[b], out.rle_cur, out.rle_tab, out.rle_bytes, n_boxes)
+        return tab, out.rle_bytes.numpy()
+
+    def _fetch_strings(self, dev: torch.Tensor, cur: torch.Tensor, tab_host: torch.Tensor, host: torch.Tensor, n_boxes: int):
+        """(table, pinned host bytes) of one packed string buffer (samrs_rle_encode's layout); `host` grows when too small."""
+        total = int(cur[0])
+        tab = tab_host[:n_boxes].numpy()
         if n_boxes and int(tab[:, 1].min()) < 0:
             need = int((-tab[:, 1] - 1).max())
             raise RuntimeError(f"RLE buffer too small: a mask needs {need} bytes and the batch already holds {total}; raise "
-                               f"rle_buffer_mb (now {self.rle_dev[b].numel() >> 20})")
-        if out.rle_bytes.numel() < total:
-            out.rle_bytes = torch.empty(max(total, 2 * out.rle_bytes.numel()), dtype=torch.uint8).pin_memory()
+                               f"rle_buffer_mb (now {dev.numel() >> 20})")
+        if host.numel() < total:
+            host = torch.empty(max(total, 2 * host.numel()), dtype=torch.uint8).pin_memory()
         if total:
             with torch.cuda.stream(self.s_d2h):
-                out.rle_bytes[:total].copy_(self.rle_dev[b][:total], non_blocking=True)
+                host[:total].copy_(dev[:total], non_blocking=True)
             self.s_d2h.synchronize()
-        return tab, out.rle_bytes.numpy()
+        return tab, host
 
     def _finish(self, pending, sink):
         items, offs, out, b = pending
@@ -587,6 +613,7 @@ class TilePipeline:
         rtab = rdat = None
         if self.rle:
             rtab, rdat = self._fetch_rle(b, out, sum(nb for _, nb in offs))
+        extra = self._fetch_extra(b, out, sum(nb for _, nb in offs))
         for i, (it, (off, nb)) in enumerate(zip(items, offs)):
             seg = (odd[i].numpy() if odd[i] is not None else None) if i in odd else out.seg[i].numpy()
             m = out.masks[i].numpy() if out.masks[i] is not None else None
@@ -598,6 +625,7 @@ class TilePipeline:
                 r.size = (int(it.image.shape[0]), int(it.image.shape[1]))
             if self.rle:
                 r.rle_table, r.rle_data = rtab[off:off + nb], rdat
+            self._extra_result(r, i, off, nb, out, extra)
             res.append(r)
         out.odd = {}
         release = lambda o=out: self.free_out.put(o)
@@ -667,11 +695,17 @@ class InstancePipeline(TilePipeline):
     (``transforms.rbox_mask_prompts``).  Of the three masks per object the one with the highest predicted IoU is kept
     (SAM's own selection rule, `samrs_select_best` on the device); per object the host receives its area and quality (and with
     ``rle=True`` its COCO RLE), the kept masks stay in HBM (``last_masks``) unless keep_masks.  No class map is painted:
-    ``TileResult.seg_mask`` is None and the class statistics stay zero (the instance drivers write neither)."""
+    ``TileResult.seg_mask`` is None and the class statistics stay zero (the instance drivers write neither).
+
+    ``gt=True`` adds the evaluation of main_sam_rhbox_mask_instance.py:204-244 on the device: every ``WorkItem`` carries
+    ``gt=(label_rgb, colors)``; the label image is staged with the tile, and after the best-mask selection `samrs_gt_match`
+    counts per object |mask AND ground truth| and |ground truth| into ``TileResult.inter`` / ``gt_area`` (union = areas +
+    gt_area - inter); with ``rle=True`` the ground-truth masks are RLE-encoded on the device too (``TileResult.gt_rle``)."""
 
     BOX_WIDTH = 8          # four (x, y) corners
 
-    def __init__(self, sam, n_classes: int, prompt: str = "box", multimask: bool = True, fill_rule: str = "auto", **kw):
+    def __init__(self, sam, n_classes: int, prompt: str = "box", multimask: bool = True, fill_rule: str = "auto", gt: bool = False,
+                 **kw):
         """prompt: "box" / "rbox_mask" (annotations = rotated boxes [n, 4, 2]) or "point"
         (main_sam_hbox_mask_instance.py:160-165: annotations = one foreground point [n, 2] per object, handed to the prompt
         encoder AS IS -- the reference does not run them through apply_coords -- labels all 1, no box, no mask;
@@ -690,6 +724,69 @@ class InstancePipeline(TilePipeline):
             o.quality = torch.empty(self.batch, self.max_boxes, dtype=torch.float32).pin_memory()
             self.free_out.put(o)
         self.last_masks = None
+        self.gt = bool(gt)
+        if self.gt:
+            dev, B, M = self.dev, self.batch, self.max_boxes
+            self.pin_col = [torch.empty(B * M, 3, dtype=torch.uint8).pin_memory() for _ in range(2)]
+            self.dev_col = [torch.empty(B * M, 3, dtype=torch.uint8, device=dev) for _ in range(2)]
+            self.gt_lab: List[List[torch.Tensor]] = [[], []]          # per input set: the label images on the device
+            self.ev_gt = [torch.cuda.Event() for _ in range(2)]
+            self.inter_dev = [torch.zeros(B, M, dtype=torch.int64, device=dev) for _ in range(2)]
+            self.gta_dev = [torch.zeros(B, M, dtype=torch.int64, device=dev) for _ in range(2)]
+            if self.rle:
+                self.gt_rle_dev = [torch.empty_like(t) for t in self.rle_dev]
+                self.gt_rle_cur = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(2)]
+                self.gt_rle_tab = [torch.zeros(B * M, 3, dtype=torch.int64, device=dev) for _ in range(2)]
+            for _ in range(self.free_out.qsize()):
+                o = self.free_out.get()
+                o.inter = torch.empty(B, M, dtype=torch.int64).pin_memory()
+                o.gt_area = torch.empty(B, M, dtype=torch.int64).pin_memory()
+                if self.rle:
+                    o.gt_rle_tab = torch.zeros(B * M, 3, dtype=torch.int64).pin_memory()
+                    o.gt_rle_cur = torch.zeros(1, dtype=torch.int64).pin_memory()
+                    o.gt_rle_bytes = torch.empty(1 << 20, dtype=torch.uint8).pin_memory()
+                self.free_out.put(o)
+
+    def _stage(self, b: int, items: List[WorkItem]):
+        if not self.gt:
+            return super()._stage(b, items)
+        gts = []
+        for it in items:                                  # check everything before anything is queued
+            if it.gt is None:
+                raise ValueError(f"InstancePipeline(gt=True): work item {it.key!r} carries no gt=(label_rgb, colors)")
+            lab, col = np.asarray(it.gt[0]), np.asarray(it.gt[1])
+            H, W = int(it.image.shape[0]), int(it.image.shape[1])
+            if lab.dtype != np.uint8 or lab.shape != (H, W, 3):
+                raise ValueError(f"work item {it.key!r}: label image {lab.dtype} {tuple(lab.shape)} does not match the image "
+                                 f"(uint8 [{H}, {W}, 3])")
+            if col.dtype != np.uint8 or col.shape != (len(it.labels), 3):
+                raise ValueError(f"work item {it.key!r}: colors must be uint8 [{len(it.labels)}, 3], got {col.dtype} {tuple(col.shape)}")
+            gts.append((lab, col))
+        out = super()._stage(b, items)
+        self.ev_gt[b].synchronize()                       # the last copies out of pin_col[b] have finished
+        n_off, labs = 0, []
+        for lab, col in gts:
+            self.pin_col[b][n_off:n_off + len(col)] = torch.from_numpy(np.ascontiguousarray(col))
+            n_off += len(col)
+        with torch.cuda.stream(self.s_h2d):               # behind the wait for the decoder of batch k-2 (super()._stage)
+            self.dev_col[b][:n_off].copy_(self.pin_col[b][:n_off], non_blocking=True)
+            for lab, _ in gts:
+                # through pinned memory, asynchronously: a pageable copy would hold this thread until the decoder of batch k-2
+                # is done (the wait above), and the decoder would idle before batch k-1 is issued.  np.copyto, not copy_ (_stage)
+                pin = torch.empty(lab.shape, dtype=torch.uint8, pin_memory=True)
+                np.copyto(pin.numpy(), lab)
+                t = pin.to(self.dev, non_blocking=True)   # the caching host allocator keeps `pin` until the copy is done
+                t.record_stream(self.s_dec)                # allocated on s_h2d, read by the decoder
+                labs.append(t)
+            self.ev_gt[b].record(self.s_h2d)
+        self.gt_lab[b] = labs
+        return out
+
+    def _decode(self, b, items, tiles, offs, out):
+        if self.gt and self.rle:
+            with torch.cuda.stream(self.s_dec):
+                self.gt_rle_cur[b].zero_()
+        super()._decode(b, items, tiles, offs, out)
 
     def _decode_tile(self, b, i, tile, hw, off, nb, out) -> None:
         from . import transforms
@@ -697,6 +794,8 @@ class InstancePipeline(TilePipeline):
         in_size = (int(tile.shape[0]), int(tile.shape[1]))
         slot, mm = b * self.batch + i, self.multimask
         kept = []
+        if self.gt:
+            self.s_dec.wait_event(self.ev_gt[b])
         for s, e in box_chunks(nb, self.box_batch):
             ann = self.dev_box[b][off + s:off + e]
             if self.prompt == "box":
@@ -713,6 +812,12 @@ class InstancePipeline(TilePipeline):
             mk, _, _ = eng.select_best(m, q, None, self.qual_dev[b][i, s:e], self.area_dev[b][i, s:e])
             if self.rle:
                 eng.rle_encode(mk, self.rle_dev[b], self.rle_cur[b], self.rle_tab[b][off + s:off + e])
+            if self.gt:                                   # main_sam_rhbox_mask_instance.py:204-238, on the device
+                gm = torch.empty_like(mk) if self.rle else None
+                eng.gt_match(mk, self.gt_lab[b][i], self.dev_col[b][off + s:off + e], self.inter_dev[b][i, s:e],
+                             self.gta_dev[b][i, s:e], gm)
+                if self.rle:                              # instance_to_json.py:44-45
+                    eng.rle_encode(gm, self.gt_rle_dev[b], self.gt_rle_cur[b], self.gt_rle_tab[b][off + s:off + e])
             kept.append(mk)
         self.last_masks = kept[-1].view(torch.bool) if kept else None
         out.masks[i] = torch.cat(kept).cpu() if (self.keep_masks and kept) else None
@@ -720,3 +825,22 @@ class InstancePipeline(TilePipeline):
 
     def _extra_outputs(self, b: int, out: _OutBuf) -> None:
         out.quality.copy_(self.qual_dev[b], non_blocking=True)
+        if self.gt:
+            out.inter.copy_(self.inter_dev[b], non_blocking=True)
+            out.gt_area.copy_(self.gta_dev[b], non_blocking=True)
+            if self.rle:
+                out.gt_rle_tab.copy_(self.gt_rle_tab[b], non_blocking=True)
+                out.gt_rle_cur.copy_(self.gt_rle_cur[b], non_blocking=True)
+
+    def _fetch_extra(self, b: int, out: _OutBuf, n_boxes: int):
+        if not (self.gt and self.rle):
+            return None
+        tab, out.gt_rle_bytes = self._fetch_strings(self.gt_rle_dev[b], out.gt_rle_cur, out.gt_rle_tab, out.gt_rle_bytes, n_boxes)
+        return tab, out.gt_rle_bytes.numpy()
+
+    def _extra_result(self, r: TileResult, i: int, off: int, nb: int, out: _OutBuf, extra) -> None:
+        if not self.gt:
+            return
+        r.inter, r.gt_area = out.inter[i, :nb].numpy().copy(), out.gt_area[i, :nb].numpy().copy()
+        if extra is not None:
+            r.gt_rle_table, r.gt_rle_data = extra[0][off:off + nb], extra[1]

@@ -96,6 +96,7 @@ def load_library() -> C.CDLL:
     lib.samrs_rle_encode.argtypes = [vp, vp, ip, ip, ip, vp, C.c_int64, vp, vp, vp]
     lib.samrs_k_convert_split.argtypes = [ip, vp, vp, vp, C.c_int64, vp]
     lib.samrs_select_best.argtypes = [vp, vp, vp, ip, ip, ip, ip, vp, vp, vp, vp]
+    lib.samrs_gt_match.argtypes = [vp, vp, ip, ip, ip, vp, vp, vp, vp, vp, vp]
     lib.samrs_k_upscaler_fused.argtypes = [ip, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, vp]
     lib.samrs_k_convert.argtypes = [ip, vp, vp, C.c_int64, vp]
     lib.samrs_k_layernorm.argtypes = [ip, vp, vp, vp, fp, vp, vp, ip, ip, ip, ip, ip, ip, vp]
@@ -123,7 +124,7 @@ def load_library() -> C.CDLL:
                  "samrs_k_gemm_f32", "samrs_k_convert", "samrs_k_layernorm", "samrs_k_window_attention",
                  "samrs_k_global_attention", "samrs_k_postprocess", "samrs_k_gemm_gln", "samrs_k_upscale2_masks",
                  "samrs_k_gemm_stats", "samrs_k_gemm_fold", "samrs_k_ln_fold_weight", "samrs_k_rowstats_convert", "samrs_k_ln_rowstat",
-                 "samrs_set_option", "samrs_get_option", "samrs_rle_encode", "samrs_k_convert_split", "samrs_select_best",
+                 "samrs_set_option", "samrs_get_option", "samrs_rle_encode", "samrs_k_convert_split", "samrs_select_best", "samrs_gt_match",
                  "samrs_k_upscaler_fused", "samrs_k_gemm_split3", "samrs_get_slot_info"):
         getattr(lib, name).restype = ip
     if lib.samrs_abi_version() != ABI_VERSION:
@@ -401,6 +402,34 @@ class Engine:
             self._check(self.lib.samrs_select_best(self.handle, m.data_ptr(), iou.data_ptr(), n, c, h, w, best.data_ptr(),
                                                    qual.data_ptr(), areas.data_ptr(), _stream()))
         return best, qual, areas
+
+    def gt_match(self, masks: torch.Tensor, label_rgb: torch.Tensor, colors: torch.Tensor, inter_out: Optional[torch.Tensor] = None,
+                 gt_area_out: Optional[torch.Tensor] = None, gt_masks_out: Optional[torch.Tensor] = None):
+        """HRSC ground-truth matching on the device (samrs_gt_match): masks [n, H, W] bool / uint8, label_rgb uint8 [H, W, 3],
+        colors uint8 [n, 3] -> (inter int64 [n], gt_area int64 [n], gt_masks uint8 [n, H, W] 0/1 or None).  Instance j's ground
+        truth is the label pixels whose RGB equals colors[j]; pass `gt_masks_out` to receive it (e.g. for `rle_encode`).  The
+        outputs may be caller-owned contiguous slices; asynchronous on the current stream."""
+        m = masks.view(torch.uint8) if masks.dtype == torch.bool else masks
+        if m.dim() != 3:
+            raise ValueError(f"masks must be [n, H, W], got {tuple(m.shape)}")
+        n, h, w = m.shape
+        if tuple(label_rgb.shape) != (h, w, 3) or label_rgb.dtype != torch.uint8:
+            raise ValueError(f"label_rgb must be uint8 [{h}, {w}, 3] (the masks' size), got {label_rgb.dtype} {tuple(label_rgb.shape)}")
+        if tuple(colors.shape) != (n, 3) or colors.dtype != torch.uint8:
+            raise ValueError(f"colors must be uint8 [{n}, 3], got {colors.dtype} {tuple(colors.shape)}")
+        for t in (m, label_rgb, colors):
+            assert t.is_cuda and t.is_contiguous()
+        inter = inter_out if inter_out is not None else torch.empty(n, dtype=torch.int64, device=self.device)
+        gta = gt_area_out if gt_area_out is not None else torch.empty(n, dtype=torch.int64, device=self.device)
+        for t in (inter, gta):
+            assert t.dtype == torch.int64 and t.is_cuda and t.is_contiguous() and t.numel() == n
+        if gt_masks_out is not None:
+            assert gt_masks_out.dtype == torch.uint8 and gt_masks_out.is_cuda and gt_masks_out.is_contiguous()
+            assert gt_masks_out.numel() == n * h * w
+        with torch.cuda.device(self.device):
+            self._check(self.lib.samrs_gt_match(self.handle, m.data_ptr(), n, h, w, label_rgb.data_ptr(), colors.data_ptr(),
+                                                inter.data_ptr(), gta.data_ptr(), _ptr(gt_masks_out), _stream()))
+        return inter, gta, gt_masks_out
 
     def paint(self, masks: torch.Tensor, labels: torch.Tensor, seg: torch.Tensor,
               class_pixels: Optional[torch.Tensor] = None, class_instances: Optional[torch.Tensor] = None,

@@ -1,0 +1,338 @@
+"""Drop-in for the reference's HRSC2016 instance drivers (``Generate Dataset/main_sam_hbox_mask_instance.py``,
+``main_sam_rbox_mask_instance.py``, ``main_sam_rhbox_mask_instance.py``): images + HRSC XML annotations (+ the ground-truth
+label images) in; ``sam_ins_<tag>.json`` (the predictions as COCO results), ``gt_ins_<tag>.json`` (the ground truth as a COCO
+dataset, ``instance_to_json.py:5-108``), ``miou.json`` and the printed ``Average mIOU: ... Area mIOU: ...`` line
+(main_sam_rhbox_mask_instance.py:202-255) out.
+
+    torchrun --nproc-per-node 8 -m samrs_amd.instances --images DIR --annotations DIR --gt-labels DIR --out OUT \\
+             --prompt box --model vit_h --checkpoint sam_vit_h_4b8939.pth
+
+``--prompt point`` is main_sam_hbox_mask_instance.py (tag ``hbox``), ``rbox_mask`` main_sam_rbox_mask_instance.py (tag ``rbox``),
+``box`` main_sam_rhbox_mask_instance.py (tag ``rhbox``); all three use ``multimask_output=False`` like the reference,
+``--multimask`` keeps the best of the three multimask outputs instead (BASELINE.json configs[3]).
+
+The GPU side is ``driver.InstancePipeline(gt=True, rle=True)``: the masks stay in HBM; per instance the host receives its
+quality, its area, |mask AND ground truth|, |ground truth| and the two COCO RLE strings, all computed on the device
+(``samrs_select_best``, ``samrs_gt_match``, ``samrs_rle_encode``).  Each rank writes one fragment per image
+(``OUT/parts/<stem>.json``); after a barrier rank 0 merges them in sorted-stem order.
+
+One deliberate difference from the reference: image ids follow the SORTED image stems.  The reference numbers images in
+``os.listdir`` order (main_sam_rhbox_mask_instance.py:83), which is unspecified.  Images without an annotation file are ignored.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import math
+import os
+import xml.etree.ElementTree as ET
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+TAGS = {"point": "hbox", "rbox_mask": "rbox", "box": "rhbox"}
+IMAGE_EXTS = (".png", ".jpg", ".jpeg", ".tif", ".bmp")
+
+
+# ------------------------------------------------------------------------------------------------
+# HRSC XML (loaddata.load_hrsc, loaddata.py:41-102)
+# ------------------------------------------------------------------------------------------------
+@dataclass
+class HrscImage:
+    """The objects of one HRSC image.  ``skip``: the reference's ``error == 1`` (an object whose seg_color does not have three
+    fields, or no objects at all); such an image appears in no output (main_sam_rhbox_mask_instance.py:114-117)."""
+    hboxes: np.ndarray      # float32 [n, 4] box_xmin, box_ymin, box_xmax, box_ymax
+    rboxes: np.ndarray      # float32 [n, 4, 2] le90 corners, best begin point first
+    colors: np.ndarray      # uint8 [n, 3] seg_color
+    points: np.ndarray      # float32 [n, 2] mbox_cx, mbox_cy
+    skip: bool
+
+
+def _line_length(p, q) -> float:
+    return math.sqrt(math.pow(p[0] - q[0], 2) + math.pow(p[1] - q[1], 2))
+
+
+def _best_begin_point(poly: Sequence[float]) -> List[float]:
+    """Rotate the four corners so that the sum of distances to (xmin, ymin), (xmax, ymin), (xmax, ymax), (xmin, ymax) is
+    smallest, the first minimum winning (mmrotate's get_best_begin_point_single); double precision on the float32 corners."""
+    pts = [(poly[2 * k], poly[2 * k + 1]) for k in range(4)]
+    xs, ys = [p[0] for p in pts], [p[1] for p in pts]
+    dst = [(min(xs), min(ys)), (max(xs), min(ys)), (max(xs), max(ys)), (min(xs), max(ys))]
+    force, flag = 100000000.0, 0
+    for i in range(4):
+        rot = pts[i:] + pts[:i]
+        f = _line_length(rot[0], dst[0]) + _line_length(rot[1], dst[1]) + _line_length(rot[2], dst[2]) + _line_length(rot[3], dst[3])
+        if f < force:
+            force, flag = f, i
+    rot = pts[flag:] + pts[:flag]
+    return [c for p in rot for c in p]
+
+
+def le90_corners(cx: float, cy: float, w: float, h: float, ang: float) -> np.ndarray:
+    """(cx, cy, w, h, angle) -> float32 [4, 2] corners by the le90 formula (utils/transform.py:193-216) in float32, in the
+    reference's order of operations and array shapes (one [1, 1] array per value), then the best begin point (:234-280)."""
+    rb = np.array([[cx, cy, w, h, ang, 0]], dtype=np.float32)
+    center, bw, bh, theta = rb[:, 0:2], rb[:, 2:3], rb[:, 3:4], rb[:, 4:5]
+    cos, sin = np.cos(theta), np.sin(theta)
+    v1 = np.concatenate([bw / 2 * cos, bw / 2 * sin], axis=-1)
+    v2 = np.concatenate([-bh / 2 * sin, bh / 2 * cos], axis=-1)
+    poly = np.concatenate([center - v1 - v2, center + v1 - v2, center + v1 + v2, center - v1 + v2], axis=-1)
+    return np.asarray(_best_begin_point(poly[0].tolist()), dtype=np.float32).reshape(4, 2)
+
+
+def read_hrsc_xml(path: str) -> HrscImage:
+    """One HRSC2016 annotation file (``HRSC_Objects/HRSC_Object``)."""
+    root = ET.parse(path).getroot()
+    hb, rb, col, pt = [], [], [], []
+    skip = False
+    for obj in root.findall("HRSC_Objects/HRSC_Object"):
+        f = lambda tag: float(obj.find(tag).text)
+        hb.append(np.array([f("box_xmin"), f("box_ymin"), f("box_xmax"), f("box_ymax")], dtype=np.float32))
+        rb.append(le90_corners(f("mbox_cx"), f("mbox_cy"), f("mbox_w"), f("mbox_h"), f("mbox_ang")))
+        text = obj.find("seg_color").text
+        fields = text.split(",") if text is not None else []
+        if len(fields) != 3:
+            skip = True
+            col.append(np.zeros(3, dtype=np.uint8))
+        else:
+            col.append(np.array([int(v) for v in fields], dtype=np.uint8))
+        pt.append(np.array([f("mbox_cx"), f("mbox_cy")], dtype=np.float32))
+    if not rb:
+        skip = True
+    n = len(rb)
+    return HrscImage(np.stack(hb) if n else np.zeros((0, 4), np.float32), np.stack(rb) if n else np.zeros((0, 4, 2), np.float32),
+                     np.stack(col) if n else np.zeros((0, 3), np.uint8), np.stack(pt) if n else np.zeros((0, 2), np.float32), skip)
+
+
+def list_images(images_dir: str, annotations_dir: str) -> Tuple[List[str], Dict[str, str], Dict[str, HrscImage]]:
+    """(sorted stems of the images that are evaluated, stem -> image file name, stem -> annotations).  Images without
+    ``<stem>.xml`` are ignored; images the reference skips (HrscImage.skip) are left out."""
+    files = {os.path.splitext(f)[0]: f for f in os.listdir(images_dir) if f.lower().endswith(IMAGE_EXTS)}
+    stems, anns = [], {}
+    for stem in sorted(files):
+        path = os.path.join(annotations_dir, stem + ".xml")
+        if not os.path.exists(path):
+            continue
+        a = read_hrsc_xml(path)
+        if a.skip:
+            continue
+        stems.append(stem)
+        anns[stem] = a
+    return stems, files, anns
+
+
+# ------------------------------------------------------------------------------------------------
+# Fragments, mIoU and the COCO files
+# ------------------------------------------------------------------------------------------------
+def fragment_path(out_dir: str, stem: str) -> str:
+    return os.path.join(out_dir, "parts", stem + ".json")
+
+
+def write_fragment(out_dir: str, stem: str, frag: dict) -> None:
+    """One image's results; written through a rename, so that --resume can take its presence as "this image is complete"."""
+    os.makedirs(os.path.join(out_dir, "parts"), exist_ok=True)
+    tmp = fragment_path(out_dir, stem) + f".tmp.{os.getpid()}"
+    with open(tmp, "w") as f:
+        json.dump(frag, f)
+    os.replace(tmp, fragment_path(out_dir, stem))
+
+
+def make_fragment(height: int, width: int, scores, rles: Sequence[str], pred_area=None, inter=None, gt_area=None,
+                  gt_rles: Optional[Sequence[str]] = None) -> dict:
+    """scores: fp32 qualities (stored as float(fp32), instance_to_json.py:103); rles / gt_rles: the COCO counts strings."""
+    frag = {"height": int(height), "width": int(width), "scores": [float(np.float32(s)) for s in scores], "rles": list(rles)}
+    if gt_rles is not None:
+        frag.update(pred_area=[int(v) for v in pred_area], inter=[int(v) for v in inter], gt_area=[int(v) for v in gt_area],
+                    gt_rles=list(gt_rles))
+    return frag
+
+
+def pending_stems(out_dir: str, stems: Sequence[str]) -> List[str]:
+    """--resume: the stems whose fragment is not on disk yet."""
+    return [s for s in stems if not os.path.exists(fragment_path(out_dir, s))]
+
+
+def miou_from_tallies(inter: Sequence[int], pred_area: Sequence[int], gt_area: Sequence[int]) -> Tuple[float, float, int]:
+    """``driver.mean_iou`` from per-instance integers (main_sam_rhbox_mask_instance.py:221-242): union = pred + gt - inter;
+    instances with an empty union are left out.  Returns (Average mIOU, Area mIOU, instances averaged)."""
+    ious, inter_all, union_all = [], [], []
+    for i, p, g in zip(inter, pred_area, gt_area):
+        union = float(int(p) + int(g) - int(i))
+        if union > 0:
+            inter_all.append(float(i))
+            union_all.append(union)
+            ious.append(float(i) / union)
+    if not ious:
+        return float("nan"), float("nan"), 0
+    return float(np.mean(ious)), float(np.sum(inter_all) / np.sum(union_all)), len(ious)
+
+
+def merge_fragments(out_dir: str, stems: Sequence[str], tag: str, with_gt: bool) -> Optional[dict]:
+    """Rank 0, after every rank has written its fragments: ``sam_ins_<tag>.json`` (binary_to_coco_pre_hrsc) and, with the
+    ground truth, ``gt_ins_<tag>.json`` (binary_to_coco_gt_hrsc) and ``miou.json``; image id = position in `stems` (sorted),
+    annotation ids restart at 0 per image.  Returns the mIoU record (None without ground truth)."""
+    frags = []
+    for stem in stems:
+        path = fragment_path(out_dir, stem)
+        if not os.path.exists(path):
+            raise RuntimeError(f"missing fragment {path}: a rank did not finish (rerun with --resume)")
+        with open(path) as f:
+            frags.append(json.load(f))
+    pred = []
+    for n, fr in enumerate(frags):
+        size = [fr["height"], fr["width"]]
+        for c, (counts, score) in enumerate(zip(fr["rles"], fr["scores"])):
+            pred.append({"image_id": int(n), "category_id": 0, "segmentation": {"size": size, "counts": counts}, "score": float(score)})
+    with open(os.path.join(out_dir, f"sam_ins_{tag}.json"), "w") as f:
+        json.dump(pred, f)
+    if not with_gt:
+        return None
+    gt = {"images": [], "annotations": [], "categories": [{"id": 0, "name": "ship", "supercategory": "None"}]}
+    for n, (stem, fr) in enumerate(zip(stems, frags)):
+        gt["images"].append({"id": int(n), "width": int(fr["width"]), "height": int(fr["height"]), "file_name": "{}.png".format(stem)})
+    inter, parea, garea = [], [], []
+    for n, fr in enumerate(frags):
+        size = [fr["height"], fr["width"]]
+        for c, counts in enumerate(fr["gt_rles"]):
+            gt["annotations"].append({"id": c, "image_id": n, "category_id": 0, "area": int(fr["gt_area"][c]), "iscrowd": 0,
+                                      "segmentation": {"size": size, "counts": counts}, "attributes": {}})
+        inter += fr["inter"]
+        parea += fr["pred_area"]
+        garea += fr["gt_area"]
+    with open(os.path.join(out_dir, f"gt_ins_{tag}.json"), "w") as f:
+        json.dump(gt, f)
+    avg, area, k = miou_from_tallies(inter, parea, garea)
+    rec = {"average": None if math.isnan(avg) else avg, "area": None if math.isnan(area) else area, "n_instances": k}
+    with open(os.path.join(out_dir, "miou.json"), "w") as f:
+        json.dump(rec, f)
+    print("Average mIOU: ", avg, "Area mIOU: ", area, flush=True)              # main_sam_rhbox_mask_instance.py:244
+    return rec
+
+
+# ------------------------------------------------------------------------------------------------
+# The run
+# ------------------------------------------------------------------------------------------------
+def run(args) -> Optional[dict]:
+    """The whole CLI; returns rank 0's mIoU record (None on other ranks and without --gt-labels)."""
+    import torch
+    import torch.distributed as dist
+    import samrs_amd
+    from . import driver, generate, tile_io
+
+    if args.prompt not in TAGS:
+        raise ValueError(f"--prompt must be one of {sorted(TAGS)}")
+    tag = TAGS[args.prompt]
+    rank = int(os.environ.get("RANK", "0"))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    share = os.environ.get("SAMRS_SHARE_GPU") == "1"          # every rank on cuda:0, collectives over gloo (generate.run)
+    if share:
+        local = 0
+    torch.cuda.set_device(local)
+    if world > 1 and not dist.is_initialized():
+        if share:
+            dist.init_process_group("gloo")
+        else:
+            dist.init_process_group("nccl", device_id=torch.device("cuda", local))
+    with_gt = bool(getattr(args, "gt_labels", None))
+    stems, files, anns = list_images(args.images, args.annotations)
+    todo = stems
+    if getattr(args, "resume", False):
+        # listed once, on rank 0, and broadcast (generate.run: ranks must index the same list)
+        todo = driver.agree_on_list(pending_stems(args.out, stems) if rank == 0 else [])
+        if rank == 0:
+            print(f"[rank 0] --resume: {len(stems) - len(todo)} of {len(stems)} images already complete", flush=True)
+    batch = getattr(args, "batch", 8)
+    multimask = bool(getattr(args, "multimask", False))
+    split = getattr(args, "split", None)
+    # single-mask: the 1x-rate operand split unless --split / SAMRS_SPLIT say otherwise (generate.default_split_options); multimask:
+    # the model's own multimask-grade default
+    opts = generate.default_split_options(split) if not multimask else ({"split": int(split)} if split is not None else None)
+    sam = samrs_amd.sam_model_registry[args.model](checkpoint=args.checkpoint, precision=getattr(args, "precision", "f16"), options=opts,
+                                                   max_images=2 * batch, max_prompts=args.box_batch).to(f"cuda:{local}")
+    max_boxes = max([len(anns[s].colors) for s in stems] + [1])
+    pipe = driver.InstancePipeline(sam, 1, prompt=args.prompt, multimask=multimask, fill_rule=getattr(args, "fill_rule", "auto"),
+                                   gt=with_gt, batch=batch, box_batch=args.box_batch, max_boxes=max_boxes, rle=True,
+                                   rle_buffer_mb=getattr(args, "rle_buffer_mb", 256), keep_masks=False)
+    os.makedirs(os.path.join(args.out, "parts"), exist_ok=True)
+    import zlib
+    wq_name = "samrs_ins/%08x" % zlib.crc32(("\n".join(todo) + "|" + args.out).encode())
+    wq = driver.WorkQueue(len(todo), chunk=batch, rank=rank, world=world, mode=getattr(args, "schedule", "static"), name=wq_name)
+
+    def load(stem: str) -> driver.WorkItem:
+        a = anns[stem]
+        img = tile_io.read_rgb(os.path.join(args.images, files[stem]))
+        ann = a.points if args.prompt == "point" else a.rboxes
+        gt = None
+        if with_gt:
+            gt = (tile_io.read_rgb(os.path.join(args.gt_labels, stem + ".png")), a.colors)
+        return driver.WorkItem(stem, img, ann, np.zeros(len(a.colors), dtype=np.int64), gt)
+
+    def batches():
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max_workers=2) as readers:    # decode of the next batch overlaps the GPU work on this one
+            nxt = None
+            for s0, s1 in wq:
+                fut = [readers.submit(load, st) for st in todo[s0:s1]]
+                if nxt is not None:
+                    yield [f.result() for f in nxt]
+                nxt = fut
+            if nxt is not None:
+                yield [f.result() for f in nxt]
+
+    def sink(results, release):
+        try:
+            for r in results:
+                n = len(r.labels)
+                rles = [r.rle(j)["counts"] for j in range(n)]
+                if with_gt:
+                    frag = make_fragment(r.size[0], r.size[1], r.quality, rles, r.areas, r.inter, r.gt_area,
+                                         [r.gt_rle(j)["counts"] for j in range(n)])
+                else:
+                    frag = make_fragment(r.size[0], r.size[1], r.quality, rles)
+                write_fragment(args.out, r.key, frag)
+        finally:
+            release()
+
+    import time
+    t0 = time.perf_counter()
+    n_done = pipe.run(batches(), sink)
+    wall = time.perf_counter() - t0
+    print(f"[rank {rank}] {n_done} images in {wall:.2f} s = {n_done / max(wall, 1e-9):.1f} images/s", flush=True)
+    if world > 1:
+        dist.barrier()
+    rec = None
+    if rank == 0:
+        rec = merge_fragments(args.out, stems, tag, with_gt)
+    if world > 1:
+        dist.barrier()                                         # nobody leaves before the merged files are on disk
+    return rec
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="SAM instance masks + ground-truth evaluation on HRSC2016 (SAMRS) on MI355X")
+    ap.add_argument("--images", required=True, help="image directory (HRSC: .bmp)")
+    ap.add_argument("--annotations", required=True, help="HRSC XML directory (<stem>.xml)")
+    ap.add_argument("--gt-labels", default=None, help="ground-truth label images <stem>.png (instance j = pixels of its seg_color); "
+                    "without it only sam_ins_<tag>.json is written")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--prompt", required=True, choices=sorted(TAGS), help="point = main_sam_hbox_mask_instance.py (tag hbox), "
+                    "rbox_mask = main_sam_rbox_mask_instance.py (tag rbox), box = main_sam_rhbox_mask_instance.py (tag rhbox)")
+    ap.add_argument("--multimask", action="store_true", help="keep the best of the three multimask outputs (BASELINE.json configs[3]); "
+                    "the reference uses multimask_output=False")
+    ap.add_argument("--model", default="vit_h")
+    ap.add_argument("--checkpoint", default=None)
+    ap.add_argument("--precision", default="f16", choices=["f16", "bf16"])
+    ap.add_argument("--split", type=int, default=None, help="engine operand-split mode (DESIGN.md section 2)")
+    ap.add_argument("--fill-rule", default="auto", help="rbox_mask: cv2.fillPoly span rule (transforms.resolve_fill_rule)")
+    ap.add_argument("--batch", type=int, default=8, help="tiles per encoder pass")
+    ap.add_argument("--box-batch", type=int, default=64, help="objects per predict call")
+    ap.add_argument("--rle-buffer-mb", type=int, default=256)
+    ap.add_argument("--schedule", default="static", choices=["static", "dynamic"])
+    ap.add_argument("--resume", action="store_true", help="skip images whose fragment OUT/parts/<stem>.json already exists")
+    return run(ap.parse_args(argv))
+
+
+if __name__ == "__main__":
+    main()
