@@ -183,6 +183,17 @@ int samrs_gt_match(samrs_engine_t* e, const uint8_t* masks, int n, int h, int w,
 int samrs_rle_encode(samrs_engine_t* e, const uint8_t* masks, int n, int h, int w, uint8_t* out, int64_t out_capacity,
                      int64_t* cursor, int64_t* table, void* stream);
 
+/* -- the generation CLI's class-map files (main_sam_hbox_semantic.py:212-215: gray/<stem>.png and color/<stem>.png), encoded on
+ * the device.  maps: uint8 [n][h][w] (255 = unlabeled), lut: uint8 [256][3] (class id -> RGB), both on the device.  The two PNG
+ * files of each map are byte-identical with what the host's samrs_io_png_write_label_pair (include/samrs_io.h) writes for
+ * (maps[i], lut).  Same buffer protocol as samrs_rle_encode: the files are packed into `out` (device bytes, 16-byte aligned,
+ * capacity out_capacity) at 16-byte aligned offsets behind *cursor (device int64, in / out), and table [n][2][2] (device int64)
+ * receives (offset, length) of the gray and the colour file of each map; length < 0 means the file did not fit (-length - 1 bytes
+ * were needed) and was not written.  h, w <= 65536 and (3 w + 1) h < 2^31.  No host synchronisation; the token scratch lives in
+ * ONE buffer per handle: all samrs_png_encode_labels calls on a handle must be stream-ordered with each other. */
+int samrs_png_encode_labels(samrs_engine_t* e, const uint8_t* maps, int n, int h, int w, const uint8_t* lut, uint8_t* out,
+                            int64_t out_capacity, int64_t* cursor, int64_t* table, void* stream);
+
 /* -- "next row" N3: one separable pass of Pillow's 8-bit resample (ResizeLongestSide.apply_image,
  * utils/transforms.py:26-31 -> PIL Image.resize BILINEAR).  `bounds` int32 [out_len,2] = (first input
  * index, tap count), `coef` int32 [out_len,ksize] 22-bit fixed point, both computed on the host exactly

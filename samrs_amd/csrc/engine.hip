@@ -223,6 +223,9 @@ struct samrs_engine {
     // COCO RLE scratch (samrs_rle_encode), grown on demand
     void* rle_scratch = nullptr;
     size_t rle_scratch_bytes = 0;
+    // class-map PNG scratch (samrs_png_encode_labels), grown on demand
+    void* png_scratch = nullptr;
+    size_t png_scratch_bytes = 0;
 
     // optional in-situ timing of the dominant kernel (MLP lin1 + GELU GEMM) with HIP events
     bool timing = false;
@@ -557,6 +560,7 @@ void samrs_destroy(samrs_engine_t* e) {
     DeviceGuard dg(e->device);
     for (void* p : e->owned) (void)hipFree(p);
     if (e->rle_scratch) (void)hipFree(e->rle_scratch);
+    if (e->png_scratch) (void)hipFree(e->png_scratch);
     delete e;
 }
 
@@ -1674,6 +1678,30 @@ int samrs_rle_encode(samrs_engine_t* e, const uint8_t* masks, int n, int h, int 
         CK(e, launch_rle_encode(masks + (size_t)off * h * w, m, h, w, e->rle_scratch, out, (long long)out_capacity,
                                 (long long*)cursor, (long long*)table + (size_t)off * 3, s));
     }
+    return SAMRS_OK;
+}
+
+// gray + colour PNG files of n class maps, packed behind *cursor into `out` (see samrs_hip.h)
+int samrs_png_encode_labels(samrs_engine_t* e, const uint8_t* maps, int n, int h, int w, const uint8_t* lut, uint8_t* out,
+                            int64_t out_capacity, int64_t* cursor, int64_t* table, void* stream) {
+    if (!e || !maps || !lut || !out || !cursor || !table || n < 1 || h < 1 || w < 1 || out_capacity < 16)
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_png_encode_labels: bad argument");
+    if (((uintptr_t)out & 15) != 0) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_png_encode_labels: out must be 16-byte aligned");
+    if (h > 65536 || w > 65536 || ((size_t)3 * w + 1) * h > 0x7fffffffull)
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_png_encode_labels: %d x %d map too large (h, w <= 65536, (3 w + 1) h < 2^31)", h, w);
+    ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t need = png_scratch_bytes(n, h, w);
+    if (need > e->png_scratch_bytes) {
+        if (e->png_scratch) {
+            CK(e, hipStreamSynchronize(s));
+            CK(e, hipFree(e->png_scratch));               // device-synchronising: nothing still reads the old scratch
+            e->png_scratch = nullptr; e->png_scratch_bytes = 0;
+        }
+        CK(e, hipMalloc(&e->png_scratch, need));
+        e->png_scratch_bytes = need;
+    }
+    CK(e, launch_png_encode(maps, n, h, w, lut, e->png_scratch, out, (long long)out_capacity, (long long*)cursor, (long long*)table, s));
     return SAMRS_OK;
 }
 

@@ -224,3 +224,12 @@ hipError_t launch_upscaler_fused(int prec, const void* keys, const void* keys_lo
 size_t rle_scratch_bytes(int n, int h, int w);
 hipError_t launch_rle_encode(const uint8_t* masks, int n, int h, int w, void* scratch, unsigned char* out, long long out_cap,
                              long long* cursor, long long* table, hipStream_t s);
+
+// ---- png_kernels.hip ------------------------------------------------------------------------
+// gray/<stem>.png and color/<stem>.png of n class maps (uint8 [n][h][w] on the device, lut uint8 [256][3] on the device), byte-
+// identical with libsamrs_io's samrs_io_png_write_label_pair.  Files packed behind *cursor into `out` (16-byte aligned, capacity
+// out_cap) at 16-byte aligned offsets; table [n][2][2] = (offset, length) of gray, colour; length < 0: did not fit (-length - 1
+// bytes were needed) and was not written.  scratch: png_scratch_bytes(n, h, w).
+size_t png_scratch_bytes(int n, int h, int w);
+hipError_t launch_png_encode(const uint8_t* maps, int n, int h, int w, const uint8_t* lut, void* scratch, unsigned char* out,
+                             long long out_cap, long long* cursor, long long* table, hipStream_t s);

@@ -321,6 +321,16 @@ class TileResult:
     gt_area: Optional[np.ndarray] = None    # int64 [n_boxes] |ground truth| (InstancePipeline(gt=True))
     gt_rle_table: Optional[np.ndarray] = None   # like rle_table, for the ground-truth masks (gt=True, rle=True)
     gt_rle_data: Optional[np.ndarray] = None
+    png_table: Optional[np.ndarray] = None  # int64 [2, 2] (offset, length) of the gray and the colour PNG in png_data (png_lut)
+    png_data: Optional[np.ndarray] = None   # uint8 view of the batch's pinned PNG byte buffer
+
+    def png(self, kind: str) -> memoryview:
+        """The bytes of ``gray/<stem>.png`` (kind "gray") or ``color/<stem>.png`` ("color") of this tile, encoded on the device
+        (samrs_png_encode_labels) and byte-identical with tile_io.write_label_pair; only when the pipeline ran with png_lut."""
+        if self.png_table is None:
+            raise ValueError("no device PNG files: the pipeline ran without png_lut")
+        off, n = (int(v) for v in self.png_table[{"gray": 0, "color": 1}[kind]])
+        return memoryview(self.png_data[off:off + n])
 
     def rle(self, j: int) -> dict:
         """COCO RLE of instance j exactly as the reference stores it (main_sam_hbox_semantic.py:201-202):
@@ -338,7 +348,7 @@ class TileResult:
 
 
 class _OutBuf:
-    def __init__(self, batch: int, side: int, max_boxes: int, rle: bool = False):
+    def __init__(self, batch: int, side: int, max_boxes: int, rle: bool = False, png: bool = False):
         self.seg = torch.empty(batch, side, side, dtype=torch.uint8).pin_memory()
         self.areas = torch.empty(batch, max_boxes, dtype=torch.int64).pin_memory()
         self.done = torch.cuda.Event()
@@ -348,6 +358,10 @@ class _OutBuf:
         self.rle_tab = torch.zeros(batch * max_boxes, 3, dtype=torch.int64).pin_memory() if rle else None
         self.rle_cur = torch.zeros(1, dtype=torch.int64).pin_memory() if rle else None
         self.rle_bytes = torch.empty(1 << 20, dtype=torch.uint8).pin_memory() if rle else None
+        # png: per tile (offset, length) of its gray and colour file, the number of bytes used, and the files (grown on demand)
+        self.png_tab = torch.zeros(batch, 2, 2, dtype=torch.int64).pin_memory() if png else None
+        self.png_cur = torch.zeros(1, dtype=torch.int64).pin_memory() if png else None
+        self.png_bytes = torch.empty(1 << 20, dtype=torch.uint8).pin_memory() if png else None
 
 
 class TilePipeline:
@@ -364,13 +378,19 @@ class TilePipeline:
     per-instance COCO RLE strings of main_sam_hbox_semantic.py:201-202, encoded on the device (`samrs_rle_encode`:
     a few KB per mask on real data) -- the full-resolution masks themselves never leave HBM unless `keep_masks`.  Bit-identical to `SemanticGenerator` (no kernel depends on batch composition or on what
     runs next to it).  Tiles of one batch may differ in size (non-1024 tiles are resized on the GPU, bit-exact with
-    PIL, and encoded through samrs_set_images_ragged)."""
+    PIL, and encoded through samrs_set_images_ragged).
+
+    With `png_lut` (uint8 [256, 3], ``tile_io.class_lut(palette)``) the class maps are also encoded on the device into the
+    complete ``gray/<stem>.png`` and ``color/<stem>.png`` files (`samrs_png_encode_labels`, byte-identical with
+    ``tile_io.write_label_pair``): ``TileResult.png(kind)``.  `png_buffer_mb` is the device buffer for one batch's files
+    (default: 6 MiB per tile, which holds a batch of all-literal 1024^2 tiles -- at most 9 bits per byte, 4.5 MiB per pair)."""
 
     BOX_WIDTH = 4          # floats per annotation: xyxy
 
     def __init__(self, sam, n_classes: int, batch: int = 8, box_batch: int = 20, keep_masks: bool = False,
                  out_depth: int = 3, max_boxes: int = 512, device_inputs: bool = False, rle: bool = False,
-                 rle_buffer_mb: int = 256, precision="auto", _multimask: bool = False):
+                 rle_buffer_mb: int = 256, precision="auto", _multimask: bool = False, png_lut: Optional[np.ndarray] = None,
+                 png_buffer_mb: Optional[int] = None):
         """precision: the operand-split mode (engine option "split") THIS PIPELINE'S OWN CALLS run in.  The option is set around
         each of the pipeline's encode / decode calls and restored afterwards (``Engine.options``), so the mode never outlives
         them: a ``SamPredictor`` built on the same model keeps the engine's own default (round 3 changed the engine's option for
@@ -404,6 +424,7 @@ class TilePipeline:
         self.sam, self.eng, self.dev = sam, eng, eng.device
         self.batch, self.box_batch, self.keep_masks, self.max_boxes = batch, box_batch, keep_masks, max_boxes
         self.rle = rle
+        self.png = png_lut is not None
         self.side = sam.cfg.img_size
         self.transform = ResizeLongestSide(sam.image_encoder.img_size)
         self.class_pixels = torch.zeros(n_classes, dtype=torch.int64, device=self.dev)
@@ -416,11 +437,21 @@ class TilePipeline:
         self.pin_in = None
         if not device_inputs:
             self.pin_in = [torch.empty(batch, side, side, 3, dtype=torch.uint8).pin_memory() for _ in range(2)]
-        if rle:      # per input set: the batch's RLE strings (packed, 16-byte aligned), a cursor, (offset, length, n_counts) per box
+        if rle or self.png:
             self.s_d2h = torch.cuda.Stream(dev)
+        if rle:      # per input set: the batch's RLE strings (packed, 16-byte aligned), a cursor, (offset, length, n_counts) per box
             self.rle_dev = [torch.empty(rle_buffer_mb << 20, dtype=torch.uint8, device=dev) for _ in range(2)]
             self.rle_cur = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(2)]
             self.rle_tab = [torch.zeros(batch * max_boxes, 3, dtype=torch.int64, device=dev) for _ in range(2)]
+        if self.png:   # the LUT once; per input set: the batch's PNG files (packed, 16-byte aligned), a cursor, (offset, length) per file
+            lut = np.ascontiguousarray(png_lut, dtype=np.uint8)
+            if lut.shape != (256, 3):
+                raise ValueError("png_lut must be uint8 [256, 3] (tile_io.class_lut)")
+            self.png_lut = torch.from_numpy(lut).to(dev)
+            self.png_buffer_mb = int(png_buffer_mb) if png_buffer_mb else 6 * batch
+            self.png_dev = [torch.empty(self.png_buffer_mb << 20, dtype=torch.uint8, device=dev) for _ in range(2)]
+            self.png_cur = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(2)]
+            self.png_tab = [torch.zeros(batch, 2, 2, dtype=torch.int64, device=dev) for _ in range(2)]
         self.dev_in = [torch.empty(batch, side, side, 3, dtype=torch.uint8, device=dev) for _ in range(2)]
         bw = self.BOX_WIDTH
         self.pin_box = [torch.empty(batch * max_boxes, bw, dtype=torch.float32).pin_memory() for _ in range(2)]
@@ -435,7 +466,7 @@ class TilePipeline:
         self.ev_in_free = [torch.cuda.Event() for _ in range(2)]     # encoder has consumed input set b
         self.free_out: "queue.Queue[_OutBuf]" = queue.Queue()
         for _ in range(out_depth):
-            self.free_out.put(_OutBuf(batch, side, max_boxes, rle))
+            self.free_out.put(_OutBuf(batch, side, max_boxes, rle, self.png))
 
     @staticmethod
     def _choose_split(sam, precision, multimask: bool) -> Optional[int]:
@@ -542,6 +573,8 @@ class TilePipeline:
                 eng.rle_encode(masks[:, 0], self.rle_dev[b], self.rle_cur[b], self.rle_tab[b][off + s:off + e])
             if self.keep_masks:
                 kept.append(masks[:, 0].view(torch.uint8))
+        if self.png and not native:                                              # an odd-sized tile: its own call
+            eng.png_encode(seg, self.png_lut, self.png_dev[b], self.png_cur[b], self.png_tab[b][i:i + 1])
         if native:
             out.seg[i].copy_(seg, non_blocking=True)
         else:
@@ -563,16 +596,37 @@ class TilePipeline:
             self.seg_dev[b].fill_(255)                                               # main_sam_hbox_semantic.py:162
             if self.rle:
                 self.rle_cur[b].zero_()
+            if self.png:
+                self.png_cur[b].zero_()
             with self._mode():
                 for i, ((t, hw), (off, nb)) in enumerate(zip(tiles, offs)):
                     self._decode_tile(b, i, t, hw, off, nb, out)
+            if self.png:
+                self._encode_png(b, tiles)
             out.areas.copy_(self.area_dev[b], non_blocking=True)
             if self.rle:
                 out.rle_tab.copy_(self.rle_tab[b], non_blocking=True)
                 out.rle_cur.copy_(self.rle_cur[b], non_blocking=True)
+            if self.png:
+                out.png_tab.copy_(self.png_tab[b], non_blocking=True)
+                out.png_cur.copy_(self.png_cur[b], non_blocking=True)
             self._extra_outputs(b, out)
             self.ev_dec[b].record(self.s_dec)
             out.done.record(self.s_dec)
+
+    def _encode_png(self, b: int, tiles) -> None:
+        """gray + colour PNG of the batch's native tiles: one samrs_png_encode_labels call per run of consecutive native tiles
+        (one call for a batch of native tiles), on s_dec after painting.  Odd-sized tiles were encoded in _decode_tile."""
+        native = [i for i, (_, hw) in enumerate(tiles) if tuple(hw) == (self.side, self.side)]
+        runs: List[List[int]] = []
+        for i in native:
+            if runs and runs[-1][-1] == i - 1:
+                runs[-1].append(i)
+            else:
+                runs.append([i])
+        for r in runs:
+            i0, i1 = r[0], r[-1] + 1
+            self.eng.png_encode(self.seg_dev[b][i0:i1], self.png_lut, self.png_dev[b], self.png_cur[b], self.png_tab[b][i0:i1])
 
     def _extra_outputs(self, b: int, out: _OutBuf) -> None:
         pass
@@ -589,14 +643,21 @@ class TilePipeline:
         tab, out.rle_bytes = self._fetch_strings(self.rle_dev[b], out.rle_cur, out.rle_tab, out.rle_bytes, n_boxes)
         return tab, out.rle_bytes.numpy()
 
-    def _fetch_strings(self, dev: torch.Tensor, cur: torch.Tensor, tab_host: torch.Tensor, host: torch.Tensor, n_boxes: int):
+    def _fetch_png(self, b: int, out: _OutBuf, n_tiles: int):
+        """The batch's PNG files, fetched like the RLE strings: table + exact byte count on the host, then one exact-size D2H."""
+        tab, out.png_bytes = self._fetch_strings(self.png_dev[b], out.png_cur, out.png_tab.view(-1, 2), out.png_bytes, 2 * n_tiles,
+                                                 what="PNG buffer too small: a file", knob="png_buffer_mb")
+        return tab.reshape(-1, 2, 2), out.png_bytes.numpy()
+
+    def _fetch_strings(self, dev: torch.Tensor, cur: torch.Tensor, tab_host: torch.Tensor, host: torch.Tensor, n_boxes: int,
+                       what: str = "RLE buffer too small: a mask", knob: str = "rle_buffer_mb"):
         """(table, pinned host bytes) of one packed string buffer (samrs_rle_encode's layout); `host` grows when too small."""
         total = int(cur[0])
         tab = tab_host[:n_boxes].numpy()
         if n_boxes and int(tab[:, 1].min()) < 0:
             need = int((-tab[:, 1] - 1).max())
-            raise RuntimeError(f"RLE buffer too small: a mask needs {need} bytes and the batch already holds {total}; raise "
-                               f"rle_buffer_mb (now {dev.numel() >> 20})")
+            raise RuntimeError(f"{what} needs {need} bytes and the batch already holds {total}; raise "
+                               f"{knob} (now {dev.numel() >> 20})")
         if host.numel() < total:
             host = torch.empty(max(total, 2 * host.numel()), dtype=torch.uint8).pin_memory()
         if total:
@@ -613,6 +674,9 @@ class TilePipeline:
         rtab = rdat = None
         if self.rle:
             rtab, rdat = self._fetch_rle(b, out, sum(nb for _, nb in offs))
+        ptab = pdat = None
+        if self.png:
+            ptab, pdat = self._fetch_png(b, out, len(items))
         extra = self._fetch_extra(b, out, sum(nb for _, nb in offs))
         for i, (it, (off, nb)) in enumerate(zip(items, offs)):
             seg = (odd[i].numpy() if odd[i] is not None else None) if i in odd else out.seg[i].numpy()
@@ -625,6 +689,8 @@ class TilePipeline:
                 r.size = (int(it.image.shape[0]), int(it.image.shape[1]))
             if self.rle:
                 r.rle_table, r.rle_data = rtab[off:off + nb], rdat
+            if self.png:
+                r.png_table, r.png_data = ptab[i], pdat
             self._extra_result(r, i, off, nb, out, extra)
             res.append(r)
         out.odd = {}
@@ -716,6 +782,8 @@ class InstancePipeline(TilePipeline):
             self.BOX_WIDTH = 2
         from . import transforms
         self.fill_rule = transforms.resolve_fill_rule(fill_rule)       # prompt="rbox_mask": the cv2.fillPoly span rule to reproduce
+        if kw.get("png_lut") is not None:
+            raise ValueError("InstancePipeline paints no class map: png_lut is a TilePipeline option")
         super().__init__(sam, n_classes, precision=kw.pop("precision", "auto"), _multimask=bool(multimask), **kw)
         self.prompt, self.multimask = prompt, bool(multimask)
         self.qual_dev = [torch.zeros(self.batch, self.max_boxes, dtype=torch.float32, device=self.dev) for _ in range(2)]

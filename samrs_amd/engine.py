@@ -97,6 +97,7 @@ def load_library() -> C.CDLL:
     lib.samrs_k_convert_split.argtypes = [ip, vp, vp, vp, C.c_int64, vp]
     lib.samrs_select_best.argtypes = [vp, vp, vp, ip, ip, ip, ip, vp, vp, vp, vp]
     lib.samrs_gt_match.argtypes = [vp, vp, ip, ip, ip, vp, vp, vp, vp, vp, vp]
+    lib.samrs_png_encode_labels.argtypes = [vp, vp, ip, ip, ip, vp, vp, C.c_int64, vp, vp, vp]
     lib.samrs_k_upscaler_fused.argtypes = [ip, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, vp]
     lib.samrs_k_convert.argtypes = [ip, vp, vp, C.c_int64, vp]
     lib.samrs_k_layernorm.argtypes = [ip, vp, vp, vp, fp, vp, vp, ip, ip, ip, ip, ip, ip, vp]
@@ -125,7 +126,7 @@ def load_library() -> C.CDLL:
                  "samrs_k_global_attention", "samrs_k_postprocess", "samrs_k_gemm_gln", "samrs_k_upscale2_masks",
                  "samrs_k_gemm_stats", "samrs_k_gemm_fold", "samrs_k_ln_fold_weight", "samrs_k_rowstats_convert", "samrs_k_ln_rowstat",
                  "samrs_set_option", "samrs_get_option", "samrs_rle_encode", "samrs_k_convert_split", "samrs_select_best", "samrs_gt_match",
-                 "samrs_k_upscaler_fused", "samrs_k_gemm_split3", "samrs_get_slot_info"):
+                 "samrs_png_encode_labels", "samrs_k_upscaler_fused", "samrs_k_gemm_split3", "samrs_get_slot_info"):
         getattr(lib, name).restype = ip
     if lib.samrs_abi_version() != ABI_VERSION:
         raise ImportError("libsamrs_hip.so ABI version mismatch; rebuild it")
@@ -386,6 +387,24 @@ class Engine:
         with torch.cuda.device(self.device):
             self._check(self.lib.samrs_rle_encode(self.handle, m.data_ptr(), n, h, w, out.data_ptr(), out.numel(),
                                                   cursor.data_ptr(), table.data_ptr(), _stream()))
+
+    def png_encode(self, maps: torch.Tensor, lut: torch.Tensor, out: torch.Tensor, cursor: torch.Tensor, table: torch.Tensor) -> None:
+        """``gray/<stem>.png`` and ``color/<stem>.png`` of the class maps `maps` ([n, H, W] or [H, W] uint8 on this device, 255 =
+        unlabeled) through `lut` (uint8 [256, 3], device; ``tile_io.class_lut``), byte-identical with
+        :func:`tile_io.write_label_pair`, appended to the byte buffer `out` (uint8, device, 16-byte aligned) behind `cursor` (int64
+        [1], device, in / out); `table` (int64 [n, 2, 2], device) receives (offset, length) of the gray and the colour file per
+        map, length < 0: did not fit (-length - 1 bytes needed).  Asynchronous on the current stream; see samrs_png_encode_labels
+        in samrs_hip.h."""
+        m = maps.reshape(-1, maps.shape[-2], maps.shape[-1]).contiguous()
+        n, h, w = m.shape
+        assert m.dtype == torch.uint8 and m.is_cuda
+        assert lut.dtype == torch.uint8 and lut.is_cuda and lut.is_contiguous() and lut.numel() == 768
+        assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and out.data_ptr() % 16 == 0
+        assert cursor.dtype == torch.int64 and cursor.is_cuda and table.dtype == torch.int64 and table.is_cuda
+        assert table.is_contiguous() and table.numel() >= 4 * n
+        with torch.cuda.device(self.device):
+            self._check(self.lib.samrs_png_encode_labels(self.handle, m.data_ptr(), n, h, w, lut.data_ptr(), out.data_ptr(),
+                                                         out.numel(), cursor.data_ptr(), table.data_ptr(), _stream()))
 
     def select_best(self, masks: torch.Tensor, iou: torch.Tensor, best_out: Optional[torch.Tensor] = None,
                     quality_out: Optional[torch.Tensor] = None, areas_out: Optional[torch.Tensor] = None):

@@ -58,9 +58,12 @@ class StageClock:
 
 def write_outputs(out_dir: str, stem: str, seg: np.ndarray, masks: Optional[np.ndarray], boxes: np.ndarray,
                   labels: np.ndarray, areas: np.ndarray, palette: np.ndarray, class_names: Sequence[str],
-                  rles: Optional[Sequence[dict]] = None, clock: Optional[StageClock] = None, png_level: int = tile_io.LEVEL_LABELS) -> None:
+                  rles: Optional[Sequence[dict]] = None, clock: Optional[StageClock] = None, png_level: int = tile_io.LEVEL_LABELS,
+                  png_files: Optional[Tuple[bytes, bytes]] = None) -> None:
     """`rles`: the per-instance COCO RLE dicts when they were encoded on the device (driver.TileResult.rle); otherwise they are
-    encoded here from `masks` (host restatement), or left out when both are None (--no-rle)."""
+    encoded here from `masks` (host restatement), or left out when both are None (--no-rle).  `png_files`: the complete
+    (gray, color) PNG files when they were encoded on the device (--png-device: driver.TileResult.png, byte-identical with the
+    LEVEL_LABELS encoder); they are written as they are and `seg` / `png_level` are not used for them."""
     import time
     t0 = time.perf_counter()
     for sub in ("gray", "color", "ins"):
@@ -70,7 +73,12 @@ def write_outputs(out_dir: str, stem: str, seg: np.ndarray, masks: Optional[np.n
     # png_level: LEVEL_LABELS (default) = the label-aware encoder for both images -- the colour image IS the class map seen through
     # the palette, so its deflate tokens are derived from the 1-byte map (4x less CPU than zlib on the RGB bytes); 1..9 = zlib for
     # color/*.png (and the run-length preset for gray/*.png), kept for A/B runs.  The decoded pixels never depend on it.
-    if png_level == tile_io.LEVEL_LABELS:
+    if png_files is not None:
+        # encoded on the device: the host only writes the bytes (same tmp + rename as the native encoder)
+        for sub, data in zip(("gray", "color"), png_files):
+            _write_atomic(os.path.join(out_dir, sub, stem + ".png"), data)
+        if clock: t0 = clock.add("write.gray_color_png", t0)
+    elif png_level == tile_io.LEVEL_LABELS:
         # one parse of the label runs, two deflate streams (:212-215)
         tile_io.write_label_pair(os.path.join(out_dir, "gray", stem + ".png"), os.path.join(out_dir, "color", stem + ".png"), seg,
                                  tile_io.class_lut(palette))
@@ -96,6 +104,18 @@ def write_outputs(out_dir: str, stem: str, seg: np.ndarray, masks: Optional[np.n
     if clock: clock.add("write.pickle", t0)
 
 
+def _write_atomic(path: str, data) -> None:
+    tmp = f"{path}.tmp.{os.getpid()}"                  # per process, as libsamrs_io's writers: never a half-written final file
+    try:
+        with open(tmp, "wb") as f:
+            f.write(data)
+        os.replace(tmp, path)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        raise
+
+
 def host_cpu_budget(local_world: Optional[int] = None) -> float:
     """CPUs THIS rank may keep busy: the container's share (cgroup v2 ``cpu.max``, else the affinity mask) divided by the ranks on
     this node (``LOCAL_WORLD_SIZE``, set by torchrun).  On the pool's GPU boxes a container is a 16-CPU slice of 256 hardware
@@ -112,31 +132,46 @@ def host_cpu_budget(local_world: Optional[int] = None) -> float:
     return max(1.0, cpus / max(1, local_world))
 
 
-def io_threads(readers: int = 0, writers: int = 0, local_world: Optional[int] = None) -> Tuple[int, int]:
+def io_threads(readers: int = 0, writers: int = 0, local_world: Optional[int] = None, png_device: bool = False) -> Tuple[int, int]:
     """(reader threads, writer threads); 0 = sized from :func:`host_cpu_budget`.  Per image the host pays ~6 ms of decode and
     ~14 ms of encode + pickle, so a third of the budget reads and the rest writes; the caps (8 / 16) are what
-    one rank at 140 images/s can use, the floor (2 / 2) keeps decode and encode overlapped with each other and with the GPU loop."""
+    one rank at 140 images/s can use, the floor (2 / 2) keeps decode and encode overlapped with each other and with the GPU loop.
+    png_device (--png-device): the PNG files come encoded from the device and a writer only writes bytes + the pickle, so the
+    readers get the share decode takes of HOST_MS_PER_IMAGE_PNG_DEVICE."""
     budget = int(host_cpu_budget(local_world))
+    if png_device:
+        share = int(round(budget * READ_MS_PER_IMAGE / HOST_MS_PER_IMAGE_PNG_DEVICE))
+        r = readers if readers > 0 else min(8, max(2, share))
+        w = writers if writers > 0 else min(16, max(2, budget - min(8, max(2, share))))
+        return r, w
     r = readers if readers > 0 else min(8, max(2, budget // 3))
     w = writers if writers > 0 else min(16, max(2, budget - min(8, max(2, budget // 3))))
     return r, w
 
 
 HOST_MS_PER_IMAGE = 20.7       # host thread time per image of this driver: read.decode 5.9 + write.gray_color_png 11.7 + pickle 2.7 + rle 0.4 (BENCH_r04 cli_inclusive)
+READ_MS_PER_IMAGE = 5.9        # read.decode of the same measurement
+# the same with --png-device: 20.7 - 11.7 + 1.0, write.gray_color_png = 0.9 - 1.1 ms when the writer only writes the device's bytes
+# (tools/png_device_bench.py under a 2-CPU affinity mask, one rank's share of 16 CPUs: 15.2 - 15.6 ms for the host encoder in the same runs)
+HOST_MS_PER_IMAGE_PNG_DEVICE = 10.0
 
 
-def host_bound_warning(readers: int, writers: int, gpu_images_per_s: float = 140.0, local_world: Optional[int] = None) -> Optional[str]:
+def host_bound_warning(readers: int, writers: int, gpu_images_per_s: float = 140.0, local_world: Optional[int] = None,
+                       png_device: bool = False) -> Optional[str]:
     """A sentence for the operator when this rank's share of the host cannot keep up with its GPU (VERDICT r04 "what's weak" 11):
     a rank that produces ``gpu_images_per_s`` needs ``gpu_images_per_s x 20.7 ms`` = ~2.9 busy CPUs for decode + encode + pickle; on a
-    16-CPU container shared by eight ranks it has two.  None when the budget suffices and the pools fit it."""
+    16-CPU container shared by eight ranks it has two.  None when the budget suffices and the pools fit it.  png_device
+    (--png-device): the host cost per image is HOST_MS_PER_IMAGE_PNG_DEVICE instead."""
+    host_ms = HOST_MS_PER_IMAGE_PNG_DEVICE if png_device else HOST_MS_PER_IMAGE
     budget = host_cpu_budget(local_world)
-    need = gpu_images_per_s * HOST_MS_PER_IMAGE * 1e-3
+    need = gpu_images_per_s * host_ms * 1e-3
     msgs = []
     if readers + writers > budget + 1e-9 and budget < need:
         msgs.append(f"{readers} reader + {writers} writer threads on a share of {budget:.1f} CPUs")
     if budget < need:
-        msgs.append(f"this rank is HOST-bound at ~{budget / (HOST_MS_PER_IMAGE * 1e-3):.0f} images/s (its GPU loop does ~{gpu_images_per_s:.0f}): "
-                    f"decode + PNG encode + pickle cost {HOST_MS_PER_IMAGE:.1f} ms of host thread time per image = {need:.1f} busy CPUs; "
+        msgs.append(f"this rank is HOST-bound at ~{budget / (host_ms * 1e-3):.0f} images/s (its GPU loop does ~{gpu_images_per_s:.0f}): "
+                    f"decode + PNG {'write' if png_device else 'encode'} + pickle cost {host_ms:.1f} ms of host thread time per image = "
+                    f"{need:.1f} busy CPUs; "
                     "give the job more CPUs per rank, or run fewer ranks per container")
     return "; ".join(msgs) if msgs else None
 
@@ -242,9 +277,12 @@ def run(args) -> Dict[str, List[int]]:
     old_pix, old_ins, old_sizes = resumed_statistics(args.out, done_before[rank::world], n_classes)
     max_boxes = max([len(ann[s]["labels"]) for s in stems] + [1])
     # per-instance RLE (main_sam_hbox_semantic.py:201-202) is encoded on the device; the full masks never cross PCIe
+    # --png-device: gray/ and color/ files encoded on the device (samrs_png_encode_labels); the host writes their bytes
+    png_device = bool(getattr(args, "png_device", False))
     pipe = driver.TilePipeline(sam, n_classes, batch=batch, box_batch=args.box_batch, rle=not args.no_rle,
                                rle_buffer_mb=getattr(args, "rle_buffer_mb", 256), max_boxes=max_boxes,
-                               out_depth=getattr(args, "out_depth", 4))
+                               out_depth=getattr(args, "out_depth", 4), png_lut=tile_io.class_lut(palette) if png_device else None,
+                               png_buffer_mb=getattr(args, "png_buffer_mb", None))
     # rank r takes chunks of `batch` consecutive stems: statically (r, r + world, ...) or from the shared counter (whose
     # store key must be unique per work list: a second run() in the same process group must not find a spent counter)
     import zlib
@@ -254,8 +292,8 @@ def run(args) -> Dict[str, List[int]]:
 
     import time
     tile_io.load_library()                                  # fail here, not on a worker thread, when libsamrs_io.so is missing
-    n_readers, n_writers = io_threads(getattr(args, "readers", 0) or 0, getattr(args, "writers", 0) or 0)
-    warn = host_bound_warning(n_readers, n_writers)
+    n_readers, n_writers = io_threads(getattr(args, "readers", 0) or 0, getattr(args, "writers", 0) or 0, png_device=png_device)
+    warn = host_bound_warning(n_readers, n_writers, png_device=png_device)
     if warn:
         import sys
         print(f"[rank {rank}] warning: {warn}", file=sys.stderr, flush=True)
@@ -335,7 +373,8 @@ def run(args) -> Dict[str, List[int]]:
                 t0 = time.perf_counter()
                 rles = [r.rle(j) for j in range(len(r.labels))] if r.rle_table is not None else None
                 if clock: clock.add("write.rle_dicts", t0)
-                write_outputs(args.out, r.key, r.seg_mask, None, r.boxes, r.labels, r.areas, palette, names, rles, clock, png_level)
+                files = (r.png("gray"), r.png("color")) if r.png_table is not None else None
+                write_outputs(args.out, r.key, r.seg_mask, None, r.boxes, r.labels, r.areas, palette, names, rles, clock, png_level, files)
             finally:
                 with lock:
                     left[0] -= 1
@@ -401,7 +440,7 @@ def run(args) -> Dict[str, List[int]]:
     return stats
 
 
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="SAM box -> semantic label generation (SAMRS) on MI355X")
     ap.add_argument("--images", required=True)
     ap.add_argument("--boxes", required=True)
@@ -436,7 +475,16 @@ def main(argv=None):
     ap.add_argument("--log", "--run-log", dest="log", default=None, help="append one JSON line per batch (time, image stems, box counts) "
                     "to this file (<file>.rank<r> with more than one rank); spell it --run-log under torchrun")
     ap.add_argument("--timing", action="store_true", help="print the host-side time per stage (decode, PNG encode, pickle, waits)")
-    run(ap.parse_args(argv))
+    ap.add_argument("--png-device", action="store_true",
+                    help="encode gray/*.png and color/*.png on the GPU (byte-identical with the default label-aware host encoder); "
+                         "the host only writes the files' bytes")
+    ap.add_argument("--png-buffer-mb", type=int, default=None,
+                    help="device buffer for one batch's PNG files with --png-device (default: 6 MiB per tile of --batch)")
+    return ap
+
+
+def main(argv=None):
+    run(build_parser().parse_args(argv))
 
 
 if __name__ == "__main__":
