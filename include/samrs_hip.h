@@ -143,6 +143,26 @@ int samrs_predict(samrs_engine_t* e, int slot, int n_prompts,
                   int in_h, int in_w, int orig_h, int orig_w,
                   void* masks_out, float* iou_out, float* lowres_out, void* stream);
 
+/* Several images' prompts in one decoder chain (same outputs as one samrs_predict per image, fewer launches).
+ *  n_images       >= 1; slots, prompt_offsets, in_hw, orig_hw and masks_out are HOST arrays read before the call returns
+ *  slots          [n_images] embedding slots, all set; they may repeat and come in any order
+ *  prompt_offsets [n_images + 1], prompt_offsets[0] = 0, non-decreasing: image i's prompts are rows
+ *                 [prompt_offsets[i], prompt_offsets[i + 1]) of boxes / point_coords / point_labels / mask_input (the
+ *                 layouts of samrs_predict); an image may have none.  The prompt kind (which arrays are present, n_points)
+ *                 is the same for every image of a call.
+ *  in_hw, orig_hw [n_images][2] input / original size (h, w) of each image
+ *  masks_out      [n_images] device pointers, each [n_i, C, orig_h_i, orig_w_i] (uint8, or fp32 with return_logits), or
+ *                 NULL (the array or an entry) to skip
+ *  iou_out [total, C] / lowres_out [total, C, 256, 256]: contiguous over all prompts of the call, or NULL
+ * Validation is that of samrs_predict for every image (SAMRS_ERR_NOT_SET names the slot; the multimask grade is checked per
+ * slot).  Calls larger than max_prompts run as consecutive chunks that may cross image boundaries; every output byte equals
+ * what samrs_predict(slots[i], ...) gives for image i alone. */
+int samrs_predict_multi(samrs_engine_t* e, int n_images, const int* slots, const int* prompt_offsets,
+                        const float* boxes, const float* point_coords, const int32_t* point_labels, int n_points,
+                        const float* mask_input, int multimask, int return_logits,
+                        const int* in_hw, const int* orig_hw, void* const* masks_out, float* iou_out, float* lowres_out,
+                        void* stream);
+
 /* -- "next row" N1: ordered painting + areas + class statistics on device --------------------
  * replaces the host loop of main_sam_hbox_semantic.py:195-206 and the sums of
  * statistic.py:15-21.  masks: uint8 [n,orig_h,orig_w] (the C = 1 output of samrs_predict),

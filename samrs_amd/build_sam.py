@@ -13,12 +13,28 @@ from __future__ import annotations
 
 import os
 from types import SimpleNamespace
-from typing import Dict, Optional
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import torch
 
 from .engine import Engine
 from .synth import CONFIGS, SamConfig, make_state_dict
+
+
+def prompt_signature(record: Dict[str, Any]) -> Tuple[bool, int, bool, bool]:
+    """(points?, points per prompt, boxes?, mask_inputs?) of one ``Sam.forward`` record: the prompt kind that one
+    samrs_predict_multi call must share."""
+    pts = record.get("point_coords")
+    return (pts is not None, int(pts.shape[1]) if pts is not None and pts.dim() == 3 else 0,
+            record.get("boxes") is not None, record.get("mask_inputs") is not None)
+
+
+def group_by_signature(records: Sequence[Dict[str, Any]]) -> List[Tuple[Tuple[bool, int, bool, bool], List[int]]]:
+    """Record indices grouped by prompt signature, groups in order of first appearance, indices ascending."""
+    groups: Dict[Tuple[bool, int, bool, bool], List[int]] = {}
+    for i, r in enumerate(records):
+        groups.setdefault(prompt_signature(r), []).append(i)
+    return list(groups.items())
 
 
 class Sam:
@@ -68,6 +84,59 @@ class Sam:
         self.default_split = self.engine.get_option("split")
         self._device = device
         return self
+
+    @torch.no_grad()
+    def forward(self, batched_input: List[Dict[str, Any]], multimask_output: bool) -> List[Dict[str, torch.Tensor]]:
+        """The reference's batched entry point (modeling/sam.py:53-131): per record an ``image`` (3xHxW, long side img_size,
+        integer values 0..255), its ``original_size`` and optional ``point_coords`` / ``point_labels``, ``boxes``,
+        ``mask_inputs`` in the input frame -> per record {"masks" bool [B, C, H, W], "iou_predictions" [B, C],
+        "low_res_logits" [B, C, 256, 256]}, in input order.
+
+        Images are encoded in chunks that fit embedding slots 1 .. max_images - 1 (slot 0 belongs to ``SamPredictor``, whose
+        answers do not change across this call); the records of a chunk that share a prompt kind are decoded in one
+        ``Engine.predict_multi`` call."""
+        if self.engine is None:
+            raise RuntimeError("move the model to a HIP device first: sam.to(device='cuda'); samrs_amd has no CPU path")
+        slots = self.max_images - 1
+        if slots < 1:
+            raise RuntimeError(f"Sam.forward encodes into embedding slots 1 .. max_images - 1, and this model was built with "
+                               f"max_images={self.max_images}; pass max_images >= 2 to sam_model_registry[...]")
+        s = self.image_encoder.img_size
+        tiles = []
+        for i, r in enumerate(batched_input):
+            img = r["image"]
+            assert img.dim() == 3 and img.shape[0] == 3 and max(*img.shape[1:]) == s, \
+                f"batched_input[{i}]['image'] must be 3xHxW with long side {s}, got {tuple(img.shape)}"
+            t = img.to(self.device)
+            if t.is_floating_point():
+                assert bool((t == t.round()).all()) and float(t.min()) >= 0 and float(t.max()) <= 255, \
+                    "Sam.forward needs integer pixel values in 0..255 (the engine takes uint8 tiles)"
+            tiles.append(t.permute(1, 2, 0).round().clamp(0, 255).to(torch.uint8).contiguous())
+            if "point_coords" in r and r.get("point_labels") is None:
+                raise AssertionError("point_labels must be supplied if point_coords is supplied.")
+            if prompt_signature(r) == (False, 0, False, False):
+                raise AssertionError(f"batched_input[{i}]: at least one prompt (points, boxes or mask_inputs) is required")
+        eng = self.engine
+        outputs: List[Optional[Dict[str, torch.Tensor]]] = [None] * len(batched_input)
+        for c0 in range(0, len(batched_input), slots):
+            idx = list(range(c0, min(c0 + slots, len(batched_input))))
+            eng.set_images_ragged([tiles[i] for i in idx], slot0=1)
+            for _, members in group_by_signature([batched_input[i] for i in idx]):
+                recs = [batched_input[idx[j]] for j in members]
+                cat = lambda key: None if recs[0].get(key) is None else torch.cat([r[key].to(self.device) for r in recs])
+                boxes = None if recs[0].get("boxes") is None else cat("boxes").reshape(-1, 4)
+                counts = [int(r["boxes"].numel() // 4) if r.get("boxes") is not None else
+                          int(r["point_coords"].shape[0]) if r.get("point_coords") is not None else int(r["mask_inputs"].shape[0])
+                          for r in recs]
+                masks, iou, low = eng.predict_multi(
+                    [1 + j for j in members], counts, boxes, cat("point_coords"), cat("point_labels"), cat("mask_inputs"),
+                    multimask_output, False,
+                    [tuple(tiles[idx[j]].shape[:2]) for j in members], [tuple(int(v) for v in r["original_size"]) for r in recs])
+                for k, j in enumerate(members):
+                    outputs[idx[j]] = {"masks": masks[k], "iou_predictions": iou[k], "low_res_logits": low[k]}
+        return outputs
+
+    __call__ = forward
 
     def cuda(self, index: Optional[int] = None) -> "Sam":
         return self.to(torch.device("cuda", index) if index is not None else "cuda")

@@ -137,14 +137,27 @@ __global__ __launch_bounds__(256) void mask_embed_kernel(MaskEmbedParams p, cons
     }
 }
 
+// per-prompt slot table (samrs_predict_multi): block k writes out[p] = slot[k] for the prompts p of run k
+constexpr int SLOT_RUNS_MAX = 64;
+struct SlotRuns {
+    int start[SLOT_RUNS_MAX + 1];
+    int slot[SLOT_RUNS_MAX];
+};
+__global__ void fill_slot_table_kernel(SlotRuns r, int* __restrict__ out) {
+    const int k = blockIdx.x;
+    for (int p = r.start[k] + threadIdx.x; p < r.start[k + 1]; p += blockDim.x) out[p] = r.slot[k];
+}
+
 template <int PREC>
-__global__ void make_keys_kernel(const float* __restrict__ emb, const float* __restrict__ dense,
-                                 const float* __restrict__ vec, float* __restrict__ out_f32,
+__global__ void make_keys_kernel(const float* __restrict__ emb, const int* __restrict__ slot_of,
+                                 const float* __restrict__ dense, const float* __restrict__ vec, float* __restrict__ out_f32,
                                  uint16_t* __restrict__ out_et, long per_batch4, long total4, int C4) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total4) return;
     const long r = i % per_batch4;
-    float4 e = reinterpret_cast<const float4*>(emb)[r];
+    // slot table (samrs_predict_multi): batch b reads the embedding of slot slot_of[b]; without it, one shared embedding
+    const long eo = slot_of ? (long)slot_of[i / per_batch4] * per_batch4 : 0;
+    float4 e = reinterpret_cast<const float4*>(emb)[eo + r];
     const float4 d = dense ? reinterpret_cast<const float4*>(dense)[i] : reinterpret_cast<const float4*>(vec)[r % C4];
     e.x += d.x; e.y += d.y; e.z += d.z; e.w += d.w;
     reinterpret_cast<float4*>(out_f32)[i] = e;
@@ -224,7 +237,7 @@ constexpr float T2I_NEG = -1.0e30f;  // finite "-inf": exp2(NEG - NEG) = 1 with 
 template <int PREC>
 __global__ __launch_bounds__(256, 2) void t2i_partial_kernel(const float* __restrict__ qp, const uint16_t* __restrict__ kp,
                                                           const uint16_t* __restrict__ vp, int ld, long bstride,
-                                                          float* __restrict__ part, int T, int tokens, int Ci, int kpw) {
+                                                          const int* __restrict__ slot_of, float* __restrict__ part, int T, int tokens, int Ci, int kpw) {
     __shared__ float sm[4][T2I_TG][16][T2I_REC];
     const int split = blockIdx.x, b = blockIdx.y, t0 = blockIdx.z * T2I_TG;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -244,8 +257,9 @@ __global__ __launch_bounds__(256, 2) void t2i_partial_kernel(const float* __rest
     }
     const int kbeg = (split * 4 + wave) * kpw;
     const int kend = kbeg + kpw < tokens ? kbeg + kpw : tokens;
-    const uint16_t* kb = kp + (size_t)b * bstride * ld + ch * 8;
-    const uint16_t* vb = vp + (size_t)b * bstride * ld + ch * 8;
+    const int kbat = slot_of ? slot_of[b] : b;      // slot table: prompt b's keys are those of its image's slot
+    const uint16_t* kb = kp + (size_t)kbat * bstride * ld + ch * 8;
+    const uint16_t* vb = vp + (size_t)kbat * bstride * ld + ch * 8;
     constexpr int U = 2;    // key groups (of 4 keys) per iteration; the next iteration's loads are already in flight
     uint4 kk[U], vv[U], kn[U], vn[U];
 #define T2I_LOAD(dk_, dv_, k0_)                                                                  \
@@ -451,7 +465,7 @@ constexpr int I2TF_AST = 136;          // A-tile row stride (ET): 272 B = 68 wor
 
 template <int PREC, bool SPLIT>
 __global__ __launch_bounds__(256, 2) void i2t_fused_kernel(const uint16_t* __restrict__ qi, int ld, long q_bstride,
-                                                        const float* __restrict__ kt, const float* __restrict__ vt,
+                                                        const int* __restrict__ slot_of, const float* __restrict__ kt, const float* __restrict__ vt,
                                                         const uint16_t* __restrict__ w, const uint16_t* __restrict__ w_lo,
                                                         const float* __restrict__ bias,
                                                         const float* __restrict__ resid, long r_bstride,
@@ -490,7 +504,8 @@ __global__ __launch_bounds__(256, 2) void i2t_fused_kernel(const uint16_t* __res
     const int tr = tid >> 3, h = tid & 7;                     // attention role: token-in-group, head
     const int g0 = blockIdx.x * groups_per_block;
     // this thread's query slice of the NEXT group is loaded while the current group is projected / normalised
-    const uint16_t* qbase = qi + (size_t)b * q_bstride * ld + (size_t)tr * ld + h * HD;
+    const int ib = slot_of ? slot_of[b] : b;        // slot table: image-side rows (query, residual) of prompt b's slot
+    const uint16_t* qbase = qi + (size_t)ib * q_bstride * ld + (size_t)tr * ld + h * HD;
     uint4 q0 = make_uint4(0u, 0u, 0u, 0u), q1 = q0;
     if (g0 * I2TF_ROWS < tokens) {
         q0 = *reinterpret_cast<const uint4*>(qbase + (size_t)g0 * I2TF_ROWS * ld);
@@ -505,7 +520,7 @@ __global__ __launch_bounds__(256, 2) void i2t_fused_kernel(const uint16_t* __res
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                rs[mt][i] = *reinterpret_cast<const float4*>(resid + ((size_t)b * r_bstride + row0 + mt * 16 + fr) * CO + wave * 64 + i * 16 + 4 * fq);
+                rs[mt][i] = *reinterpret_cast<const float4*>(resid + ((size_t)ib * r_bstride + row0 + mt * 16 + fr) * CO + wave * 64 + i * 16 + 4 * fq);
         // ---- attention of (token tr, head h) over the T prompt tokens ------------------------------------------
         {
             const uint32_t qw[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
@@ -1285,14 +1300,24 @@ hipError_t launch_mask_embed(const MaskEmbedParams& p, const float* mask_in, flo
     mask_embed_kernel<<<g, 256, 0, s>>>(p, mask_in, dense, grid);
     return hipGetLastError();
 }
+hipError_t launch_fill_slot_table(const int* start, const int* slot, int n_runs, int* out, hipStream_t s) {
+    for (int k0 = 0; k0 < n_runs; k0 += SLOT_RUNS_MAX) {
+        SlotRuns r{};
+        const int nr = n_runs - k0 < SLOT_RUNS_MAX ? n_runs - k0 : SLOT_RUNS_MAX;
+        for (int k = 0; k < nr; ++k) { r.start[k] = start[k0 + k]; r.slot[k] = slot[k0 + k]; }
+        r.start[nr] = start[k0 + nr];
+        fill_slot_table_kernel<<<nr, 64, 0, s>>>(r, out);
+    }
+    return hipGetLastError();
+}
 hipError_t launch_make_keys(int prec, const float* emb, const float* dense, const float* vec, float* out_f32,
-                            void* out_et, int n_batches, int tokens, int C, hipStream_t s) {
+                            void* out_et, int n_batches, int tokens, int C, hipStream_t s, const int* slot_of) {
     const long per4 = (long)tokens * C / 4, tot4 = per4 * n_batches;
     const int blocks = (int)((tot4 + 255) / 256);
     if (prec == PREC_BF16)
-        make_keys_kernel<PREC_BF16><<<blocks, 256, 0, s>>>(emb, dense, vec, out_f32, (uint16_t*)out_et, per4, tot4, C / 4);
+        make_keys_kernel<PREC_BF16><<<blocks, 256, 0, s>>>(emb, slot_of, dense, vec, out_f32, (uint16_t*)out_et, per4, tot4, C / 4);
     else
-        make_keys_kernel<PREC_F16><<<blocks, 256, 0, s>>>(emb, dense, vec, out_f32, (uint16_t*)out_et, per4, tot4, C / 4);
+        make_keys_kernel<PREC_F16><<<blocks, 256, 0, s>>>(emb, slot_of, dense, vec, out_f32, (uint16_t*)out_et, per4, tot4, C / 4);
     return hipGetLastError();
 }
 hipError_t launch_add_f32(const float* a, const float* b, float* out, long n, hipStream_t s) {
@@ -1310,7 +1335,8 @@ size_t t2i_workspace_floats(int n, int T) {
     return (size_t)n * ((T + T2I_TG - 1) / T2I_TG) * T2I_MAX_SPLITS * (T2I_TG * 16) * T2I_REC;
 }
 hipError_t launch_t2i_attention(int prec, const float* qp, const void* kp, const void* vp, int ld, long bstride,
-                                float* o, float* workspace, int n, int T, int tokens, int Ci, int heads, hipStream_t s) {
+                                float* o, float* workspace, int n, int T, int tokens, int Ci, int heads, hipStream_t s,
+                                const int* slot_of) {
     if (Ci != 128 || heads != 8 || T > TOK_MAX || !workspace) return hipErrorInvalidValue;
     // keys per wave: a multiple of 16 (4 groups of 4 keys per iteration), at most T2I_MAX_SPLITS blocks of 4 waves
     int splits = (tokens + 255) / 256;
@@ -1320,8 +1346,8 @@ hipError_t launch_t2i_attention(int prec, const float* qp, const void* kp, const
     dim3 g(splits, n, tgs), b(256);
     const uint16_t* k = (const uint16_t*)kp;
     const uint16_t* v = (const uint16_t*)vp;
-    if (prec == PREC_BF16) t2i_partial_kernel<PREC_BF16><<<g, b, 0, s>>>(qp, k, v, ld, bstride, workspace, T, tokens, Ci, kpw);
-    else t2i_partial_kernel<PREC_F16><<<g, b, 0, s>>>(qp, k, v, ld, bstride, workspace, T, tokens, Ci, kpw);
+    if (prec == PREC_BF16) t2i_partial_kernel<PREC_BF16><<<g, b, 0, s>>>(qp, k, v, ld, bstride, slot_of, workspace, T, tokens, Ci, kpw);
+    else t2i_partial_kernel<PREC_F16><<<g, b, 0, s>>>(qp, k, v, ld, bstride, slot_of, workspace, T, tokens, Ci, kpw);
     t2i_merge_kernel<<<dim3(n, tgs), T2I_TG * 16, 0, s>>>(workspace, o, splits, T, Ci);
     return hipGetLastError();
 }
@@ -1340,7 +1366,7 @@ hipError_t launch_i2t_attention(int prec, const void* qi, int ld, long bstride, 
 hipError_t launch_i2t_fused(int prec, const void* qi, int ld, long q_bstride, const float* kt, const float* vt, const void* w,
                             const void* w_lo, const float* bias, const float* resid, long r_bstride, const float* gamma,
                             const float* beta, float eps, float* outF, void* outE, void* outE_lo, int n, int T, int tokens, int Ci,
-                            int C, hipStream_t s) {
+                            int C, hipStream_t s, const int* slot_of) {
     if (Ci != 128 || C != 256 || T < 1 || T > TOK_MAX || tokens % I2TF_ROWS) return hipErrorInvalidValue;
     const int groups = tokens / I2TF_ROWS;
     int gpb = 4;                                   // groups per block: W fragments (64 / 128 KB per block) are loaded once
@@ -1350,7 +1376,7 @@ hipError_t launch_i2t_fused(int prec, const void* qi, int ld, long q_bstride, co
     const size_t sh = (size_t)(2 * T * 8 * I2T_HS + 3 * 256 + 2 * 4 * I2TF_ROWS) * sizeof(float) +
                       (size_t)(split ? 2 : 1) * I2TF_ROWS * I2TF_AST * 2;
 #define I2TF_LAUNCH(P, S)                                                                                                       \
-    i2t_fused_kernel<P, S><<<g, b, sh, s>>>((const uint16_t*)qi, ld, q_bstride, kt, vt, (const uint16_t*)w, (const uint16_t*)w_lo, \
+    i2t_fused_kernel<P, S><<<g, b, sh, s>>>((const uint16_t*)qi, ld, q_bstride, slot_of, kt, vt, (const uint16_t*)w, (const uint16_t*)w_lo, \
                                            bias, resid, r_bstride, gamma, beta, eps, outF, (uint16_t*)outE, (uint16_t*)outE_lo, T, \
                                            tokens, gpb)
     if (prec == PREC_BF16) { if (split) I2TF_LAUNCH(PREC_BF16, true); else I2TF_LAUNCH(PREC_BF16, false); }

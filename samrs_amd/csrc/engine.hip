@@ -213,6 +213,7 @@ struct samrs_engine {
     uint16_t* KE = nullptr;
     uint16_t* KE_lo = nullptr;     // split remainder of the final keys (operand of the first transposed conv)
     float* DENSE = nullptr;        // mask-prompt dense embedding (allocated on first use)
+    int* SLOT_OF = nullptr;        // [Bb] slot of every prompt of a chunk that spans several images (samrs_predict_multi; first use)
     uint16_t* KVQ = nullptr;       // [Bb*tokens][384]
     uint16_t* OI = nullptr;        // [Bb*tokens][128]
     float* U1raw = nullptr;        // [Bb*tokens][256]
@@ -1287,68 +1288,140 @@ int samrs_reset_image(samrs_engine_t* e, int slot) {
 }
 
 // -------------------------------------------------------------------------------------------------
-static int predict_chunk(samrs_engine_t* e, int slot, int n, const float* boxes, const float* point_coords,
+// One image of a predict call: its slot, its prompt rows [p0, p1) of the call's prompt arrays, its sizes and its mask output
+// (row p0 of it).  A chunk of the call holds the parts ("segments") of one or more images, in prompt order.
+struct PredictImage {
+    int slot, p0, p1, in_h, in_w, orig_h, orig_w;
+    void* masks;
+};
+
+static int predict_chunk(samrs_engine_t* e, const PredictImage* seg, int n_seg, int n, const float* boxes, const float* point_coords,
                          const int32_t* point_labels, int n_points, const float* mask_input, int multimask,
-                         int return_logits, int in_h, int in_w, int orig_h, int orig_w, void* masks_out, float* iou_out,
-                         float* lowres_out, void* stream);
+                         int return_logits, float* iou_out, float* lowres_out, void* stream);
+
+// The three multimask tokens need more operand precision than token 0 (C4 fixtures at ViT-H: IoU 0.9983 - 0.9992 at the 1x
+// rate, >= 0.999 from the v-third split on).  The mode an image was encoded in travels with its slot, so a multimask
+// predict on an embedding some single-mask pipeline produced is refused instead of silently answering in that mode.
+static std::string slot_note(int slot) { return " (slot " + std::to_string(slot) + ")"; }
+
+static int check_multimask_grade(samrs_engine_t* e, int slot, bool multi) {
+    if (e->allow_reduced || !e->grade_multimask || slot < 0 || slot >= e->cfg.max_images || !e->slot_set[slot]) return SAMRS_OK;
+    const int sm = e->slot_split[slot];
+    // the depth the IoU >= 0.999 claim was measured at: every block for the full bits, the leading three quarters for the
+    // v-third form (the automatic depths of run_encoder); an embedding whose split reached fewer blocks ("split_depth" set by
+    // hand) is not multimask-grade either (round-4 advisor finding: the recorded depth was never consulted)
+    const int need_depth = sm < 0 ? 0 : (sm & (SPLIT_ATTN | SPLIT_MLP | SPLIT_LIN2)) ? e->cfg.depth : (3 * e->cfg.depth + 3) / 4;
+    if (sm >= 0 && (!(sm & e->grade_multimask) || e->slot_depth[slot] < need_depth ||
+                    (e->split & (SPLIT_OI | SPLIT_UP)) != (SPLIT_OI | SPLIT_UP)))
+        return fail(e, SAMRS_ERR_PRECISION, "multimask_output=True on an embedding encoded with split=%d over %d of %d blocks (decoder split=%d): "
+                    "this model's multimask outputs need a block-GEMM split bit (64 or 16) at its automatic depth and the decoder "
+                    "bits 4 | 8 to hold IoU >= 0.999; re-encode the image in the engine's default mode, or set option "
+                    "\"allow_reduced\" = 1%s", sm, e->slot_depth[slot], need_depth, e->split, multi ? slot_note(slot).c_str() : "");
+    return SAMRS_OK;
+}
+
+// The checks of one call, before anything is launched (so a refused call leaves no partial output behind).
+static int check_predict(samrs_engine_t* e, const PredictImage* im, int n_img, bool multi, const float* boxes, const float* point_coords,
+                         const int32_t* point_labels, int n_points, const float* mask_input) {
+    if (!e->finalized) return fail(e, SAMRS_ERR_BAD_WEIGHTS, "weights not finalized");
+    const samrs_config& c = e->cfg;
+    for (int i = 0; i < n_img; ++i) {
+        const int slot = im[i].slot;
+        if (slot < 0 || slot >= c.max_images)
+            return multi ? fail(e, SAMRS_ERR_CAPACITY, "image %d: slot %d out of range (max_images=%d)", i, slot, c.max_images)
+                         : fail(e, SAMRS_ERR_CAPACITY, "slot out of range");
+        if (!e->slot_set[slot])
+            return multi ? fail(e, SAMRS_ERR_NOT_SET, "An image must be set with .set_image(...) before mask prediction "
+                                "(image %d: slot %d is not set).", i, slot)
+                         : fail(e, SAMRS_ERR_NOT_SET, "An image must be set with .set_image(...) before mask prediction.");
+    }
+    if (!boxes && !point_coords && !mask_input) return fail(e, SAMRS_ERR_BAD_ARG, "at least one prompt (points, boxes or mask_input) is required");
+    if (point_coords && !point_labels) return fail(e, SAMRS_ERR_BAD_ARG, "point_labels must be supplied if point_coords is supplied.");
+    if (point_coords && (n_points < 1 || n_points > c.max_points)) return fail(e, SAMRS_ERR_CAPACITY, "n_points=%d exceeds max_points=%d", n_points, c.max_points);
+    for (int i = 0; i < n_img; ++i)
+        if (im[i].in_h < 1 || im[i].in_w < 1 || im[i].in_h > c.img_size || im[i].in_w > c.img_size || im[i].orig_h < 1 || im[i].orig_w < 1)
+            return multi ? fail(e, SAMRS_ERR_BAD_SHAPE, "image %d: bad input/original size", i) : fail(e, SAMRS_ERR_BAD_SHAPE, "bad input/original size");
+    return SAMRS_OK;
+}
 
 // The reference takes any number of prompts per call (its instance drivers pass every object of an image at once,
 // main_sam_rbox_mask_instance.py:159-164).  The engine's workspaces hold max_prompts prompts, so a larger call is
 // run as consecutive chunks of max_prompts on the same stream, each writing its slice of the caller's buffers;
-// results do not depend on the chunking (no cross-prompt arithmetic, no atomics anywhere on the path).
-int samrs_predict(samrs_engine_t* e, int slot, int n, const float* boxes, const float* point_coords,
-                  const int32_t* point_labels, int n_points, const float* mask_input, int multimask,
-                  int return_logits, int in_h, int in_w, int orig_h, int orig_w, void* masks_out, float* iou_out,
-                  float* lowres_out, void* stream) {
-    if (!e) return SAMRS_ERR_BAD_ARG;
-    if (n < 1) return fail(e, SAMRS_ERR_BAD_ARG, "n_prompts must be >= 1");
-    // The three multimask tokens need more operand precision than token 0 (C4 fixtures at ViT-H: IoU 0.9983 - 0.9992 at the 1x
-    // rate, >= 0.999 from the v-third split on).  The mode an image was encoded in travels with its slot, so a multimask
-    // predict on an embedding some single-mask pipeline produced is refused instead of silently answering in that mode.
-    if (multimask && !e->allow_reduced && e->grade_multimask && slot >= 0 && slot < e->cfg.max_images && e->slot_set[slot]) {
-        const int sm = e->slot_split[slot];
-        // the depth the IoU >= 0.999 claim was measured at: every block for the full bits, the leading three quarters for the
-        // v-third form (the automatic depths of run_encoder); an embedding whose split reached fewer blocks ("split_depth" set by
-        // hand) is not multimask-grade either (round-4 advisor finding: the recorded depth was never consulted)
-        const int need_depth = sm < 0 ? 0 : (sm & (SPLIT_ATTN | SPLIT_MLP | SPLIT_LIN2)) ? e->cfg.depth : (3 * e->cfg.depth + 3) / 4;
-        if (sm >= 0 && (!(sm & e->grade_multimask) || e->slot_depth[slot] < need_depth ||
-                        (e->split & (SPLIT_OI | SPLIT_UP)) != (SPLIT_OI | SPLIT_UP)))
-            return fail(e, SAMRS_ERR_PRECISION, "multimask_output=True on an embedding encoded with split=%d over %d of %d blocks (decoder split=%d): "
-                        "this model's multimask outputs need a block-GEMM split bit (64 or 16) at its automatic depth and the decoder "
-                        "bits 4 | 8 to hold IoU >= 0.999; re-encode the image in the engine's default mode, or set option "
-                        "\"allow_reduced\" = 1", sm, e->slot_depth[slot], need_depth, e->split);
-    }
+// results do not depend on the chunking (no cross-prompt arithmetic, no atomics anywhere on the path).  A chunk may
+// span several images (samrs_predict_multi): every prompt reads its own image's slot, nothing else changes.
+static int predict_images(samrs_engine_t* e, const PredictImage* im, int n_img, const float* boxes, const float* point_coords,
+                          const int32_t* point_labels, int n_points, const float* mask_input, int multimask, int return_logits,
+                          float* iou_out, float* lowres_out, void* stream) {
     const int cap = e->cfg.max_prompts;
     const size_t nsel = multimask ? 3 : 1;
-    const size_t mask_stride = nsel * (size_t)(orig_h > 0 ? orig_h : 0) * (size_t)(orig_w > 0 ? orig_w : 0) * (return_logits ? 4 : 1);
     const int np = point_coords ? n_points : 0;
+    const int n = n_img ? im[n_img - 1].p1 : 0;
+    std::vector<PredictImage> seg;
+    int first = 0;                                          // first image that still has prompts at `off`
     for (int off = 0; off < n; off += cap) {
         const int m = (n - off) < cap ? (n - off) : cap;
+        seg.clear();
+        for (int i = first; i < n_img && im[i].p0 < off + m; ++i) {
+            const int a = im[i].p0 > off ? im[i].p0 : off, b = im[i].p1 < off + m ? im[i].p1 : off + m;
+            if (b <= a) continue;
+            PredictImage sgm = im[i];
+            const size_t mask_stride = nsel * (size_t)im[i].orig_h * (size_t)im[i].orig_w * (return_logits ? 4 : 1);
+            sgm.p0 = a - off; sgm.p1 = b - off;
+            sgm.masks = im[i].masks ? (void*)((unsigned char*)im[i].masks + (size_t)(a - im[i].p0) * mask_stride) : nullptr;
+            seg.push_back(sgm);
+        }
+        while (first < n_img && im[first].p1 <= off + m) ++first;
         const int rc = predict_chunk(
-            e, slot, m, boxes ? boxes + (size_t)off * 4 : nullptr, point_coords ? point_coords + (size_t)off * np * 2 : nullptr,
-            point_labels ? point_labels + (size_t)off * np : nullptr, n_points,
-            mask_input ? mask_input + (size_t)off * 256 * 256 : nullptr, multimask, return_logits, in_h, in_w, orig_h, orig_w,
-            masks_out ? (void*)((unsigned char*)masks_out + (size_t)off * mask_stride) : nullptr,
+            e, seg.data(), (int)seg.size(), m, boxes ? boxes + (size_t)off * 4 : nullptr,
+            point_coords ? point_coords + (size_t)off * np * 2 : nullptr, point_labels ? point_labels + (size_t)off * np : nullptr,
+            n_points, mask_input ? mask_input + (size_t)off * 256 * 256 : nullptr, multimask, return_logits,
             iou_out ? iou_out + (size_t)off * nsel : nullptr, lowres_out ? lowres_out + (size_t)off * nsel * 256 * 256 : nullptr, stream);
         if (rc) return rc;
     }
     return SAMRS_OK;
 }
 
-static int predict_chunk(samrs_engine_t* e, int slot, int n, const float* boxes, const float* point_coords,
+int samrs_predict(samrs_engine_t* e, int slot, int n, const float* boxes, const float* point_coords,
+                  const int32_t* point_labels, int n_points, const float* mask_input, int multimask,
+                  int return_logits, int in_h, int in_w, int orig_h, int orig_w, void* masks_out, float* iou_out,
+                  float* lowres_out, void* stream) {
+    if (!e) return SAMRS_ERR_BAD_ARG;
+    if (n < 1) return fail(e, SAMRS_ERR_BAD_ARG, "n_prompts must be >= 1");
+    if (multimask) { const int rc = check_multimask_grade(e, slot, false); if (rc != SAMRS_OK) return rc; }
+    const PredictImage im{slot, 0, n, in_h, in_w, orig_h, orig_w, masks_out};
+    { const int rc = check_predict(e, &im, 1, false, boxes, point_coords, point_labels, n_points, mask_input); if (rc != SAMRS_OK) return rc; }
+    return predict_images(e, &im, 1, boxes, point_coords, point_labels, n_points, mask_input, multimask, return_logits, iou_out,
+                          lowres_out, stream);
+}
+
+int samrs_predict_multi(samrs_engine_t* e, int n_images, const int* slots, const int* prompt_offsets, const float* boxes,
+                        const float* point_coords, const int32_t* point_labels, int n_points, const float* mask_input, int multimask,
+                        int return_logits, const int* in_hw, const int* orig_hw, void* const* masks_out, float* iou_out,
+                        float* lowres_out, void* stream) {
+    if (!e) return SAMRS_ERR_BAD_ARG;
+    if (n_images < 1 || !slots || !prompt_offsets || !in_hw || !orig_hw)
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_predict_multi: n_images must be >= 1 and slots, prompt_offsets, in_hw, orig_hw non-null");
+    if (prompt_offsets[0] != 0) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_predict_multi: prompt_offsets[0] must be 0, got %d", prompt_offsets[0]);
+    std::vector<PredictImage> im((size_t)n_images);
+    for (int i = 0; i < n_images; ++i) {
+        if (prompt_offsets[i + 1] < prompt_offsets[i])
+            return fail(e, SAMRS_ERR_BAD_ARG, "samrs_predict_multi: prompt_offsets must not decrease (image %d: %d -> %d)", i,
+                        prompt_offsets[i], prompt_offsets[i + 1]);
+        im[i] = PredictImage{slots[i], prompt_offsets[i], prompt_offsets[i + 1], in_hw[2 * i], in_hw[2 * i + 1], orig_hw[2 * i],
+                             orig_hw[2 * i + 1], masks_out ? masks_out[i] : nullptr};
+    }
+    if (multimask)
+        for (int i = 0; i < n_images; ++i) { const int rc = check_multimask_grade(e, slots[i], true); if (rc != SAMRS_OK) return rc; }
+    { const int rc = check_predict(e, im.data(), n_images, true, boxes, point_coords, point_labels, n_points, mask_input); if (rc != SAMRS_OK) return rc; }
+    return predict_images(e, im.data(), n_images, boxes, point_coords, point_labels, n_points, mask_input, multimask, return_logits,
+                          iou_out, lowres_out, stream);
+}
+
+static int predict_chunk(samrs_engine_t* e, const PredictImage* seg, int n_seg, int n, const float* boxes, const float* point_coords,
                          const int32_t* point_labels, int n_points, const float* mask_input, int multimask,
-                         int return_logits, int in_h, int in_w, int orig_h, int orig_w, void* masks_out, float* iou_out,
-                         float* lowres_out, void* stream) {
-    if (!e->finalized) return fail(e, SAMRS_ERR_BAD_WEIGHTS, "weights not finalized");
+                         int return_logits, float* iou_out, float* lowres_out, void* stream) {
     const samrs_config& c = e->cfg;
-    if (slot < 0 || slot >= c.max_images) return fail(e, SAMRS_ERR_CAPACITY, "slot out of range");
-    if (!e->slot_set[slot]) return fail(e, SAMRS_ERR_NOT_SET, "An image must be set with .set_image(...) before mask prediction.");
     if (n < 1 || n > c.max_prompts) return fail(e, SAMRS_ERR_CAPACITY, "n_prompts=%d exceeds max_prompts=%d", n, c.max_prompts);
-    if (!boxes && !point_coords && !mask_input) return fail(e, SAMRS_ERR_BAD_ARG, "at least one prompt (points, boxes or mask_input) is required");
-    if (point_coords && !point_labels) return fail(e, SAMRS_ERR_BAD_ARG, "point_labels must be supplied if point_coords is supplied.");
-    if (point_coords && (n_points < 1 || n_points > c.max_points)) return fail(e, SAMRS_ERR_CAPACITY, "n_points=%d exceeds max_points=%d", n_points, c.max_points);
-    if (in_h < 1 || in_w < 1 || in_h > c.img_size || in_w > c.img_size || orig_h < 1 || orig_w < 1)
-        return fail(e, SAMRS_ERR_BAD_SHAPE, "bad input/original size");
     hipStream_t s = (hipStream_t)stream;
     ON_DEVICE(e);
     const int C = e->C, Ci = C / 2, tokens = e->tokens, prec = e->prec, g = e->grid;
@@ -1380,11 +1453,23 @@ static int predict_chunk(samrs_engine_t* e, int slot, int n, const float* boxes,
     pp.mask_tokens = W(e, "mask_decoder.mask_tokens.weight");
     CK(e, launch_prompt_tokens(pp, e->TOK0, e->Q, T, s));       // tokens and (a copy) the initial queries
 
-    const float* emb = e->EMB + (size_t)slot * tokens * C;
     const bool shared0 = (mask_input == nullptr);
-    // layer-0 image side of this slot (prepare_slot_keys, at set_image time)
-    const float* k0f = e->K0F + (size_t)slot * tokens * C;
-    const uint16_t* kvq0 = e->KVQ0 + (size_t)slot * tokens * 3 * Ci;
+    // image side: one image -> its slot's rows with batch stride 0, as for every single-image call; several images ->
+    // the per-prompt slot table, and the slot stores with a stride of one slot (only the addressing differs)
+    const int* slot_tab = nullptr;
+    const size_t slot0 = n_seg == 1 ? (size_t)seg[0].slot : 0;
+    if (n_seg > 1) {
+        if (!e->SLOT_OF) CK(e, dalloc(e, &e->SLOT_OF, (size_t)c.max_prompts));
+        std::vector<int> start((size_t)n_seg + 1), slot((size_t)n_seg);
+        for (int k = 0; k < n_seg; ++k) { start[k] = seg[k].p0; slot[k] = seg[k].slot; }
+        start[n_seg] = seg[n_seg - 1].p1;
+        CK(e, launch_fill_slot_table(start.data(), slot.data(), n_seg, e->SLOT_OF, s));
+        slot_tab = e->SLOT_OF;
+    }
+    const float* emb = e->EMB + slot0 * tokens * C;
+    // layer-0 image side of the slot(s) (prepare_slot_keys, at set_image time)
+    const float* k0f = e->K0F + slot0 * tokens * C;
+    const uint16_t* kvq0 = e->KVQ0 + slot0 * tokens * 3 * Ci;
     if (!shared0) {
         if (!e->DENSE) CK(e, dalloc(e, &e->DENSE, (size_t)c.max_prompts * tokens * C));
         MaskEmbedParams mp{W(e, "prompt_encoder.mask_downscaling.0.weight"), W(e, "prompt_encoder.mask_downscaling.0.bias"),
@@ -1393,7 +1478,7 @@ static int predict_chunk(samrs_engine_t* e, int slot, int n, const float* boxes,
                            W(e, "prompt_encoder.mask_downscaling.4.weight"), W(e, "prompt_encoder.mask_downscaling.4.bias"),
                            W(e, "prompt_encoder.mask_downscaling.6.weight"), W(e, "prompt_encoder.mask_downscaling.6.bias")};
         CK(e, launch_mask_embed(mp, mask_input, e->DENSE, n, g, s));
-        CK(e, launch_make_keys(prec, emb, e->DENSE, nullptr, e->KF, e->KE, n, tokens, C, s));
+        CK(e, launch_make_keys(prec, emb, e->DENSE, nullptr, e->KF, e->KE, n, tokens, C, s, slot_tab));
     }
 
     // ---- two-way transformer (transformer.py:62-106,151-182) ----
@@ -1413,12 +1498,13 @@ static int predict_chunk(samrs_engine_t* e, int slot, int n, const float* boxes,
         CK(e, lin(e->TO, C, L.self.ow, L.self.ob, e->Q, C, BT, C, C, false, li > 0));
         CK(e, ln_tok(L.n1w, L.n1b));
         // image-side projections for this layer: K_t2i | V_t2i | Q_i2t  (PE folded in as add2d)
-        const long bstride = sh ? 0 : tokens;
+        const long bstride = sh && !slot_tab ? 0 : tokens;     // with the slot table: a stride of one slot
+        const int* tab = sh ? slot_tab : nullptr;
         const uint16_t* kvq = sh ? kvq0 : e->KVQ;
         if (!sh) CK(e, launch_gemm_et(prec, e->KE, L.kvq_w, e->KVQ, L.kvq_b, L.kvq_pe, tokens, Mi, 3 * Ci, C, false, false, false, s));
         // (2) tokens -> image
         CK(e, lin2(e->Q, e->TOK0, C, L.t2i.qw, L.t2i.qb, e->QP, Ci, BT, Ci, C));
-        CK(e, launch_t2i_attention(prec, e->QP, kvq, kvq + Ci, 3 * Ci, bstride, e->O128, e->T2IW, n, T, tokens, Ci, 8, s));
+        CK(e, launch_t2i_attention(prec, e->QP, kvq, kvq + Ci, 3 * Ci, bstride, e->O128, e->T2IW, n, T, tokens, Ci, 8, s, tab));
         CK(e, lin(e->O128, Ci, L.t2i.ow, L.t2i.ob, e->Q, C, BT, C, Ci, false, true));
         CK(e, ln_tok(L.n2w, L.n2b));
         // (3) MLP (ReLU)
@@ -1441,8 +1527,18 @@ static int predict_chunk(samrs_engine_t* e, int slot, int n, const float* boxes,
             // remainder of the final keys for the first transposed conv
             CK(e, launch_i2t_fused(prec, kvq + 2 * Ci, 3 * Ci, bstride, e->KT, e->VT, L.i2t_ow,
                                    (e->split & SPLIT_OI) ? L.i2t_ow_lo : nullptr, L.i2t.ob, sh ? k0f : e->KF,
-                                   sh ? 0 : tokens, L.n4w, L.n4b, 1e-5f, li == 1 ? nullptr : e->KF, e->KE,
-                                   (li == 1 && (e->split & SPLIT_UP)) ? e->KE_lo : nullptr, n, T, tokens, Ci, C, s));
+                                   bstride, L.n4w, L.n4b, 1e-5f, li == 1 ? nullptr : e->KF, e->KE,
+                                   (li == 1 && (e->split & SPLIT_UP)) ? e->KE_lo : nullptr, n, T, tokens, Ci, C, s, tab));
+        } else if (tab) {
+            // small test geometries only (tokens % 32 != 0) or decoder_fusion = 0: the shared layer 0 once per image segment
+            for (int k = 0; k < n_seg; ++k) {
+                const size_t p0 = (size_t)seg[k].p0, ns = (size_t)(seg[k].p1 - seg[k].p0), sl = (size_t)seg[k].slot;
+                CK(e, launch_i2t_attention(prec, e->KVQ0 + sl * tokens * 3 * Ci + 2 * Ci, 3 * Ci, 0, e->KT + p0 * T * Ci,
+                                           e->VT + p0 * T * Ci, e->OI + p0 * tokens * Ci, (int)ns, T, tokens, Ci, 8, s));
+                CK(e, launch_gemm_et(prec, e->OI + p0 * tokens * Ci, L.i2t_ow, e->KF + p0 * tokens * C, L.i2t.ob,
+                                     e->K0F + sl * tokens * C, tokens, (int)ns * tokens, C, Ci, true, false, false, s));
+            }
+            CK(e, launch_layernorm(prec, e->KF, L.n4w, L.n4b, 1e-5f, e->KE, e->KF, Mi, C, 0, g, 0, s));
         } else {
             CK(e, launch_i2t_attention(prec, kvq + 2 * Ci, 3 * Ci, bstride, e->KT, e->VT, e->OI, n, T, tokens, Ci, 8, s));
             if (sh)
@@ -1518,8 +1614,11 @@ static int predict_chunk(samrs_engine_t* e, int slot, int n, const float* boxes,
         CK(e, launch_mask_product(prec, e->U2, e->HYPER, low, n, g, 4, sel0, nsel, s));
     }
     // ---- postprocess (sam.py:133-162) + threshold (predictor.py:242-243) ----
-    if (masks_out)
-        CK(e, launch_postprocess(low, n * nsel, in_h, in_w, orig_h, orig_w, c.img_size, return_logits, masks_out, s));
+    // one launch per image segment: sizes and output buffer are the image's
+    for (int k = 0; k < n_seg; ++k)
+        if (seg[k].masks)
+            CK(e, launch_postprocess(low + (size_t)seg[k].p0 * nsel * 256 * 256, (seg[k].p1 - seg[k].p0) * nsel, seg[k].in_h, seg[k].in_w,
+                                     seg[k].orig_h, seg[k].orig_w, c.img_size, return_logits, seg[k].masks, s));
     return SAMRS_OK;
 }
 

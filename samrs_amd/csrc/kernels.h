@@ -134,18 +134,24 @@ struct MaskEmbedParams {
 };
 hipError_t launch_mask_embed(const MaskEmbedParams& p, const float* mask_in, float* dense, int n, int grid, hipStream_t s);
 // out_f32[b, t, :] = emb[t, :] + (dense ? dense[b, t, :] : vec[:]) and its ET copy
+// (slot_of: emb[slot_of[b], t, :] instead, emb then being the [slots][tokens][C] embedding store)
+// per-prompt slot table on the stream: out[p] = slot[k] for p in [start[k], start[k + 1]), k < n_runs (host arrays,
+// passed by value in the kernel arguments, so nothing reads them after the call returns)
+hipError_t launch_fill_slot_table(const int* start, const int* slot, int n_runs, int* out, hipStream_t s);
 hipError_t launch_make_keys(int prec, const float* emb, const float* dense, const float* vec, float* out_f32,
-                            void* out_et, int n_batches, int tokens, int C, hipStream_t s);
+                            void* out_et, int n_batches, int tokens, int C, hipStream_t s, const int* slot_of = nullptr);
 hipError_t launch_add_f32(const float* a, const float* b, float* out, long n, hipStream_t s);
 // token self attention: q,k,v [n*T, C] -> o [n*T, C]; heads of dim C/heads
 hipError_t launch_token_self_attn(const float* q, const float* k, const float* v, float* o, int n, int T, int C,
                                   int heads, hipStream_t s);
 // tokens -> image attention. qp [n*T, Ci] fp32; kp/vp ET rows of `ld` elements, batch stride in rows
-// (0 = shared by all prompts); o [n*T, Ci] fp32.
+// (0 = shared by all prompts); o [n*T, Ci] fp32.  slot_of (device int [n], optional): prompt b reads the rows of batch
+// slot_of[b] instead of batch b -- the layer-0 keys of several images' slots in one launch (samrs_predict_multi).
 constexpr int T2I_MAX_SPLITS = 16;
 size_t t2i_workspace_floats(int n_prompts, int T);     // scratch for the per-split partial softmax states
 hipError_t launch_t2i_attention(int prec, const float* qp, const void* kp, const void* vp, int ld, long batch_stride_rows,
-                                float* out, float* workspace, int n, int T, int tokens, int Ci, int heads, hipStream_t s);
+                                float* out, float* workspace, int n, int T, int tokens, int Ci, int heads, hipStream_t s,
+                                const int* slot_of = nullptr);
 // image -> tokens attention. qi ET rows of `ld` elements (batch stride in rows, 0 = shared);
 // kt, vt [n*T, Ci] fp32; out ET [n*tokens, Ci].
 hipError_t launch_i2t_attention(int prec, const void* qi, int ld, long batch_stride_rows, const float* kt,
@@ -178,10 +184,12 @@ hipError_t launch_rbox_prompt(const int32_t* pts, int n, int nv, int h, int w, i
                               float* out, hipStream_t s,
                               int fill_rule = 0 /* 0: OpenCV <= 4.5.1 spans (ceil .. floor), 1: OpenCV >= 4.5.2 (round .. round) */);
 // fused transformer.py:176-181: keys = LayerNorm(resid + out_proj(attention(q_i2t, k_tokens, v_tokens))) -> outF (fp32) and outE (ET)
+// slot_of: as in launch_t2i_attention, for the query side and the residual (q_bstride / r_bstride then stride slots)
 hipError_t launch_i2t_fused(int prec, const void* qi, int ld, long q_bstride, const float* kt, const float* vt, const void* w,
                             const void* w_lo /* null: un-split out-projection */, const float* bias, const float* resid,
                             long r_bstride, const float* gamma, const float* beta, float eps, float* outF, void* outE,
-                            void* outE_lo /* optional split remainder of outE */, int n, int T, int tokens, int Ci, int C, hipStream_t s);
+                            void* outE_lo /* optional split remainder of outE */, int n, int T, int tokens, int Ci, int C, hipStream_t s,
+                            const int* slot_of = nullptr);
 
 // ---- gemm.hip: operand split with the two correction terms on MXFP4 operands (gemm_et_mx_kernel) ------------------------------
 // C = A B^T (f16 segment, K) + A4lo B4hi^T + A4hi B4lo^T (block-scaled fp4 segments over the padded K axis Kp) + bias.

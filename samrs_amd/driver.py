@@ -390,7 +390,7 @@ class TilePipeline:
     def __init__(self, sam, n_classes: int, batch: int = 8, box_batch: int = 20, keep_masks: bool = False,
                  out_depth: int = 3, max_boxes: int = 512, device_inputs: bool = False, rle: bool = False,
                  rle_buffer_mb: int = 256, precision="auto", _multimask: bool = False, png_lut: Optional[np.ndarray] = None,
-                 png_buffer_mb: Optional[int] = None):
+                 png_buffer_mb: Optional[int] = None, batch_decode: bool = False):
         """precision: the operand-split mode (engine option "split") THIS PIPELINE'S OWN CALLS run in.  The option is set around
         each of the pipeline's encode / decode calls and restored afterwards (``Engine.options``), so the mode never outlives
         them: a ``SamPredictor`` built on the same model keeps the engine's own default (round 3 changed the engine's option for
@@ -402,7 +402,10 @@ class TilePipeline:
         hi + lo operands (split 79: what the three multimask tokens need for IoU >= 0.999, C4 fixtures; 0.90x the throughput).
         An explicit choice -- builder ``options={"split": ...}`` or SAMRS_SPLIT -- is never overridden.
         "engine" = the engine's option as it stands at each call; an int = that mode (and, for a multimask pipeline, the
-        caller's consent to run its multimask predicts in it: option "allow_reduced")."""
+        caller's consent to run its multimask predicts in it: option "allow_reduced").
+        batch_decode: decode the prompts of every tile of a batch in one ``Engine.predict_multi`` call (one decoder chain per
+        batch instead of one per tile and box chunk); painting, RLE and PNG encoding then run per tile as before, and every
+        output is the same byte for byte."""
         from .transforms import ResizeLongestSide
         eng = sam.engine
         if eng is None:
@@ -424,6 +427,7 @@ class TilePipeline:
         self.sam, self.eng, self.dev = sam, eng, eng.device
         self.batch, self.box_batch, self.keep_masks, self.max_boxes = batch, box_batch, keep_masks, max_boxes
         self.rle = rle
+        self.batch_decode = bool(batch_decode)
         self.png = png_lut is not None
         self.side = sam.cfg.img_size
         self.transform = ResizeLongestSide(sam.image_encoder.img_size)
@@ -557,16 +561,36 @@ class TilePipeline:
             self.ev_enc[b].record(self.s_enc)
             self.ev_in_free[b].record(self.s_enc)
 
-    def _decode_tile(self, b: int, i: int, tile, hw, off: int, nb: int, out: _OutBuf) -> None:
-        """Everything the reference does per image after set_image (main_sam_hbox_semantic.py:157-206), on s_dec."""
+    multimask = False
+
+    def _tile_prompts(self, b: int, tile, hw, off: int, nb: int):
+        """(boxes, point_coords, point_labels, mask_input) of a tile's nb prompts, as _decode_tile issues them per chunk."""
+        in_size = (int(tile.shape[0]), int(tile.shape[1]))
+        return self._input_frame_boxes(self.dev_box[b][off:off + nb], hw, in_size), None, None, None
+
+    def _decode_multi(self, b: int, tiles, offs):
+        """batch_decode: the prompts of every tile of batch b in one predict_multi call -> per tile (masks, iou)."""
+        per = [self._tile_prompts(b, t, hw, off, nb) for (t, hw), (off, nb) in zip(tiles, offs)]
+        args = [None if per[0][j] is None else torch.cat([p[j] for p in per]) for j in range(4)]
+        masks, iou, _ = self.eng.predict_multi([b * self.batch + i for i in range(len(tiles))], [nb for _, nb in offs], *args,
+                                               self.multimask, False, [(int(t.shape[0]), int(t.shape[1])) for t, _ in tiles],
+                                               [tuple(hw) for _, hw in tiles])
+        return list(zip(masks, iou))
+
+    def _decode_tile(self, b: int, i: int, tile, hw, off: int, nb: int, out: _OutBuf, pre=None) -> None:
+        """Everything the reference does per image after set_image (main_sam_hbox_semantic.py:157-206), on s_dec.  pre: the
+        tile's (masks, iou) from _decode_multi (batch_decode), or None to predict here, chunk by chunk."""
         eng, (H, W) = self.eng, hw
         in_size = (int(tile.shape[0]), int(tile.shape[1]))
         native = (H, W) == (self.side, self.side)
         seg = self.seg_dev[b][i] if native else torch.full((H, W), 255, dtype=torch.uint8, device=self.dev)
         kept = []
         for s, e in box_chunks(nb, self.box_batch):                          # :157-181
-            tb = self._input_frame_boxes(self.dev_box[b][off + s:off + e], (H, W), in_size)   # :174
-            masks, _, _ = eng.predict(b * self.batch + i, tb, None, None, None, False, False, in_size, (H, W))
+            if pre is not None:
+                masks = pre[0][s:e]
+            else:
+                tb = self._input_frame_boxes(self.dev_box[b][off + s:off + e], (H, W), in_size)   # :174
+                masks, _, _ = eng.predict(b * self.batch + i, tb, None, None, None, False, False, in_size, (H, W))
             eng.paint(masks[:, 0], self.dev_lab[b][off + s:off + e], seg, self.class_pixels, self.class_instances,
                       areas_out=self.area_dev[b][i, s:e])
             if self.rle:                                                          # :201-202, on the device
@@ -599,8 +623,9 @@ class TilePipeline:
             if self.png:
                 self.png_cur[b].zero_()
             with self._mode():
+                pre = self._decode_multi(b, tiles, offs) if self.batch_decode and sum(nb for _, nb in offs) else None
                 for i, ((t, hw), (off, nb)) in enumerate(zip(tiles, offs)):
-                    self._decode_tile(b, i, t, hw, off, nb, out)
+                    self._decode_tile(b, i, t, hw, off, nb, out, None if pre is None else pre[i])
             if self.png:
                 self._encode_png(b, tiles)
             out.areas.copy_(self.area_dev[b], non_blocking=True)
@@ -856,7 +881,21 @@ class InstancePipeline(TilePipeline):
                 self.gt_rle_cur[b].zero_()
         super()._decode(b, items, tiles, offs, out)
 
-    def _decode_tile(self, b, i, tile, hw, off, nb, out) -> None:
+    def _tile_prompts(self, b: int, tile, hw, off: int, nb: int):
+        from . import transforms
+        in_size = (int(tile.shape[0]), int(tile.shape[1]))
+        ann = self.dev_box[b][off:off + nb]
+        if self.prompt == "box":
+            polys = ann.view(-1, 4, 2)
+            return self._input_frame_boxes(torch.cat([polys.amin(1), polys.amax(1)], dim=1), hw, in_size), None, None, None
+        if self.prompt == "rbox_mask":
+            side = 4 * self.sam.cfg.grid
+            pr = (transforms.rbox_mask_prompts_device(ann.view(-1, 4, 2), hw, self.side, device=self.dev, fill_rule=self.fill_rule)
+                  if nb else torch.empty(0, side, side, dtype=torch.float32, device=self.dev))
+            return None, None, None, pr[:, None]
+        return None, ann.view(-1, 1, 2), torch.ones(nb, 1, dtype=torch.int32, device=self.dev), None
+
+    def _decode_tile(self, b, i, tile, hw, off, nb, out, pre=None) -> None:
         from . import transforms
         eng, (H, W) = self.eng, hw
         in_size = (int(tile.shape[0]), int(tile.shape[1]))
@@ -866,7 +905,9 @@ class InstancePipeline(TilePipeline):
             self.s_dec.wait_event(self.ev_gt[b])
         for s, e in box_chunks(nb, self.box_batch):
             ann = self.dev_box[b][off + s:off + e]
-            if self.prompt == "box":
+            if pre is not None:
+                m, q = pre[0][s:e], pre[1][s:e]
+            elif self.prompt == "box":
                 polys = ann.view(-1, 4, 2)
                 hb = torch.cat([polys.amin(1), polys.amax(1)], dim=1)                                   # :125-130
                 m, q, _ = eng.predict(slot, self._input_frame_boxes(hb, (H, W), in_size), None, None, None, mm, False, in_size, (H, W))

@@ -9,7 +9,7 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import os
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -43,6 +43,12 @@ class samrs_config(C.Structure):
 
 _lib = None
 
+# samrs_predict_multi(e, n_images, slots, prompt_offsets, boxes, point_coords, point_labels, n_points, mask_input, multimask,
+#                     return_logits, in_hw, orig_hw, masks_out, iou_out, lowres_out, stream)
+PREDICT_MULTI_ARGTYPES = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                          C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.c_void_p,
+                          C.c_void_p, C.c_void_p]
+
 
 def load_library() -> C.CDLL:
     """Loads the in-tree shared library; raises if it has not been built (``__graft_entry__.build()``)."""
@@ -71,6 +77,7 @@ def load_library() -> C.CDLL:
     lib.samrs_set_embedding.argtypes = [vp, ip, vp, vp]
     lib.samrs_reset_image.argtypes = [vp, ip]
     lib.samrs_predict.argtypes = [vp, ip, ip, vp, vp, vp, ip, vp, ip, ip, ip, ip, ip, ip, vp, vp, vp, vp]
+    lib.samrs_predict_multi.argtypes = PREDICT_MULTI_ARGTYPES
     lib.samrs_paint.argtypes = [vp, vp, vp, ip, ip, ip, vp, vp, vp, vp, ip, vp]
     lib.samrs_debug_encoder_prefix.argtypes = [vp, vp, ip, ip, ip, ip, vp, vp]
     lib.samrs_debug_encoder_prefix.restype = ip
@@ -121,7 +128,7 @@ def load_library() -> C.CDLL:
         getattr(lib, name).restype = ip
     lib.samrs_get_slot_info.argtypes = [vp, ip, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     for name in ("samrs_load_weight", "samrs_finalize_weights", "samrs_set_images", "samrs_set_images_ragged", "samrs_get_embedding",
-                 "samrs_set_embedding", "samrs_reset_image", "samrs_predict", "samrs_paint", "samrs_k_gemm",
+                 "samrs_set_embedding", "samrs_reset_image", "samrs_predict", "samrs_predict_multi", "samrs_paint", "samrs_k_gemm",
                  "samrs_k_gemm_f32", "samrs_k_convert", "samrs_k_layernorm", "samrs_k_window_attention",
                  "samrs_k_global_attention", "samrs_k_postprocess", "samrs_k_gemm_gln", "samrs_k_upscale2_masks",
                  "samrs_k_gemm_stats", "samrs_k_gemm_fold", "samrs_k_ln_fold_weight", "samrs_k_rowstats_convert", "samrs_k_ln_rowstat",
@@ -144,6 +151,43 @@ def _stream() -> int:
 
 class EngineError(RuntimeError):
     pass
+
+
+def multi_call_args(slots: Sequence[int], counts: Sequence[int], input_sizes: Sequence[Sequence[int]],
+                    original_sizes: Sequence[Sequence[int]], n_rows: int) -> Tuple[List[int], List[int], List[int], List[int]]:
+    """Host-side checks of a predict_multi call (nothing touches the device): one slot, prompt count, input size and original
+    size per image, counts summing to the rows of the prompt tensors -> (slots, prompt_offsets, in_hw, orig_hw) flat lists."""
+    n_img = len(slots)
+    if n_img < 1:
+        raise ValueError("predict_multi needs at least one image")
+    if not (len(counts) == len(input_sizes) == len(original_sizes) == n_img):
+        raise ValueError(f"predict_multi: {n_img} slots but {len(counts)} prompt counts, {len(input_sizes)} input sizes and "
+                         f"{len(original_sizes)} original sizes")
+    offsets = [0]
+    for c in counts:
+        if int(c) < 0:
+            raise ValueError(f"predict_multi: negative prompt count {c}")
+        offsets.append(offsets[-1] + int(c))
+    if offsets[-1] != n_rows:
+        raise ValueError(f"predict_multi: the prompt counts sum to {offsets[-1]} but the prompt tensors have {n_rows} rows")
+    in_hw, orig_hw = [], []
+    for name, sizes, out in (("input", input_sizes, in_hw), ("original", original_sizes, orig_hw)):
+        for hw in sizes:
+            if len(hw) != 2:
+                raise ValueError(f"predict_multi: every {name} size must be (h, w), got {tuple(hw)}")
+            out.extend((int(hw[0]), int(hw[1])))
+    return [int(v) for v in slots], offsets, in_hw, orig_hw
+
+
+def _prompt_rows(boxes, point_coords, mask_input) -> Optional[int]:
+    """Batch size of a prompt batch as the shapes state it (None: no prompt), before any conversion."""
+    if point_coords is not None:
+        return int(point_coords.shape[0]) if point_coords.dim() == 3 else None
+    if boxes is not None:
+        return boxes.numel() // 4
+    if mask_input is not None:
+        return int(mask_input.shape[0])
+    return None
 
 
 class PrecisionError(EngineError):
@@ -315,10 +359,9 @@ class Engine:
     def reset_image(self, slot: int = 0) -> None:
         self._check(self.lib.samrs_reset_image(self.handle, slot))
 
-    def predict(self, slot: int, boxes: Optional[torch.Tensor], point_coords: Optional[torch.Tensor],
-                point_labels: Optional[torch.Tensor], mask_input: Optional[torch.Tensor], multimask_output: bool,
-                return_logits: bool, input_size: Tuple[int, int], original_size: Tuple[int, int],
-                want_masks: bool = True) -> Tuple[Optional[torch.Tensor], torch.Tensor, torch.Tensor]:
+    def _prompt_arrays(self, boxes, point_coords, point_labels, mask_input):
+        """The shape contract of one prompt batch -> (boxes, point_coords, point_labels, mask_input) as contiguous device
+        tensors of the library's types, and their common batch size."""
         dev = self.device
         f32 = dict(dtype=torch.float32, device=dev)
         if point_coords is not None and point_labels is None:
@@ -355,6 +398,15 @@ class Engine:
             n = int(mask_input.shape[0])
         if n is None:
             raise AssertionError("at least one prompt (points, boxes or mask_input) is required")
+        return boxes, point_coords, point_labels, mask_input, n
+
+    def predict(self, slot: int, boxes: Optional[torch.Tensor], point_coords: Optional[torch.Tensor],
+                point_labels: Optional[torch.Tensor], mask_input: Optional[torch.Tensor], multimask_output: bool,
+                return_logits: bool, input_size: Tuple[int, int], original_size: Tuple[int, int],
+                want_masks: bool = True) -> Tuple[Optional[torch.Tensor], torch.Tensor, torch.Tensor]:
+        dev = self.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        boxes, point_coords, point_labels, mask_input, n = self._prompt_arrays(boxes, point_coords, point_labels, mask_input)
         if n < 1:
             raise ValueError("empty prompt batch")
         npts = 0 if point_coords is None else point_coords.shape[1]
@@ -373,6 +425,42 @@ class Engine:
         if masks is not None and not return_logits:
             masks = masks.view(torch.bool)
         return masks, iou, low
+
+    def predict_multi(self, slots: Sequence[int], counts: Sequence[int], boxes: Optional[torch.Tensor],
+                      point_coords: Optional[torch.Tensor], point_labels: Optional[torch.Tensor], mask_input: Optional[torch.Tensor],
+                      multimask_output: bool, return_logits: bool, input_sizes: Sequence[Tuple[int, int]],
+                      original_sizes: Sequence[Tuple[int, int]], want_masks: bool = True):
+        """The prompts of several images in one decoder chain (samrs_predict_multi).  Image i (embedding slot ``slots[i]``;
+        slots may repeat) owns the next ``counts[i]`` rows of the prompt tensors, which have the layouts of :meth:`predict`
+        and one prompt kind for all images.  Returns per-image lists (masks [n_i, C, H_i, W_i] bool -- fp32 logits with
+        return_logits, None without want_masks --, iou [n_i, C], low-res logits [n_i, C, 256, 256]); entry i equals
+        ``predict(slots[i], <image i's rows>, ...)`` byte for byte."""
+        rows = _prompt_rows(boxes, point_coords, mask_input)
+        slots, offsets, in_hw, orig_hw = multi_call_args(slots, counts, input_sizes, original_sizes, rows if rows is not None else 0)
+        n_img, counts = len(slots), [offsets[i + 1] - offsets[i] for i in range(len(slots))]
+        boxes, point_coords, point_labels, mask_input, n = self._prompt_arrays(boxes, point_coords, point_labels, mask_input)
+        dev = self.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        npts = 0 if point_coords is None else point_coords.shape[1]
+        c = 3 if multimask_output else 1
+        masks = [None] * n_img
+        if want_masks:
+            masks = [torch.empty(counts[i], c, orig_hw[2 * i], orig_hw[2 * i + 1],
+                                 dtype=torch.float32 if return_logits else torch.uint8, device=dev) for i in range(n_img)]
+        iou = torch.empty(n, c, **f32)
+        low = torch.empty(n, c, 256, 256, **f32)
+        if n > 0:
+            ia = C.c_int * n_img
+            mptr = (C.c_void_p * n_img)(*[m.data_ptr() if m is not None and m.numel() else None for m in masks])
+            with torch.cuda.device(dev):
+                self._check(self.lib.samrs_predict_multi(
+                    self.handle, n_img, ia(*slots), (C.c_int * (n_img + 1))(*offsets), _ptr(boxes), _ptr(point_coords),
+                    _ptr(point_labels), npts, _ptr(mask_input), int(bool(multimask_output)), int(bool(return_logits)),
+                    (C.c_int * (2 * n_img))(*in_hw), (C.c_int * (2 * n_img))(*orig_hw), mptr, iou.data_ptr(), low.data_ptr(),
+                    _stream()))
+        if want_masks and not return_logits:
+            masks = [m.view(torch.bool) for m in masks]
+        return masks, list(torch.split(iou, counts)), list(torch.split(low, counts))
 
     def rle_encode(self, masks: torch.Tensor, out: torch.Tensor, cursor: torch.Tensor, table: torch.Tensor) -> None:
         """COCO RLE strings of `masks` ([n, H, W] bool / uint8 on this device) appended to the byte buffer `out` (uint8, device)

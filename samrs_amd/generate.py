@@ -282,7 +282,8 @@ def run(args) -> Dict[str, List[int]]:
     pipe = driver.TilePipeline(sam, n_classes, batch=batch, box_batch=args.box_batch, rle=not args.no_rle,
                                rle_buffer_mb=getattr(args, "rle_buffer_mb", 256), max_boxes=max_boxes,
                                out_depth=getattr(args, "out_depth", 4), png_lut=tile_io.class_lut(palette) if png_device else None,
-                               png_buffer_mb=getattr(args, "png_buffer_mb", None))
+                               png_buffer_mb=getattr(args, "png_buffer_mb", None),
+                               batch_decode=bool(getattr(args, "batch_decode", False)))
     # rank r takes chunks of `batch` consecutive stems: statically (r, r + world, ...) or from the shared counter (whose
     # store key must be unique per work list: a second run() in the same process group must not find a spent counter)
     import zlib
@@ -480,6 +481,8 @@ def build_parser() -> argparse.ArgumentParser:
                          "the host only writes the files' bytes")
     ap.add_argument("--png-buffer-mb", type=int, default=None,
                     help="device buffer for one batch's PNG files with --png-device (default: 6 MiB per tile of --batch)")
+    ap.add_argument("--batch-decode", action="store_true",
+                    help="decode the boxes of all tiles of a batch in one decoder chain (Engine.predict_multi); same outputs")
     return ap
 
 

@@ -254,7 +254,8 @@ def run(args) -> Optional[dict]:
     max_boxes = max([len(anns[s].colors) for s in stems] + [1])
     pipe = driver.InstancePipeline(sam, 1, prompt=args.prompt, multimask=multimask, fill_rule=getattr(args, "fill_rule", "auto"),
                                    gt=with_gt, batch=batch, box_batch=args.box_batch, max_boxes=max_boxes, rle=True,
-                                   rle_buffer_mb=getattr(args, "rle_buffer_mb", 256), keep_masks=False)
+                                   rle_buffer_mb=getattr(args, "rle_buffer_mb", 256), keep_masks=False,
+                                   batch_decode=bool(getattr(args, "batch_decode", False)))
     os.makedirs(os.path.join(args.out, "parts"), exist_ok=True)
     import zlib
     wq_name = "samrs_ins/%08x" % zlib.crc32(("\n".join(todo) + "|" + args.out).encode())
@@ -331,6 +332,8 @@ def main(argv=None):
     ap.add_argument("--rle-buffer-mb", type=int, default=256)
     ap.add_argument("--schedule", default="static", choices=["static", "dynamic"])
     ap.add_argument("--resume", action="store_true", help="skip images whose fragment OUT/parts/<stem>.json already exists")
+    ap.add_argument("--batch-decode", action="store_true",
+                    help="decode the prompts of all images of a batch in one decoder chain (Engine.predict_multi); same outputs")
     return run(ap.parse_args(argv))
 
 
