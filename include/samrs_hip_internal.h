@@ -34,7 +34,9 @@ void samrs_debug_set_gemm_skew(int xcd_units, int cu_units);
 int samrs_debug_has_experiments(void);
 
 /* -- test hook: copy a prefix of a named internal decoder buffer (Q, KF, KE, KVQ, OI, U1raw, U1, U2,
- * HYPER, ...) to a device buffer; used to localise run-to-run differences. */
+ * HYPER, TOK0, K0F, DENSE, ...) to a device buffer; used to localise run-to-run differences and by the stage-by-stage decoder
+ * test.  A buffer that does not exist yet (DENSE before the first mask prompt, any name before samrs_finalize_weights) is an
+ * error, not a copy from a null pointer. */
 int samrs_debug_copy_buffer(samrs_engine_t* e, const char* name, void* dst, size_t bytes, void* stream);
 
 /* -- measurement hook: when enabled, samrs_set_images brackets every launch of the dominant kernel
@@ -117,6 +119,51 @@ int samrs_k_upscale2_masks(int prec, const void* u1, const void* w_et, const voi
 int samrs_k_upscaler_fused(int prec, const void* keys_et, const void* keys_lo_et, const void* w1_et, const void* w1_lo_et,
                            const float* b1, const float* ln, const void* w2_et, const void* w2_lo_et, const float* b2,
                            const float* hyper, float* low, int n, int grid, int n_mask_tokens, int sel0, int n_sel, void* stream);
+/* -- prompt encoder and two-way transformer glue (decoder_kernels.hip), one kernel each; tests/test_decoder_kernels_gpu.py.
+ * None takes an engine handle: the weights arrive as pointers.  A shape the launcher does not cover returns non-zero with
+ * nothing launched.
+ *   samrs_k_prompt_tokens   tokens [n][T][256] (and the same bits to tokens2 when given) = iou token | 4 mask tokens | points
+ *                           (+ one pad point when there is no box) | 2 box corners; T = 5 + n_points (+ 1) (+ 2), checked.
+ *                           boxes [n][4] / point_coords [n][n_points][2] / point_labels int32 [n][n_points] (either group or both);
+ *                           gauss [2][128], point_emb [4][256], not_a_point / iou_token [256], mask_tokens [4][256].
+ *   samrs_k_dense_pe        pe [grid * grid][256]
+ *   samrs_k_mask_embed      mask_in [n][4 grid][4 grid] -> dense [n][grid * grid][256]; conv 2x2/2 (w0 [4][1][2][2]) + LN2d(4) + GELU,
+ *                           conv 2x2/2 (w3 [16][4][2][2]) + LN2d(16) + GELU, conv 1x1 (w6 [256][16]).  grid * grid % 16 == 0.
+ *   samrs_k_fill_slot_table out[p] = slot[k] for start[k] <= p < start[k + 1], k < n_runs; start / slot are HOST arrays
+ *   samrs_k_make_keys       out_f32 / out_et [n_batches][tokens][C] = emb[slot_of ? slot_of[b] : 0] + (dense ? dense[b] : vec[C])
+ *   samrs_k_token_self_attn q, k, v, o fp32 [n][T][C], head dim 32, T <= 16
+ *   samrs_k_t2i_attention   qp fp32 [n][T][128]; kp / vp ET rows of ld elements, batch bstride rows apart (slot_of: batch slot_of[b]);
+ *                           out fp32 [n][T][128]; workspace of samrs_k_t2i_workspace_floats(n, T) floats.  T <= 16.
+ *   samrs_k_i2t_attention   qi ET rows of ld elements (batch stride bstride rows); kt, vt fp32 [n][T][128]; out ET [n][tokens][128]
+ *   samrs_k_i2t_fused       LayerNorm(resid + out_proj(that attention)) -> outF fp32 (optional), outE, outE_lo (optional)
+ *                           [n][tokens][256]; w (w_lo: split) ET [256][128]; resid fp32 rows of 256, batch stride r_bstride rows;
+ *                           slot_of strides the query and the residual.  tokens % 32 == 0, 1 <= T <= 16.
+ *   samrs_k_group_ln_gelu   in fp32 [rows][4 * 64] -> LayerNorm per 64-group (gamma, beta [64]) + GELU -> out ET
+ *   samrs_k_mask_product    up2 ET [n * grid^2 * 16][32], hyper [n][n_mask_tokens][32] -> low [n][n_sel][4 grid][4 grid], n_sel <= 4 */
+int samrs_k_prompt_tokens(const float* boxes, const float* point_coords, const int32_t* point_labels, int n_prompts, int n_points,
+                          float img_size, const float* gauss, const float* point_emb, const float* not_a_point, const float* iou_token,
+                          const float* mask_tokens, float* tokens, float* tokens2, int T, void* stream);
+int samrs_k_dense_pe(const float* gauss, float* pe, int grid, void* stream);
+int samrs_k_mask_embed(const float* w0, const float* b0, const float* ln1w, const float* ln1b, const float* w3, const float* b3,
+                       const float* ln4w, const float* ln4b, const float* w6, const float* b6, const float* mask_in, float* dense,
+                       int n, int grid, void* stream);
+int samrs_k_fill_slot_table(const int32_t* start_host, const int32_t* slot_host, int n_runs, int32_t* out, void* stream);
+int samrs_k_make_keys(int prec, const float* emb, const float* dense, const float* vec, float* out_f32, void* out_et, int n_batches,
+                      int tokens, int C, const int32_t* slot_of, void* stream);
+int samrs_k_token_self_attn(const float* q, const float* k, const float* v, float* o, int n, int T, int C, int heads, void* stream);
+int64_t samrs_k_t2i_workspace_floats(int n, int T);
+int samrs_k_t2i_attention(int prec, const float* qp, const void* kp_et, const void* vp_et, int ld, int64_t bstride, float* out,
+                          float* workspace, int n, int T, int tokens, int Ci, int heads, const int32_t* slot_of, void* stream);
+int samrs_k_i2t_attention(int prec, const void* qi_et, int ld, int64_t bstride, const float* kt, const float* vt, void* out_et, int n,
+                          int T, int tokens, int Ci, int heads, void* stream);
+int samrs_k_i2t_fused(int prec, const void* qi_et, int ld, int64_t q_bstride, const float* kt, const float* vt, const void* w_et,
+                      const void* w_lo_et, const float* bias, const float* resid, int64_t r_bstride, const float* gamma,
+                      const float* beta, float eps, float* outF, void* outE, void* outE_lo, int n, int T, int tokens, int Ci, int C,
+                      const int32_t* slot_of, void* stream);
+int samrs_k_group_ln_gelu(int prec, const float* in, const float* gamma, const float* beta, float eps, void* out_et, int64_t rows,
+                          int groups, int gsize, void* stream);
+int samrs_k_mask_product(int prec, const void* up2_et, const float* hyper, float* low, int n, int grid, int n_mask_tokens, int sel0,
+                         int n_sel, void* stream);
 /* Operand split with the two correction terms on MXFP4 operands (gfx950 v_mfma_scale_f32_16x16x128_f8f6f4, e2m1 codes + one E8M0
  * scale per 32 k; option "lo_format" = 4):
  *   samrs_k_mx4_pack   x (fp32 [rows][K]) or the ET pair (hi_in, lo_in) -> fp4 codes of hi / lo, q_* [rows][Kp / 2] bytes, and their

@@ -343,8 +343,10 @@ def _ln(x: Tensor, sd: SD, name: str) -> Tensor:
 
 
 def two_way_transformer(sd: SD, cfg, src: Tensor, pos: Tensor, tokens: Tensor,
-                        rd: Rounding = _EXACT) -> Tuple[Tensor, Tensor]:
-    """transformer.py:62-106 (outer) and :151-182 (block).  src/pos [B,256,64,64], tokens [B,T,256]."""
+                        rd: Rounding = _EXACT, taps: Optional[dict] = None) -> Tuple[Tensor, Tensor]:
+    """transformer.py:62-106 (outer) and :151-182 (block).  src/pos [B,256,64,64], tokens [B,T,256].  ``taps`` (if given)
+    receives the queries [B,T,256] and keys [B,4096,256] after each layer ("queries{i}", "keys{i}") and the queries after
+    norm_final_attn ("queries_final")."""
     H = cfg.dec_heads
     keys = src.flatten(2).permute(0, 2, 1)
     kpe = pos.flatten(2).permute(0, 2, 1)
@@ -371,9 +373,14 @@ def two_way_transformer(sd: SD, cfg, src: Tensor, pos: Tensor, tokens: Tensor,
         o, _ = _dec_attn(sd, p + ".cross_attn_image_to_token", keys + kpe, queries + qpe, queries, H, rd.p("dec.keys"), ident,
                          oq=rd.p("dec.kvq_out"))
         keys = _ln(keys + _linear(o, sd, p + ".cross_attn_image_to_token.out_proj", rd.p("dec.oi")), sd, p + ".norm4")
+        if taps is not None:
+            taps[f"queries{i}"] = queries.clone()
+            taps[f"keys{i}"] = keys.clone()
     p = "mask_decoder.transformer.final_attn_token_to_image"                  # :98-104
     o, _ = _dec_attn(sd, p, queries + qpe, keys + kpe, keys, H, ident, rd.p("dec.keys"), ok=rd.p("dec.kvq_out"))
     queries = _ln(queries + _linear(o, sd, p + ".out_proj", ident), sd, "mask_decoder.transformer.norm_final_attn")
+    if taps is not None:
+        taps["queries_final"] = queries.clone()
     return queries, keys
 
 
@@ -385,15 +392,20 @@ def _mlp3(sd: SD, p: str, x: Tensor) -> Tensor:
 
 
 def mask_decoder(sd: SD, cfg, emb: Tensor, pos: Tensor, sparse: Tensor, dense: Tensor,
-                 multimask_output: bool, rd: Rounding = _EXACT) -> Tuple[Tensor, Tensor]:
-    """mask_decoder.py:71-174.  emb [1,256,64,64]; returns low-res [B,C,256,256], iou [B,C]."""
+                 multimask_output: bool, rd: Rounding = _EXACT, taps: Optional[dict] = None) -> Tuple[Tensor, Tensor]:
+    """mask_decoder.py:71-174.  emb [1,256,64,64]; returns low-res [B,C,256,256], iou [B,C].  ``taps`` (if given) receives the
+    prompt tokens [B,T,256] ("tokens"), the dense embedding [B,4096,256] in token order ("dense"), the transformer's taps and
+    the hypernetwork outputs [B,4,32] ("hyper")."""
     B = sparse.shape[0]
     out_tok = torch.cat([sd["mask_decoder.iou_token.weight"], sd["mask_decoder.mask_tokens.weight"]], dim=0)
     tokens = torch.cat([out_tok[None].expand(B, -1, -1), sparse], dim=1)      # :127-129
     src = emb.expand(B, -1, -1, -1) + dense                                   # :136-137
     pos_src = pos.expand(B, -1, -1, -1)
     b, c, h, w = src.shape
-    hs, keys = two_way_transformer(sd, cfg, src, pos_src, tokens, rd)
+    if taps is not None:
+        taps["tokens"] = tokens.clone()
+        taps["dense"] = dense.expand(B, -1, -1, -1).flatten(2).permute(0, 2, 1).clone()
+    hs, keys = two_way_transformer(sd, cfg, src, pos_src, tokens, rd, taps)
     iou_tok = hs[:, 0]
     mask_toks = hs[:, 1:1 + cfg.num_mask_tokens]
     up = keys.transpose(1, 2).reshape(b, c, h, w)
@@ -405,6 +417,8 @@ def mask_decoder(sd: SD, cfg, emb: Tensor, pos: Tensor, sparse: Tensor, dense: T
     up = F.gelu(up)
     hyper = torch.stack([_mlp3(sd, f"mask_decoder.output_hypernetworks_mlps.{i}", mask_toks[:, i])
                          for i in range(cfg.num_mask_tokens)], dim=1)         # :156-159
+    if taps is not None:
+        taps["hyper"] = hyper.clone()
     b, c, h, w = up.shape
     masks = (hyper @ rd.p("dec.prod")(up).reshape(b, c, h * w)).reshape(b, -1, h, w)      # :167
     iou = _mlp3(sd, "mask_decoder.iou_prediction_head", iou_tok)              # :172

@@ -1814,7 +1814,10 @@ int samrs_debug_copy_buffer(samrs_engine_t* e, const char* name, void* dst, size
     else if (n == "U1") src = e->U1; else if (n == "U2") src = e->U2; else if (n == "HYPER") src = e->HYPER;
     else if (n == "K0F") src = e->K0F; else if (n == "K0E") src = e->K0E; else if (n == "O128") src = e->O128;
     else if (n == "MH") src = e->MH; else if (n == "KT") src = e->KT; else if (n == "VT") src = e->VT; else if (n == "QP") src = e->QP;
-    if (!src) return fail(e, SAMRS_ERR_BAD_ARG, "unknown buffer %s", name);
+    else if (n == "DENSE") src = e->DENSE;      // allocated by the first mask prompt
+    else return fail(e, SAMRS_ERR_BAD_ARG, "unknown buffer %s", name);
+    // every other name is allocated by samrs_finalize_weights: null before it
+    if (!src) return fail(e, SAMRS_ERR_BAD_ARG, "buffer %s is not allocated yet", name);
     CK(e, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return SAMRS_OK;
 }
@@ -2016,6 +2019,79 @@ int samrs_k_gemm_mx_gelu_mxout(int prec, const void* A, const void* B, void* C_e
 }
 int samrs_k_convert_split(int prec, const float* in, void* out_hi, void* out_lo, int64_t n, void* stream) {
     KRET(launch_convert(prec, in, out_hi, (long)n, (hipStream_t)stream, out_lo));
+}
+// prompt encoder / two-way transformer glue, one kernel each.  The checks in front of a launcher are those the engine's own call
+// sites guarantee by construction and the launcher therefore does not repeat; a shape it refuses itself comes back through KRET.
+int samrs_k_prompt_tokens(const float* boxes, const float* point_coords, const int32_t* point_labels, int n_prompts, int n_points,
+                          float img_size, const float* gauss, const float* point_emb, const float* not_a_point, const float* iou_token,
+                          const float* mask_tokens, float* tokens, float* tokens2, int T, void* stream) {
+    if (!tokens || !gauss || !point_emb || !not_a_point || !iou_token || !mask_tokens || n_prompts < 1) return SAMRS_ERR_BAD_ARG;
+    if ((point_coords != nullptr) != (point_labels != nullptr) || (point_coords && n_points < 1)) return SAMRS_ERR_BAD_ARG;
+    PromptParams pp{};
+    pp.boxes = boxes; pp.point_coords = point_coords; pp.point_labels = point_labels;
+    pp.n_prompts = n_prompts; pp.n_points = point_coords ? n_points : 0;
+    pp.img_size = img_size;
+    pp.gauss = gauss;
+    for (int i = 0; i < 4; ++i) pp.point_emb[i] = point_emb + i * 256;
+    pp.not_a_point = not_a_point; pp.iou_token = iou_token; pp.mask_tokens = mask_tokens;
+    const int npt = point_coords ? n_points + (boxes ? 0 : 1) : 0;
+    if (T != 5 + npt + (boxes ? 2 : 0)) return SAMRS_ERR_BAD_SHAPE;
+    KRET(launch_prompt_tokens(pp, tokens, tokens2, T, (hipStream_t)stream));
+}
+int samrs_k_dense_pe(const float* gauss, float* pe, int grid, void* stream) {
+    if (!gauss || !pe || grid < 1) return SAMRS_ERR_BAD_ARG;
+    KRET(launch_dense_pe(gauss, pe, grid, (hipStream_t)stream));
+}
+int samrs_k_mask_embed(const float* w0, const float* b0, const float* ln1w, const float* ln1b, const float* w3, const float* b3,
+                       const float* ln4w, const float* ln4b, const float* w6, const float* b6, const float* mask_in, float* dense,
+                       int n, int grid, void* stream) {
+    if (!mask_in || !dense || n < 1) return SAMRS_ERR_BAD_ARG;
+    if (grid < 1 || (grid * grid) % 16) return SAMRS_ERR_BAD_SHAPE;
+    const MaskEmbedParams mp{w0, b0, ln1w, ln1b, w3, b3, ln4w, ln4b, w6, b6};
+    KRET(launch_mask_embed(mp, mask_in, dense, n, grid, (hipStream_t)stream));
+}
+int samrs_k_fill_slot_table(const int32_t* start_host, const int32_t* slot_host, int n_runs, int32_t* out, void* stream) {
+    if (!start_host || !slot_host || !out || n_runs < 1) return SAMRS_ERR_BAD_ARG;
+    KRET(launch_fill_slot_table(start_host, slot_host, n_runs, out, (hipStream_t)stream));
+}
+int samrs_k_make_keys(int prec, const float* emb, const float* dense, const float* vec, float* out_f32, void* out_et, int n_batches,
+                      int tokens, int C, const int32_t* slot_of, void* stream) {
+    if (!emb || (!dense && !vec) || !out_f32 || !out_et || n_batches < 1) return SAMRS_ERR_BAD_ARG;
+    if (tokens < 1 || C < 4 || C % 4) return SAMRS_ERR_BAD_SHAPE;
+    KRET(launch_make_keys(prec, emb, dense, vec, out_f32, out_et, n_batches, tokens, C, (hipStream_t)stream, slot_of));
+}
+int samrs_k_token_self_attn(const float* q, const float* k, const float* v, float* o, int n, int T, int C, int heads, void* stream) {
+    if (n < 1 || T < 1 || heads < 1) return SAMRS_ERR_BAD_SHAPE;
+    KRET(launch_token_self_attn(q, k, v, o, n, T, C, heads, (hipStream_t)stream));
+}
+int64_t samrs_k_t2i_workspace_floats(int n, int T) { return (int64_t)t2i_workspace_floats(n, T); }
+int samrs_k_t2i_attention(int prec, const float* qp, const void* kp, const void* vp, int ld, int64_t bstride, float* out,
+                          float* workspace, int n, int T, int tokens, int Ci, int heads, const int32_t* slot_of, void* stream) {
+    if (n < 1 || T < 1 || tokens < 1) return SAMRS_ERR_BAD_SHAPE;
+    KRET(launch_t2i_attention(prec, qp, kp, vp, ld, (long)bstride, out, workspace, n, T, tokens, Ci, heads, (hipStream_t)stream, slot_of));
+}
+int samrs_k_i2t_attention(int prec, const void* qi, int ld, int64_t bstride, const float* kt, const float* vt, void* out, int n,
+                          int T, int tokens, int Ci, int heads, void* stream) {
+    if (n < 1 || T < 1 || T > 16 || tokens < 1 || heads < 1) return SAMRS_ERR_BAD_SHAPE;
+    KRET(launch_i2t_attention(prec, qi, ld, (long)bstride, kt, vt, out, n, T, tokens, Ci, heads, (hipStream_t)stream));
+}
+int samrs_k_i2t_fused(int prec, const void* qi, int ld, int64_t q_bstride, const float* kt, const float* vt, const void* w,
+                      const void* w_lo, const float* bias, const float* resid, int64_t r_bstride, const float* gamma,
+                      const float* beta, float eps, float* outF, void* outE, void* outE_lo, int n, int T, int tokens, int Ci, int C,
+                      const int32_t* slot_of, void* stream) {
+    if (n < 1 || tokens < 1 || !outE || !resid) return SAMRS_ERR_BAD_ARG;
+    KRET(launch_i2t_fused(prec, qi, ld, (long)q_bstride, kt, vt, w, w_lo, bias, resid, (long)r_bstride, gamma, beta, eps, outF, outE,
+                          outE_lo, n, T, tokens, Ci, C, (hipStream_t)stream, slot_of));
+}
+int samrs_k_group_ln_gelu(int prec, const float* in, const float* gamma, const float* beta, float eps, void* out, int64_t rows,
+                          int groups, int gsize, void* stream) {
+    if (rows < 1) return SAMRS_ERR_BAD_SHAPE;
+    KRET(launch_group_ln_gelu(prec, in, gamma, beta, eps, out, (long)rows, groups, gsize, (hipStream_t)stream));
+}
+int samrs_k_mask_product(int prec, const void* up2, const float* hyper, float* low, int n, int grid, int n_mask_tokens, int sel0,
+                         int n_sel, void* stream) {
+    if (n < 1 || grid < 1 || (16 * grid * grid) % 256 || sel0 < 0 || sel0 + n_sel > n_mask_tokens) return SAMRS_ERR_BAD_SHAPE;
+    KRET(launch_mask_product(prec, up2, hyper, low, n, grid, n_mask_tokens, sel0, n_sel, (hipStream_t)stream));
 }
 
 }  // extern "C"

@@ -126,6 +126,26 @@ def load_library() -> C.CDLL:
     lib.samrs_k_gemm_mx_gelu_mxout.argtypes = [ip, vp, vp, vp, vp, ip, ip, ip, ip, vp, vp, vp, vp, vp, vp, vp, vp, ip, vp, vp, vp, vp, vp]
     for name in ("samrs_k_mx4_pack", "samrs_k_gemm_mx", "samrs_k_layernorm_mx", "samrs_k_attention_mx", "samrs_k_gemm_mx_gelu_mxout"):
         getattr(lib, name).restype = ip
+    # decoder kernels, one each (include/samrs_hip_internal.h; tests/test_decoder_kernels_gpu.py)
+    lib.samrs_k_prompt_tokens.argtypes = [vp, vp, vp, ip, ip, fp, vp, vp, vp, vp, vp, vp, vp, ip, vp]
+    lib.samrs_k_dense_pe.argtypes = [vp, vp, ip, vp]
+    lib.samrs_k_mask_embed.argtypes = [vp] * 12 + [ip, ip, vp]
+    lib.samrs_k_fill_slot_table.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32), ip, vp, vp]
+    lib.samrs_k_make_keys.argtypes = [ip, vp, vp, vp, vp, vp, ip, ip, ip, vp, vp]
+    lib.samrs_k_token_self_attn.argtypes = [vp, vp, vp, vp, ip, ip, ip, ip, vp]
+    lib.samrs_k_t2i_workspace_floats.argtypes = [ip, ip]
+    lib.samrs_k_t2i_workspace_floats.restype = i64
+    lib.samrs_k_t2i_attention.argtypes = [ip, vp, vp, vp, ip, i64, vp, vp, ip, ip, ip, ip, ip, vp, vp]
+    lib.samrs_k_i2t_attention.argtypes = [ip, vp, ip, i64, vp, vp, vp, ip, ip, ip, ip, ip, vp]
+    lib.samrs_k_i2t_fused.argtypes = [ip, vp, ip, i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, fp, vp, vp, vp, ip, ip, ip, ip, ip, vp, vp]
+    lib.samrs_k_group_ln_gelu.argtypes = [ip, vp, vp, vp, fp, vp, i64, ip, ip, vp]
+    lib.samrs_k_mask_product.argtypes = [ip, vp, vp, vp, ip, ip, ip, ip, ip, vp]
+    for name in ("samrs_k_prompt_tokens", "samrs_k_dense_pe", "samrs_k_mask_embed", "samrs_k_fill_slot_table", "samrs_k_make_keys",
+                 "samrs_k_token_self_attn", "samrs_k_t2i_attention", "samrs_k_i2t_attention", "samrs_k_i2t_fused",
+                 "samrs_k_group_ln_gelu", "samrs_k_mask_product", "samrs_debug_copy_buffer", "samrs_debug_outlier_columns"):
+        getattr(lib, name).restype = ip
+    lib.samrs_debug_copy_buffer.argtypes = [vp, C.c_char_p, vp, C.c_size_t, vp]
+    lib.samrs_debug_outlier_columns.argtypes = [vp, ip, ip, C.POINTER(C.c_int32)]
     lib.samrs_get_slot_info.argtypes = [vp, ip, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     for name in ("samrs_load_weight", "samrs_finalize_weights", "samrs_set_images", "samrs_set_images_ragged", "samrs_get_embedding",
                  "samrs_set_embedding", "samrs_reset_image", "samrs_predict", "samrs_predict_multi", "samrs_paint", "samrs_k_gemm",
@@ -328,12 +348,20 @@ class Engine:
     def outlier_columns(self, block: int, gemm: int):
         """Test hook: the outlier K-columns the engine picked for block GEMM `gemm` (0 qkv, 1 lin1, 2 lin2, 3 proj) of encoder block `block`."""
         buf = (C.c_int32 * 32)()
-        self.lib.samrs_debug_outlier_columns.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32)]
-        self.lib.samrs_debug_outlier_columns.restype = C.c_int
         n = self.lib.samrs_debug_outlier_columns(self.handle, block, gemm, buf)
         if n < 0:
             self._check(n)
         return [int(buf[i]) for i in range(n)]
+
+    def debug_copy_buffer(self, name: str, dst: torch.Tensor) -> torch.Tensor:
+        """Test hook: fill `dst` (a contiguous tensor on this engine's device) with the leading dst.numel() elements of the named
+        internal decoder buffer (TOK0, DENSE, K0F, KF, KE, Q, HYPER, ...: samrs_hip_internal.h).  The caller picks dtype and shape."""
+        if not dst.is_contiguous() or dst.device != torch.device(self.device):
+            raise ValueError("debug_copy_buffer: dst must be a contiguous tensor on the engine's device")
+        with torch.cuda.device(self.device):
+            self._check(self.lib.samrs_debug_copy_buffer(self.handle, name.encode(), dst.data_ptr(), dst.numel() * dst.element_size(),
+                                                         _stream()))
+        return dst
 
     def time_dominant_kernel(self, enable: bool) -> None:
         self._check(self.lib.samrs_debug_time_dominant_kernel(self.handle, int(enable)))

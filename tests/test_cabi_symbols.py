@@ -24,6 +24,13 @@ def declared_functions(header="samrs_hip.h"):
     return sorted(set(re.findall(r"\b(samrs_[a-z0-9_]+)\s*\(", text)))
 
 
+def pointer_taking_functions(header):
+    """names of the functions a header declares with at least one pointer parameter"""
+    text = open(os.path.join(ROOT, "include", header)).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    return sorted({m.group(1) for m in re.finditer(r"\b(samrs_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text) if "*" in m.group(2)})
+
+
 def test_header_declares_the_boundary():
     names = declared_functions()
     for must in ["samrs_create", "samrs_destroy", "samrs_load_weight", "samrs_finalize_weights", "samrs_set_images",
@@ -80,3 +87,22 @@ def test_ctypes_binding_declares_argtypes_for_the_public_surface(lib_path):
     lib = engine.load_library()
     missing = [n for n in declared_functions() if n != "samrs_abi_version" and getattr(lib, n).argtypes is None]
     assert not missing, f"no argtypes in samrs_amd/engine.py for: {missing}"
+
+
+def test_ctypes_binding_declares_argtypes_for_the_internal_pointer_takers(lib_path):
+    """The same for include/samrs_hip_internal.h: every kernel-level entry point (samrs_k_*) and test hook (samrs_debug_*) that
+    takes a pointer is called by the tests with 64-bit device pointers, so samrs_amd/engine.py must declare its argtypes, with
+    one entry per parameter of the prototype."""
+    from samrs_amd import engine
+    lib = engine.load_library()
+    names = pointer_taking_functions("samrs_hip_internal.h")
+    assert len(names) >= 39 and "samrs_k_t2i_attention" in names and "samrs_debug_copy_buffer" in names, names
+    assert "samrs_debug_set_gemm_variant" not in names and "samrs_k_mx_scale_bytes" not in names        # no pointer parameter
+    missing = [n for n in names if getattr(lib, n).argtypes is None]
+    assert not missing, f"no argtypes in samrs_amd/engine.py for: {missing}"
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "samrs_hip_internal.h")).read(), flags=re.S)
+    wrong = []
+    for m in re.finditer(r"\b(samrs_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
+        if m.group(1) in names and len(getattr(lib, m.group(1)).argtypes) != len(m.group(2).split(",")):
+            wrong.append((m.group(1), len(getattr(lib, m.group(1)).argtypes), len(m.group(2).split(","))))
+    assert not wrong, f"argtypes length differs from the prototype: {wrong}"

@@ -4,6 +4,10 @@ torch fp32/fp64 CPU statement of the same op on the same (already rounded) opera
 Tolerances: MFMA operands are bf16 / f16, accumulation is fp32.  With operands pre-rounded on the
 host the only differences left are fp32 summation order and the rounding of ET outputs
 (one ulp: 2^-8 relative for bf16, 2^-11 for f16).
+
+This file holds the encoder, the GEMMs and the upscaler tail; the prompt-encoder and mask-decoder kernels (prompt tokens, dense
+PE, mask embedding, slot table, keys, the three decoder attentions, the fused i2t kernel, group LN + GELU, mask product) are in
+tests/test_decoder_kernels_gpu.py.
 """
 import math
 

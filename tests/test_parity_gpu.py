@@ -32,12 +32,12 @@ def _oracle():
 _CACHE = {}
 
 
-def get_predictor(name, precision, max_prompts=16, max_images=1):
-    key = (name, precision, max_prompts, max_images)
+def get_predictor(name, precision, max_prompts=16, max_images=1, max_points=4):
+    key = (name, precision, max_prompts, max_images) + ((max_points,) if max_points != 4 else ())
     if key not in _CACHE:
         import samrs_amd
         sam = samrs_amd.sam_model_registry[name](precision=precision, max_prompts=max_prompts, max_images=max_images,
-                                                 max_points=4)
+                                                 max_points=max_points)
         sam.to(device="cuda")
         _CACHE[key] = samrs_amd.SamPredictor(sam)
     return _CACHE[key]
@@ -256,6 +256,136 @@ def test_decoder_alone_all_prompt_types(precision):
         if not (l2 < tol_l2 and err < tol_max and ierr < (2e-3 if precision == "f16" else 2e-2)):
             bad.append(tag)
     assert not bad, bad
+
+
+def _prompt_side_fp64(so, sd64, cfg, points, boxes, mask):
+    """float64 statement of the three pure-fp32 stages (prompt tokens, dense embedding, layer-0 keys' addend) for the
+    fp32 rule of tests/test_decoder_kernels_gpu.py: the oracle's own code on a float64 state dict; the mask path restated,
+    because the oracle casts the mask to float32."""
+    import torch.nn.functional as F
+    sparse, dense = so.prompt_encoder(sd64, cfg, points, boxes, None)
+    if mask is not None:
+        p = "prompt_encoder.mask_downscaling"
+
+        def ln2d(x, w, b):
+            u = x.mean(1, keepdim=True)
+            s = ((x - u) ** 2).mean(1, keepdim=True)
+            return (x - u) / torch.sqrt(s + 1e-6) * w[None, :, None, None] + b[None, :, None, None]
+        y = F.conv2d(mask.double(), sd64[p + ".0.weight"], sd64[p + ".0.bias"], stride=2)
+        y = F.gelu(ln2d(y, sd64[p + ".1.weight"], sd64[p + ".1.bias"]))
+        y = F.conv2d(y, sd64[p + ".3.weight"], sd64[p + ".3.bias"], stride=2)
+        y = F.gelu(ln2d(y, sd64[p + ".4.weight"], sd64[p + ".4.bias"]))
+        dense = F.conv2d(y, sd64[p + ".6.weight"], sd64[p + ".6.bias"])
+    out_tok = torch.cat([sd64["mask_decoder.iou_token.weight"], sd64["mask_decoder.mask_tokens.weight"]], dim=0)
+    tokens = torch.cat([out_tok[None].expand(sparse.shape[0], -1, -1), sparse], dim=1)
+    return tokens, dense.expand(sparse.shape[0], -1, -1, -1).flatten(2).permute(0, 2, 1)
+
+
+@pytest.mark.parametrize("fusion", [1, 0], ids=["fused", "unfused"])
+@pytest.mark.parametrize("precision", ["f16", "bf16"])
+def test_decoder_stagewise(precision, fusion):
+    """The decoder stage by stage (the counterpart of test_encoder_blockwise): oracle embedding installed, one predict per
+    prompt kind (box; 8 points, which adds the pad point: T = 14; box + mask), then the engine's internal buffers against
+    the oracle's taps.  What each buffer holds when samrs_predict returns (predict_chunk, engine.hip):
+
+      buffer  stage                                                     tap            rule
+      TOK0    prompt tokens [n, T, 256], fp32                           tokens         fp32
+      DENSE   mask-prompt dense embedding [n, 4096, 256], fp32          dense          fp32 (mask prompts only; before the
+              (allocated by the first mask prompt)                                     first one the copy is refused)
+      K0F     slot's layer-0 keys = embedding + no-mask vector, fp32,   emb + no_mask  fp32 (written when the embedding is
+              [4096, 256]; not rewritten by a mask prompt                              installed; every prompt kind)
+      KF      FUSED path: keys after LAYER 0, fp32 -- the last layer    keys0          decoder bound
+              passes outF = nullptr to the fused i2t kernel and only
+              writes KE.  UN-FUSED path (decoder_fusion = 0): the       keys1          decoder bound
+              LayerNorm of every layer writes KF and KE: keys after
+              layer 1
+      KE      keys after layer 1 in the operand type, both paths        keys1          decoder bound
+      Q       queries after norm_final_attn [n, T, 256], fp32           queries_final  decoder bound
+      HYPER   hypernetwork outputs [n, 4, 32], fp32                     hyper          decoder bound
+
+    fp32 rule: rel L2 <= max(8 x the oracle's own fp32 noise against its float64 evaluation, 3e-6).  Decoder bound: the rel L2
+    the project states for the decoder's end (test_decoder_alone_all_prompt_types): 1.5e-3 f16, 1.2e-2 bf16.  The queries
+    after layers 0 and 1 are overwritten in place by the time the call returns; the taps record them for tools."""
+    so = _oracle()
+    name = "vit_tiny"
+    cfg = synth.CONFIGS[name]
+    pred = get_predictor(name, precision, max_points=8)
+    eng = pred.model.engine
+    orc = get_oracle(name)
+    sd64 = {k: v.double() for k, v in orc.sd.items()}
+    img = synth.make_image(0)
+    orc.set_image(img)
+    pred.set_image(img)
+    eng.set_embedding(orc.features.cuda(), pred.slot)
+    size = img.shape[:2]
+    n, tokens, C = 3, cfg.grid * cfg.grid, cfg.out_chans
+    g = torch.Generator().manual_seed(5)
+    boxes = so.apply_boxes(torch.from_numpy(synth.make_boxes(3, n)[0]), size)
+    coords = so.apply_coords(torch.rand(n, 8, 2, generator=g) * 1023, size)
+    labels = torch.randint(0, 2, (n, 8), generator=g, dtype=torch.int32)
+    labels[1, 5:] = -1
+    mask = torch.randn(n, 1, 256, 256, generator=g) * 4.0
+    tol = 1.5e-3 if precision == "f16" else 1.2e-2
+    et = torch.float16 if precision == "f16" else torch.bfloat16
+    no_mask = orc.sd["prompt_encoder.no_mask_embed.weight"].reshape(1, C)
+    emb_tok = orc.features.flatten(2).permute(0, 2, 1)[0]                       # [4096, 256]
+    bad = []
+
+    def check(tag, what, got, ref, bound, extra=""):
+        r = ((got.double().cpu() - ref.double()).norm() / ref.double().norm()).item()
+        print(f"stagewise {precision} {'fused' if fusion else 'unfused'} {tag} {what}: rel L2 {r:.3e} (bound {bound:.2e}){extra}")
+        if not r <= bound:
+            bad.append((tag, what, r, bound))
+
+    def fp32_rule(ref32, ref64):
+        noise = ((ref32.double() - ref64).norm() / ref64.norm()).item()
+        return max(8.0 * noise, 3e-6), f", oracle fp32 noise {noise:.2e}"
+
+    def buf(bname, shape, dtype=torch.float32):
+        return eng.debug_copy_buffer(bname, torch.empty(shape, dtype=dtype, device="cuda"))
+
+    eng.set_option("decoder_fusion", fusion)
+    try:
+        for tag, b, pts, m in [("box", boxes, None, None), ("points8", None, (coords, labels), None), ("box+mask", boxes, None, mask)]:
+            taps = {}
+            sparse, dense = so.prompt_encoder(orc.sd, cfg, None if pts is None else (pts[0], pts[1].long()), b, m)
+            so.mask_decoder(orc.sd, cfg, orc.features, orc.pe, sparse, dense, False, taps=taps)
+            T = taps["tokens"].shape[1]
+            cu = lambda t: None if t is None else t.cuda()
+            eng.predict(pred.slot, cu(b), cu(None if pts is None else pts[0]), cu(None if pts is None else pts[1]), cu(m), False, True,
+                        pred.input_size, pred.original_size)
+            tok64, dense64 = _prompt_side_fp64(so, sd64, cfg, None if pts is None else (pts[0], pts[1].long()), b, m)
+            bound, extra = fp32_rule(taps["tokens"], tok64)
+            check(tag, f"TOK0 (T = {T})", buf("TOK0", (n, T, C)), tok64, bound, extra)
+            k0_64 = emb_tok.double() + no_mask.double()
+            bound, extra = fp32_rule(emb_tok + no_mask, k0_64)
+            check(tag, "K0F", buf("K0F", (tokens, C)), k0_64, bound, extra)
+            if m is not None:
+                bound, extra = fp32_rule(taps["dense"], dense64)
+                check(tag, "DENSE", buf("DENSE", (n, tokens, C)), dense64, bound, extra)
+            check(tag, "KF = keys after layer 0" if fusion else "KF = keys after layer 1", buf("KF", (n, tokens, C)),
+                  taps["keys0" if fusion else "keys1"], tol)
+            check(tag, "KE = keys after layer 1", buf("KE", (n, tokens, C), torch.int16).view(et).float(), taps["keys1"], tol)
+            check(tag, "Q = queries after norm_final_attn", buf("Q", (n, T, C)), taps["queries_final"], tol)
+            check(tag, "HYPER", buf("HYPER", (n, 4, C // 8)), taps["hyper"], tol)
+    finally:
+        eng.set_option("decoder_fusion", 1)
+    assert not bad, bad
+
+
+def test_debug_copy_buffer_refuses_what_is_not_there():
+    """DENSE exists from the first mask prompt on: before it (a fresh engine) the copy is an error, as is an unknown name."""
+    import samrs_amd
+    sam = samrs_amd.sam_model_registry["vit_tiny"](precision="f16", max_prompts=2, max_images=1, max_points=1)
+    sam.to(device="cuda")
+    eng = sam.engine
+    dst = torch.full((256,), float("nan"), device="cuda")
+    for bad_name in ("DENSE", "NO_SUCH_BUFFER"):
+        with pytest.raises(AssertionError, match=bad_name):          # SAMRS_ERR_BAD_ARG
+            eng.debug_copy_buffer(bad_name, dst)
+    assert bool(torch.isnan(dst).all())
+    eng.debug_copy_buffer("TOK0", dst)
+    eng.close()
 
 
 def test_operand_split_buys_what_the_error_budget_says():

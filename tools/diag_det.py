@@ -1,11 +1,9 @@
-import sys, os, ctypes as C, torch
+import sys, os, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import samrs_amd
 from samrs_amd import synth
 sam = samrs_amd.sam_model_registry["vit_tiny"](precision="f16", max_prompts=8, max_images=1).to("cuda")
-eng = sam.engine; lib = eng.lib
-lib.samrs_debug_copy_buffer.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p]
-lib.samrs_debug_copy_buffer.restype = C.c_int
+eng = sam.engine
 img = torch.as_tensor(synth.make_noise_image(40)).cuda()[None]
 eng.set_images(img, 0)
 boxes, _ = synth.make_boxes(40, 4)
@@ -17,11 +15,8 @@ bufs = {"TOK0": n*T*256*4, "Q": n*T*256*4, "QP": n*T*128*4, "O128": n*T*128*4, "
 def run():
     m, q, l = eng.predict(0, b, None, None, None, False, False, (1024, 1024), (1024, 1024))
     out = {}
-    s = torch.cuda.current_stream().cuda_stream
     for k, nb in bufs.items():
-        t = torch.empty(nb, dtype=torch.uint8, device="cuda")
-        assert lib.samrs_debug_copy_buffer(eng.handle, k.encode(), t.data_ptr(), nb, s) == 0
-        out[k] = t
+        out[k] = eng.debug_copy_buffer(k, torch.empty(nb, dtype=torch.uint8, device="cuda"))
     torch.cuda.synchronize()
     out["low"] = l.clone().view(torch.uint8).flatten()
     return out
