@@ -306,9 +306,41 @@ int samrs_resample_pass_u8(const uint8_t* in, uint8_t* out, const int32_t* bound
  *   "outlier_blocks" / "outlier_columns" / "outlier_dominant_blocks"  read-only: encoder blocks with at least one outlier column in
  *                    qkv / lin1; the number of columns picked over all four block GEMMs; blocks in which the picked columns carry more
  *                    than half of the qkv or proj operand-error mass -- in the v-third modes (79 / 207) those blocks run the plain
- *                    launches with the exact lo terms of their outlier columns instead of the MXFP4 lo terms of all columns. */
+ *                    launches with the exact lo terms of their outlier columns instead of the MXFP4 lo terms of all columns.
+ *   "range_profile"  [SAMRS_RANGE_PROFILE, default 0] the checkpoint audit (samrs_audit_* below).  1 = on every encoder pass each audit
+ *                    SITE -- the operand tensors "range_check" scans, q | k | v apart -- adds its range profile (counts of zeros,
+ *                    subnormals, saturated values, inf / nan, the largest magnitude, a histogram of floor(log2 |x|)) to a per-site row on
+ *                    the device; 2 = the same plus, for the A operand of every block GEMM, per-column sum of squares and largest magnitude
+ *                    (what "outlier_cols" guesses from the weights, measured).  One more pass over those tensors (two with 2): a
+ *                    validation mode.  Independent of "range_check"; every "split" mode and both operand types.  0 launches nothing.
+ *   "audit_passes"   [SAMRS_AUDIT_PASSES, default 0] write N > 0: reset the audit state, set "range_profile" = 2 and profile the next N
+ *                    encoder passes (samrs_set_images* calls); the engine then sets "range_profile" back to 0 by itself, so the steady
+ *                    state launches nothing extra.  Read: passes left.  Write 0: stop a running audit. */
 int samrs_set_option(samrs_engine_t* e, const char* name, int value);
 int samrs_get_option(const samrs_engine_t* e, const char* name, int* value);
+
+/* -- checkpoint audit: where in the encoder do the operand tensors sit in the operand type's range, and which K-columns of the block GEMMs
+ * are really hot (options "range_profile" / "audit_passes"; python -m samrs_amd.audit prints the report).
+ * Sites, in data-flow order, 7 depth + 3 of them (fixed at samrs_finalize_weights; 0 sites before): per encoder block i
+ * "blocks.i.qkv_in" (norm1 output), "blocks.i.q", "blocks.i.k", "blocks.i.v", "blocks.i.proj_in" (attention output), "blocks.i.lin1_in"
+ * (norm2 output), "blocks.i.lin2_in" (GELU(lin1)); then "neck.conv1_in" (the residual stream rounded to the operand type), "neck.conv2_in",
+ * "decoder.keys0".  samrs_audit_site_name copies the name (truncated to name_len - 1 characters) and, if `columns` is not NULL, the K of
+ * the site's column statistics (qkv_in, proj_in, lin1_in: embed_dim; lin2_in: 4 embed_dim; every other site 0 = none).
+ * A profile row is 48 int64, accumulated over the profiled passes:
+ *   [0] elements scanned   [1] zeros   [2] subnormals of the operand type (f16: 0 < |x| < 2^-14)   [3] elements AT the largest finite
+ *   magnitude (f16 0x7bff = 65504, what the saturating conversions write)   [4] inf or nan   [5] the largest finite magnitude seen as its
+ *   15-bit pattern `bits & 0x7fff` (a running maximum)   [6], [7] zero   [8 + b], b = 0 .. 39: finite non-zero elements with
+ *   floor(log2 |x|) == b - 24, clamped into [-24, 15] (f16 covers exactly this range; bf16 clamps at both ends).
+ *   [1] + [4] + sum of the bins == [0]; the elements of [2] and [3] are also in their bins.
+ * samrs_audit_read_profile copies all rows to HOST memory and samrs_audit_read_columns one site's column statistics (sumsq [K] = sum of
+ * x^2 over the n_rows rows seen, max_abs [K]; a bf16 magnitude above 1.8e19 makes its column's sum inf); both synchronise the device
+ * (diagnostics, like option "saturated").  All sums are integer atomics or ordered fp64 sums of fp32 partials: bitwise reproducible.
+ * reset != 0 clears the whole audit state (rows and column statistics) after the copy.  samrs_audit_read_columns returns
+ * SAMRS_ERR_BAD_ARG for a site without column statistics, or when no pass has been profiled with "range_profile" = 2 since the last reset. */
+int samrs_audit_site_count(const samrs_engine_t* e, int* n_sites);
+int samrs_audit_site_name(const samrs_engine_t* e, int site, char* name, int name_len, int* columns);
+int samrs_audit_read_profile(samrs_engine_t* e, int64_t* rows, int reset);
+int samrs_audit_read_columns(samrs_engine_t* e, int site, double* sumsq, float* max_abs, int64_t* n_rows);
 
 /* Rotated-box MASK prompts, replacing the cv2 pre-step of `Generate Dataset/main_sam_rbox_mask_instance.py:125-141`
  * (fillPoly -> +-1000 -> resize to the ResizeLongestSide shape -> pad with -1000 -> resize to 256x256).

@@ -198,6 +198,15 @@ int samrs_k_gemm_mx_gelu_mxout(int prec, const void* A, const void* B, void* C_e
                                const void* sb_hi, const void* sb_lo, int gelu, void* o4_hi, void* o4_lo, void* so_hi, void* so_lo, void* stream);
 /* fp32 -> hi (= samrs_k_convert) and lo = ET(x - hi): the two-term operand split */
 int samrs_k_convert_split(int prec, const float* in, void* out_hi_et, void* out_lo_et, int64_t n, void* stream);
+/* the checkpoint audit's two kernels alone (audit_kernels.hip; row layout and semantics: samrs_hip.h samrs_audit_read_profile).
+ *   samrs_k_range_profile  ADDS the profile of x_et -- n elements as rows of `cols` live elements at a row stride of `ld` elements
+ *                          (cols <= 0: one dense run; n, cols, ld % 8 == 0, 16-byte aligned) -- into row48 (device int64 [48])
+ *   samrs_k_column_stats   x_et [M][K] with row stride ld (K, ld % 8 == 0): sumsq[c] += sum over the rows of x^2 (device double [K]),
+ *                          maxbits[c] = max(maxbits[c], bits & 0x7fff) (device uint32 [K]); partials: device fp32 scratch
+ *                          [ceil(M / R)][K] with R = samrs_k_audit_rows_per_partial(), the rows one fp32 chain sums before fp64 takes over */
+int samrs_k_range_profile(int prec, const void* x_et, long n, int cols, int ld, int64_t* row48, void* stream);
+int samrs_k_column_stats(int prec, const void* x_et, int M, int K, int ld, float* partials, double* sumsq, uint32_t* maxbits, void* stream);
+int samrs_k_audit_rows_per_partial(void);
 
 #ifdef __cplusplus
 }

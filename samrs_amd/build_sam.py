@@ -46,9 +46,14 @@ class Sam:
     image_format: str = "RGB"
 
     def __init__(self, cfg: SamConfig, state_dict: Dict[str, torch.Tensor], precision: str = "f16",
-                 max_images: int = 1, max_prompts: int = 64, max_points: int = 4, options: Optional[Dict[str, int]] = None):
+                 max_images: int = 1, max_prompts: int = 64, max_points: int = 4, options: Optional[Dict[str, int]] = None,
+                 audit_passes: int = 0):
         """``options``: per-engine options applied BEFORE the weights are loaded (include/samrs_hip.h samrs_set_option:
-        "split", "decoder_fusion", "ln_fold", "gemm_variant")."""
+        "split", "decoder_fusion", "ln_fold", "gemm_variant").  ``audit_passes`` = N > 0: the first N encoder passes are profiled
+        (samrs_amd/audit.py); when the engine has switched the profile off, ``audit_report`` is filled in and an
+        ``OperandRangeWarning`` names the worst sites if there is a finding.  0: nothing is launched or read."""
+        self.audit_passes = int(audit_passes)
+        self.audit_report: Optional[Dict[str, Any]] = None
         self.cfg = cfg
         self.options = dict(options or {})
         self._state_dict = state_dict
@@ -83,7 +88,29 @@ class Sam:
         # the engine's option as it is
         self.default_split = self.engine.get_option("split")
         self._device = device
+        if self.audit_passes > 0:
+            self.engine.start_audit(self.audit_passes, self._audit_finished)
         return self
+
+    def finish_audit(self) -> Optional[Dict[str, Any]]:
+        """The audit report of a model built with ``audit_passes``; a run that ended before the N-th encoder pass stops the audit
+        here and reports the passes it did profile (None when there was none)."""
+        eng = self.engine
+        if self.audit_report is None and eng is not None and eng._audit_done is not None:
+            left = eng.get_option("audit_passes")
+            eng.start_audit(0)
+            if left < self.audit_passes:
+                self.audit_passes -= left
+                self._audit_finished(eng)
+        return self.audit_report
+
+    def _audit_finished(self, engine: Engine) -> None:
+        import warnings
+        from . import audit
+        self.audit_report = audit.collect(engine, self._state_dict, self.cfg, self.audit_passes)
+        text = audit.warning_text(self.audit_report)
+        if text:
+            warnings.warn(text, audit.OperandRangeWarning, stacklevel=4)
 
     @torch.no_grad()
     def forward(self, batched_input: List[Dict[str, Any]], multimask_output: bool) -> List[Dict[str, torch.Tensor]]:

@@ -190,6 +190,18 @@ struct samrs_engine {
     int range_check = 0;
     unsigned long long* range_counter = nullptr;
     unsigned long long range_seen = 0;             // counter value at the end of the last checked encoder pass (mode 2)
+    // options "range_profile" (0 off, 1 range profile per site, 2 + column statistics of the block GEMMs' A operands) and "audit_passes"
+    // (profile the next N encoder passes in mode 2, then switch off): samrs_hip.h samrs_audit_*.  Sites are fixed at samrs_finalize_weights;
+    // the device buffers are allocated by the first pass that needs them (audit_prepare).
+    struct AuditSite { std::string name; int columns; size_t col_off; };     // columns: K of the site's column statistics (0 = none)
+    std::vector<AuditSite> audit_sites;
+    size_t audit_columns = 0;                      // sum of AuditSite::columns
+    int range_profile = 0, audit_passes = 0;
+    long long* audit_rows = nullptr;               // [n_sites][AUDIT_PROFILE_WORDS]
+    double* audit_sumsq = nullptr;                 // [audit_columns], site s at col_off
+    uint32_t* audit_maxbits = nullptr;             // likewise
+    float* audit_partials = nullptr;               // scratch of one column-statistics launch: [max_images * tokens / AUDIT_ROWS_PER_PARTIAL][4 D]
+    std::vector<long long> audit_col_rows;         // per site: rows its column statistics have seen (host side)
 
     // decoder weights
     std::vector<DecLayer> layers;
@@ -546,6 +558,10 @@ samrs_engine_t* samrs_create(const samrs_config* cfg, int device, char* err, int
     e->outlier_ratio_pct = env_int("SAMRS_OUTLIER_RATIO_PCT", 400);
     if (e->outlier_ratio_pct < 101) e->outlier_ratio_pct = 101;
     if (e->gelu_fast > 1) e->gelu_fast = 1;
+    e->range_profile = env_int("SAMRS_RANGE_PROFILE", 0);
+    if (e->range_profile < 0 || e->range_profile > 2) e->range_profile = 0;
+    e->audit_passes = env_int("SAMRS_AUDIT_PASSES", 0);
+    if (e->audit_passes > 0) e->range_profile = 2; else e->audit_passes = 0;
     if (const int rc0 = env_int("SAMRS_RANGE_CHECK", 0)) {
         if (samrs_set_option(e, "range_check", rc0) != SAMRS_OK) {
             if (err && err_len > 0) snprintf(err, err_len, "SAMRS_RANGE_CHECK=%d: %s", rc0, e->err.c_str());
@@ -602,6 +618,8 @@ int samrs_load_weight(samrs_engine_t* e, const char* name, const float* host, co
     e->w.emplace(n, std::move(t));
     return SAMRS_OK;
 }
+
+static void audit_build_sites(samrs_engine_t* e);      // the checkpoint audit's site table (defined with the audit helpers below)
 
 int samrs_finalize_weights(samrs_engine_t* e, void* stream) {
     if (!e) return SAMRS_ERR_BAD_ARG;
@@ -858,6 +876,7 @@ int samrs_finalize_weights(samrs_engine_t* e, void* stream) {
     CK(e, dalloc(e, &e->HYPER, Bb * 4 * (C / 8))); CK(e, dalloc(e, &e->IOU, Bb * 4));
     CK(e, dalloc(e, &e->LOW, Bb * 3 * 256 * 256));
     CK(e, hipStreamSynchronize(s));
+    audit_build_sites(e);
     e->finalized = true;
     return SAMRS_OK;
 }
@@ -867,6 +886,69 @@ int samrs_finalize_weights(samrs_engine_t* e, void* stream) {
 // differ in size (HRSC / DIOR images after ResizeLongestSide): only the im2col reads pixels, everything downstream
 // works on the zero-padded 64 x 64 token grid (sam.py:170-173).
 static int prepare_slot_keys(samrs_engine_t* e, int slot0, int n, hipStream_t s);
+
+// ---- checkpoint audit (options "range_profile" / "audit_passes") --------------------------------------------------------------------
+enum { AUDIT_QKV_IN = 0, AUDIT_Q, AUDIT_K, AUDIT_V, AUDIT_PROJ_IN, AUDIT_LIN1_IN, AUDIT_LIN2_IN, AUDIT_PER_BLOCK };
+enum { AUDIT_NECK1_IN = 0, AUDIT_NECK2_IN, AUDIT_KEYS0, AUDIT_TAIL };
+
+static void audit_build_sites(samrs_engine_t* e) {
+    static const char* const per_block[AUDIT_PER_BLOCK] = {"qkv_in", "q", "k", "v", "proj_in", "lin1_in", "lin2_in"};
+    e->audit_sites.clear();
+    e->audit_columns = 0;
+    auto add = [&](const std::string& name, int columns) {
+        e->audit_sites.push_back({name, columns, e->audit_columns});
+        e->audit_columns += (size_t)columns;
+    };
+    for (int i = 0; i < e->cfg.depth; ++i)
+        for (int k = 0; k < AUDIT_PER_BLOCK; ++k)
+            add("blocks." + std::to_string(i) + "." + per_block[k],
+                (k == AUDIT_QKV_IN || k == AUDIT_PROJ_IN || k == AUDIT_LIN1_IN) ? e->D : k == AUDIT_LIN2_IN ? 4 * e->D : 0);
+    add("neck.conv1_in", 0); add("neck.conv2_in", 0); add("decoder.keys0", 0);
+    e->audit_col_rows.assign(e->audit_sites.size(), 0);
+}
+
+// the device buffers, zeroed, on first use (the caller is on the engine's device)
+static int audit_prepare(samrs_engine_t* e, bool with_columns) {
+    if (!e->audit_rows) {
+        const size_t n = e->audit_sites.size() * AUDIT_PROFILE_WORDS;
+        CK(e, dalloc(e, &e->audit_rows, n));
+        CK(e, hipMemset(e->audit_rows, 0, n * sizeof(long long)));
+        CK(e, hipDeviceSynchronize());
+    }
+    if (with_columns && !e->audit_sumsq) {
+        CK(e, dalloc(e, &e->audit_sumsq, e->audit_columns));
+        CK(e, dalloc(e, &e->audit_maxbits, e->audit_columns));
+        CK(e, dalloc(e, &e->audit_partials, column_stats_partial_floats(e->cfg.max_images * e->tokens, 4 * e->D)));
+        CK(e, hipMemset(e->audit_sumsq, 0, e->audit_columns * sizeof(double)));
+        CK(e, hipMemset(e->audit_maxbits, 0, e->audit_columns * sizeof(uint32_t)));
+        CK(e, hipDeviceSynchronize());          // the zeros are in place before a pass on another stream adds to them
+    }
+    return SAMRS_OK;
+}
+
+// forget everything profiled so far (device-synchronising: a pass may still be adding to the buffers)
+static int audit_reset(samrs_engine_t* e) {
+    if (e->audit_rows || e->audit_sumsq) CK(e, hipDeviceSynchronize());
+    if (e->audit_rows) CK(e, hipMemset(e->audit_rows, 0, e->audit_sites.size() * AUDIT_PROFILE_WORDS * sizeof(long long)));
+    if (e->audit_sumsq) {
+        CK(e, hipMemset(e->audit_sumsq, 0, e->audit_columns * sizeof(double)));
+        CK(e, hipMemset(e->audit_maxbits, 0, e->audit_columns * sizeof(uint32_t)));
+    }
+    e->audit_col_rows.assign(e->audit_sites.size(), 0);
+    return SAMRS_OK;
+}
+
+// one site of the running pass: `rows` rows of `cols` live elements at a stride of `ld`, right behind the tensor's producer on `s`
+static int audit_scan(samrs_engine_t* e, int site, const uint16_t* x, int rows, int cols, int ld, hipStream_t s) {
+    if (site < 0 || site >= (int)e->audit_sites.size()) return fail(e, SAMRS_ERR_BAD_ARG, "audit site %d out of range", site);
+    CK(e, launch_range_profile(e->prec, x, (long)rows * cols, cols, ld, e->audit_rows + (size_t)site * AUDIT_PROFILE_WORDS, s));
+    const samrs_engine::AuditSite& a = e->audit_sites[site];
+    if (e->range_profile == 2 && a.columns == cols) {
+        CK(e, launch_column_stats(e->prec, x, rows, cols, ld, e->audit_partials, e->audit_sumsq + a.col_off, e->audit_maxbits + a.col_off, s));
+        e->audit_col_rows[site] += rows;
+    }
+    return SAMRS_OK;
+}
 
 static int encode(samrs_engine_t* e, const uint8_t* const* images, const int* in_h, const int* in_w, int n, int slot0,
                   void* stream, int n_blocks, bool do_neck) {
@@ -884,6 +966,7 @@ static int encode(samrs_engine_t* e, const uint8_t* const* images, const int* in
     const int D = e->D, C = e->C, g = e->grid, tokens = e->tokens, prec = e->prec;
     const int M = n * tokens;
     for (int i = 0; i < n; ++i) e->slot_set[slot0 + i] = 0;
+    if (e->range_profile) { const int rc = audit_prepare(e, e->range_profile == 2); if (rc != SAMRS_OK) return rc; }
 
     // patch embed: im2col (normalise + zero pad) -> GEMM (+bias +pos_embed) -> X.  One im2col launch per run of
     // same-size tiles that sit back to back in memory (the whole batch for a contiguous tile stack).
@@ -946,6 +1029,10 @@ static int encode(samrs_engine_t* e, const uint8_t* const* images, const int* in
 #define RANGE_SCAN(ptr_, count_) do { if (e->range_check) CK(e, launch_range_scan(prec, (ptr_), (long)(count_), e->range_counter, s)); } while (0)
     // ... of a tensor whose rows carry pad columns (the LayerNorm output on the padded-stride route): the live columns only
 #define RANGE_SCAN_ROWS(ptr_, rows_, cols_, ld_) do { if (e->range_check) CK(e, launch_range_scan(prec, (ptr_), (long)(rows_) * (cols_), e->range_counter, s, (cols_), (ld_))); } while (0)
+    // option "range_profile": the same places, one audit site each (q | k | v apart; the D live columns of a LayerNorm output only, not
+    // its outlier extension, whose hi half is a copy)
+#define AUDIT_SITE(site_, ptr_, rows_, cols_, ld_) do { if (e->range_profile) { const int rc_ = audit_scan(e, (site_), (ptr_), (rows_), (cols_), (ld_), s); if (rc_ != SAMRS_OK) return rc_; } } while (0)
+    const int audit_tail = AUDIT_PER_BLOCK * c.depth;
     // padded operand rows for the plain qkv / lin1 launches (they run on the persistent ET kernels at these shapes: gemm_ld_ok)
     const bool pad_ok = e->ldk && e->operand_pad_on && !fold && !ln_tail;
     // outlier-column extension of the plain qkv / lin1 launches (EncBlock::oc_*): not with the folded / tail LayerNorm forms (other producers of Y)
@@ -1027,6 +1114,11 @@ static int encode(samrs_engine_t* e, const uint8_t* const* images, const int* in
             RANGE_SCAN_ROWS(e->Y, M, y_live, y_ld);  // the live columns only: pad columns may hold an earlier pass's values
             RANGE_SCAN(e->QKV, (size_t)M * 3 * D);
             RANGE_SCAN(e->AO, (size_t)M * D);
+        }
+        if (e->range_profile) {
+            AUDIT_SITE(AUDIT_PER_BLOCK * i + AUDIT_QKV_IN, e->Y, M, D, y_ld);
+            for (int t = 0; t < 3; ++t) AUDIT_SITE(AUDIT_PER_BLOCK * i + AUDIT_Q + t, e->QKV + (size_t)t * D, M, D, 3 * D);
+            AUDIT_SITE(AUDIT_PER_BLOCK * i + AUDIT_PROJ_IN, e->AO, M, D, D);
         }
         y_ld = D; y_live = D;
         // lin1 takes the plain launch below exactly when none of these holds; then norm2 writes the padded layout for it
@@ -1119,6 +1211,10 @@ static int encode(samrs_engine_t* e, const uint8_t* const* images, const int* in
             RANGE_SCAN_ROWS(e->Y, M, y_live, y_ld);
             RANGE_SCAN(e->H, (size_t)M * 4 * D);
         }
+        if (e->range_profile) {
+            AUDIT_SITE(AUDIT_PER_BLOCK * i + AUDIT_LIN1_IN, e->Y, M, D, y_ld);
+            AUDIT_SITE(AUDIT_PER_BLOCK * i + AUDIT_LIN2_IN, e->H, M, 4 * D, 4 * D);
+        }
         if (fold) {
             CK(e, launch_gemm_et_stats(prec, e->H, b.lin2_w, e->X, b.lin2_b, e->Y, e->STATS, M, D, 4 * D, s));
             if (i + 1 < c.depth) CK(e, launch_ln_rowstat(e->STATS, e->ROWSTAT, M, 1e-6f, s));
@@ -1155,6 +1251,7 @@ static int encode(samrs_engine_t* e, const uint8_t* const* images, const int* in
     if (sp_neck) CK(e, launch_convert(prec, e->X, e->Y, (long)M * D, s, lo_buf));
     else if (!(fold && c.depth > 0 && n_blocks >= c.depth)) CK(e, launch_convert(prec, e->X, e->Y, (long)M * D, s));
     RANGE_SCAN(e->Y, (size_t)M * D);       // the RAW residual stream rounded to the operand type: the one operand without a LayerNorm in front
+    AUDIT_SITE(audit_tail + AUDIT_NECK1_IN, e->Y, M, D, D);
     if (sp_neck && one3p && gemm_split3_ok((int)M, C, D, true)) {
         CK(e, launch_gemm_et_split3(prec, e->Y, lo_buf, e->neck0_w, e->neck0_w_lo, e->N1, nullptr, (int)M, C, D, true, false, s));
     } else {
@@ -1167,6 +1264,7 @@ static int encode(samrs_engine_t* e, const uint8_t* const* images, const int* in
     CK(e, launch_layernorm(prec, e->N1, W(e, "image_encoder.neck.1.weight"), W(e, "image_encoder.neck.1.bias"), 1e-6f,
                            e->N1e, nullptr, M, C, 0, g, 0, s, sp_neck ? lo_buf : nullptr));
     RANGE_SCAN(e->N1e, (size_t)M * C);
+    AUDIT_SITE(audit_tail + AUDIT_NECK2_IN, e->N1e, M, C, C);
     CK(e, launch_neck_im2col(e->N1e, e->H, n, g, C, s));
     uint16_t* H2lo = e->H + (size_t)M * 9 * C;
     if (sp_neck) CK(e, launch_neck_im2col(lo_buf, H2lo, n, g, C, s));
@@ -1200,6 +1298,10 @@ static int encode(samrs_engine_t* e, const uint8_t* const* images, const int* in
         }
     }
 #undef RANGE_SCAN
+    AUDIT_SITE(audit_tail + AUDIT_KEYS0, e->K0E + (size_t)slot0 * tokens * C, M, C, C);
+#undef AUDIT_SITE
+    // "audit_passes": a full pass has been profiled; after the last one the profile switches itself off
+    if (e->audit_passes > 0 && --e->audit_passes == 0) e->range_profile = 0;
     for (int i = 0; i < n; ++i) {
         e->slot_set[slot0 + i] = 1;
         e->slot_split[slot0 + i] = e->split;
@@ -1707,6 +1809,21 @@ int samrs_set_option(samrs_engine_t* e, const char* name, int value) {
         }
         e->range_seen = 0;
     }
+    else if (n == "range_profile") {
+        if (value < 0 || value > 2) return fail(e, SAMRS_ERR_BAD_ARG, "range_profile is 0 (off), 1 (range profile per site) or 2 (and column statistics)");
+        e->range_profile = value;
+        if (!value) e->audit_passes = 0;
+    }
+    else if (n == "audit_passes") {
+        if (value < 0) return fail(e, SAMRS_ERR_BAD_ARG, "audit_passes is the number of encoder passes to profile (0 stops a running audit)");
+        if (value > 0) {
+            ON_DEVICE(e);
+            const int rc = audit_reset(e);
+            if (rc != SAMRS_OK) return rc;
+            e->range_profile = 2;
+        } else if (e->audit_passes > 0) e->range_profile = 0;
+        e->audit_passes = value;
+    }
     else if (n == "lo_format") {
         if (value != 0 && value != 4) return fail(e, SAMRS_ERR_BAD_ARG, "lo_format is 0 (f16 lo terms) or 4 (MXFP4 lo terms)");
         if (value == 4 && e->finalized && !e->mx_ready && !e->mx_mlp_ready)
@@ -1746,6 +1863,8 @@ int samrs_get_option(const samrs_engine_t* e, const char* name, int* value) {
         }
         *value = c > 0x7fffffffull ? 0x7fffffff : (int)c;
     }
+    else if (n == "range_profile") *value = e->range_profile;
+    else if (n == "audit_passes") *value = e->audit_passes;
     else if (n == "lo_format") *value = (e->finalized && !e->mx_ready && !e->mx_mlp_ready) ? 0 : e->lo_format;
     else if (n == "grade_multimask") *value = e->grade_multimask;     // read-only
     else return SAMRS_ERR_BAD_ARG;
@@ -1957,6 +2076,66 @@ int samrs_debug_outlier_columns(samrs_engine_t* e, int block, int gemm, int32_t*
     }
     return b.oc_n[gemm];
 }
+// ---- checkpoint audit: the public reads (samrs_hip.h) and the two kernels alone (samrs_hip_internal.h)
+int samrs_audit_site_count(const samrs_engine_t* e, int* n_sites) {
+    if (!e || !n_sites) return SAMRS_ERR_BAD_ARG;
+    *n_sites = (int)e->audit_sites.size();
+    return SAMRS_OK;
+}
+int samrs_audit_site_name(const samrs_engine_t* e, int site, char* name, int name_len, int* columns) {
+    if (!e || !name || name_len < 1 || site < 0 || site >= (int)e->audit_sites.size()) return SAMRS_ERR_BAD_ARG;
+    snprintf(name, (size_t)name_len, "%s", e->audit_sites[site].name.c_str());
+    if (columns) *columns = e->audit_sites[site].columns;
+    return SAMRS_OK;
+}
+int samrs_audit_read_profile(samrs_engine_t* e, int64_t* rows, int reset) {
+    if (!e || !rows) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_audit_read_profile: null argument");
+    const size_t n = e->audit_sites.size() * AUDIT_PROFILE_WORDS;
+    if (!e->audit_rows) {                  // nothing profiled yet
+        for (size_t i = 0; i < n; ++i) rows[i] = 0;
+        return SAMRS_OK;
+    }
+    ON_DEVICE(e);
+    CK(e, hipDeviceSynchronize());
+    CK(e, hipMemcpy(rows, e->audit_rows, n * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return reset ? audit_reset(e) : SAMRS_OK;
+}
+int samrs_audit_read_columns(samrs_engine_t* e, int site, double* sumsq, float* max_abs, int64_t* n_rows) {
+    if (!e || !sumsq || !max_abs || !n_rows) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_audit_read_columns: null argument");
+    if (site < 0 || site >= (int)e->audit_sites.size()) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_audit_read_columns: site %d of %d", site, (int)e->audit_sites.size());
+    const samrs_engine::AuditSite& a = e->audit_sites[site];
+    if (a.columns == 0)
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_audit_read_columns: site %s has no column statistics (the block GEMMs' A operands have: qkv_in, proj_in, lin1_in, lin2_in)", a.name.c_str());
+    if (!e->audit_sumsq || e->audit_col_rows[site] == 0)
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_audit_read_columns: no encoder pass has been profiled with option \"range_profile\" = 2 (or \"audit_passes\") since the last reset");
+    ON_DEVICE(e);
+    CK(e, hipDeviceSynchronize());
+    std::vector<uint32_t> bits((size_t)a.columns);
+    CK(e, hipMemcpy(sumsq, e->audit_sumsq + a.col_off, sizeof(double) * a.columns, hipMemcpyDeviceToHost));
+    CK(e, hipMemcpy(bits.data(), e->audit_maxbits + a.col_off, sizeof(uint32_t) * a.columns, hipMemcpyDeviceToHost));
+    for (int c = 0; c < a.columns; ++c) {
+        uint32_t u;                        // the operand type's magnitude pattern as fp32 bits
+        if (e->prec == PREC_BF16) u = bits[c] << 16;
+        else {
+            const uint32_t ex = bits[c] >> 10, m = bits[c] & 0x3ffu;
+            if (ex == 31) u = 0x7f800000u | (m << 13);
+            else if (ex) u = ((ex + 112) << 23) | (m << 13);
+            else { const float f = (float)m * 5.9604644775390625e-8f /* 2^-24 */; memcpy(&u, &f, 4); }
+        }
+        memcpy(&max_abs[c], &u, 4);
+    }
+    *n_rows = (int64_t)e->audit_col_rows[site];
+    return SAMRS_OK;
+}
+int samrs_k_range_profile(int prec, const void* x, long n, int cols, int ld, int64_t* row48, void* stream) {
+    if (!x || !row48 || n < 0) return SAMRS_ERR_BAD_ARG;
+    KRET(launch_range_profile(prec, x, n, cols, ld, reinterpret_cast<long long*>(row48), (hipStream_t)stream));
+}
+int samrs_k_column_stats(int prec, const void* x, int M, int K, int ld, float* partials, double* sumsq, uint32_t* maxbits, void* stream) {
+    if (!x || !partials || !sumsq || !maxbits) return SAMRS_ERR_BAD_ARG;
+    KRET(launch_column_stats(prec, x, M, K, ld, partials, sumsq, maxbits, (hipStream_t)stream));
+}
+int samrs_k_audit_rows_per_partial(void) { return AUDIT_ROWS_PER_PARTIAL; }
 int samrs_rbox_mask_prompt(const int32_t* pts, int n, int n_vertices, int h, int w, int th, int tw, int img_size, int out_size,
                            float* out, void* stream) {
     if (!pts || !out) return SAMRS_ERR_BAD_ARG;

@@ -112,6 +112,17 @@ hipError_t launch_global_attention(int prec, const void* qkv, const float* rel_h
 hipError_t launch_neck_im2col(const void* in, void* A, int n_images, int grid, int C, hipStream_t s);
 hipError_t launch_transpose_f32(const float* in, float* out, int rows, int cols, hipStream_t s);
 
+// ---- audit_kernels.hip (engine options "range_profile" / "audit_passes") ---------------------
+constexpr int AUDIT_PROFILE_WORDS = 48;        // int64 words of one profile row (layout: samrs_hip.h samrs_audit_read_profile)
+constexpr int AUDIT_ROWS_PER_PARTIAL = 256;    // rows one fp32 partial of the column statistics sums in sequence
+// adds the profile of an ET tensor (n elements as rows of `cols` live elements at a stride of `ld`; cols <= 0: dense; all % 8 == 0)
+// into row48: integer atomics only, the result does not depend on the order of the blocks
+hipError_t launch_range_profile(int prec, const void* x, long n, int cols, int ld, long long* row48, hipStream_t s);
+// per column of an ET matrix [M][K] (row stride ld): sumsq[c] += sum of squares (fp32 chains of AUDIT_ROWS_PER_PARTIAL rows stored to
+// partials [column_stats_partial_floats(M, K)], added in slab order in fp64), maxbits[c] = max(maxbits[c], bits & 0x7fff)
+size_t column_stats_partial_floats(int M, int K);
+hipError_t launch_column_stats(int prec, const void* x, int M, int K, int ld, float* partials, double* sumsq, uint32_t* maxbits, hipStream_t s);
+
 // ---- decoder_kernels.hip --------------------------------------------------------------------
 struct PromptParams {
     const float* boxes;          // [n,4] or null

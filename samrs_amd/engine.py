@@ -147,6 +147,17 @@ def load_library() -> C.CDLL:
     lib.samrs_debug_copy_buffer.argtypes = [vp, C.c_char_p, vp, C.c_size_t, vp]
     lib.samrs_debug_outlier_columns.argtypes = [vp, ip, ip, C.POINTER(C.c_int32)]
     lib.samrs_get_slot_info.argtypes = [vp, ip, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    # checkpoint audit (samrs_hip.h samrs_audit_*; the two kernels alone: samrs_hip_internal.h)
+    lib.samrs_audit_site_count.argtypes = [vp, C.POINTER(ip)]
+    lib.samrs_audit_site_name.argtypes = [vp, ip, C.c_char_p, ip, C.POINTER(ip)]
+    lib.samrs_audit_read_profile.argtypes = [vp, vp, ip]
+    lib.samrs_audit_read_columns.argtypes = [vp, ip, vp, vp, C.POINTER(C.c_int64)]
+    lib.samrs_k_range_profile.argtypes = [ip, vp, C.c_long, ip, ip, vp, vp]
+    lib.samrs_k_column_stats.argtypes = [ip, vp, ip, ip, ip, vp, vp, vp, vp]
+    lib.samrs_k_audit_rows_per_partial.argtypes = []
+    for name in ("samrs_audit_site_count", "samrs_audit_site_name", "samrs_audit_read_profile", "samrs_audit_read_columns",
+                 "samrs_k_range_profile", "samrs_k_column_stats", "samrs_k_audit_rows_per_partial"):
+        getattr(lib, name).restype = ip
     for name in ("samrs_load_weight", "samrs_finalize_weights", "samrs_set_images", "samrs_set_images_ragged", "samrs_get_embedding",
                  "samrs_set_embedding", "samrs_reset_image", "samrs_predict", "samrs_predict_multi", "samrs_paint", "samrs_k_gemm",
                  "samrs_k_gemm_f32", "samrs_k_convert", "samrs_k_layernorm", "samrs_k_window_attention",
@@ -249,6 +260,7 @@ class Engine:
             self.handle = self.lib.samrs_create(C.byref(c), self.device.index, err, 512)
         if not self.handle:
             raise EngineError("samrs_create failed: " + err.value.decode())
+        self._audit_done = None        # start_audit: called once when the engine has profiled its passes
 
     # -- error mapping: same exception types / messages as the reference (predictor.py:133-134 ...)
     def _check(self, rc: int) -> None:
@@ -323,6 +335,8 @@ class Engine:
         n, h, w, _ = images_u8.shape
         with torch.cuda.device(self.device):
             self._check(self.lib.samrs_set_images(self.handle, images_u8.data_ptr(), n, h, w, slot0, _stream()))
+        if self._audit_done is not None:
+            self._audit_poll()
 
     def set_images_ragged(self, images_u8, slot0: int = 0) -> None:
         """One encoder pass over tiles of DIFFERENT sizes: a sequence of uint8 [H_i, W_i, 3] device tensors, each with
@@ -335,6 +349,8 @@ class Engine:
         ws = (C.c_int * n)(*[int(t.shape[1]) for t in images_u8])
         with torch.cuda.device(self.device):
             self._check(self.lib.samrs_set_images_ragged(self.handle, ptrs, hs, ws, n, slot0, _stream()))
+        if self._audit_done is not None:
+            self._audit_poll()
 
     def debug_encoder_prefix(self, images_u8: torch.Tensor, n_blocks: int) -> torch.Tensor:
         """Test hook: residual stream [n, 64, 64, D] after patch embed + the first n_blocks blocks."""
@@ -352,6 +368,52 @@ class Engine:
         if n < 0:
             self._check(n)
         return [int(buf[i]) for i in range(n)]
+
+    # -- checkpoint audit (options "range_profile" / "audit_passes"; samrs_amd/audit.py turns the numbers into a report)
+    PROFILE_WORDS = 48
+
+    def audit_sites(self) -> List[Tuple[str, int]]:
+        """(name, K of the site's column statistics or 0) of every audit site, in data-flow order (samrs_audit_site_name)."""
+        n, k = C.c_int(), C.c_int()
+        self._check(self.lib.samrs_audit_site_count(self.handle, C.byref(n)))
+        buf = C.create_string_buffer(64)
+        out = []
+        for i in range(n.value):
+            self._check(self.lib.samrs_audit_site_name(self.handle, i, buf, 64, C.byref(k)))
+            out.append((buf.value.decode(), int(k.value)))
+        return out
+
+    def range_profile(self, reset: bool = False) -> np.ndarray:
+        """int64 [n_sites, 48]: the profile rows accumulated so far (samrs_audit_read_profile; synchronises the device).  ``reset``
+        clears the whole audit state afterwards, column statistics included."""
+        rows = np.zeros((len(self.audit_sites()), self.PROFILE_WORDS), dtype=np.int64)
+        self._check(self.lib.samrs_audit_read_profile(self.handle, rows.ctypes.data, int(bool(reset))))
+        return rows
+
+    def column_stats(self, site) -> Dict[str, object]:
+        """{"sumsq" float64 [K], "max_abs" float32 [K], "n_rows"} of one block-GEMM operand site (index or name) after passes profiled
+        with ``range_profile`` = 2 (samrs_audit_read_columns); AssertionError (SAMRS_ERR_BAD_ARG) where there is nothing to read."""
+        sites = self.audit_sites()
+        if isinstance(site, str):
+            names = [s[0] for s in sites]
+            if site not in names:
+                raise KeyError(f"no audit site {site!r}")
+            site = names.index(site)
+        k = sites[site][1] if 0 <= site < len(sites) else 0
+        sumsq, max_abs, n_rows = np.zeros(max(k, 1), np.float64), np.zeros(max(k, 1), np.float32), C.c_int64()
+        self._check(self.lib.samrs_audit_read_columns(self.handle, int(site), sumsq.ctypes.data, max_abs.ctypes.data, C.byref(n_rows)))
+        return {"sumsq": sumsq, "max_abs": max_abs, "n_rows": int(n_rows.value)}
+
+    def start_audit(self, passes: int, done=None) -> None:
+        """Profile the next ``passes`` encoder passes (option ``audit_passes``); ``done(engine)`` is called once, from the
+        set_images* call after which the engine has switched the profile off by itself."""
+        self.set_option("audit_passes", int(passes))
+        self._audit_done = done if passes > 0 else None
+
+    def _audit_poll(self) -> None:
+        if self.get_option("audit_passes") == 0:          # a host-side read: no synchronisation
+            done, self._audit_done = self._audit_done, None
+            done(self)
 
     def debug_copy_buffer(self, name: str, dst: torch.Tensor) -> torch.Tensor:
         """Test hook: fill `dst` (a contiguous tensor on this engine's device) with the leading dst.numel() elements of the named

@@ -254,6 +254,7 @@ def run(args) -> Dict[str, List[int]]:
     # has read the environment, so an unconditional 15 silently replaced SAMRS_SPLIT=63 / 79).
     opts = default_split_options(getattr(args, "split", None))
     sam = samrs_amd.sam_model_registry[args.model](checkpoint=args.checkpoint, precision=args.precision, options=opts,
+                                                   audit_passes=getattr(args, "audit_passes", 0),
                                                    max_images=2 * batch, max_prompts=args.box_batch).to(f"cuda:{local}")
     exts = (".png", ".jpg", ".jpeg", ".tif", ".bmp")
     files = {os.path.splitext(f)[0]: f for f in os.listdir(args.images) if f.lower().endswith(exts)}
@@ -438,6 +439,9 @@ def run(args) -> Dict[str, List[int]]:
         with open(os.path.join(args.out, "statistic", "class_stats.json"), "w") as f:       # statistic.py:28-31
             json.dump(stats, f)
         np.save(os.path.join(args.out, "statistic", "all_mask_size.npy"), np.asarray(all_sizes, dtype=np.int64))
+        if getattr(args, "audit_passes", 0) > 0 and sam.finish_audit() is not None:
+            from . import audit
+            audit.write_json(sam.audit_report, os.path.join(args.out, "statistic", "audit.json"))
     return stats
 
 
@@ -467,6 +471,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--writers", type=int, default=0, help="PNG / pickle writer threads (0 = from the same budget, between 2 and 16)")
     ap.add_argument("--split", type=int, default=None, help="engine operand-split mode (15 = block GEMMs at the 1x f16 rate, the default of "
                     "this single-mask driver; 79 = multimask-grade; 31 / 63 = reference-grade; DESIGN.md section 2)")
+    ap.add_argument("--audit-passes", type=int, default=0, metavar="N",
+                    help="profile the operand ranges of the first N encoder passes (samrs_amd.audit): a warning names tensors that saturate "
+                         "the operand type, rank 0 writes OUT/statistic/audit.json; recommended (4) for a new checkpoint, 0 = off")
     ap.add_argument("--png-level", type=int, default=tile_io.LEVEL_LABELS,
                     help="-2 (default): the label-aware PNG encoder for gray/ and color/ (deflate tokens derived from the class map); 1..9: zlib "
                          "level of color/*.png, run-length preset for gray/*.png.  The decoded pixels are the same either way")

@@ -250,6 +250,7 @@ def run(args) -> Optional[dict]:
     # the model's own multimask-grade default
     opts = generate.default_split_options(split) if not multimask else ({"split": int(split)} if split is not None else None)
     sam = samrs_amd.sam_model_registry[args.model](checkpoint=args.checkpoint, precision=getattr(args, "precision", "f16"), options=opts,
+                                                   audit_passes=getattr(args, "audit_passes", 0),
                                                    max_images=2 * batch, max_prompts=args.box_batch).to(f"cuda:{local}")
     max_boxes = max([len(anns[s].colors) for s in stems] + [1])
     pipe = driver.InstancePipeline(sam, 1, prompt=args.prompt, multimask=multimask, fill_rule=getattr(args, "fill_rule", "auto"),
@@ -306,6 +307,9 @@ def run(args) -> Optional[dict]:
     rec = None
     if rank == 0:
         rec = merge_fragments(args.out, stems, tag, with_gt)
+        if getattr(args, "audit_passes", 0) > 0 and sam.finish_audit() is not None:
+            from . import audit
+            audit.write_json(sam.audit_report, os.path.join(args.out, "statistic", "audit.json"))
     if world > 1:
         dist.barrier()                                         # nobody leaves before the merged files are on disk
     return rec
@@ -326,6 +330,9 @@ def main(argv=None):
     ap.add_argument("--checkpoint", default=None)
     ap.add_argument("--precision", default="f16", choices=["f16", "bf16"])
     ap.add_argument("--split", type=int, default=None, help="engine operand-split mode (DESIGN.md section 2)")
+    ap.add_argument("--audit-passes", type=int, default=0, metavar="N",
+                    help="profile the operand ranges of the first N encoder passes (samrs_amd.audit): a warning names tensors that saturate "
+                         "the operand type, rank 0 writes OUT/statistic/audit.json; recommended (4) for a new checkpoint, 0 = off")
     ap.add_argument("--fill-rule", default="auto", help="rbox_mask: cv2.fillPoly span rule (transforms.resolve_fill_rule)")
     ap.add_argument("--batch", type=int, default=8, help="tiles per encoder pass")
     ap.add_argument("--box-batch", type=int, default=64, help="objects per predict call")
