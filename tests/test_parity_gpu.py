@@ -197,6 +197,50 @@ def test_folded_layernorm_matches_unfolded(precision):
         eng.close()
 
 
+def test_split_depth_hands_over_from_a_split_block_to_a_plain_block():
+    """An explicit "split_depth" below the model's depth: block 0 runs the operand-split route, block 1 the plain one -- the hand-over the
+    ViT-H default makes after 24 of its 32 blocks (mode 79), at a small shape.  vit_tiny1280 (D = 1280, depth 2: the one-launch, MXFP4 and
+    padded-stride routes of ViT-H), one seeded 1024^2 tile, f16; the full attention-side split (31, lo terms on MXFP4 = the default at this
+    width, and on f16) and the v-third form (79).  Exact (in)equalities only: split_depth = depth is the automatic depth; the first block does
+    not depend on what follows it; the slot records the depth; the second block really changed route."""
+    import samrs_amd
+    name = "vit_tiny1280"
+    cfg = synth.CONFIGS[name]
+    assert cfg.depth == 2
+    t = torch.as_tensor(synth.make_image(0), device="cuda")[None].contiguous()
+
+    def embedding(eng):
+        eng.set_images(t, 0)
+        return eng.get_embedding(0).clone()
+
+    for split, lo_formats in ((31, (4, 0)), (79, (4,))):
+        sam = samrs_amd.sam_model_registry[name](precision="f16", max_prompts=8, max_points=1, options={"split": split}).to("cuda")
+        eng = sam.engine
+        try:
+            assert eng.get_option("split") == split and eng.get_option("lo_format") == 4 and eng.get_option("split_depth") == 0
+            for lo_format in lo_formats:
+                tag = f"split {split}, lo_format {lo_format}"
+                with eng.options(lo_format=lo_format):
+                    assert eng.get_option("lo_format") == lo_format
+                    emb0 = embedding(eng)
+                    assert eng.get_slot_info(0)["split_depth"] == cfg.depth, tag
+                    pre0 = eng.debug_encoder_prefix(t, 1).clone()
+                    with eng.options(split_depth=cfg.depth):
+                        assert torch.equal(embedding(eng), emb0), f"{tag}: split_depth = depth is not the automatic depth"
+                    with eng.options(split_depth=1):
+                        assert torch.equal(eng.debug_encoder_prefix(t, 1), pre0), f"{tag}: block 0 depends on split_depth"
+                        emb1 = embedding(eng)
+                        info = eng.get_slot_info(0)
+                        assert info["is_set"] == 1 and info["split"] == split and info["split_depth"] == 1, (tag, info)
+                        with eng.options(split=15):
+                            emb15 = embedding(eng)
+                    assert emb0.abs().max() > 0
+                    assert not torch.equal(emb1, emb0), f"{tag}: split_depth = 1 left block 1 on the split route"
+                    assert not torch.equal(emb1, emb15), f"{tag}: split_depth = 1 took block 0 off the split route"
+        finally:
+            eng.close()
+
+
 @pytest.mark.parametrize("name", ["vit_tiny", "vit_tiny80", "vit_tiny1280"])
 @pytest.mark.parametrize("precision", ["f16", "bf16"])
 def test_embedding_and_masks_vs_oracle(name, precision):
