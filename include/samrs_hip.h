@@ -203,6 +203,25 @@ int samrs_gt_match(samrs_engine_t* e, const uint8_t* masks, int n, int h, int w,
 int samrs_rle_encode(samrs_engine_t* e, const uint8_t* masks, int n, int h, int w, uint8_t* out, int64_t out_capacity,
                      int64_t* cursor, int64_t* table, void* stream);
 
+/* -- mask clean-up before the masks become labels: `remove_small_regions` of utils/amg.py:267-291 on the device, for a batch of
+ * masks that never leave HBM (the reference's runs on the host through cv2, one mask per call).  masks uint8 [n][h][w] device, in /
+ * out (non-zero = set in, 0 / 1 out): the C = 1 output of samrs_predict, or the kept masks of samrs_select_best.  A region is an
+ * 8-connected component; it is small when it has fewer than min_area pixels (a region of exactly min_area pixels stays).
+ *   SAMRS_REGION_HOLES    every unset pixel in a small component of the complement becomes set;
+ *   SAMRS_REGION_ISLANDS  every set pixel in a small component is cleared; if EVERY component is small, exactly one is kept, the
+ *                         largest (amg.py:287-289) -- among equally large ones the one whose first pixel in row-major order comes
+ *                         first.  That tie rule is this library's: the reference takes np.argmax over cv2's label numbers, whose
+ *                         order cv2 does not promise;
+ *   SAMRS_REGION_BOTH     holes, then islands on the result (automatic_mask_generator.py postprocess_small_regions).
+ * areas_out int64 [n] = pixels set after the cleanup, changed_out int64 [n] = pixels whose value changed (either may be NULL).
+ * Integer arithmetic only, bitwise reproducible, no host synchronisation; h * w < 2^30, any h, w >= 1.  Labels and areas (8 bytes
+ * per pixel per mask in flight; a call with more than 32 masks runs as consecutive chunks of 32 on the stream: 256 MiB at 1024^2)
+ * live in ONE scratch buffer per handle that grows on demand: all samrs_clean_masks calls on a handle must be stream-ordered with
+ * each other (same stream, or an event between them); two handles never share it. */
+enum samrs_region_mode { SAMRS_REGION_HOLES = 1, SAMRS_REGION_ISLANDS = 2, SAMRS_REGION_BOTH = 3 };
+int samrs_clean_masks(samrs_engine_t* e, uint8_t* masks, int n, int h, int w, int min_area, int mode,
+                      int64_t* areas_out, int64_t* changed_out, void* stream);
+
 /* -- the generation CLI's class-map files (main_sam_hbox_semantic.py:212-215: gray/<stem>.png and color/<stem>.png), encoded on
  * the device.  maps: uint8 [n][h][w] (255 = unlabeled), lut: uint8 [256][3] (class id -> RGB), both on the device.  The two PNG
  * files of each map are byte-identical with what the host's samrs_io_png_write_label_pair (include/samrs_io.h) writes for

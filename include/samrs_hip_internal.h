@@ -207,6 +207,10 @@ int samrs_k_convert_split(int prec, const float* in, void* out_hi_et, void* out_
 int samrs_k_range_profile(int prec, const void* x_et, long n, int cols, int ld, int64_t* row48, void* stream);
 int samrs_k_column_stats(int prec, const void* x_et, int M, int K, int ld, float* partials, double* sumsq, uint32_t* maxbits, void* stream);
 int samrs_k_audit_rows_per_partial(void);
+/* the connected-component labelling of samrs_clean_masks alone (region_kernels.hip): masks uint8 [n][h][w] (non-zero = set) ->
+ * labels_out int32 [n][h][w] = the flattened root of every pixel, i.e. the smallest row-major pixel index of its 8-connected
+ * component of the set pixels (complement != 0: of the unset pixels), -1 where the pixel is not in that working set */
+int samrs_k_region_labels(const uint8_t* masks, int n, int h, int w, int complement, int32_t* labels_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -231,6 +231,9 @@ struct samrs_engine {
     // COCO RLE scratch (samrs_rle_encode), grown on demand
     void* rle_scratch = nullptr;
     size_t rle_scratch_bytes = 0;
+    // labels + areas + counters of samrs_clean_masks, grown on demand
+    void* region_scratch = nullptr;
+    size_t region_scratch_bytes = 0;
     // class-map PNG scratch (samrs_png_encode_labels), grown on demand
     void* png_scratch = nullptr;
     size_t png_scratch_bytes = 0;
@@ -584,6 +587,7 @@ void samrs_destroy(samrs_engine_t* e) {
     DeviceGuard dg(e->device);
     for (void* p : e->owned) (void)hipFree(p);
     if (e->rle_scratch) (void)hipFree(e->rle_scratch);
+    if (e->region_scratch) (void)hipFree(e->region_scratch);
     if (e->png_scratch) (void)hipFree(e->png_scratch);
     delete e;
 }
@@ -2049,6 +2053,33 @@ int samrs_rle_encode(samrs_engine_t* e, const uint8_t* masks, int n, int h, int 
     return SAMRS_OK;
 }
 
+// small islands and holes of n masks removed in place (see samrs_hip.h)
+int samrs_clean_masks(samrs_engine_t* e, uint8_t* masks, int n, int h, int w, int min_area, int mode, int64_t* areas_out,
+                      int64_t* changed_out, void* stream) {
+    if (!e || !masks || n < 1 || h < 1 || w < 1 || min_area < 1 || mode < SAMRS_REGION_HOLES || mode > SAMRS_REGION_BOTH)
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_clean_masks: bad argument");
+    if ((size_t)h * w >= (1ull << 30)) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_clean_masks: h * w = %lld must stay below 2^30", (long long)h * w);
+    ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    const int chunk = REGION_CHUNK;                     // masks per pass: bounds the scratch (8 MiB per 1024^2 mask)
+    const size_t need = region_scratch_bytes(n < chunk ? n : chunk, h, w);
+    if (need > e->region_scratch_bytes) {
+        if (e->region_scratch) {
+            CK(e, hipStreamSynchronize(s));
+            CK(e, hipFree(e->region_scratch));            // device-synchronising: nothing still reads the old scratch
+            e->region_scratch = nullptr; e->region_scratch_bytes = 0;
+        }
+        CK(e, hipMalloc(&e->region_scratch, need));
+        e->region_scratch_bytes = need;
+    }
+    for (int off = 0; off < n; off += chunk) {
+        const int m = n - off < chunk ? n - off : chunk;
+        CK(e, launch_clean_masks(masks + (size_t)off * h * w, m, h, w, min_area, mode, e->region_scratch,
+                                 areas_out ? (long long*)areas_out + off : nullptr, changed_out ? (long long*)changed_out + off : nullptr, s));
+    }
+    return SAMRS_OK;
+}
+
 // gray + colour PNG files of n class maps, packed behind *cursor into `out` (see samrs_hip.h)
 int samrs_png_encode_labels(samrs_engine_t* e, const uint8_t* maps, int n, int h, int w, const uint8_t* lut, uint8_t* out,
                             int64_t out_capacity, int64_t* cursor, int64_t* table, void* stream) {
@@ -2303,6 +2334,9 @@ int samrs_k_neck_im2col(const void* in, void* A, int n_images, int grid, int C, 
 int samrs_k_postprocess(const float* low, int n_masks, int in_h, int in_w, int orig_h, int orig_w, int img_size,
                         int return_logits, void* out, void* stream) {
     KRET(launch_postprocess(low, n_masks, in_h, in_w, orig_h, orig_w, img_size, return_logits, out, (hipStream_t)stream));
+}
+int samrs_k_region_labels(const uint8_t* masks, int n, int h, int w, int complement, int32_t* labels_out, void* stream) {
+    KRET(launch_region_labels(masks, n, h, w, complement, labels_out, (hipStream_t)stream));
 }
 int samrs_k_gemm_gln(int prec, const void* A, const void* B, void* C, const float* bias, const float* gamma_beta, int M, int N,
                      int K, const void* A_lo, const void* B_lo, void* stream) {

@@ -252,3 +252,16 @@ hipError_t launch_rle_encode(const uint8_t* masks, int n, int h, int w, void* sc
 size_t png_scratch_bytes(int n, int h, int w);
 hipError_t launch_png_encode(const uint8_t* maps, int n, int h, int w, const uint8_t* lut, void* scratch, unsigned char* out,
                              long long out_cap, long long* cursor, long long* table, hipStream_t s);
+
+// ---- region_kernels.hip ---------------------------------------------------------------------
+// Small-region removal (utils/amg.py:267-291 remove_small_regions, 8-connectivity) on n <= REGION_CHUNK masks uint8 [n][h][w], in
+// place (non-zero = set in, 0 / 1 out).  mode: 1 holes, 2 islands, 3 holes then islands.  areas_out / changed_out (device int64 [n],
+// either may be null): pixels set afterwards / pixels whose value changed.  scratch: region_scratch_bytes(n, h, w) = int32 labels +
+// int32 areas (8 bytes per pixel) + 32 bytes of counters per mask.  h * w < 2^30.
+constexpr int REGION_CHUNK = 32;                       // measured: chunks of 8 take 1.7x the time per mask (launches too small to fill the device)
+size_t region_scratch_bytes(int n, int h, int w);
+hipError_t launch_clean_masks(uint8_t* masks, int n, int h, int w, int min_area, int mode, void* scratch, long long* areas_out,
+                              long long* changed_out, hipStream_t s);
+// the labelling alone (any n): labels_out int32 [n][h][w] = the smallest row-major pixel index of the pixel's 8-connected component
+// of the set pixels (complement != 0: of the unset pixels), -1 outside that working set.  Needs no scratch.
+hipError_t launch_region_labels(const uint8_t* masks, int n, int h, int w, int complement, int32_t* labels_out, hipStream_t s);

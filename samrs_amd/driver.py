@@ -323,6 +323,7 @@ class TileResult:
     gt_rle_data: Optional[np.ndarray] = None
     png_table: Optional[np.ndarray] = None  # int64 [2, 2] (offset, length) of the gray and the colour PNG in png_data (png_lut)
     png_data: Optional[np.ndarray] = None   # uint8 view of the batch's pinned PNG byte buffer
+    changed: Optional[np.ndarray] = None    # int64 [n_boxes] pixels the small-region clean-up changed (min_region_area > 0)
 
     def png(self, kind: str) -> memoryview:
         """The bytes of ``gray/<stem>.png`` (kind "gray") or ``color/<stem>.png`` ("color") of this tile, encoded on the device
@@ -348,9 +349,10 @@ class TileResult:
 
 
 class _OutBuf:
-    def __init__(self, batch: int, side: int, max_boxes: int, rle: bool = False, png: bool = False):
+    def __init__(self, batch: int, side: int, max_boxes: int, rle: bool = False, png: bool = False, changed: bool = False):
         self.seg = torch.empty(batch, side, side, dtype=torch.uint8).pin_memory()
         self.areas = torch.empty(batch, max_boxes, dtype=torch.int64).pin_memory()
+        self.changed = torch.empty(batch, max_boxes, dtype=torch.int64).pin_memory() if changed else None
         self.done = torch.cuda.Event()
         self.masks: List[Optional[torch.Tensor]] = [None] * batch     # keep_masks: host copies of the full masks
         self.odd: dict = {}                                           # tiles that are not side x side: their class maps
@@ -390,7 +392,8 @@ class TilePipeline:
     def __init__(self, sam, n_classes: int, batch: int = 8, box_batch: int = 20, keep_masks: bool = False,
                  out_depth: int = 3, max_boxes: int = 512, device_inputs: bool = False, rle: bool = False,
                  rle_buffer_mb: int = 256, precision="auto", _multimask: bool = False, png_lut: Optional[np.ndarray] = None,
-                 png_buffer_mb: Optional[int] = None, batch_decode: bool = False):
+                 png_buffer_mb: Optional[int] = None, batch_decode: bool = False, min_region_area: int = 0,
+                 region_mode: str = "both"):
         """precision: the operand-split mode (engine option "split") THIS PIPELINE'S OWN CALLS run in.  The option is set around
         each of the pipeline's encode / decode calls and restored afterwards (``Engine.options``), so the mode never outlives
         them: a ``SamPredictor`` built on the same model keeps the engine's own default (round 3 changed the engine's option for
@@ -405,8 +408,19 @@ class TilePipeline:
         caller's consent to run its multimask predicts in it: option "allow_reduced").
         batch_decode: decode the prompts of every tile of a batch in one ``Engine.predict_multi`` call (one decoder chain per
         batch instead of one per tile and box chunk); painting, RLE and PNG encoding then run per tile as before, and every
-        output is the same byte for byte."""
+        output is the same byte for byte.
+        min_region_area: > 0 removes, on the device and before anything else reads the masks, every 8-connected island
+        (region_mode "islands"), hole ("holes") or both ("both": holes first) of fewer than that many pixels
+        (``Engine.clean_masks`` = segment_anything's ``remove_small_regions``): class map, areas, class statistics, RLE strings,
+        device PNGs and kept masks all see the cleaned masks, and ``TileResult.changed`` counts the pixels changed per
+        instance.  0 (default) issues no call at all."""
         from .transforms import ResizeLongestSide
+        from .engine import REGION_MODES
+        if int(min_region_area) < 0:
+            raise ValueError("min_region_area must be >= 0 (0 = off)")
+        if region_mode not in REGION_MODES:
+            raise ValueError(f"region_mode must be one of {sorted(REGION_MODES)}, got {region_mode!r}")
+        self.min_region_area, self.region_mode = int(min_region_area), region_mode
         eng = sam.engine
         if eng is None:
             raise RuntimeError("move the model to the GPU first: sam.to('cuda')")
@@ -464,13 +478,15 @@ class TilePipeline:
         self.dev_lab = [torch.empty(batch * max_boxes, dtype=torch.int32, device=dev) for _ in range(2)]
         self.seg_dev = [torch.empty(batch, side, side, dtype=torch.uint8, device=dev) for _ in range(2)]
         self.area_dev = [torch.zeros(batch, max_boxes, dtype=torch.int64, device=dev) for _ in range(2)]
+        if self.min_region_area:
+            self.chg_dev = [torch.zeros(batch, max_boxes, dtype=torch.int64, device=dev) for _ in range(2)]
         self.ev_h2d = [torch.cuda.Event() for _ in range(2)]
         self.ev_enc = [torch.cuda.Event() for _ in range(2)]
         self.ev_dec = [torch.cuda.Event() for _ in range(2)]
         self.ev_in_free = [torch.cuda.Event() for _ in range(2)]     # encoder has consumed input set b
         self.free_out: "queue.Queue[_OutBuf]" = queue.Queue()
         for _ in range(out_depth):
-            self.free_out.put(_OutBuf(batch, side, max_boxes, rle, self.png))
+            self.free_out.put(_OutBuf(batch, side, max_boxes, rle, self.png, self.min_region_area > 0))
 
     @staticmethod
     def _choose_split(sam, precision, multimask: bool) -> Optional[int]:
@@ -591,6 +607,9 @@ class TilePipeline:
             else:
                 tb = self._input_frame_boxes(self.dev_box[b][off + s:off + e], (H, W), in_size)   # :174
                 masks, _, _ = eng.predict(b * self.batch + i, tb, None, None, None, False, False, in_size, (H, W))
+            if self.min_region_area:                                              # before anything else reads the masks
+                eng.clean_masks(masks[:, 0], self.min_region_area, self.region_mode, areas_out=False,     # paint counts them
+                                changed_out=self.chg_dev[b][i, s:e])
             eng.paint(masks[:, 0], self.dev_lab[b][off + s:off + e], seg, self.class_pixels, self.class_instances,
                       areas_out=self.area_dev[b][i, s:e])
             if self.rle:                                                          # :201-202, on the device
@@ -629,6 +648,8 @@ class TilePipeline:
             if self.png:
                 self._encode_png(b, tiles)
             out.areas.copy_(self.area_dev[b], non_blocking=True)
+            if self.min_region_area:
+                out.changed.copy_(self.chg_dev[b], non_blocking=True)
             if self.rle:
                 out.rle_tab.copy_(self.rle_tab[b], non_blocking=True)
                 out.rle_cur.copy_(self.rle_cur[b], non_blocking=True)
@@ -716,6 +737,8 @@ class TilePipeline:
                 r.rle_table, r.rle_data = rtab[off:off + nb], rdat
             if self.png:
                 r.png_table, r.png_data = ptab[i], pdat
+            if self.min_region_area:
+                r.changed = out.changed[i, :nb].numpy().copy()
             self._extra_result(r, i, off, nb, out, extra)
             res.append(r)
         out.odd = {}
@@ -919,6 +942,9 @@ class InstancePipeline(TilePipeline):
                 m, q, _ = eng.predict(slot, None, ann.view(-1, 1, 2), pl, None, mm, False, in_size, (H, W))
             # best of the C masks by predicted IoU, its quality and area: one pass on the device, straight into the tables
             mk, _, _ = eng.select_best(m, q, None, self.qual_dev[b][i, s:e], self.area_dev[b][i, s:e])
+            if self.min_region_area:                      # the area table then holds the cleaned areas (select_best's are stale)
+                eng.clean_masks(mk, self.min_region_area, self.region_mode, areas_out=self.area_dev[b][i, s:e],
+                                changed_out=self.chg_dev[b][i, s:e])
             if self.rle:
                 eng.rle_encode(mk, self.rle_dev[b], self.rle_cur[b], self.rle_tab[b][off + s:off + e])
             if self.gt:                                   # main_sam_rhbox_mask_instance.py:204-238, on the device

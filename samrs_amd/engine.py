@@ -23,6 +23,7 @@ PREC_BF16, PREC_F16 = 0, 1
 PRECISIONS = {"bf16": PREC_BF16, "f16": PREC_F16, "fp16": PREC_F16}
 
 ABI_VERSION = 5
+REGION_MODES = {"holes": 1, "islands": 2, "both": 3}        # enum samrs_region_mode
 # "split" option bits (include/samrs_hip.h): rounding points that run as a two-term operand split
 SPLIT_PATCH, SPLIT_NECK, SPLIT_OI, SPLIT_UP, SPLIT_DEFAULT = 1, 2, 4, 8, 15
 SPLIT_ATTN, SPLIT_MLP, SPLIT_ATTN_V, SPLIT_LIN2, SPLIT_ALL = 16, 32, 64, 128, 255          # reference-grade bits: set before the weights are loaded
@@ -104,6 +105,10 @@ def load_library() -> C.CDLL:
     lib.samrs_k_convert_split.argtypes = [ip, vp, vp, vp, C.c_int64, vp]
     lib.samrs_select_best.argtypes = [vp, vp, vp, ip, ip, ip, ip, vp, vp, vp, vp]
     lib.samrs_gt_match.argtypes = [vp, vp, ip, ip, ip, vp, vp, vp, vp, vp, vp]
+    lib.samrs_clean_masks.argtypes = [vp, vp, ip, ip, ip, ip, ip, vp, vp, vp]
+    lib.samrs_clean_masks.restype = ip
+    lib.samrs_k_region_labels.argtypes = [vp, ip, ip, ip, ip, vp, vp]
+    lib.samrs_k_region_labels.restype = ip
     lib.samrs_png_encode_labels.argtypes = [vp, vp, ip, ip, ip, vp, vp, C.c_int64, vp, vp, vp]
     lib.samrs_k_upscaler_fused.argtypes = [ip, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, vp]
     lib.samrs_k_convert.argtypes = [ip, vp, vp, C.c_int64, vp]
@@ -599,6 +604,49 @@ class Engine:
             self._check(self.lib.samrs_select_best(self.handle, m.data_ptr(), iou.data_ptr(), n, c, h, w, best.data_ptr(),
                                                    qual.data_ptr(), areas.data_ptr(), _stream()))
         return best, qual, areas
+
+    def clean_masks(self, masks: torch.Tensor, min_area: int, mode="both", areas_out=None, changed_out=None):
+        """Small islands and holes removed on the device, in place (samrs_clean_masks; ``remove_small_regions`` of
+        utils/amg.py:267-291): masks [n, H, W] bool / uint8, contiguous (a contiguous slice such as ``predict(...)[0][:, 0]`` of a
+        C = 1 output is fine) -> (masks, areas int64 [n] = pixels set afterwards, changed int64 [n] = pixels whose value changed).
+        A region is an 8-connected component and is small below `min_area` pixels; mode "holes" fills the small components of the
+        complement, "islands" clears the small components (keeping the largest when all are small; ties: the one whose first
+        pixel in row-major order comes first), "both" does holes, then islands.  `areas_out` / `changed_out`: None = a new
+        tensor, a caller-owned contiguous int64 [n] slice, or False = not wanted (the library gets NULL and the tuple holds None
+        there).  Asynchronous on the current stream."""
+        m = masks.view(torch.uint8) if masks.dtype == torch.bool else masks
+        if m.dim() != 3 or m.dtype != torch.uint8:
+            raise ValueError(f"masks must be bool / uint8 [n, H, W], got {masks.dtype} {tuple(masks.shape)}")
+        if not (m.is_cuda and m.is_contiguous()):
+            raise ValueError("masks must be a contiguous tensor on the engine's device (they are rewritten in place)")
+        code = REGION_MODES.get(mode) if isinstance(mode, str) else int(mode)
+        if code is None:
+            raise ValueError(f"mode must be one of {sorted(REGION_MODES)}, got {mode!r}")
+        n, h, w = m.shape
+        outs = []
+        for name, t in (("areas_out", areas_out), ("changed_out", changed_out)):
+            if t is False:
+                t = None
+            elif t is None:
+                t = torch.empty(n, dtype=torch.int64, device=self.device)
+            elif not (isinstance(t, torch.Tensor) and t.dtype == torch.int64 and t.is_cuda and t.is_contiguous() and t.numel() == n):
+                raise ValueError(f"{name} must be a contiguous int64 [{n}] tensor on the engine's device, None or False")
+            outs.append(t)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.samrs_clean_masks(self.handle, m.data_ptr(), n, h, w, int(min_area), code, _ptr(outs[0]),
+                                                   _ptr(outs[1]), _stream()))
+        return masks, outs[0], outs[1]
+
+    def region_labels(self, masks: torch.Tensor, complement: bool = False) -> torch.Tensor:
+        """Test hook (samrs_k_region_labels): int32 [n, H, W], every pixel's flattened root = the smallest row-major pixel index of
+        its 8-connected component of the set (complement: the unset) pixels, -1 outside that working set."""
+        m = masks.view(torch.uint8) if masks.dtype == torch.bool else masks
+        assert m.dim() == 3 and m.dtype == torch.uint8 and m.is_cuda and m.is_contiguous()
+        n, h, w = m.shape
+        out = torch.empty(n, h, w, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.samrs_k_region_labels(m.data_ptr(), n, h, w, int(bool(complement)), out.data_ptr(), _stream()))
+        return out
 
     def gt_match(self, masks: torch.Tensor, label_rgb: torch.Tensor, colors: torch.Tensor, inter_out: Optional[torch.Tensor] = None,
                  gt_area_out: Optional[torch.Tensor] = None, gt_masks_out: Optional[torch.Tensor] = None):

@@ -280,11 +280,15 @@ def run(args) -> Dict[str, List[int]]:
     # per-instance RLE (main_sam_hbox_semantic.py:201-202) is encoded on the device; the full masks never cross PCIe
     # --png-device: gray/ and color/ files encoded on the device (samrs_png_encode_labels); the host writes their bytes
     png_device = bool(getattr(args, "png_device", False))
+    # --min-region-area: islands and holes below that many pixels are removed from every mask on the device (samrs_clean_masks)
+    # before it is painted, counted and RLE-encoded
+    min_region_area = int(getattr(args, "min_region_area", 0) or 0)
     pipe = driver.TilePipeline(sam, n_classes, batch=batch, box_batch=args.box_batch, rle=not args.no_rle,
                                rle_buffer_mb=getattr(args, "rle_buffer_mb", 256), max_boxes=max_boxes,
                                out_depth=getattr(args, "out_depth", 4), png_lut=tile_io.class_lut(palette) if png_device else None,
                                png_buffer_mb=getattr(args, "png_buffer_mb", None),
-                               batch_decode=bool(getattr(args, "batch_decode", False)))
+                               batch_decode=bool(getattr(args, "batch_decode", False)),
+                               min_region_area=min_region_area, region_mode=getattr(args, "region_mode", "both"))
     # rank r takes chunks of `batch` consecutive stems: statically (r, r + world, ...) or from the shared counter (whose
     # store key must be unique per work list: a second run() in the same process group must not find a spent counter)
     import zlib
@@ -352,6 +356,7 @@ def run(args) -> Dict[str, List[int]]:
         return items
 
     done = [0]
+    cleaned = [0, 0]                 # --min-region-area: pixels changed, instances with a changed pixel (this run's images)
     sizes: List[int] = []
     writers = ThreadPoolExecutor(max_workers=n_writers)
     pending: List = []
@@ -397,6 +402,9 @@ def run(args) -> Dict[str, List[int]]:
         reap(block=False)
         for r in results:
             sizes.extend(int(a) for a in r.areas if a > 0)                                           # statistic.py:44-49
+            if r.changed is not None:
+                cleaned[0] += int(r.changed.sum())
+                cleaned[1] += int((r.changed > 0).sum())
         done[0] += len(results)
         if rank == 0 and (done[0] // batch) % 50 == 0:
             print(f"[rank 0] {done[0]} images", flush=True)
@@ -431,6 +439,12 @@ def run(args) -> Dict[str, List[int]]:
     all_sizes = driver.gather_mask_sizes(sizes)
     stats = {"class_pixel_num": pix.cpu().tolist(), "class_instance_num": ins.cpu().tolist(),
              "mask_num": len(all_sizes)}                                                             # statistic.py:53
+    if min_region_area > 0:          # what the clean-up did, over the images processed in THIS run (a resumed run's earlier images are not re-read)
+        dev = pipe.class_pixels.device
+        cpx, cin = driver.reduce_statistics(torch.tensor([cleaned[0]], dtype=torch.int64, device=dev),
+                                            torch.tensor([cleaned[1]], dtype=torch.int64, device=dev))
+        stats["region_cleanup"] = {"min_region_area": min_region_area, "region_mode": getattr(args, "region_mode", "both"),
+                                   "changed_pixel_num": int(cpx.item()), "changed_instance_num": int(cin.item())}
     if clock:
         stats["timing"] = {"images": done[0], "loop_seconds": wall, "stage_thread_seconds": dict(clock.t),   # this rank's loop
                            "readers": n_readers, "writers": n_writers, "cpu_budget": round(host_cpu_budget(), 1)}
@@ -490,7 +504,18 @@ def build_parser() -> argparse.ArgumentParser:
                     help="device buffer for one batch's PNG files with --png-device (default: 6 MiB per tile of --batch)")
     ap.add_argument("--batch-decode", action="store_true",
                     help="decode the boxes of all tiles of a batch in one decoder chain (Engine.predict_multi); same outputs")
+    add_region_arguments(ap, " Under --resume the totals cover the images processed in this run only.")
     return ap
+
+
+def add_region_arguments(ap: argparse.ArgumentParser, resume_note: str = "") -> None:
+    """--min-region-area / --region-mode, shared by this CLI and samrs_amd.instances."""
+    ap.add_argument("--min-region-area", type=int, default=0, metavar="N",
+                    help="remove mask islands and fill mask holes (8-connected regions) of fewer than N pixels on the GPU before the masks "
+                         "are painted, counted and RLE-encoded (segment_anything's remove_small_regions); 0 (default) = off.  The run's "
+                         "total changed pixels and changed instances go into the statistics output." + resume_note)
+    ap.add_argument("--region-mode", default="both", choices=["holes", "islands", "both"],
+                    help="with --min-region-area: fill small holes, remove small islands, or both (holes first)")
 
 
 def main(argv=None):

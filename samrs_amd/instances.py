@@ -256,7 +256,9 @@ def run(args) -> Optional[dict]:
     pipe = driver.InstancePipeline(sam, 1, prompt=args.prompt, multimask=multimask, fill_rule=getattr(args, "fill_rule", "auto"),
                                    gt=with_gt, batch=batch, box_batch=args.box_batch, max_boxes=max_boxes, rle=True,
                                    rle_buffer_mb=getattr(args, "rle_buffer_mb", 256), keep_masks=False,
-                                   batch_decode=bool(getattr(args, "batch_decode", False)))
+                                   batch_decode=bool(getattr(args, "batch_decode", False)),
+                                   min_region_area=int(getattr(args, "min_region_area", 0) or 0),
+                                   region_mode=getattr(args, "region_mode", "both"))
     os.makedirs(os.path.join(args.out, "parts"), exist_ok=True)
     import zlib
     wq_name = "samrs_ins/%08x" % zlib.crc32(("\n".join(todo) + "|" + args.out).encode())
@@ -315,7 +317,7 @@ def run(args) -> Optional[dict]:
     return rec
 
 
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="SAM instance masks + ground-truth evaluation on HRSC2016 (SAMRS) on MI355X")
     ap.add_argument("--images", required=True, help="image directory (HRSC: .bmp)")
     ap.add_argument("--annotations", required=True, help="HRSC XML directory (<stem>.xml)")
@@ -341,7 +343,13 @@ def main(argv=None):
     ap.add_argument("--resume", action="store_true", help="skip images whose fragment OUT/parts/<stem>.json already exists")
     ap.add_argument("--batch-decode", action="store_true",
                     help="decode the prompts of all images of a batch in one decoder chain (Engine.predict_multi); same outputs")
-    return run(ap.parse_args(argv))
+    from . import generate
+    generate.add_region_arguments(ap)
+    return ap
+
+
+def main(argv=None):
+    return run(build_parser().parse_args(argv))
 
 
 if __name__ == "__main__":

@@ -1,0 +1,122 @@
+#!/usr/bin/env python3
+"""What TilePipeline(min_region_area=16, region_mode="both") costs on the c2 shape (ViT-H, 8 x 1024^2 tiles per step, 32 boxes
+each, rle=True): the option off and on, arms alternating on one box, one JSON line per run with images/s of the loop and the
+decoder stream's time per step (hipEvents on the decoder stream around each batch's decode, after its wait for the encoder).
+Then samrs_clean_masks alone: ms per call on 32 masks of 1024^2, for the masks this (random-init) model paints and for a blob
+with 1 % pin-holes and 0.3 % speckle (the shape a trained model's masks have), one JSON line each.
+usage: clean_masks_bench.py [--steps 24] [--reps 2] [--model vit_h] [--warm 3] [--standalone-only]
+(`rocprofv3 --kernel-trace --stats -- python tools/clean_masks_bench.py --standalone-only` gives the split across the phases)"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(1, os.path.join(ROOT, "tests"))
+import samrs_amd  # noqa: E402
+from samrs_amd import driver, synth  # noqa: E402
+from region_ref import speckled_ellipse  # noqa: E402  (tests/region_ref.py: the blob-with-speckle recipe of the tests)
+
+BATCH, BOXES, T = 8, 32, 16
+
+
+def items(n):
+    base = [synth.make_image(i) for i in range(8)]
+    out = []
+    for i in range(n):
+        b, l = synth.make_boxes(i, BOXES)
+        out.append(driver.WorkItem(f"T{i:05d}", base[i % 8], b, l))
+    return out
+
+
+def run_arm(sam, work, on):
+    pipe = driver.TilePipeline(sam, 18, batch=BATCH, box_batch=BOXES, max_boxes=BOXES, rle=True, min_region_area=T if on else 0)
+    events = []
+    changed = [0]
+    # timing events around TilePipeline._decode, behind the wait for the encoder that _decode itself begins with (a private
+    # method, as in tools/batch_decode_bench.py: if _decode's first wait changes, this wrapper has to follow)
+    decode = pipe._decode
+
+    def timed(b, its, tiles, offs, out):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        pipe.s_dec.wait_event(pipe.ev_enc[b])          # the decode's own first wait: time the work, not the wait for the encoder
+        e0.record(pipe.s_dec)
+        decode(b, its, tiles, offs, out)
+        e1.record(pipe.s_dec)
+        events.append((e0, e1))
+
+    def sink(res, rel):
+        for r in res:
+            if r.changed is not None:
+                changed[0] += int(r.changed.sum())
+        rel()
+
+    pipe._decode = timed
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    n = pipe.run(driver.batched(work, BATCH), sink)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    dec = [a.elapsed_time(b) for a, b in events]
+    return {"arm": "clean_on" if on else "clean_off", "images": n, "images_per_s": round(n / dt, 1),
+            "decode_ms_per_step": round(sum(dec) / len(dec), 3), "decode_ms_per_step_min": round(min(dec), 3),
+            "changed_pixels_per_mask": round(changed[0] / (n * BOXES), 1)}
+
+
+def standalone(sam, name, masks, reps=10):
+    eng = sam.engine
+    work = torch.empty_like(masks)
+    ms = []
+    for mode in ("holes", "islands", "both"):
+        for _ in range(reps + 2):
+            work.copy_(masks)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            _, areas, changed = eng.clean_masks(work, T, mode)
+            e1.record()
+            torch.cuda.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        t = sorted(ms[-reps:])
+        print(json.dumps({"standalone": name, "mode": mode, "masks": int(masks.shape[0]), "side": int(masks.shape[-1]),
+                          "min_area": T, "ms_per_call_median": round(t[len(t) // 2], 3), "ms_per_call_min": round(t[0], 3),
+                          "changed_pixels_per_mask": round(float(changed.sum()) / masks.shape[0], 1)}), flush=True)
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=24)
+    ap.add_argument("--reps", type=int, default=2)
+    ap.add_argument("--model", default="vit_h")
+    ap.add_argument("--warm", type=int, default=3, help="steps of an unmeasured first run per arm")
+    ap.add_argument("--standalone-only", action="store_true", help="skip the pipeline arms")
+    a = ap.parse_args()
+    sd = synth.make_state_dict(synth.CONFIGS[a.model], 0)
+    sam = samrs_amd.sam_model_registry[a.model](state_dict=sd, precision="f16", max_images=2 * BATCH, max_prompts=64,
+                                                max_points=1).to("cuda")
+    if not a.standalone_only:
+        work = items(a.steps * BATCH)
+        for arm in (False, True):
+            run_arm(sam, work[:a.warm * BATCH], arm)
+        for rep in range(a.reps):
+            for arm in (False, True):
+                r = run_arm(sam, work, arm)
+                r["rep"] = rep
+                print(json.dumps(r), flush=True)
+    # the call alone: the masks this model paints for one tile's 32 boxes, and 32 blobs with speckle
+    pred = samrs_amd.SamPredictor(sam)
+    pred.set_image(synth.make_image(0))
+    b, _ = synth.make_boxes(0, BOXES)
+    tb = pred.transform.apply_boxes_torch(torch.from_numpy(b).cuda(), (1024, 1024))
+    masks, _, _ = pred.predict_torch(None, None, tb, None, multimask_output=False)
+    standalone(sam, "decoder_masks_random_init", masks[:, 0].view(torch.uint8).contiguous())
+    standalone(sam, "blob_with_speckle", torch.from_numpy(np.stack([speckled_ellipse(i) for i in range(BOXES)])).cuda())
+    sam.engine.close()
+
+
+if __name__ == "__main__":
+    main()
