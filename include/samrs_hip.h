@@ -203,6 +203,33 @@ int samrs_gt_match(samrs_engine_t* e, const uint8_t* masks, int n, int h, int w,
 int samrs_rle_encode(samrs_engine_t* e, const uint8_t* masks, int n, int h, int w, uint8_t* out, int64_t out_capacity,
                      int64_t* cursor, int64_t* table, void* stream);
 
+/* -- scene mode: a scene larger than the encoder's input is decoded window by window (samrs_amd/scene.py plans the windows; every
+ * box is decoded in exactly one), and the windows' masks are composited in the scene's own frame on the device.  The reference's
+ * rule "boxes are painted in annotation order, a later box wins" (main_sam_hbox_semantic.py:162,195-199) holds across windows
+ * through a caller-owned map of the highest annotation rank set at each pixel.
+ *
+ * samrs_scene_claim: masks uint8 [n][h][w] (non-zero = set): the masks of one predict call, all decoded in the window
+ * (x0, y0, w, h) of an H x W scene.  ranks int32 [n] (device): each mask's position in the scene's annotation order.  order int32
+ * [H][W], caller-owned, initialised to -1: order[p] = max(order[p], max{ranks[j] : mask j set at p}).  areas_out / class_pixels /
+ * class_instances: exactly samrs_paint's (labels int32 [n], may be NULL when both class arrays are).  A pixel has one writer per
+ * call: calls on one map must be stream-ordered with each other, and then the map does not depend on their order.  n == 0 is a
+ * no-op.  16-byte mask loads when w % 16 == 0 and masks is 16-byte aligned, byte loads otherwise.
+ * samrs_scene_resolve: seg[p] = order[p] < 0 ? 255 : (uint8) labels_by_rank[order[p]] (labels_by_rank int32 [n_ranks], device; a
+ * rank >= n_ranks resolves to 255).
+ * A window not inside the scene, n < 0 or a null pointer: SAMRS_ERR_BAD_ARG, and nothing is written. */
+int samrs_scene_claim(samrs_engine_t* e, const uint8_t* masks, const int32_t* ranks, const int32_t* labels, int n, int h, int w,
+                      int x0, int y0, int H, int W, int32_t* order, int64_t* areas_out,
+                      int64_t* class_pixels, int64_t* class_instances, int n_classes, void* stream);
+int samrs_scene_resolve(samrs_engine_t* e, const int32_t* order, const int32_t* labels_by_rank, int n_ranks, int H, int W,
+                        uint8_t* seg, void* stream);
+/* samrs_rle_encode of each mask as if pasted at (x0, y0) on an all-zero H x W canvas, without materialising the canvas: table /
+ * cursor / overflow protocol unchanged; the strings are those of {"size": [H, W]}.  H * W < 2^30 and w < 8192; a window not inside
+ * the canvas, n < 0 or a size over the limit: SAMRS_ERR_BAD_ARG.  n == 0 is a no-op.  Shares the handle's RLE scratch with
+ * samrs_rle_encode (stream-ordered with each other); a call with many or large masks runs as consecutive chunks on the stream so
+ * that the scratch stays below 256 MiB, or one mask's worth. */
+int samrs_rle_encode_placed(samrs_engine_t* e, const uint8_t* masks, int n, int h, int w, int x0, int y0, int H, int W,
+                            uint8_t* out, int64_t out_capacity, int64_t* cursor, int64_t* table, void* stream);
+
 /* -- mask clean-up before the masks become labels: `remove_small_regions` of utils/amg.py:267-291 on the device, for a batch of
  * masks that never leave HBM (the reference's runs on the host through cv2, one mask per call).  masks uint8 [n][h][w] device, in /
  * out (non-zero = set in, 0 / 1 out): the C = 1 output of samrs_predict, or the kept masks of samrs_select_best.  A region is an

@@ -2053,6 +2053,62 @@ int samrs_rle_encode(samrs_engine_t* e, const uint8_t* masks, int n, int h, int 
     return SAMRS_OK;
 }
 
+// scene mode (see samrs_hip.h): one window's masks into the scene's rank map, the map into the class map, and the window's masks
+// as COCO RLE strings in the scene's frame
+int samrs_scene_claim(samrs_engine_t* e, const uint8_t* masks, const int32_t* ranks, const int32_t* labels, int n, int h, int w,
+                      int x0, int y0, int H, int W, int32_t* order, int64_t* areas, int64_t* cpix, int64_t* cins, int n_classes,
+                      void* stream) {
+    if (!e || (n > 0 && (!masks || !ranks)) || !order || n < 0 || h < 1 || w < 1 || H < 1 || W < 1)
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_scene_claim: bad argument");
+    if (x0 < 0 || y0 < 0 || x0 > W - w || y0 > H - h)
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_scene_claim: window (%d, %d, %d, %d) is not inside the %d x %d scene", x0, y0, w, h, H, W);
+    if ((cpix || cins) && (!areas || !labels)) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_scene_claim: class statistics need areas_out and labels");
+    ON_DEVICE(e);
+    CK(e, launch_scene_claim(masks, ranks, labels, n, h, w, x0, y0, H, W, order, (unsigned long long*)areas, (unsigned long long*)cpix,
+                             (unsigned long long*)cins, n_classes, (hipStream_t)stream));
+    return SAMRS_OK;
+}
+int samrs_scene_resolve(samrs_engine_t* e, const int32_t* order, const int32_t* labels_by_rank, int n_ranks, int H, int W, uint8_t* seg,
+                        void* stream) {
+    if (!e || !order || !seg || n_ranks < 0 || (n_ranks > 0 && !labels_by_rank) || H < 1 || W < 1)
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_scene_resolve: bad argument");
+    ON_DEVICE(e);
+    CK(e, launch_scene_resolve(order, labels_by_rank, n_ranks, H, W, seg, (hipStream_t)stream));
+    return SAMRS_OK;
+}
+int samrs_rle_encode_placed(samrs_engine_t* e, const uint8_t* masks, int n, int h, int w, int x0, int y0, int H, int W, uint8_t* out,
+                            int64_t out_capacity, int64_t* cursor, int64_t* table, void* stream) {
+    if (!e || (n > 0 && (!masks || !table)) || !out || !cursor || n < 0 || h < 1 || w < 1 || H < 1 || W < 1 || out_capacity < 16)
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_rle_encode_placed: bad argument");
+    if (x0 < 0 || y0 < 0 || x0 > W - w || y0 > H - h)
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_rle_encode_placed: window (%d, %d, %d, %d) is not inside the %d x %d canvas", x0, y0, w, h, H, W);
+    if ((size_t)H * W >= (1ull << 30) || w >= 8192)
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_rle_encode_placed: canvas or window too large (H * W must be < 2^30, w < 8192)");
+    if (n == 0) return SAMRS_OK;
+    ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    // masks per pass: as many as keep the scratch below 256 MiB (32 at most, as samrs_rle_encode), one at least
+    const size_t per = rle_placed_scratch_bytes(1, h, w, x0, H, W);
+    int chunk = (int)(((size_t)256 << 20) / per);
+    chunk = chunk < 1 ? 1 : (chunk > 32 ? 32 : chunk);
+    const size_t need = rle_placed_scratch_bytes(n < chunk ? n : chunk, h, w, x0, H, W);
+    if (need > e->rle_scratch_bytes) {
+        if (e->rle_scratch) {
+            CK(e, hipStreamSynchronize(s));
+            CK(e, hipFree(e->rle_scratch));               // device-synchronising: nothing still reads the old scratch
+            e->rle_scratch = nullptr; e->rle_scratch_bytes = 0;
+        }
+        CK(e, hipMalloc(&e->rle_scratch, need));
+        e->rle_scratch_bytes = need;
+    }
+    for (int off = 0; off < n; off += chunk) {
+        const int m = n - off < chunk ? n - off : chunk;
+        CK(e, launch_rle_encode_placed(masks + (size_t)off * h * w, m, h, w, x0, y0, H, W, e->rle_scratch, out, (long long)out_capacity,
+                                       (long long*)cursor, (long long*)table + (size_t)off * 3, s));
+    }
+    return SAMRS_OK;
+}
+
 // small islands and holes of n masks removed in place (see samrs_hip.h)
 int samrs_clean_masks(samrs_engine_t* e, uint8_t* masks, int n, int h, int w, int min_area, int mode, int64_t* areas_out,
                       int64_t* changed_out, void* stream) {

@@ -244,6 +244,22 @@ size_t rle_scratch_bytes(int n, int h, int w);
 hipError_t launch_rle_encode(const uint8_t* masks, int n, int h, int w, void* scratch, unsigned char* out, long long out_cap,
                              long long* cursor, long long* table, hipStream_t s);
 
+// the same for masks [n][h][w] pasted at (x0, y0) on an all-zero H x W canvas (scene mode): strings, table and cursor as above,
+// in the canvas's frame.  H * W < 2^30, w + 1 <= 8192.  scratch: rle_placed_scratch_bytes(n, h, w, x0, H, W).
+size_t rle_placed_scratch_bytes(int n, int h, int w, int x0, int H, int W);
+hipError_t launch_rle_encode_placed(const uint8_t* masks, int n, int h, int w, int x0, int y0, int H, int W, void* scratch,
+                                    unsigned char* out, long long out_cap, long long* cursor, long long* table, hipStream_t s);
+
+// ---- scene_kernels.hip ----------------------------------------------------------------------
+// order int32 [H][W] (-1 = unclaimed): order[p] = max(order[p], max{ranks[j] : mask j set at p}) over the masks uint8 [n][h][w] of
+// the window (x0, y0, w, h); areas (zeroed, then counted) and the class statistics as launch_paint.  n == 0 is a no-op.
+hipError_t launch_scene_claim(const uint8_t* masks, const int32_t* ranks, const int32_t* labels, int n, int h, int w, int x0, int y0,
+                              int H, int W, int32_t* order, unsigned long long* areas, unsigned long long* class_pixels,
+                              unsigned long long* class_instances, int n_classes, hipStream_t s);
+// seg[p] = order[p] < 0 ? 255 : (uint8) labels_by_rank[order[p]]
+hipError_t launch_scene_resolve(const int32_t* order, const int32_t* labels_by_rank, int n_ranks, int H, int W, uint8_t* seg,
+                                hipStream_t s);
+
 // ---- png_kernels.hip ------------------------------------------------------------------------
 // gray/<stem>.png and color/<stem>.png of n class maps (uint8 [n][h][w] on the device, lut uint8 [256][3] on the device), byte-
 // identical with libsamrs_io's samrs_io_png_write_label_pair.  Files packed behind *cursor into `out` (16-byte aligned, capacity

@@ -78,6 +78,60 @@ __global__ __launch_bounds__(256) void rle_bitpack_kernel(const uint8_t* __restr
     }
 }
 
+// The same bit matrix for a mask [h][w] pasted at (x0, y0) on an all-zero canvas of H rows: WC = w (+ 1) columns of ceil(H / 32)
+// words, canvas rows outside [y0, y0 + h) zero, and -- when the window does not touch the canvas's right edge -- one all-zero
+// column behind the window, so that a run reaching the bottom of the window's last column ends there.  Thread t: window columns
+// 4t .. 4t + 3 of the block's 1024, canvas rows 128 blockIdx.x .. + 127.
+__global__ __launch_bounds__(256) void rle_bitpack_placed_kernel(const uint8_t* __restrict__ masks, uint32_t* __restrict__ bits,
+                                                                 int h, int w, int y0, int H, int WC, int YW) {
+    const int m = blockIdx.y;
+    const int x = blockIdx.z * 1024 + threadIdx.x * 4;
+    const int yb = blockIdx.x * 128;
+    if (x >= WC) return;
+    const uint8_t* src = masks + (size_t)m * h * w;
+    uint32_t wd[4][4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) wd[c][r] = 0u;
+    const bool wide = (w & 3) == 0 && (((uintptr_t)src) & 3) == 0;       // whole 4-byte words of a row
+    if (x < w && yb < y0 + h && yb + 128 > y0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+#pragma unroll 8
+            for (int b = 0; b < 32; ++b) {
+                const int y = yb + 32 * r + b - y0;                        // window row
+                uint32_t px = 0u;
+                if (y >= 0 && y < h) {
+                    if (wide) {
+                        px = *reinterpret_cast<const uint32_t*>(src + (size_t)y * w + x);
+                    } else {
+#pragma unroll
+                        for (int c = 0; c < 4; ++c)
+                            if (x + c < w) px |= (uint32_t)src[(size_t)y * w + x + c] << (8 * c);
+                    }
+                }
+                const uint32_t t = nz_bytes(px);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) wd[c][r] |= ((t >> (8 * c + 7)) & 1u) << b;
+            }
+        }
+    }
+    const int yw0 = blockIdx.x * 4;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        if (x + c >= WC) break;
+        uint32_t* dst = bits + ((size_t)m * WC + x + c) * YW + yw0;
+        if (yw0 + 4 <= YW && (YW & 3) == 0) {
+            *reinterpret_cast<uint4*>(dst) = make_uint4(wd[c][0], wd[c][1], wd[c][2], wd[c][3]);
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if (yw0 + r < YW) dst[r] = wd[c][r];
+        }
+    }
+}
+
 // exclusive block scan of one value per thread (blockDim.x <= 1024 threads, a multiple of 64); returns the exclusive prefix,
 // *total = sum
 __device__ __forceinline__ uint32_t block_scan_excl(uint32_t v, uint32_t* sm /*[17]*/, uint32_t* total) {
@@ -126,12 +180,13 @@ __host__ __device__ inline size_t rle_ctr_chunk(int n, int m, int c) { return (s
 __host__ __device__ inline size_t rle_ctr_blk(int n, int m, int b) { return (size_t)n * (1 + RLE_CC_MAX) + (size_t)m * RLE_NB + b; }
 
 // Run boundaries: element i (column-major) is one <=> v[i] != v[i-1], v[-1] = 0.  grid (column chunks, n), thread = column.
+// pos_base: the position of the bit matrix's first element (0; x0 H for a window placed on a canvas: launch_rle_encode_placed).
 // WRITE = false: boundaries per chunk -> col_chunk; WRITE = true: positions (uint32, ascending) behind the chunks before it, and
 // the last chunk's block publishes n_counts = boundaries + 1.  A column's words are read four at a time.
 template <bool WRITE>
 __global__ __launch_bounds__(RLE_COLS) void rle_positions_kernel(const uint32_t* __restrict__ bits_all, uint32_t* __restrict__ pos_all,
                                                                  uint32_t* __restrict__ ctr, int n, int H, int W, int YW,
-                                                                 size_t pos_stride) {
+                                                                 size_t pos_stride, uint32_t pos_base) {
     __shared__ uint32_t sm[17];
     const int m = blockIdx.y, chunk = blockIdx.x;
     const uint32_t* bits = bits_all + (size_t)m * W * YW;
@@ -193,7 +248,7 @@ __global__ __launch_bounds__(RLE_COLS) void rle_positions_kernel(const uint32_t*
                 while (t) {
                     const int b = __ffs((int)t) - 1;
                     t &= t - 1;
-                    pos[off++] = (uint32_t)x * (uint32_t)H + (uint32_t)(yw * 32 + b);
+                    pos[off++] = pos_base + (uint32_t)x * (uint32_t)H + (uint32_t)(yw * 32 + b);
                 }
             }
         }
@@ -312,8 +367,47 @@ hipError_t launch_rle_encode(const uint8_t* masks, int n, int h, int w, void* sc
     uint32_t* ctr = reinterpret_cast<uint32_t*>(p);
     const uint32_t HW = (uint32_t)((size_t)h * w);
     rle_bitpack_kernel<<<dim3((h + 127) / 128, n, (w + 1023) / 1024), 256, 0, s>>>(masks, bits, h, w, YW);
-    rle_positions_kernel<false><<<dim3(chunks, n), RLE_COLS, 0, s>>>(bits, pos, ctr, n, h, w, YW, pos_stride);
-    rle_positions_kernel<true><<<dim3(chunks, n), RLE_COLS, 0, s>>>(bits, pos, ctr, n, h, w, YW, pos_stride);
+    rle_positions_kernel<false><<<dim3(chunks, n), RLE_COLS, 0, s>>>(bits, pos, ctr, n, h, w, YW, pos_stride, 0u);
+    rle_positions_kernel<true><<<dim3(chunks, n), RLE_COLS, 0, s>>>(bits, pos, ctr, n, h, w, YW, pos_stride, 0u);
+    rle_chars_kernel<false><<<dim3(RLE_NB, n), RLE_THREADS, 0, s>>>(pos, ctr, n, HW, pos_stride, out, out_cap, cursor, table);
+    rle_chars_kernel<true><<<dim3(RLE_NB, n), RLE_THREADS, 0, s>>>(pos, ctr, n, HW, pos_stride, out, out_cap, cursor, table);
+    rle_cursor_kernel<<<1, 64, 0, s>>>(ctr, cursor, out_cap, n);
+    return hipGetLastError();
+}
+
+// ---- a window's masks encoded in the frame of a larger canvas (scene mode) ------------------------------------------------------
+// Mask [h][w] pasted at (x0, y0) on an all-zero H x W canvas: the bit matrix is built per WINDOW column over the CANVAS height, so
+// runs join across columns exactly when the canvas's column-major order says so (h == H), positions start at x0 H, and the last
+// count runs to H W.  Boundaries: one per window pixel at most, one below each column (y0 + h < H) or one behind the last column.
+static inline int rle_placed_cols(int w, int x0, int W) { return w + (x0 + w < W ? 1 : 0); }
+static inline size_t rle_placed_pos_stride(int h, int w) { return ((size_t)h + 1) * w + 2; }
+size_t rle_placed_scratch_bytes(int n, int h, int w, int x0, int H, int W) {
+    const size_t yw = (size_t)(H + 31) / 32;
+    const size_t bits = (((size_t)n * rle_placed_cols(w, x0, W) * yw * 4) + 255) & ~(size_t)255;
+    const size_t pos = (((size_t)n * rle_placed_pos_stride(h, w) * 4) + 255) & ~(size_t)255;
+    const size_t ctr = (size_t)n * (1 + RLE_CC_MAX + RLE_NB) * 4 + 256;
+    return bits + pos + ctr;
+}
+
+hipError_t launch_rle_encode_placed(const uint8_t* masks, int n, int h, int w, int x0, int y0, int H, int W, void* scratch,
+                                    unsigned char* out, long long out_cap, long long* cursor, long long* table, hipStream_t s) {
+    if (n < 1 || h < 1 || w < 1 || x0 < 0 || y0 < 0 || x0 > W - w || y0 > H - h || (size_t)H * W >= (1ull << 30))
+        return hipErrorInvalidValue;
+    const int WC = rle_placed_cols(w, x0, W);
+    const int chunks = (WC + RLE_COLS - 1) / RLE_COLS;
+    if (chunks > RLE_CC_MAX) return hipErrorInvalidValue;
+    const int YW = (H + 31) / 32;
+    unsigned char* p = reinterpret_cast<unsigned char*>(scratch);
+    uint32_t* bits = reinterpret_cast<uint32_t*>(p);
+    p += (((size_t)n * WC * YW * 4) + 255) & ~(size_t)255;
+    uint32_t* pos = reinterpret_cast<uint32_t*>(p);
+    const size_t pos_stride = rle_placed_pos_stride(h, w);
+    p += (((size_t)n * pos_stride * 4) + 255) & ~(size_t)255;
+    uint32_t* ctr = reinterpret_cast<uint32_t*>(p);
+    const uint32_t HW = (uint32_t)((size_t)H * W), base = (uint32_t)((size_t)x0 * H);
+    rle_bitpack_placed_kernel<<<dim3((H + 127) / 128, n, (WC + 1023) / 1024), 256, 0, s>>>(masks, bits, h, w, y0, H, WC, YW);
+    rle_positions_kernel<false><<<dim3(chunks, n), RLE_COLS, 0, s>>>(bits, pos, ctr, n, H, WC, YW, pos_stride, base);
+    rle_positions_kernel<true><<<dim3(chunks, n), RLE_COLS, 0, s>>>(bits, pos, ctr, n, H, WC, YW, pos_stride, base);
     rle_chars_kernel<false><<<dim3(RLE_NB, n), RLE_THREADS, 0, s>>>(pos, ctr, n, HW, pos_stride, out, out_cap, cursor, table);
     rle_chars_kernel<true><<<dim3(RLE_NB, n), RLE_THREADS, 0, s>>>(pos, ctr, n, HW, pos_stride, out, out_cap, cursor, table);
     rle_cursor_kernel<<<1, 64, 0, s>>>(ctr, cursor, out_cap, n);

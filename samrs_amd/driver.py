@@ -324,6 +324,8 @@ class TileResult:
     png_table: Optional[np.ndarray] = None  # int64 [2, 2] (offset, length) of the gray and the colour PNG in png_data (png_lut)
     png_data: Optional[np.ndarray] = None   # uint8 view of the batch's pinned PNG byte buffer
     changed: Optional[np.ndarray] = None    # int64 [n_boxes] pixels the small-region clean-up changed (min_region_area > 0)
+    windows: Optional[List[Tuple[int, int, int, int]]] = None   # scene mode (scene.ScenePipeline): the planned (x0, y0, w, h) windows
+    window_of: Optional[List[int]] = None   # scene mode: window_of[j] = index into `windows` of the window box j was decoded in
 
     def png(self, kind: str) -> memoryview:
         """The bytes of ``gray/<stem>.png`` (kind "gray") or ``color/<stem>.png`` ("color") of this tile, encoded on the device

@@ -102,6 +102,11 @@ def load_library() -> C.CDLL:
     lib.samrs_set_option.argtypes = [vp, C.c_char_p, ip]
     lib.samrs_get_option.argtypes = [vp, C.c_char_p, C.POINTER(ip)]
     lib.samrs_rle_encode.argtypes = [vp, vp, ip, ip, ip, vp, C.c_int64, vp, vp, vp]
+    lib.samrs_scene_claim.argtypes = [vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, ip, vp, vp, vp, vp, ip, vp]
+    lib.samrs_scene_resolve.argtypes = [vp, vp, vp, ip, ip, ip, vp, vp]
+    lib.samrs_rle_encode_placed.argtypes = [vp, vp, ip, ip, ip, ip, ip, ip, ip, vp, C.c_int64, vp, vp, vp]
+    for name in ("samrs_scene_claim", "samrs_scene_resolve", "samrs_rle_encode_placed"):
+        getattr(lib, name).restype = ip
     lib.samrs_k_convert_split.argtypes = [ip, vp, vp, vp, C.c_int64, vp]
     lib.samrs_select_best.argtypes = [vp, vp, vp, ip, ip, ip, ip, vp, vp, vp, vp]
     lib.samrs_gt_match.argtypes = [vp, vp, ip, ip, ip, vp, vp, vp, vp, vp, vp]
@@ -693,3 +698,72 @@ class Engine:
             self._check(self.lib.samrs_paint(self.handle, m.data_ptr(), labels.data_ptr(), n, h, w, seg.data_ptr(),
                                              areas.data_ptr(), _ptr(class_pixels), _ptr(class_instances), ncls, _stream()))
         return areas
+
+    # -- scene mode (samrs_amd/scene.py): windows of one large scene composited in the scene's frame ------------------------
+    def _check_scene(self, rc: int) -> None:
+        """A window that is not inside its scene is a caller's planning error, not a malformed prompt: EngineError."""
+        if rc == ERR_BAD_ARG:
+            raise EngineError(self.lib.samrs_last_error(self.handle).decode())
+        self._check(rc)
+
+    def scene_claim(self, masks: torch.Tensor, ranks: torch.Tensor, window: Sequence[int], order: torch.Tensor,
+                    labels: Optional[torch.Tensor] = None, class_pixels: Optional[torch.Tensor] = None,
+                    class_instances: Optional[torch.Tensor] = None, areas_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The masks of one predict call ([n, h, w] bool / uint8), all decoded in `window` = (x0, y0, w, h) of the scene whose rank
+        map is `order` (int32 [H, W] on this device, initialised to -1): order[p] = max(order[p], ranks[j]) wherever mask j is set
+        (`ranks` int32 [n]: the masks' positions in the scene's annotation order).  Areas and class statistics as `paint`; see
+        samrs_scene_claim in samrs_hip.h.  Asynchronous on the current stream."""
+        m = masks.view(torch.uint8) if masks.dtype == torch.bool else masks
+        m = (m if m.dim() == 3 else m.reshape(-1, m.shape[-2], m.shape[-1])).contiguous()
+        n, h, w = m.shape
+        x0, y0, ww, wh = (int(v) for v in window)
+        if (ww, wh) != (w, h):
+            raise ValueError(f"window {tuple(window)} does not have the masks' size {w} x {h}")
+        assert order.dtype == torch.int32 and order.dim() == 2 and order.is_cuda and order.is_contiguous()
+        H, W = int(order.shape[0]), int(order.shape[1])
+        ranks = ranks.to(dtype=torch.int32, device=self.device).contiguous()
+        assert ranks.numel() == n
+        if labels is not None:
+            labels = labels.to(dtype=torch.int32, device=self.device).contiguous()
+            assert labels.numel() == n
+        if areas_out is not None:
+            assert areas_out.dtype == torch.int64 and areas_out.is_contiguous() and areas_out.numel() == n and areas_out.is_cuda
+        areas = areas_out if areas_out is not None else torch.empty(n, dtype=torch.int64, device=self.device)
+        ncls = 0 if class_pixels is None else class_pixels.numel()
+        with torch.cuda.device(self.device):
+            self._check_scene(self.lib.samrs_scene_claim(self.handle, m.data_ptr(), ranks.data_ptr(), _ptr(labels), n, h, w, x0, y0, H, W,
+                                                         order.data_ptr(), areas.data_ptr(), _ptr(class_pixels), _ptr(class_instances),
+                                                         ncls, _stream()))
+        return areas
+
+    def scene_resolve(self, order: torch.Tensor, labels_by_rank: torch.Tensor, seg: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The scene's class map from its rank map: seg[p] = 255 where order[p] < 0, else the label of annotation order[p]
+        (samrs_scene_resolve); `seg`: a caller-owned contiguous uint8 [H, W], or None for a new tensor."""
+        assert order.dtype == torch.int32 and order.dim() == 2 and order.is_cuda and order.is_contiguous()
+        H, W = int(order.shape[0]), int(order.shape[1])
+        lab = labels_by_rank.to(dtype=torch.int32, device=self.device).contiguous()
+        if seg is None:
+            seg = torch.empty(H, W, dtype=torch.uint8, device=self.device)
+        assert seg.dtype == torch.uint8 and seg.is_cuda and seg.is_contiguous() and tuple(seg.shape) == (H, W)
+        with torch.cuda.device(self.device):
+            self._check_scene(self.lib.samrs_scene_resolve(self.handle, order.data_ptr(), lab.data_ptr() if lab.numel() else None,
+                                                           lab.numel(), H, W, seg.data_ptr(), _stream()))
+        return seg
+
+    def rle_encode_placed(self, masks: torch.Tensor, window: Sequence[int], size: Sequence[int], out: torch.Tensor,
+                          cursor: torch.Tensor, table: torch.Tensor) -> None:
+        """`rle_encode` of each mask ([n, h, w] bool / uint8) as if pasted at `window` = (x0, y0, w, h) on an all-zero canvas of
+        `size` = (H, W): the strings of ``{"size": [H, W]}``, without the canvas ever existing (samrs_rle_encode_placed)."""
+        m = masks.view(torch.uint8) if masks.dtype == torch.bool else masks
+        m = (m if m.dim() == 3 else m.reshape(-1, m.shape[-2], m.shape[-1])).contiguous()
+        n, h, w = m.shape
+        x0, y0, ww, wh = (int(v) for v in window)
+        if (ww, wh) != (w, h):
+            raise ValueError(f"window {tuple(window)} does not have the masks' size {w} x {h}")
+        assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and out.data_ptr() % 16 == 0
+        assert cursor.dtype == torch.int64 and cursor.is_cuda and table.dtype == torch.int64 and table.is_cuda
+        assert table.is_contiguous() and table.numel() >= 3 * n
+        with torch.cuda.device(self.device):
+            self._check_scene(self.lib.samrs_rle_encode_placed(self.handle, m.data_ptr(), n, h, w, x0, y0, int(size[0]), int(size[1]),
+                                                               out.data_ptr(), out.numel(), cursor.data_ptr(), table.data_ptr(),
+                                                               _stream()))

@@ -283,12 +283,23 @@ def run(args) -> Dict[str, List[int]]:
     # --min-region-area: islands and holes below that many pixels are removed from every mask on the device (samrs_clean_masks)
     # before it is painted, counted and RLE-encoded
     min_region_area = int(getattr(args, "min_region_area", 0) or 0)
-    pipe = driver.TilePipeline(sam, n_classes, batch=batch, box_batch=args.box_batch, rle=not args.no_rle,
-                               rle_buffer_mb=getattr(args, "rle_buffer_mb", 256), max_boxes=max_boxes,
-                               out_depth=getattr(args, "out_depth", 4), png_lut=tile_io.class_lut(palette) if png_device else None,
-                               png_buffer_mb=getattr(args, "png_buffer_mb", None),
-                               batch_decode=bool(getattr(args, "batch_decode", False)),
-                               min_region_area=min_region_area, region_mode=getattr(args, "region_mode", "both"))
+    # --scene-window: images larger than the window are decoded window by window and composited in their own frame on the device
+    # (scene.ScenePipeline); the files written per image stem are the same, at the scene's size
+    scene_window = int(getattr(args, "scene_window", 0) or 0)
+    if scene_window > 0:
+        from . import scene
+        pipe = scene.ScenePipeline(sam, n_classes, window=scene_window, overlap=getattr(args, "scene_overlap", 256),
+                                   context=getattr(args, "scene_context", 2.0), batch=batch, box_batch=args.box_batch,
+                                   rle=not args.no_rle, rle_buffer_mb=getattr(args, "rle_buffer_mb", 256),
+                                   png_lut=tile_io.class_lut(palette) if png_device else None,
+                                   min_region_area=min_region_area, region_mode=getattr(args, "region_mode", "both"))
+    else:
+        pipe = driver.TilePipeline(sam, n_classes, batch=batch, box_batch=args.box_batch, rle=not args.no_rle,
+                                   rle_buffer_mb=getattr(args, "rle_buffer_mb", 256), max_boxes=max_boxes,
+                                   out_depth=getattr(args, "out_depth", 4), png_lut=tile_io.class_lut(palette) if png_device else None,
+                                   png_buffer_mb=getattr(args, "png_buffer_mb", None),
+                                   batch_decode=bool(getattr(args, "batch_decode", False)),
+                                   min_region_area=min_region_area, region_mode=getattr(args, "region_mode", "both"))
     # rank r takes chunks of `batch` consecutive stems: statically (r, r + world, ...) or from the shared counter (whose
     # store key must be unique per work list: a second run() in the same process group must not find a spent counter)
     import zlib
@@ -417,7 +428,10 @@ def run(args) -> Dict[str, List[int]]:
         run_log.write(json.dumps({"t": 0.0, "rank": rank, "world": world, "model": args.model, "split": pipe.split_mode if pipe.split_mode is not None else sam.engine.get_option("split"),
                                   "images_total": n_all, "images_todo": len(stems), "batch": batch, "box_batch": args.box_batch}) + "\n")
     try:
-        pipe.run(batches(), sink)
+        if scene_window > 0:
+            pipe.run((it for items in batches() for it in items), sink)
+        else:
+            pipe.run(batches(), sink)
         if clock: clock.add("loop.pipe_run_total", t_run)
     finally:
         writers.shutdown(wait=True)
@@ -459,8 +473,22 @@ def run(args) -> Dict[str, List[int]]:
     return stats
 
 
+class _Parser(argparse.ArgumentParser):
+    """Flag combinations that would otherwise be silently ignored are usage errors."""
+
+    def parse_args(self, args=None, namespace=None):
+        ns = super().parse_args(args, namespace)
+        if ns.scene_window < 0:
+            self.error("--scene-window must be >= 0 (0 = off)")
+        if ns.scene_window > 0 and ns.batch_decode:
+            self.error("--batch-decode does not apply with --scene-window: scene mode decodes each window's boxes on their own")
+        if ns.scene_window > 0 and not 0 <= ns.scene_overlap < ns.scene_window:
+            self.error("--scene-overlap must satisfy 0 <= overlap < --scene-window")
+        return ns
+
+
 def build_parser() -> argparse.ArgumentParser:
-    ap = argparse.ArgumentParser(description="SAM box -> semantic label generation (SAMRS) on MI355X")
+    ap = _Parser(description="SAM box -> semantic label generation (SAMRS) on MI355X")
     ap.add_argument("--images", required=True)
     ap.add_argument("--boxes", required=True)
     ap.add_argument("--out", required=True)
@@ -504,6 +532,13 @@ def build_parser() -> argparse.ArgumentParser:
                     help="device buffer for one batch's PNG files with --png-device (default: 6 MiB per tile of --batch)")
     ap.add_argument("--batch-decode", action="store_true",
                     help="decode the boxes of all tiles of a batch in one decoder chain (Engine.predict_multi); same outputs")
+    ap.add_argument("--scene-window", type=int, default=0, metavar="N",
+                    help="scene mode: decode images larger than N pixels window by window (N x N windows, each box in exactly one) and "
+                         "composite class map, areas and RLE in the image's own frame on the GPU; 0 (default) = off: every image is "
+                         "one SAM image")
+    ap.add_argument("--scene-overlap", type=int, default=256, help="with --scene-window: pixels neighbouring windows share")
+    ap.add_argument("--scene-context", type=float, default=2.0,
+                    help="with --scene-window: a box no grid window holds gets a window of its own, this many times its longer side")
     add_region_arguments(ap, " Under --resume the totals cover the images processed in this run only.")
     return ap
 
