@@ -585,6 +585,13 @@ __device__ __forceinline__ void store_attention_row_mx(const f32x16_t (&O)[DT], 
 // =========================================================================================
 // windowed attention.  Work item = (window, head); 8 waves, wave w < 7 owns the 32-query strip w
 // (7 strips cover the 196 window tokens), keys are visited tile by tile with an online softmax.
+// The REAL queries of an item are numbered densely: a bottom / right window of real extent vh x vw
+// holds nq = vh * vw of them, slot q = (q / vw, q % vw), and only the first ceil(nq / 32) waves run
+// the tile loop (grid 64: 4 strips instead of 7 in the 8 edge windows of an image, 2 in the corner:
+// 146 strips per (image, head) instead of 175).  Only the queries move: the key side, padding keys
+// included, is the same for every query as with the window-order numbering (dense = 0,
+// SAMRS_WIN_DENSE=0), and a query's result does not depend on which lane or strip carries it, so
+// the output is bit-identical.
 // qkv rows are in plain TOKEN order [img][y][x]; the kernel does the window partition itself.  A
 // window position that falls in the bottom/right padding is a zero token after norm1 in the
 // reference (image_encoder.py:168-172,256-259), so its k / v are exactly the qkv BIAS: the kernel
@@ -647,7 +654,8 @@ __global__ __launch_bounds__(512) void window_attention_kernel(
     const float* __restrict__ rel_w, uint16_t* __restrict__ out, int grid, int heads, int n_items,
     uint16_t* __restrict__ out_lo = nullptr /* LO == 1: the split remainder of out (reference-grade mode) */, MxOut mx = MxOut(),
     uint32_t lo_heads = 0xffffffffu /* LO == 1: bit h set = head h writes its remainder (the outlier extension of proj needs the
-                                       heads that hold its columns only: engine.hip EncBlock::oc_heads) */) {
+                                       heads that hold its columns only: engine.hip EncBlock::oc_heads) */,
+    int dense = 1 /* 0: queries numbered in window order, 7 strips per item whatever the window's real extent */) {
     using C = WinCfg<HD>;
     constexpr int KS = HD / 16;
     constexpr bool PL = (PIPE & 1) != 0;          // software-pipelined tile loop
@@ -659,6 +667,7 @@ __global__ __launch_bounds__(512) void window_attention_kernel(
     uint16_t* Bia = Tab + 2 * 32 * HD;     // [2][D]: k bias | v bias (the k / v of a padding token)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);      // for the per-item "does this wave own a strip" branch
     const int hh = lane >> 5, ql = lane & 31;
     const int D = heads * HD;
     const int nw = (grid + C::WS - 1) / C::WS;
@@ -684,9 +693,9 @@ __global__ __launch_bounds__(512) void window_attention_kernel(
     constexpr int CH = HD / 8;  // 16-byte chunks per row
     constexpr int NKC = C::N * CH, NVI = (C::N / 2) * CH;        // real rows / key pairs only
     constexpr int PK = (NKC + C::THREADS - 1) / C::THREADS, PV = (NVI + C::THREADS - 1) / C::THREADS;
-    const int q = 32 * (wave < C::NT ? wave : 0) + ql;   // query index inside the window (wave 7 only stages)
-    const int qc = q < C::N ? q : C::N - 1;
-    const int qh = qc / C::WS, qw = qc % C::WS;
+    const int q = 32 * (wave < C::NT ? wave : 0) + ql;   // query slot inside the item (wave 7 only stages)
+    // slot q of an item with row length vw_ (<= 14, q < 224): its window row, exact for these ranges (q * err < 65536)
+    auto slot_row = [](int q_, int vw_) -> int { return (int)(((uint32_t)q_ * ((65536u + (uint32_t)vw_ - 1u) / (uint32_t)vw_)) >> 16); };
 
     // All global loads of an item (this wave's Q fragments, this thread's K chunks and V key pairs) are
     // issued back to back; n_* describe the item they belong to.
@@ -703,15 +712,16 @@ __global__ __launch_bounds__(512) void window_attention_kernel(
     // the bias chunk when the registers are written to LDS: the issue sequence is straight-line, 13 loads back to back
     // (the earlier form branched per load and waited on an LDS read of the bias before each one: 19 % of the item,
     // profiles/r02_window_attention_phase_timing.txt).
-#define WIN_TOK(r_, off_, pad_)                                                                                      \
-    const int ty_##off_ = y0_ + (r_) / C::WS, tx_##off_ = x0_ + (r_) % C::WS;                                        \
+#define WIN_TOK2(dy_, dx_, off_, pad_)                                                                               \
+    const int ty_##off_ = y0_ + (dy_), tx_##off_ = x0_ + (dx_);                                                      \
     const bool pad_ = ty_##off_ >= grid || tx_##off_ >= grid;                                                        \
     const int off_ = (min(ty_##off_, grid - 1) * grid + min(tx_##off_, grid - 1)) * (3 * D)
     // The issue is split into a head (item decode) and 5 groups of loads: a computing wave spreads the groups over its
     // first key tiles (a burst of 13 loads per lane from all 8 waves at once fills the TA queue and every wave then
-    // blocks in issue: 12 % of the item); wave 7, which only stages, issues everything at once.
+    // blocks in issue: 12 % of the item); a wave that only stages (wave 7; a wave past the item's last strip) issues everything at once.
     const uint16_t* n_base = qkv;
     int n_y0 = 0, n_x0 = 0;
+    int n_vw = C::WS, n_nq = C::N;        // the item's query numbering: row length and number of slots in use (wave-uniform)
 #define WIN_HEAD(it_)                                                                                                \
     do {                                                                                                             \
         const int wi_ = (it_) / heads;                                                                               \
@@ -722,12 +732,15 @@ __global__ __launch_bounds__(512) void window_attention_kernel(
         n_x0 = (win_ % nw) * C::WS;                                                                                  \
         n_base = qkv + (size_t)n_im * img_rows * (3 * D) + n_head * HD;                                              \
         n_pad = 0u;                                                                                                  \
+        n_vw = dense ? min(C::WS, grid - n_x0) : C::WS;                                                              \
+        n_nq = dense ? min(C::WS, grid - n_y0) * n_vw : C::N;                                                        \
     } while (0)
 #define WIN_LOAD_Q()                                                                                                 \
     do {                                                                                                             \
         const int y0_ = n_y0, x0_ = n_x0;                                                                            \
-        WIN_TOK(qc, qo_, qp_);                                                                                       \
-        n_qoff = (q < C::N && !qp_) ? qo_ : -1;                                                                      \
+        const int qc_ = min(q, n_nq - 1), qh_ = slot_row(qc_, n_vw);                                                 \
+        WIN_TOK2(qh_, qc_ - qh_ * n_vw, qo_, qp_);                                                                   \
+        n_qoff = (q < n_nq && !qp_) ? qo_ : -1;                                                                      \
         _Pragma("unroll") for (int ks_ = 0; ks_ < KS; ++ks_)                                                         \
             qdst[ks_] = *reinterpret_cast<const uint4*>(n_base + qo_ + 16 * ks_ + 8 * hh);                           \
     } while (0)
@@ -753,10 +766,6 @@ __global__ __launch_bounds__(512) void window_attention_kernel(
         const int c = tid + i * C::THREADS;
         if (c < NVI) vpk[i >> 1] |= slot_field(2 * (c % (C::N / 2)), c / (C::N / 2)) << (12 * (i & 1));      // key 2 kp; key 2 kp + 1 = the next column
     }
-#define WIN_TOK2(dy_, dx_, off_, pad_)                                                                               \
-    const int ty_##off_ = y0_ + (dy_), tx_##off_ = x0_ + (dx_);                                                      \
-    const bool pad_ = ty_##off_ >= grid || tx_##off_ >= grid;                                                        \
-    const int off_ = (min(ty_##off_, grid - 1) * grid + min(tx_##off_, grid - 1)) * (3 * D)
 #define WIN_LOAD_K(i_)                                                                                               \
     do {                                                                                                             \
         const int y0_ = n_y0, x0_ = n_x0;                                                                            \
@@ -861,20 +870,23 @@ __global__ __launch_bounds__(512) void window_attention_kernel(
         const int qoff = n_qoff;
         const bool qin = qoff >= 0;           // a real token (padding / tile-padding queries are dropped)
         const int im = n_im, head = n_head;
+        // this item's query numbering (WIN_HEAD below moves n_* on to the next item): strips in use, this lane's window position
+        const int n_strips = (n_nq + 31) >> 5;                    // <= NT
+        const int qc = min(q, n_nq - 1), qh = slot_row(qc, n_vw), qw = qc - qh * n_vw;
         WIN_STAMP(1)
         __syncthreads();
         WIN_STAMP(2)
         // ---- next item's loads: in flight during the whole compute below --------------------------------
         const bool has_next = it + (int)gridDim.x < n_items;
         if (has_next) {
-            if (wave >= C::NT) WIN_ISSUE(it + (int)gridDim.x);
+            if (wave_u >= n_strips) WIN_ISSUE(it + (int)gridDim.x);
             else WIN_HEAD(it + (int)gridDim.x);
         }
         WIN_STAMP(3)
 #ifdef WIN_TIMING
         ++n_done;
 #endif
-        if (wave >= C::NT) continue;          // wave 7 only stages
+        if (wave_u >= n_strips) continue;     // wave 7, and a wave whose strip holds no real query of this item: staging only
 
         // ---- decomposed rel-pos: RH[j] = q . rel_h[qh - j + 13], RW[j] = q . rel_w[qw - j + 13] -----
         // (log2 domain; image_encoder.py:325-361 uses the UNSCALED q)
@@ -1050,7 +1062,6 @@ __global__ __launch_bounds__(512) void window_attention_kernel(
 #undef WIN_LOAD_K
 #undef WIN_LOAD_Q
 #undef WIN_HEAD
-#undef WIN_TOK
 #undef WIN_TOK2
 }
 
@@ -1766,6 +1777,8 @@ static hipError_t launch_win(const void* qkv, const float* qb, const float* rh, 
 #else
     auto k = window_attention_kernel<PREC, HD, LO, 0>;
 #endif
+    // SAMRS_WIN_DENSE=0: the window-order query numbering, 7 strips per item (A/B runs and the bit-identity test); bit-identical output
+    static const int dense = [] { const char* v = getenv("SAMRS_WIN_DENSE"); return (v && atoi(v) == 0) ? 0 : 1; }();
     HIP_CHECK_RET(set_lds(k, C::LDS_BYTES));
     if (heads * HD > C::MAX_D) return hipErrorInvalidValue;
     const int nw = (grid + C::WS - 1) / C::WS;
@@ -1776,7 +1789,8 @@ static hipError_t launch_win(const void* qkv, const float* qb, const float* rh, 
         return n > 0 ? n : 256;
     }();
     dim3 g(n_items < n_cu ? n_items : n_cu), b(C::THREADS);      // persistent: one block per CU (LDS-limited)
-    k<<<g, b, C::LDS_BYTES, s>>>((const uint16_t*)qkv, qb, rh, rw, (uint16_t*)out, grid, heads, n_items, (uint16_t*)out_lo, mx, lo_heads);
+    k<<<g, b, C::LDS_BYTES, s>>>((const uint16_t*)qkv, qb, rh, rw, (uint16_t*)out, grid, heads, n_items, (uint16_t*)out_lo, mx, lo_heads,
+                                 dense);
     return hipGetLastError();
 }
 
