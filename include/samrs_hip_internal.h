@@ -27,6 +27,14 @@ int samrs_debug_outlier_columns(samrs_engine_t* e, int block, int gemm, int32_t*
 /* -- process-wide test / tuning hooks of the KERNEL-LEVEL entry points below (samrs_k_gemm has no handle): GEMM tile variant,
  * and the start skew of the first round of GEMM blocks, per XCD / per CU group, in 1024-cycle units (0, 0 = off). */
 void samrs_debug_set_gemm_variant(int variant);
+/* -- probe, no HIP call: which kernel a samrs_k_gemm call of this shape and these flags would run under `variant` (8 = automatic; the
+ * SAMRS_GEMM_W4X / SAMRS_GEMM_M32 switches of the process apply).  has_add2d: a 2-D addend is given; ld: operand row stride, 0 = K (the
+ * engine's padded qkv / lin1 operands).  out[8] = enum GemmKernel of csrc/gemm_select.h, ni, mode, persistent, reject (1 = the call
+ * returns an error with nothing launched), then what the engine's three planning questions answer for (M, N, K, gelu) under the same
+ * variant: operands may be padded (a plain ET launch runs on a kernel that takes `ld`), the outlier-column stage fits, the LayerNorm
+ * tail fits. */
+void samrs_debug_gemm_choice(int prec, int M, int N, int K, int out_f32, int gelu, int accumulate, int has_add2d, int ld, int variant,
+                             int32_t* out);
 void samrs_debug_set_gemm_skew(int xcd_units, int cu_units);
 /* 1 when the library was built with `make EXPERIMENTS=1`: the kernels that were measured and not adopted (GEMM variants 30 - 36 on
  * v_mfma_f32_32x32x16, the LayerNorm fold "ln_fold", the timing ablations 60 - 92 / 100 - 196) exist; 0 in the product build, where those

@@ -114,7 +114,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(
     float eps, uint16_t* __restrict__ out_et, float* __restrict__ out_f32, int rows_out, int D,
     int window_mode, int grid, int window, uint16_t* __restrict__ out_lo /* optional: the split remainder of out_et */,
     MxOut mx /* optional (plain row order only): hi and lo of the output as MXFP4 codes + scale tiles, gemm_et_mx_kernel's A operands */,
-    int ld_out /* row stride of out_et in elements (>= D; gemm.hip tl_gemm_ld); out_lo / out_f32 / mx rows stay dense */,
+    int ld_out /* row stride of out_et in elements (>= D; kernels.h GemmOpts::ld); out_lo / out_f32 / mx rows stay dense */,
     const int* __restrict__ oc_idx /* optional: n_oc <= 32 OUTLIER columns of the output (engine.hip outlier_columns) */, int n_oc) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);

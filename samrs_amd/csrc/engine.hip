@@ -168,7 +168,7 @@ struct samrs_engine {
     unsigned int* ln_counters = nullptr;   // per 256-row panel: tiles of the running proj / lin2 launch that have stored (gemm.hip LnTail)
     // option "operand_pad" (default 1): the K = D operands of the plain qkv / lin1 launches -- the LayerNorm output and the weights -- are
     // stored with a row stride of ldk = D + 128 elements where D rows are an even number of 256-byte units (ViT-H: 2560 B -> 2816 B), so
-    // that the rows a tile fetches per k-slice spread over all memory channels instead of half of them (gemm.hip tl_gemm_ld)
+    // that the rows a tile fetches per k-slice spread over all memory channels instead of half of them (GemmOpts::ld)
     int operand_pad_on = 1;
     int ldk = 0;                   // 0: no padded copies exist (other widths)
     // option "outlier_cols" (default 7; SAMRS_OUTLIER_COLS; bit 0: qkv / lin1, bit 1: lin2, bit 2: proj): hi + lo terms for the outlier
@@ -297,18 +297,6 @@ struct GemmVariantScope {
     int prev;
     explicit GemmVariantScope(int v) : prev(swap_gemm_variant_override(v)) {}
     ~GemmVariantScope() { (void)swap_gemm_variant_override(prev); }
-};
-// ... and so do the operand row stride (swap_gemm_ld) and the erf form of the GELU epilogue (swap_gelu_form) of ONE plain launch: the
-// previous value is back on every way out of the scope, before the launch's status is looked at
-struct GemmLdScope {
-    int prev;
-    explicit GemmLdScope(int ld) : prev(swap_gemm_ld(ld)) {}
-    ~GemmLdScope() { (void)swap_gemm_ld(prev); }
-};
-struct GeluFormScope {
-    int prev;
-    explicit GeluFormScope(int form) : prev(swap_gelu_form(form)) {}
-    ~GeluFormScope() { (void)swap_gelu_form(prev); }
 };
 #define ON_DEVICE(e) DeviceGuard _dg((e)->device); CK((e), _dg.status); GemmVariantScope _gvs((e)->gemm_variant)
 
@@ -1267,8 +1255,7 @@ static int run_block_attn(samrs_engine_t* e, const PassRoute& p, const BlockRout
         CK(e, gemm_hilo(prec, false, MainPass::LAST, e->Y, e->Ylo, b.qkv_w, b.qkv_w_lo, e->F32T, b.qkv_b, nullptr, 0, M, 3 * D, D, false, s));
         CK(e, launch_convert(prec, e->F32T, e->QKV, (long)M * 3 * D, s));
     } else {
-        GemmLdScope ld(r.qkv_ld);
-        CK(e, launch_gemm_et(prec, e->Y, qkv_w, e->QKV, b.qkv_b, nullptr, 0, M, 3 * D, r.qkv_K, false, false, false, s));
+        CK(e, launch_gemm_et(prec, e->Y, qkv_w, e->QKV, b.qkv_b, nullptr, 0, M, 3 * D, r.qkv_K, false, false, false, s, GemmOpts{r.qkv_ld, 1}));
     }
     if (!b.global)
         CK(e, launch_window_attention(prec, e->QKV, b.qkv_b, b.rel_h, b.rel_w, e->AO, n, g, c.window_size, c.num_heads, e->hd, s,
@@ -1330,10 +1317,8 @@ static int run_block_mlp(samrs_engine_t* e, const PassRoute& p, const BlockRoute
         CK(e, gemm_hilo(prec, r.lin1_one, MainPass::LAST, e->Y, e->Ylo, b.lin1_w, b.lin1_w_lo, e->F32T, b.lin1_b, nullptr, 0, M, 4 * D, D, false, s));
         CK(e, launch_gelu_split(prec, e->F32T, e->H, e->Hlo, (long)M * 4 * D, s));
     } else {
-        GeluFormScope form(p.fast_gelu ? 2 : 1);
-        GemmLdScope ld(r.lin1_ld);
         CK(e, launch_gemm_et(prec, e->Y, weight_copy(r.lin1_wc, b.lin1_w, b.lin1_wp, b.lin1_wx), e->H, b.lin1_b, nullptr, 0, M, 4 * D, r.lin1_K,
-                             false, true, false, s));
+                             false, true, false, s, GemmOpts{r.lin1_ld, p.fast_gelu ? 2 : 1}));
     }
     if (e->timing) {
         CK(e, hipEventRecord(t1, s));
@@ -1889,6 +1874,10 @@ int samrs_paint(samrs_engine_t* e, const uint8_t* masks, const int32_t* labels, 
 }
 
 void samrs_debug_set_gemm_variant(int v) { set_gemm_variant(v); }
+void samrs_debug_gemm_choice(int prec, int M, int N, int K, int out_f32, int gelu, int accumulate, int has_add2d, int ld, int variant,
+                             int32_t* out) {
+    gemm_debug_choice(prec, M, N, K, out_f32 != 0, gelu != 0, accumulate != 0, has_add2d != 0, ld, variant, out);
+}
 void samrs_debug_set_gemm_skew(int xcd_units, int cu_units) { set_gemm_skew(xcd_units, cu_units); }
 int samrs_debug_has_experiments(void) { return gemm_has_experiments() ? 1 : 0; }
 int samrs_select_best(samrs_engine_t* e, const uint8_t* masks, const float* iou, int n, int n_sel, int h, int w, uint8_t* best_out,

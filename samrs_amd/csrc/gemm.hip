@@ -19,13 +19,37 @@
 // the epilogue then uses 8-byte (ET) / 16-byte (fp32) vector accesses and float4 bias loads.
 #include <cstdlib>
 
+#include <type_traits>
+
 #include "common.h"
+#include "gemm_select.h"
 #include "kernels.h"
+
+using namespace gemm_sel;
 
 namespace {
 
-constexpr int BM = 128, BN = 128, BK = 64;
-constexpr int GEMM_THREADS = 256;
+// f(std::integral_constant<int, PREC_*>) for the operand type named at run time
+template <class F>
+hipError_t with_prec(int prec, F&& f) {
+    if (prec == PREC_BF16) return f(std::integral_constant<int, PREC_BF16>{});
+    if (prec == PREC_F16) return f(std::integral_constant<int, PREC_F16>{});
+    return hipErrorInvalidValue;
+}
+// CUs of the current device: the grid of a persistent kernel.  cu_count() asks once per process (the first launch's device; the
+// devices of one box are the same part); the launchers that always asked per call go on doing so (cu_count_now()), since engines of
+// one process may sit on different devices (DeviceGuard).
+int cu_count_now() {
+    int dev = 0, n = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+    return n > 0 ? n : 256;
+}
+int cu_count() {
+    static const int n = cu_count_now();
+    return n;
+}
+
+constexpr int GEMM_THREADS = 256;      // BM / BN / BK and the other tile shapes the selection rule reads: gemm_select.h
 
 // physical 16-byte chunk of logical chunk c in row r of a [rows][64] ET tile
 __device__ __forceinline__ int swz(int r, int c) { return c ^ ((r >> 1) & 7); }
@@ -509,7 +533,7 @@ __device__ __forceinline__ void epilogue_pair_et(f32x4_t (&acc)[5][8], unsigned 
 // draining every K step (rocprofv3 on the 2-stage kernel: 47 % of wave cycles parked in
 // s_waitcnt/s_barrier, MFMA busy 30 %).  144 KiB LDS -> one block (8 waves) per CU.
 // ---------------------------------------------------------------------------------------------
-constexpr int PBM = 256, PBN = 128, PTHREADS = 512, PSTAGES = 3;
+constexpr int PBN = 128, PTHREADS = 512, PSTAGES = 3;
 constexpr int PSTAGE_ELEMS = (PBM + PBN) * BK;          // A rows then B rows, 64 ET each
 constexpr int P_GLDS_PER_TILE = (PBM + PBN) * BK * 2 / (PTHREADS * 16);   // 6 per thread
 
@@ -710,8 +734,7 @@ hipError_t launch_gemm_stag(const void* A, const void* B, void* C, const float* 
 // (MI355X_MICROARCH.md, LDS table) need the 16-byte chunk index XORed with g(row>>2),
 // g = [0,2,3,1]: checked conflict-free for all four lane groups.
 // ---------------------------------------------------------------------------------------------
-constexpr int QBM = 256, QBN = 256, QBK = 32, QSTAGES = 4, QTHREADS = 512;
-constexpr int WBN = 320;     // NI = 5 flavour: 256x320 tile (wave tile 128x80), 4 x 36 KiB ring
+constexpr int QSTAGES = 4, QTHREADS = 512;     // WBN = 320: the NI = 5 flavour, 256x320 tile (wave tile 128x80), 4 x 36 KiB ring
 
 __device__ __forceinline__ int qswz(int r, int c) { return c ^ ((0x78 >> (2 * ((r >> 2) & 3))) & 3); }
 
@@ -894,7 +917,6 @@ __global__ __launch_bounds__(QTHREADS) void gemm_et_big_kernel(
 // SPREAD: the DMA pieces are issued between the MFMAs of a C segment instead of as one burst.
 // M % 256 == 0, N % (64 NI) == 0, K % 64 == 0.
 // ---------------------------------------------------------------------------------------------
-constexpr int XBK = 64;
 
 // Start skew of the FIRST round of blocks (experiment / tuning knob, SAMRS_GEMM_SKEW=<xcd units>,<cu-group units> in
 // 1024-cycle steps): all 256 CUs start a GEMM together and reach their epilogues together, so the output tile writes
@@ -1485,15 +1507,13 @@ __global__ __launch_bounds__(QTHREADS) void gemm_et_x64p_kernel(
 #undef X64P_MFMA
 }
 
-// erf form of the ET-output GELU epilogue of the persistent 256x320 kernel (lin1 of ViT-H): 1 = fp32-epsilon class (A-S 7.1.26),
-// 2 = the cheaper one (A-S 7.1.28, common.h gelu_erf2_et); set around an engine's launches (engine.hip run_encoder)
-thread_local int tl_gelu_form = 1;
-// Row stride (elements) of the A and B operands of the calling thread's next plain ET launches, 0 = K.  Round 5, late: at K = 1280 an
+// gelu_form (GemmOpts): erf form of the ET-output GELU epilogue of the persistent kernels (lin1 of ViT-H): 1 = fp32-epsilon class
+// (A-S 7.1.26), 2 = the cheaper one (A-S 7.1.28, common.h gelu_erf2_et)
+// ld (GemmOpts): row stride (elements) of the A and B operands of a plain ET launch, 0 = K.  Round 5, late: at K = 1280 an
 // operand row is 2560 B = ten 256-byte units, so the 256 rows a tile fetches per k-slice fall on half of the memory channels; stored with a
 // stride of 1408 elements (eleven units: every channel) the same kernels run their main loops ~4 % faster (tools/gemm_bench.py STRIDE_PROBE:
 // lin1 + GELU 432.2 us at K = 1280, 451.5 at K = 1408 with 10 % more stages).  Only the persistent ET kernels take a stride (gemm_ld_ok says
 // whether a launch will run on one of them); the engine pads the LayerNorm output and keeps padded copies of the qkv / lin1 weights.
-thread_local int tl_gemm_ld = 0;
 // lin1's output -- the MLP hidden tensor, read once, by lin2 -- is written with NON-TEMPORAL stores when it is larger than the 256 MB
 // Infinity Cache it would otherwise be allocated in (8 tiles of ViT-H: 336 MB per launch; SAMRS_NT_HIDDEN=0 / 1 forces the choice).
 // Measured on MI355X, libraries alternated on one box (profiles/r05_nt_streams.txt): lin1 424 -> 408 us in situ (the write-allocates no
@@ -1507,13 +1527,9 @@ static bool stream_hidden(long M, long N) {
 }
 template <int PREC>
 hipError_t launch_gemm_x64p(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, bool out_f32, bool gelu,
-                            bool accumulate, hipStream_t s) {
+                            bool accumulate, int ld, int gelu_form, hipStream_t s) {
     const int ntiles = (M / QBM) * (N / WBN);
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
+    const int n_cu = cu_count();
     dim3 grid(ntiles < n_cu ? ntiles : n_cu), block(QTHREADS);
     const uint16_t* a = reinterpret_cast<const uint16_t*>(A);
     const uint16_t* b = reinterpret_cast<const uint16_t*>(B);
@@ -1523,10 +1539,9 @@ hipError_t launch_gemm_x64p(const void* A, const void* B, void* C, const float* 
         else gemm_et_x64p_kernel<PREC, true, false><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, acc);
     } else {
         const bool so = gelu && stream_hidden(M, N);
-        const int ld = tl_gemm_ld;
 #define X64P_ARGS a, b, C, bias, M, N, K, acc, nullptr, nullptr, nullptr, nullptr, 0, MxOut(), ld
-        if (gelu && tl_gelu_form == 2 && so) gemm_et_x64p_kernel<PREC, false, 2, false, false, false, true><<<grid, block, 0, s>>>(X64P_ARGS);
-        else if (gelu && tl_gelu_form == 2) gemm_et_x64p_kernel<PREC, false, 2><<<grid, block, 0, s>>>(X64P_ARGS);
+        if (gelu && gelu_form == 2 && so) gemm_et_x64p_kernel<PREC, false, 2, false, false, false, true><<<grid, block, 0, s>>>(X64P_ARGS);
+        else if (gelu && gelu_form == 2) gemm_et_x64p_kernel<PREC, false, 2><<<grid, block, 0, s>>>(X64P_ARGS);
         else if (gelu && so) gemm_et_x64p_kernel<PREC, false, true, false, false, false, true><<<grid, block, 0, s>>>(X64P_ARGS);
         else if (gelu) gemm_et_x64p_kernel<PREC, false, true><<<grid, block, 0, s>>>(X64P_ARGS);
         else gemm_et_x64p_kernel<PREC, false, false><<<grid, block, 0, s>>>(X64P_ARGS);
@@ -1540,11 +1555,7 @@ template <int PREC>
 hipError_t launch_gemm_x64p_mxo(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, bool gelu,
                                 void* o4_hi, void* o4_lo, void* so_hi, void* so_lo, hipStream_t s) {
     const int ntiles = (M / QBM) * (N / WBN);
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
+    const int n_cu = cu_count();
     dim3 grid(ntiles < n_cu ? ntiles : n_cu), block(QTHREADS);
     const uint16_t* a = reinterpret_cast<const uint16_t*>(A);
     const uint16_t* b = reinterpret_cast<const uint16_t*>(B);
@@ -1890,11 +1901,7 @@ template <int PREC, int SPREAD>
 hipError_t launch_gemm_m32(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, bool out_f32, bool gelu,
                            bool accumulate, bool persistent, hipStream_t s) {
     const int ntiles = (M / QBM) * (N / WBN);
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
+    const int n_cu = cu_count();
     dim3 grid(persistent && ntiles > n_cu ? n_cu : ntiles), block(QTHREADS);
     const uint16_t* a = reinterpret_cast<const uint16_t*>(A);
     const uint16_t* b = reinterpret_cast<const uint16_t*>(B);
@@ -2128,11 +2135,7 @@ template <int PREC>
 hipError_t launch_gemm_w4(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, bool out_f32, bool gelu,
                           bool accumulate, bool persistent, hipStream_t s) {
     const int ntiles = (M / QBM) * (N / WBN);
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
+    const int n_cu = cu_count();
     dim3 grid(persistent && ntiles > n_cu ? n_cu : ntiles), block(W4THREADS);
     const uint16_t* a = reinterpret_cast<const uint16_t*>(A);
     const uint16_t* b = reinterpret_cast<const uint16_t*>(B);
@@ -2179,7 +2182,6 @@ __device__ __forceinline__ void mfma16_asm(f32x4_t& c, const uint4& a, const uin
     }
 }
 
-constexpr int W4X_BN = 256;
 constexpr int W4X_ROWS = QBM + W4X_BN;                 // 512 stage rows
 constexpr int W4X_STAGE_ELEMS = W4X_ROWS * XBK;        // 64 KiB per stage
 constexpr int W4X_SCR_BYTES = 4 * 16 * 272;            // epilogue scratch: per wave one m-tile of 16 rows x 272 B (epilogue_coalesced, NI = 8, JC = 1)
@@ -2359,28 +2361,19 @@ __global__ __attribute__((amdgpu_flat_work_group_size(W4THREADS, W4THREADS), amd
 #undef W4X_STAGE
 }
 
-static bool w4x_ok(int M, int N, int K, const float* add2d, bool out_f32) {
-    return M % QBM == 0 && N % W4X_BN == 0 && K % XBK == 0 && K >= 4 * XBK && !add2d && !out_f32;
-}
-
 template <int PREC>
 hipError_t launch_gemm_w4x(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, bool out_f32, bool gelu,
-                           bool accumulate, hipStream_t s) {
+                           bool accumulate, int ld, int gelu_form, hipStream_t s) {
     const int ntiles = (M / QBM) * (N / W4X_BN);
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
+    const int n_cu = cu_count();
     dim3 grid(ntiles > n_cu ? n_cu : ntiles), block(W4THREADS);
     const uint16_t* a = reinterpret_cast<const uint16_t*>(A);
     const uint16_t* b = reinterpret_cast<const uint16_t*>(B);
     const int acc = accumulate ? 1 : 0;
     if (out_f32) return hipErrorInvalidValue;
     const bool so = gelu && stream_hidden(M, N);
-    const int ld = tl_gemm_ld;
-    if (gelu && tl_gelu_form == 2 && so) gemm_et_w4x_kernel<PREC, false, 2, true><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, acc, ld);
-    else if (gelu && tl_gelu_form == 2) gemm_et_w4x_kernel<PREC, false, 2><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, acc, ld);
+    if (gelu && gelu_form == 2 && so) gemm_et_w4x_kernel<PREC, false, 2, true><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, acc, ld);
+    else if (gelu && gelu_form == 2) gemm_et_w4x_kernel<PREC, false, 2><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, acc, ld);
     else if (gelu && so) gemm_et_w4x_kernel<PREC, false, 1, true><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, acc, ld);
     else if (gelu) gemm_et_w4x_kernel<PREC, false, 1><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, acc, ld);
     else gemm_et_w4x_kernel<PREC, false, 0><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, acc, ld);
@@ -2393,9 +2386,7 @@ template <int PREC>
 hipError_t launch_gemm_m32_stats(const void* A, const void* B, float* C, const float* bias, void* Xh, float* stats,
                                  int M, int N, int K, int spread, hipStream_t s) {
     const int ntiles = (M / QBM) * (N / WBN);
-    int dev = 0, n_cu = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (n_cu <= 0) n_cu = 256;
+    const int n_cu = cu_count_now();
     dim3 grid(ntiles > n_cu ? n_cu : ntiles), block(QTHREADS);
     const uint16_t* a = reinterpret_cast<const uint16_t*>(A);
     const uint16_t* b = reinterpret_cast<const uint16_t*>(B);
@@ -2408,9 +2399,7 @@ template <int PREC>
 hipError_t launch_gemm_x64p_fold(const void* A, const void* B, void* C, const float* bias, const float* cvec, const float* rowstat,
                                  int M, int N, int K, bool gelu, hipStream_t s) {
     const int ntiles = (M / QBM) * (N / WBN);
-    int dev = 0, n_cu = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-    if (n_cu <= 0) n_cu = 256;
+    const int n_cu = cu_count_now();
     dim3 grid(ntiles < n_cu ? ntiles : n_cu), block(QTHREADS);
     const uint16_t* a = reinterpret_cast<const uint16_t*>(A);
     const uint16_t* b = reinterpret_cast<const uint16_t*>(B);
@@ -2419,11 +2408,7 @@ hipError_t launch_gemm_x64p_fold(const void* A, const void* B, void* C, const fl
     else gemm_et_x64p_kernel<PREC, false, false, true><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, 0, rs, cvec);
     return hipGetLastError();
 }
-static bool m32_ok(int M, int N, int K, const float* add2d) {
-    return M % QBM == 0 && N % WBN == 0 && K % (2 * XBK) == 0 && K >= 2 * XBK && !add2d;
-}
-
-#endif  // SAMRS_EXPERIMENTS (fold launchers, m32_ok)
+#endif  // SAMRS_EXPERIMENTS (fold launchers)
 template <int PREC, int NI, int MODE>
 hipError_t launch_gemm_x64(const void* A, const void* B, void* C, const float* bias, const float* add2d, int period,
                            int M, int N, int K, bool out_f32, bool gelu, bool accumulate, hipStream_t s) {
@@ -2477,7 +2462,7 @@ hipError_t launch_gemm_big(const void* A, const void* B, void* C, const float* b
 // overlaps the other block's main loop.  Per K step and wave: 3 DMA pieces, 8 ds_read_b128,
 // 16 MFMAs, two raw barriers (L | C segments, wave groups staggered by one interval).
 // ---------------------------------------------------------------------------------------------
-constexpr int DBM = 256, DBN = 128, DBK = 32, DSTAGES = 3, DTHREADS = 512;
+constexpr int DSTAGES = 3, DTHREADS = 512;
 constexpr int DSTAGE_ELEMS = (DBM + DBN) * DBK;               // 12288 ET = 24 KiB
 constexpr int D_DMA_PER_TILE = (DBM + DBN) * DBK * 2 / (DTHREADS * 16);   // 3 per thread
 
@@ -2651,7 +2636,7 @@ hipError_t launch_gemm_dual(const void* A, const void* B, void* C, const float* 
 // LDS image of a tile: row r = 32 16-byte chunks, chunk c of the row at position c ^ (r & 15): the fragment reads of a
 // 16-row group (lane (fr, fq) reads chunk 4 ks + fq of row fr) are conflict-free, and a DMA piece is two whole rows.
 // ---------------------------------------------------------------------------------------------
-constexpr int K2_ROWS = 128, K2_K = 256, K2_TILE_BYTES = K2_ROWS * K2_K * 2;
+constexpr int K2_TILE_BYTES = K2_ROWS * K2_K * 2;
 
 // RS = row split: RS waves share a column slice (each keeps its own copy of the weight fragments) and take every RS-th
 // 16-row group -- N = 256: 8 waves instead of 4, twice the loads in flight per CU for the L2-latency-bound 2-D addend.
@@ -2784,11 +2769,7 @@ __global__ __launch_bounds__(64 * NW * RS) void gemm_et_k256_kernel(
 template <int PREC>
 hipError_t launch_gemm_k256(const void* A, const void* B, void* C, const float* bias, const float* add2d, int period,
                             int M, int N, hipStream_t s) {
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
+    const int n_cu = cu_count();
     const int ntiles = M / K2_ROWS;
     dim3 grid(ntiles < n_cu ? ntiles : n_cu);
     const uint16_t* a = reinterpret_cast<const uint16_t*>(A);
@@ -2805,10 +2786,6 @@ hipError_t launch_gemm_k256(const void* A, const void* B, void* C, const float* 
     else return hipErrorInvalidValue;
 #undef K2_LAUNCH
     return hipGetLastError();
-}
-// shapes the streaming kernel takes: ET output without GELU / accumulate, K = 256, N = 256 or 384, whole 128-row tiles
-static bool k256_ok(int M, int N, int K, bool out_f32, bool gelu, bool accumulate) {
-    return !out_f32 && !gelu && !accumulate && K == K2_K && (N == 256 || N == 384) && M % K2_ROWS == 0;
 }
 
 thread_local int tl_gemm_variant = -1;   // per-engine override, set around an engine's launches (engine.hip GemmVariantScope)
@@ -3296,226 +3273,131 @@ __global__ __launch_bounds__(256) void mx4_pack_kernel(const float* __restrict__
 
 }  // namespace
 
-// true when a plain ET launch of this shape (no 2-D addend, automatic variant) runs on gemm_et_x64p_kernel / gemm_et_w4x_kernel, the two
-// kernels that take an operand row stride (tl_gemm_ld): whole rounds of 256 x 320 tiles, K in 64-k pair stages
-static void gemm_env_once() {          // tuning knob for A/B runs: SAMRS_GEMM_VARIANT=<n>
-    static const bool once = [] {
+// what the selection rule (gemm_select.h) reads from the process
+static GemmEnv gemm_env() {
+    static const bool once = [] {          // tuning knob for A/B runs: SAMRS_GEMM_VARIANT=<n>
         if (const char* v = getenv("SAMRS_GEMM_VARIANT")) g_gemm_variant = atoi(v);
         return true;
     }();
     (void)once;
+    static const bool w4x_auto = [] { const char* v = getenv("SAMRS_GEMM_W4X"); return v ? atoi(v) != 0 : true; }();
+    GemmEnv e;
+    // an engine handle's own choice (samrs_set_option "gemm_variant") overrides the process-wide test hook for its launches
+    e.variant = tl_gemm_variant >= 0 ? tl_gemm_variant : g_gemm_variant;
+    e.w4x_auto = w4x_auto;
+#ifdef SAMRS_EXPERIMENTS
+    static const int m32_mask = [] { const char* v = getenv("SAMRS_GEMM_M32"); return v ? atoi(v) : 0; }();
+    e.m32_mask = m32_mask;
+    e.experiments = true;
+#else
+    e.m32_mask = 0;
+    e.experiments = false;       // the 32x32x16 kernels and the ablations are not in this build (make EXPERIMENTS=1)
+#endif
+    return e;
 }
-bool gemm_ld_ok(int M, int N, int K, bool gelu) {
-    (void)gelu;
-    gemm_env_once();
-    const int gv = tl_gemm_variant >= 0 ? tl_gemm_variant : g_gemm_variant;
-    if (gv != 8 || M % QBM || N % WBN || K % XBK || K % QBK) return false;
-    const long t320 = (long)(M / QBM) * (N / WBN);
-    return t320 >= 256 && t320 % 256 == 0;
-}
-int swap_gemm_ld(int ld) { const int old = tl_gemm_ld; tl_gemm_ld = ld; return old; }
+bool gemm_ld_ok(int M, int N, int K, bool gelu) { return gemm_plan_ld_ok(M, N, K, gelu, gemm_env()); }
+bool gemm_ext_ok(int M, int N, int K) { return gemm_plan_ext_ok(M, N, K, gemm_env()); }
+bool gemm_lntail_ok(int M, int N, int K) { return gemm_plan_lntail_ok(M, N, K, gemm_env()); }
 
-// fp32 residual outputs with the outlier-column stage: the shapes the 256 x 320 pair-stage kernel takes by the automatic rule
-bool gemm_ext_ok(int M, int N, int K) {
-    gemm_env_once();
-    const int gv = tl_gemm_variant >= 0 ? tl_gemm_variant : g_gemm_variant;
-    return gv == 8 && M > 0 && M % QBM == 0 && N % WBN == 0 && K % XBK == 0 && K >= 2 * XBK && (long)(M / QBM) * (N / WBN) >= 256;
+// the rule's answer for a call, without a launch (samrs_debug_gemm_choice): out8 = kernel, ni, mode, persistent, reject, and what the
+// three planning predicates say of the shape under the same variant
+void gemm_debug_choice(int prec, int M, int N, int K, bool out_f32, bool gelu, bool accumulate, bool has_add2d, int ld, int variant,
+                       int32_t* out8) {
+    GemmEnv e = gemm_env();
+    e.variant = variant;
+    const GemmChoice ch = gemm_select(GemmCall{M, N, K, out_f32, gelu, accumulate, has_add2d, ld, prec == PREC_F16}, e);
+    out8[0] = (int32_t)ch.kernel; out8[1] = ch.ni; out8[2] = ch.mode; out8[3] = ch.persistent ? 1 : 0;
+    out8[4] = (ch.reject || (prec != PREC_F16 && prec != PREC_BF16)) ? 1 : 0;
+    out8[5] = gemm_plan_ld_ok(M, N, K, gelu, e) ? 1 : 0; out8[6] = gemm_plan_ext_ok(M, N, K, e) ? 1 : 0; out8[7] = gemm_plan_lntail_ok(M, N, K, e) ? 1 : 0;
 }
+
 hipError_t launch_gemm_et_ext(int prec, const void* A, const void* B, const void* Ax, const void* Bx, float* C, const float* bias,
                               int M, int N, int K, hipStream_t s) {
     if (!A || !B || !Ax || !Bx || !C || !gemm_ext_ok(M, N, K)) return hipErrorInvalidValue;
-    if (prec == PREC_BF16) return launch_gemm_x64_ext<PREC_BF16>(A, B, Ax, Bx, C, bias, M, N, K, s);
-    if (prec == PREC_F16) return launch_gemm_x64_ext<PREC_F16>(A, B, Ax, Bx, C, bias, M, N, K, s);
-    return hipErrorInvalidValue;
+    return with_prec(prec, [&](auto P) { return launch_gemm_x64_ext<P.value>(A, B, Ax, Bx, C, bias, M, N, K, s); });
 }
+
+namespace {
+template <int V>
+using Int = std::integral_constant<int, V>;
+}
+
+#ifdef SAMRS_EXPERIMENTS
+// the timing ablations (f16, ET output, no GELU): one instantiation per ablation number
+static hipError_t launch_gemm_abl(const GemmChoice& ch, const void* A, const void* B, void* C, const float* bias, const float* add2d,
+                                  int period, int M, int N, int K, hipStream_t s) {
+    const bool big = ch.kernel == GemmKernel::ABL_BIG;
+    dim3 grid((M / QBM) * (N / (big ? QBN : WBN))), block(QTHREADS);
+    const uint16_t* a = reinterpret_cast<const uint16_t*>(A);
+    const uint16_t* b = reinterpret_cast<const uint16_t*>(B);
+#define ABL_CASE(x) case x: gemm_et_big_kernel<PREC_F16, false, false, x><<<grid, block, 0, s>>>(a, b, C, bias, add2d, period, M, N, K, 0); break;
+#define XABL_CASE(x) case x: gemm_et_x64_kernel<PREC_F16, false, false, 5, 3, x><<<grid, block, 0, s>>>(a, b, C, bias, add2d, period, M, N, K, 0, g_x64_skew); break;
+    if (big) switch (ch.abl) {
+        ABL_CASE(0) ABL_CASE(1) ABL_CASE(4) ABL_CASE(6) ABL_CASE(8) ABL_CASE(7) ABL_CASE(16) ABL_CASE(22) ABL_CASE(23) ABL_CASE(24)
+        default: return hipErrorInvalidValue;
+    } else switch (ch.abl) {
+        XABL_CASE(0) XABL_CASE(1) XABL_CASE(2) XABL_CASE(4) XABL_CASE(16) XABL_CASE(6) XABL_CASE(7) XABL_CASE(22) XABL_CASE(23) XABL_CASE(17)
+        XABL_CASE(32) XABL_CASE(33) XABL_CASE(64)
+        default: return hipErrorInvalidValue;
+    }
+#undef ABL_CASE
+#undef XABL_CASE
+    return hipGetLastError();
+}
+#endif
 
 hipError_t launch_gemm_et(int prec, const void* A, const void* B, void* C, const float* bias,
                           const float* add2d, int add2d_period, int M, int N, int K, bool out_f32,
-                          bool gelu, bool accumulate, hipStream_t s) {
-    if (M % BM || N % BN || K % BK || M <= 0 || N <= 0 || K <= 0) return hipErrorInvalidValue;
+                          bool gelu, bool accumulate, hipStream_t s, GemmOpts opts) {
     if (add2d && add2d_period <= 0) return hipErrorInvalidValue;
-    if (add2d && gelu) return hipErrorInvalidValue;   // not needed by the path; the coalesced epilogue orders them differently
-    gemm_env_once();
-    // an engine handle's own choice (samrs_set_option "gemm_variant") overrides the process-wide test hook for its launches
-    const int gv = tl_gemm_variant >= 0 ? tl_gemm_variant : g_gemm_variant;
-    // a padded operand stride is understood by the persistent ET kernels only: refuse anything else instead of reading garbage
-    if (tl_gemm_ld != 0 && (tl_gemm_ld < K || !gemm_ld_ok(M, N, K, gelu) || out_f32 || add2d)) return hipErrorInvalidValue;
-#define GEMM_DISPATCH(P)                                                                                         \
-    switch (gv) {                                                                                    \
-        case 0: return launch_gemm_prec<P, false, 1>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s); \
-        case 1: return launch_gemm_prec<P, true, 1>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);  \
-        case 3: return launch_gemm_prec<P, false, 8>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s); \
-        default: return launch_gemm_prec<P, true, 8>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s); \
-    }
+    const GemmChoice ch = gemm_select(GemmCall{M, N, K, out_f32, gelu, accumulate, add2d != nullptr, opts.ld, prec == PREC_F16}, gemm_env());
+    if (ch.reject) return hipErrorInvalidValue;
+    return with_prec(prec, [&](auto P) -> hipError_t {
+        constexpr int PR = P.value;
+        auto base = [&](auto GLDS, auto GROUP_M) {
+            return launch_gemm_prec<PR, (GLDS.value != 0), GROUP_M.value>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
+        };
+        auto x64 = [&](auto NI, auto MODE) {
+            return launch_gemm_x64<PR, NI.value, MODE.value>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
+        };
+        switch (ch.kernel) {
+            case GemmKernel::BASE:
+                if (ch.glds) return ch.group_m == 1 ? base(Int<1>{}, Int<1>{}) : base(Int<1>{}, Int<8>{});
+                return ch.group_m == 1 ? base(Int<0>{}, Int<1>{}) : base(Int<0>{}, Int<8>{});
+            case GemmKernel::STAG: return launch_gemm_stag<PR>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
+            case GemmKernel::DUAL: return launch_gemm_dual<PR>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
+            case GemmKernel::DUAL_LOCKSTEP: return launch_gemm_dual<PR, false>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
+            case GemmKernel::STAG_256x256: return launch_gemm_big<PR>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
+            case GemmKernel::STAG_256x320: return launch_gemm_big<PR, 5>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
+            case GemmKernel::X64:
+                switch (ch.ni * 8 + ch.mode) {
+                    case 4 * 8 + 0: return x64(Int<4>{}, Int<0>{});
+                    case 5 * 8 + 0: return x64(Int<5>{}, Int<0>{});
+                    case 4 * 8 + 1: return x64(Int<4>{}, Int<1>{});
+                    case 5 * 8 + 1: return x64(Int<5>{}, Int<1>{});
+                    case 4 * 8 + 2: return x64(Int<4>{}, Int<2>{});
+                    case 5 * 8 + 2: return x64(Int<5>{}, Int<2>{});
+                    case 4 * 8 + 3: return x64(Int<4>{}, Int<3>{});
+                    case 5 * 8 + 7: return x64(Int<5>{}, Int<7>{});
+                    case 5 * 8 + 3: return x64(Int<5>{}, Int<3>{});
+                }
+                return hipErrorInvalidValue;
+            case GemmKernel::X64P: return launch_gemm_x64p<PR>(A, B, C, bias, M, N, K, out_f32, gelu, accumulate, opts.ld, opts.gelu_form, s);
+            case GemmKernel::W4X: return launch_gemm_w4x<PR>(A, B, C, bias, M, N, K, out_f32, gelu, accumulate, opts.ld, opts.gelu_form, s);
+            case GemmKernel::K256: return launch_gemm_k256<PR>(A, B, C, bias, add2d, add2d_period, M, N, s);
 #ifdef SAMRS_EXPERIMENTS
-    if (gv >= 60 && gv < 92 && prec == PREC_F16 && !out_f32 && M % QBM == 0 && N % QBN == 0) {
-        dim3 grid((M / QBM) * (N / QBN)), block(QTHREADS);
-        const uint16_t* a = reinterpret_cast<const uint16_t*>(A);
-        const uint16_t* b = reinterpret_cast<const uint16_t*>(B);
-#define ABL_CASE(x) case 60 + x: gemm_et_big_kernel<PREC_F16, false, false, x><<<grid, block, 0, s>>>(a, b, C, bias, add2d, add2d_period, M, N, K, 0); break;
-        switch (gv) {
-            ABL_CASE(0) ABL_CASE(1) ABL_CASE(4) ABL_CASE(6) ABL_CASE(8) ABL_CASE(7) ABL_CASE(16) ABL_CASE(22) ABL_CASE(23) ABL_CASE(24)
-            default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-#endif
-    // 40: K = 256 streaming kernel (decoder image side); automatic for its shapes once there are >= 2 tiles per CU
-    if ((gv == 40 || (gv == 8 && M / K2_ROWS >= 512)) && k256_ok(M, N, K, out_f32, gelu, accumulate)) {
-        if (prec == PREC_BF16) return launch_gemm_k256<PREC_BF16>(A, B, C, bias, add2d, add2d_period, M, N, s);
-        if (prec == PREC_F16) return launch_gemm_k256<PREC_F16>(A, B, C, bias, add2d, add2d_period, M, N, s);
-        return hipErrorInvalidValue;
-    }
-    // variant 8 ("auto", default): per-shape pick measured on MI355X (tools/gemm_bench.py) -- the
-    // 2-blocks-per-CU kernel wins where the epilogue dominates (GELU output, or short K with a
-    // narrow N), the 64-wide-K single-block kernel wins on long K / wide N.
-    int variant = gv;
-    // 20 / 21: pair-stage (64-deep, whole-cache-line DMA) 256x256 / 256x320 kernel; 22 / 23: the same with the DMA pieces
-    // spread between the MFMAs.  Shapes they do not cover fall through to the automatic choice.
-    if (variant == 28 && !(M % QBM == 0 && N % WBN == 0 && K % XBK == 0 && !add2d)) variant = 8;
-    if (variant >= 20 && variant <= 27 || variant == 35) {     // 20 + mode * 2 + (NI == 5): mode bit 0 = spread DMA, bit 1 = one barrier per stage
-        const int ni = (variant & 1) ? 5 : 4, mode = (variant - 20) >> 1;
-        if (M % QBM == 0 && N % (64 * ni) == 0 && K % XBK == 0) {
-#define X64_CASE(P, NI_, MD_) return launch_gemm_x64<P, NI_, MD_>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s)
-#define X64_MODES(P)                                                             \
-            switch (variant) {                                                   \
-                case 20: X64_CASE(P, 4, 0); case 21: X64_CASE(P, 5, 0);          \
-                case 22: X64_CASE(P, 4, 1); case 23: X64_CASE(P, 5, 1);          \
-                case 24: X64_CASE(P, 4, 2); case 25: X64_CASE(P, 5, 2);          \
-                case 26: X64_CASE(P, 4, 3); case 35: X64_CASE(P, 5, 7); default: X64_CASE(P, 5, 3); \
-            }
-            (void)mode;
-            if (prec == PREC_F16) { X64_MODES(PREC_F16) }
-            if (prec == PREC_BF16) { X64_MODES(PREC_BF16) }
-#undef X64_MODES
-#undef X64_CASE
-            return hipErrorInvalidValue;
-        }
-        variant = 8;
-    }
-#ifdef SAMRS_EXPERIMENTS
-    // 100 + abl: ablations of the barrier-light 256x320 kernel (f16, ET output, no GELU): timing experiments only
-    if (variant >= 100 && variant < 196 && prec == PREC_F16 && !out_f32 && M % QBM == 0 && N % WBN == 0 && K % XBK == 0) {
-        dim3 grid((M / QBM) * (N / WBN)), block(QTHREADS);
-        const uint16_t* a = reinterpret_cast<const uint16_t*>(A);
-        const uint16_t* b = reinterpret_cast<const uint16_t*>(B);
-#define XABL_CASE(x) case 100 + x: gemm_et_x64_kernel<PREC_F16, false, false, 5, 3, x><<<grid, block, 0, s>>>(a, b, C, bias, add2d, add2d_period, M, N, K, 0, g_x64_skew); break;
-        switch (variant) {
-            XABL_CASE(0) XABL_CASE(1) XABL_CASE(2) XABL_CASE(4) XABL_CASE(16) XABL_CASE(6) XABL_CASE(7) XABL_CASE(22) XABL_CASE(23) XABL_CASE(17)
-            XABL_CASE(32) XABL_CASE(33) XABL_CASE(64)
-            default: return hipErrorInvalidValue;
-        }
-#undef XABL_CASE
-        return hipGetLastError();
-    }
-#endif
-    if (variant == 8) {
-        const bool big_ok = M % QBM == 0 && K % QBK == 0;
-        const long t256 = big_ok && N % QBN == 0 ? (long)(M / QBM) * (N / QBN) : 0;
-        const long t320 = big_ok && N % WBN == 0 ? (long)(M / QBM) * (N / WBN) : 0;
-        // the 256x320 tile: pair-stage kernel (whole-line DMA, one barrier per 64 k, DMA pieces spread between the MFMAs;
-        // measured +1.5 ... +4 % over the 32-deep ring on all four encoder shapes, bit-identical) when K allows, else
-        // the 32-deep staggered kernel
-        const int wide = (K % XBK == 0) ? 27 : 10;
-        // fp32 residual outputs (proj, lin2: N = 1280): 256x320 tiles -> an exact number of rounds over the 256 CUs
-        if (out_f32 && t320 >= 256) variant = wide;
-        // f16 outputs (qkv N = 3840, lin1+GELU N = 5120): the wide tile whenever it fills whole rounds (6 / 8 rounds at
-        // batch 8, exactly one round for lin1 of a single image), else 256x256 as long as there are >= 4 rounds of tiles
-        // (ET outputs without a 2-D addend: the persistent flavour, +3 % on qkv / lin1; its one-m-tile fp32 epilogue loses on proj)
-        else if (!out_f32 && t320 >= 256 && t320 % 256 == 0) variant = (wide == 27 && !add2d) ? 28 : wide;
-        else if (!out_f32 && N >= 2048 && t256 >= 1024) variant = 6;
-        else variant = (gelu || (K <= 1536 && N <= 1536)) ? 7 : 5;
-    }
-    // ET + GELU outputs whose 256 x 256 tiles fill whole rounds (lin1 of ViT-H: 2560 tiles = 10 rounds at batch 8; 5 at batch 4) go to
-    // the four-wave 128 x 128-wave-tile kernel (variant 38; bit-identical with the kernel it replaces, so no mode's arithmetic moves).
-    // Measured on MI355X: as a 2.5 s loop of its own 412 us against 429 and 1.03 against 1.08 pJ / FLOP (profiles/r05_gemm_energy.txt);
-    // INSIDE the tile loop, beside the decoder's kernels, the launch itself is no faster (0.4342 against 0.4330 ms) and the step gains
-    // 0.2 % (142.68 / 142.68 / 142.88 against 142.21 / 142.57 / 142.52 images/s, alternated on one box: profiles/r05_ab_loop.txt).
-    // Plain ET outputs (qkv: 7.5 rounds) and the fp32 outputs (2.5 rounds) are slower on it in both settings and stay where they were.
-    // SAMRS_GEMM_W4X=0 switches the rule off (A/B runs).
-    static const bool w4x_auto = [] { const char* v = getenv("SAMRS_GEMM_W4X"); return v ? atoi(v) != 0 : true; }();
-    if (variant == 28 && w4x_auto && gelu && w4x_ok(M, N, K, add2d, out_f32)) {
-        const long t256 = (long)(M / QBM) * (N / W4X_BN);
-        if (t256 % 256 == 0 && t256 >= 1024) variant = 38;
-    }
-    // 30 / 31: 32x32x16 symmetric-schedule kernel, persistent / one tile per block.  SAMRS_GEMM_M32=<mask> lets the automatic
-    // rule pick it for A/B runs of the whole loop: bit 0 = ET outputs (qkv, lin1), bit 1 = fp32 outputs (proj, lin2),
-    // bit 2 = one tile per block instead of persistent, bit 3 = spread pieces
-#ifdef SAMRS_EXPERIMENTS
-    static const int m32_mask = [] { const char* v = getenv("SAMRS_GEMM_M32"); return v ? atoi(v) : 0; }();
-    if ((variant == 27 || variant == 28) && tl_gemm_ld == 0 /* the m32 / w4 kernels take no operand stride */ && m32_ok(M, N, K, add2d) &&
-        (m32_mask & (out_f32 ? 2 : 1)))
-        variant = (m32_mask & 16) ? 34 : 30 + ((m32_mask & 4) ? 1 : 0) + ((m32_mask & 8) ? 2 : 0);
-    if (variant >= 30 && variant <= 33 && !m32_ok(M, N, K, add2d)) variant = add2d ? 27 : 28;
-    if (variant >= 30 && variant <= 33) {     // 30 / 31: all pieces in step 3; 32 / 33: pieces spread over two steps
-        const bool pers = !(variant & 1);
-        if (variant < 32) {
-            if (prec == PREC_BF16) return launch_gemm_m32<PREC_BF16, 0>(A, B, C, bias, M, N, K, out_f32, gelu, accumulate, pers, s);
-            if (prec == PREC_F16) return launch_gemm_m32<PREC_F16, 0>(A, B, C, bias, M, N, K, out_f32, gelu, accumulate, pers, s);
-        } else {
-            if (prec == PREC_BF16) return launch_gemm_m32<PREC_BF16, 1>(A, B, C, bias, M, N, K, out_f32, gelu, accumulate, pers, s);
-            if (prec == PREC_F16) return launch_gemm_m32<PREC_F16, 1>(A, B, C, bias, M, N, K, out_f32, gelu, accumulate, pers, s);
-        }
-        return hipErrorInvalidValue;
-    }
-    // 34 / 36: the four-wave, 512-register flavour of the symmetric schedule (persistent / one tile per block)
-    if ((variant == 34 || variant == 36) && !m32_ok(M, N, K, add2d)) variant = add2d ? 27 : 28;
-    if (variant == 34 || variant == 36) {
-        if (prec == PREC_BF16) return launch_gemm_w4<PREC_BF16>(A, B, C, bias, M, N, K, out_f32, gelu, accumulate, variant == 34, s);
-        if (prec == PREC_F16) return launch_gemm_w4<PREC_F16>(A, B, C, bias, M, N, K, out_f32, gelu, accumulate, variant == 34, s);
-        return hipErrorInvalidValue;
-    }
+            case GemmKernel::M32:
+                if (ch.mode) return launch_gemm_m32<PR, 1>(A, B, C, bias, M, N, K, out_f32, gelu, accumulate, ch.persistent, s);
+                return launch_gemm_m32<PR, 0>(A, B, C, bias, M, N, K, out_f32, gelu, accumulate, ch.persistent, s);
+            case GemmKernel::W4: return launch_gemm_w4<PR>(A, B, C, bias, M, N, K, out_f32, gelu, accumulate, ch.persistent, s);
+            case GemmKernel::ABL_BIG:
+            case GemmKernel::ABL_X64: return launch_gemm_abl(ch, A, B, C, bias, add2d, add2d_period, M, N, K, s);
 #else
-    if (variant >= 30 && variant <= 36) variant = add2d ? 27 : 28;     // the 32x32x16 kernels are not in this build (make EXPERIMENTS=1)
+            default: break;      // the rule picks the experiment kernels in a build that has them only
 #endif
-    // 38: the four-wave 256 x 256 kernel on 16x16x32 MFMAs with 128 x 128 wave tiles (round 5); shapes it does not cover fall back
-    if (variant == 38 && !w4x_ok(M, N, K, add2d, out_f32)) variant = add2d ? 27 : 28;
-    if (variant == 38) {
-        if (prec == PREC_BF16) return launch_gemm_w4x<PREC_BF16>(A, B, C, bias, M, N, K, out_f32, gelu, accumulate, s);
-        if (prec == PREC_F16) return launch_gemm_w4x<PREC_F16>(A, B, C, bias, M, N, K, out_f32, gelu, accumulate, s);
+        }
         return hipErrorInvalidValue;
-    }
-    if (variant == 28 && M % QBM == 0 && N % WBN == 0 && K % XBK == 0 && !add2d) {   // persistent pair-stage kernel
-        if (prec == PREC_BF16) return launch_gemm_x64p<PREC_BF16>(A, B, C, bias, M, N, K, out_f32, gelu, accumulate, s);
-        if (prec == PREC_F16) return launch_gemm_x64p<PREC_F16>(A, B, C, bias, M, N, K, out_f32, gelu, accumulate, s);
-        return hipErrorInvalidValue;
-    }
-    if (variant == 28) variant = 27;
-    if (variant == 27 && M % QBM == 0 && N % WBN == 0 && K % XBK == 0) {   // chosen by the automatic rule above
-        if (prec == PREC_BF16) return launch_gemm_x64<PREC_BF16, 5, 3>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
-        if (prec == PREC_F16) return launch_gemm_x64<PREC_F16, 5, 3>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
-        return hipErrorInvalidValue;
-    }
-    if (variant == 9 && M % DBM == 0 && K % DBK == 0) {   // 2 blocks / CU, lock-step (one barrier per K step)
-        if (prec == PREC_BF16) return launch_gemm_dual<PREC_BF16, false>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
-        if (prec == PREC_F16) return launch_gemm_dual<PREC_F16, false>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
-        return hipErrorInvalidValue;
-    }
-    if (variant == 7 && M % DBM == 0 && K % DBK == 0) {   // 2 blocks / CU
-        if (prec == PREC_BF16) return launch_gemm_dual<PREC_BF16>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
-        if (prec == PREC_F16) return launch_gemm_dual<PREC_F16>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
-        return hipErrorInvalidValue;
-    }
-    if (variant == 11) variant = 10;      // (the round-1 persistent 32-deep kernel was removed: 28 is its successor)
-    if (variant == 10 && M % QBM == 0 && N % WBN == 0 && K % QBK == 0) {   // 256x320 staggered kernel
-        if (prec == PREC_BF16) return launch_gemm_big<PREC_BF16, 5>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
-        if (prec == PREC_F16) return launch_gemm_big<PREC_F16, 5>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
-        return hipErrorInvalidValue;
-    }
-    if (variant == 10) variant = 5;
-    if (variant == 6 && M % QBM == 0 && N % QBN == 0 && K % QBK == 0) {   // 256x256 staggered kernel
-        if (prec == PREC_BF16) return launch_gemm_big<PREC_BF16>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
-        if (prec == PREC_F16) return launch_gemm_big<PREC_F16>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
-        return hipErrorInvalidValue;
-    }
-    if ((variant == 5 || variant == 6 || variant == 7 || variant == 9) && M % PBM == 0) {   // staggered-group pipelined kernel
-        if (prec == PREC_BF16) return launch_gemm_stag<PREC_BF16>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
-        if (prec == PREC_F16) return launch_gemm_stag<PREC_F16>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
-        return hipErrorInvalidValue;
-    }
-    if (prec == PREC_BF16) { GEMM_DISPATCH(PREC_BF16) }
-    if (prec == PREC_F16) { GEMM_DISPATCH(PREC_F16) }
-    return hipErrorInvalidValue;
+    });
 }
 
 // LayerNorm folded into the neighbouring GEMMs (ViT-H: the residual stream has N = 1280 = LN_NS x 160 columns).
@@ -3532,18 +3414,14 @@ hipError_t launch_gemm_et_fold(int, const void*, const void*, void*, const float
 #else
 hipError_t launch_gemm_et_stats(int prec, const void* A, const void* B, float* C, const float* bias, void* Xh, float* stats,
                                 int M, int N, int K, hipStream_t s) {
-    if (!m32_ok(M, N, K, nullptr) || N != 160 * LN_NS || !Xh || !stats) return hipErrorInvalidValue;
+    if (!m32_ok(M, N, K, false) || N != 160 * LN_NS || !Xh || !stats) return hipErrorInvalidValue;
     static const int spread = [] { const char* v = getenv("SAMRS_GEMM_M32"); return v ? ((atoi(v) & 8) ? 1 : 0) : 1; }();
-    if (prec == PREC_BF16) return launch_gemm_m32_stats<PREC_BF16>(A, B, C, bias, Xh, stats, M, N, K, spread, s);
-    if (prec == PREC_F16) return launch_gemm_m32_stats<PREC_F16>(A, B, C, bias, Xh, stats, M, N, K, spread, s);
-    return hipErrorInvalidValue;
+    return with_prec(prec, [&](auto P) { return launch_gemm_m32_stats<P.value>(A, B, C, bias, Xh, stats, M, N, K, spread, s); });
 }
 hipError_t launch_gemm_et_fold(int prec, const void* Xh, const void* Wf, void* C, const float* bias_f, const float* cvec,
                                const float* rowstat, int M, int N, int K, bool gelu, hipStream_t s) {
     if (M % QBM || N % WBN || K != 160 * LN_NS || !bias_f || !cvec || !rowstat) return hipErrorInvalidValue;
-    if (prec == PREC_BF16) return launch_gemm_x64p_fold<PREC_BF16>(Xh, Wf, C, bias_f, cvec, rowstat, M, N, K, gelu, s);
-    if (prec == PREC_F16) return launch_gemm_x64p_fold<PREC_F16>(Xh, Wf, C, bias_f, cvec, rowstat, M, N, K, gelu, s);
-    return hipErrorInvalidValue;
+    return with_prec(prec, [&](auto P) { return launch_gemm_x64p_fold<P.value>(Xh, Wf, C, bias_f, cvec, rowstat, M, N, K, gelu, s); });
 }
 #endif  // SAMRS_EXPERIMENTS
 
@@ -3564,9 +3442,7 @@ static hipError_t launch_gemm_split3_prec(const uint16_t* a, const uint16_t* al,
                 a, b, C, bias, add2d, add2d_period, M, N, K, accumulate ? 1 : 0, 0, al, bl);
     } else {
         const int ntiles = (M / QBM) * (N / WBN);
-        int dev = 0, n_cu = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-        if (n_cu <= 0) n_cu = 256;
+        const int n_cu = cu_count_now();
         gemm_et_x64p_kernel<PREC, false, false, false, true><<<dim3(ntiles < n_cu ? ntiles : n_cu), dim3(QTHREADS), 0, s>>>(
             a, b, C, bias, M, N, K, 0, nullptr, nullptr, al, bl, split_from_n);
     }
@@ -3587,18 +3463,15 @@ hipError_t launch_gemm_et_split3(int prec, const void* A, const void* A_lo, cons
     const uint16_t* al = reinterpret_cast<const uint16_t*>(A_lo);
     const uint16_t* b = reinterpret_cast<const uint16_t*>(B);
     const uint16_t* bl = reinterpret_cast<const uint16_t*>(B_lo);
-    if (prec == PREC_BF16) return launch_gemm_split3_prec<PREC_BF16>(a, al, b, bl, C, bias, M, N, K, out_f32, accumulate, split_from_n, add2d, add2d_period, s);
-    if (prec == PREC_F16) return launch_gemm_split3_prec<PREC_F16>(a, al, b, bl, C, bias, M, N, K, out_f32, accumulate, split_from_n, add2d, add2d_period, s);
-    return hipErrorInvalidValue;
+    return with_prec(prec, [&](auto P) {
+        return launch_gemm_split3_prec<P.value>(a, al, b, bl, C, bias, M, N, K, out_f32, accumulate, split_from_n, add2d, add2d_period, s);
+    });
 }
 
 // C (fp32) += A B^T + bias, then out_et = LayerNorm(C rows) * gamma + beta in the operand type, by the LayerNorm tail of the 256 x 320
 // pair-stage kernel (gemm_et_x64_kernel<LNT>).  Only where that kernel is what launch_gemm_et would pick for the shape anyway (fp32
 // output with at least one full round of 256 x 320 tiles) and N is one LayerNorm row; otherwise hipErrorInvalidValue and the caller
 // launches GEMM and LayerNorm separately.  counters: M / 256 zeroed uint32 (left zero by every launch).
-bool gemm_lntail_ok(int M, int N, int K) {
-    return M > 0 && M % QBM == 0 && N % WBN == 0 && N <= 1280 && K % XBK == 0 && K >= 2 * XBK && (long)(M / QBM) * (N / WBN) >= 256;
-}
 hipError_t launch_gemm_et_lntail(int prec, const void* A, const void* B, float* C, const float* bias, int M, int N, int K,
                                  const float* gamma, const float* beta, float eps, void* out_et, unsigned int* counters, hipStream_t s) {
     if (!gemm_lntail_ok(M, N, K) || !A || !B || !C || !gamma || !beta || !out_et || !counters) return hipErrorInvalidValue;
@@ -3607,15 +3480,12 @@ hipError_t launch_gemm_et_lntail(int prec, const void* A, const void* B, float* 
     dim3 grid((M / QBM) * (N / WBN)), block(QTHREADS);
     const uint16_t* a = reinterpret_cast<const uint16_t*>(A);
     const uint16_t* b = reinterpret_cast<const uint16_t*>(B);
-    if (prec == PREC_F16)
-        gemm_et_x64_kernel<PREC_F16, true, false, 5, 3, 0, false, true><<<grid, block, 0, s>>>(a, b, C, bias, nullptr, 1, M, N, K, 1, g_x64_skew, nullptr, nullptr, ln);
-    else if (prec == PREC_BF16)
-        gemm_et_x64_kernel<PREC_BF16, true, false, 5, 3, 0, false, true><<<grid, block, 0, s>>>(a, b, C, bias, nullptr, 1, M, N, K, 1, g_x64_skew, nullptr, nullptr, ln);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+    return with_prec(prec, [&](auto P) {
+        gemm_et_x64_kernel<P.value, true, false, 5, 3, 0, false, true><<<grid, block, 0, s>>>(a, b, C, bias, nullptr, 1, M, N, K, 1, g_x64_skew, nullptr, nullptr, ln);
+        return hipGetLastError();
+    });
 }
 
-int swap_gelu_form(int v) { const int old = tl_gelu_form; tl_gelu_form = v; return old; }
 void set_gemm_variant(int v) { g_gemm_variant = v; }
 int swap_gemm_variant_override(int v) { const int old = tl_gemm_variant; tl_gemm_variant = v; return old; }
 void set_gemm_skew(int xcd_units, int cu_units) { g_x64_skew = (xcd_units & 0xffff) | (cu_units << 16); }
@@ -3650,9 +3520,7 @@ hipError_t launch_gemm_f32(const float* A, int lda, const float* W, const float*
 hipError_t launch_gemm_et_gln(int prec, const void* A, const void* B, void* C, const float* bias, const float* gamma_beta,
                               int M, int N, int K, hipStream_t s, const void* A_lo, const void* B_lo) {
     if (M % DBM || N % DBN || K % DBK || M <= 0 || !gamma_beta || ((A_lo == nullptr) != (B_lo == nullptr))) return hipErrorInvalidValue;
-    if (prec == PREC_BF16) return launch_gemm_dual_gln<PREC_BF16>(A, B, C, bias, gamma_beta, M, N, K, s, A_lo, B_lo);
-    if (prec == PREC_F16) return launch_gemm_dual_gln<PREC_F16>(A, B, C, bias, gamma_beta, M, N, K, s, A_lo, B_lo);
-    return hipErrorInvalidValue;
+    return with_prec(prec, [&](auto P) { return launch_gemm_dual_gln<P.value>(A, B, C, bias, gamma_beta, M, N, K, s, A_lo, B_lo); });
 }
 
 
@@ -3679,9 +3547,7 @@ hipError_t launch_gemm_et_mx(int prec, const void* A, const void* B, void* C, co
     // epilogue -- the f16 main loop of gemm_et_x64p_kernel is ~5 % faster than this kernel's (SAMRS_MX_LIN1=0: A/B switch)
     static const bool x64p_lin1 = [] { const char* v = getenv("SAMRS_MX_LIN1"); return !(v && atoi(v) == 0); }();
     if (x64p_lin1 && o4_hi && split_from_n == N && N % XBK == 0 && K % XBK == 0) {
-        if (prec == PREC_F16) return launch_gemm_x64p_mxo<PREC_F16>(A, B, C, bias, M, N, K, gelu, o4_hi, o4_lo, so_hi, so_lo, s);
-        if (prec == PREC_BF16) return launch_gemm_x64p_mxo<PREC_BF16>(A, B, C, bias, M, N, K, gelu, o4_hi, o4_lo, so_hi, so_lo, s);
-        return hipErrorInvalidValue;
+        return with_prec(prec, [&](auto P) { return launch_gemm_x64p_mxo<P.value>(A, B, C, bias, M, N, K, gelu, o4_hi, o4_lo, so_hi, so_lo, s); });
     }
     MxOperands mx;
     mx.a4_lo = (const unsigned char*)a4_lo; mx.a4_hi = (const unsigned char*)a4_hi;
@@ -3690,32 +3556,23 @@ hipError_t launch_gemm_et_mx(int prec, const void* A, const void* B, void* C, co
     mx.sb_hi = (const unsigned char*)sb_hi; mx.sb_lo = (const unsigned char*)sb_lo;
     mx.Kp = Kp; mx.split_from_n = split_from_n;
     const int ntiles = (M / QBM) * (N / WBN);
-    static const int n_cu = [] {
-        const char* v = getenv("SAMRS_MX_PERSIST");          // 0: one block per tile (A/B runs)
-        if (v && atoi(v) == 0) return 1 << 30;
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
+    static const bool one_tile = [] { const char* v = getenv("SAMRS_MX_PERSIST"); return v && atoi(v) == 0; }();   // 0: one block per tile (A/B runs)
+    const int n_cu = one_tile ? 1 << 30 : cu_count();
     const dim3 grid(ntiles < n_cu ? ntiles : n_cu), block(QTHREADS);
     const uint16_t* a = reinterpret_cast<const uint16_t*>(A);
     const uint16_t* b = reinterpret_cast<const uint16_t*>(B);
     const int acc = accumulate ? 1 : 0;
     MxOut mxo;
     mxo.q_hi = (unsigned char*)o4_hi; mxo.q_lo = (unsigned char*)o4_lo; mxo.s_hi = (unsigned char*)so_hi; mxo.s_lo = (unsigned char*)so_lo;
-#define MXL(P_)                                                                                                          \
-    do {                                                                                                                 \
-        if (out_f32) gemm_et_mx_kernel<P_, true><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, acc, mx, MxOut(), ld, ext ? 1 : 0);                \
-        else if (o4_hi && gelu) gemm_et_mx_kernel<P_, false, true, true><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, acc, mx, mxo, ld, ext ? 1 : 0);  \
-        else if (o4_hi) gemm_et_mx_kernel<P_, false, false, true><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, acc, mx, mxo, ld, ext ? 1 : 0);         \
-        else if (gelu) gemm_et_mx_kernel<P_, false, true, false><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, acc, mx, MxOut(), ld, ext ? 1 : 0);               \
-        else gemm_et_mx_kernel<P_, false><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, acc, mx, MxOut(), ld, ext ? 1 : 0);                       \
-    } while (0)
-    if (prec == PREC_F16) MXL(PREC_F16);
-    else if (prec == PREC_BF16) MXL(PREC_BF16);
-    else return hipErrorInvalidValue;
-#undef MXL
-    return hipGetLastError();
+    return with_prec(prec, [&](auto P) {
+        constexpr int PR = P.value;
+        if (out_f32) gemm_et_mx_kernel<PR, true><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, acc, mx, MxOut(), ld, ext ? 1 : 0);
+        else if (o4_hi && gelu) gemm_et_mx_kernel<PR, false, true, true><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, acc, mx, mxo, ld, ext ? 1 : 0);
+        else if (o4_hi) gemm_et_mx_kernel<PR, false, false, true><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, acc, mx, mxo, ld, ext ? 1 : 0);
+        else if (gelu) gemm_et_mx_kernel<PR, false, true, false><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, acc, mx, MxOut(), ld, ext ? 1 : 0);
+        else gemm_et_mx_kernel<PR, false><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, acc, mx, MxOut(), ld, ext ? 1 : 0);
+        return hipGetLastError();
+    });
 }
 
 // fp32 [rows][K] (x) or the ET pair (hi_in, lo_in) -> fp4 hi / lo [rows][Kp / 2] + their scale tiles; Kp = K / G * GP
@@ -3727,11 +3584,12 @@ hipError_t launch_mx4_pack(int prec, const float* x, const void* hi_in, const vo
     const dim3 grid((unsigned)((items * 8 + 255) / 256)), block(256);
     const uint16_t* hi = reinterpret_cast<const uint16_t*>(hi_in);
     const uint16_t* lo = reinterpret_cast<const uint16_t*>(lo_in);
-#define MXP(P_, F_) mx4_pack_kernel<P_, F_><<<grid, block, 0, s>>>(x, hi, lo, (uint16_t*)out_hi, (unsigned char*)q_hi, (unsigned char*)q_lo, \
-                                                                  (unsigned char*)s_hi, (unsigned char*)s_lo, rows, K, G, GP, is_b ? 1 : 0, perm)
-    if (prec == PREC_F16) { if (x) MXP(PREC_F16, true); else MXP(PREC_F16, false); }
-    else if (prec == PREC_BF16) { if (x) MXP(PREC_BF16, true); else MXP(PREC_BF16, false); }
-    else return hipErrorInvalidValue;
-#undef MXP
-    return hipGetLastError();
+    return with_prec(prec, [&](auto P) {
+        auto pack = [&](auto SRC_F32) {
+            mx4_pack_kernel<P.value, SRC_F32.value><<<grid, block, 0, s>>>(x, hi, lo, (uint16_t*)out_hi, (unsigned char*)q_hi, (unsigned char*)q_lo,
+                                                                        (unsigned char*)s_hi, (unsigned char*)s_lo, rows, K, G, GP, is_b ? 1 : 0, perm);
+        };
+        if (x) pack(std::true_type{}); else pack(std::false_type{});
+        return hipGetLastError();
+    });
 }

@@ -4,9 +4,19 @@
 #include <stdint.h>
 
 // ---- gemm.hip -------------------------------------------------------------------------------
+// Which kernel runs a launch is decided by gemm_select (gemm_select.h) from the shape, the flags and the variant in force.
+struct GemmOpts {
+    int ld = 0;           // row stride of A and B in elements, 0 = K: the persistent ET kernels alone read with it (gemm_ld_ok says whether
+                          // a launch of the shape runs on one of them; anything else refuses a stride)
+    int gelu_form = 1;    // erf form of their GELU epilogue (lin1): 1 = fp32-epsilon class, 2 = cheaper
+};
 hipError_t launch_gemm_et(int prec, const void* A, const void* B, void* C, const float* bias,
                           const float* add2d, int add2d_period, int M, int N, int K, bool out_f32,
-                          bool gelu, bool accumulate, hipStream_t s);
+                          bool gelu, bool accumulate, hipStream_t s, GemmOpts opts = {});
+// the rule's answer for such a call under `variant`, nothing launched: out8 = kernel (enum GemmKernel), ni, mode, persistent, reject,
+// gemm_ld_ok(M, N, K, gelu), gemm_ext_ok(M, N, K), gemm_lntail_ok(M, N, K) as they answer under that variant
+void gemm_debug_choice(int prec, int M, int N, int K, bool out_f32, bool gelu, bool accumulate, bool has_add2d, int ld, int variant,
+                       int32_t* out8);
 // C (ET) = GELU(LayerNorm2d over every 64-column group of (A B^T + bias)), eps 1e-6; gamma_beta = gamma[64] | beta[64]
 // A_lo / B_lo (both or neither): split-precision product of hi + lo operands; C is then FP32 [M][N] instead of ET
 hipError_t launch_gemm_et_gln(int prec, const void* A, const void* B, void* C, const float* bias, const float* gamma_beta,
@@ -35,11 +45,7 @@ bool gemm_has_experiments();     // built with -DSAMRS_EXPERIMENTS (make EXPERIM
 bool gemm_lntail_ok(int M, int N, int K);
 hipError_t launch_gemm_et_lntail(int prec, const void* A, const void* B, float* C, const float* bias, int M, int N, int K,
                                  const float* gamma, const float* beta, float eps, void* out_et, unsigned int* counters, hipStream_t s);
-int swap_gelu_form(int v);                // thread-local erf form of lin1's GELU epilogue (1 = fp32-epsilon class, 2 = cheaper); returns the previous value
-// Operand row stride of the calling thread's next plain ET GEMM launches (elements; 0 = K): the persistent ET kernels read A and B with
-// it (gemm.hip tl_gemm_ld).  gemm_ld_ok: a launch of this shape runs on one of them (anything else refuses a stride).
-int swap_gemm_ld(int ld);
-bool gemm_ld_ok(int M, int N, int K, bool gelu);
+bool gemm_ld_ok(int M, int N, int K, bool gelu);     // a plain ET launch of this shape takes an operand row stride (GemmOpts::ld)
 // C (fp32 [M][N], the residual stream) += A B^T + A_x B_x^T + bias: proj / lin2 with ONE more 64-k stage read from two dense side operands
 // A_x [M][64], B_x [N][64] (hi + lo of the outlier columns, engine.hip EncBlock::oc_*).  gemm_ext_ok: the shapes of the 256 x 320
 // pair-stage kernel (ViT-H at >= 2 tiles); other shapes add the side product with an accumulating launch of their own.

@@ -156,6 +156,9 @@ def load_library() -> C.CDLL:
         getattr(lib, name).restype = ip
     lib.samrs_debug_copy_buffer.argtypes = [vp, C.c_char_p, vp, C.c_size_t, vp]
     lib.samrs_debug_outlier_columns.argtypes = [vp, ip, ip, C.POINTER(C.c_int32)]
+    if hasattr(lib, "samrs_debug_gemm_choice"):       # an older build of the same ABI (SAMRS_LIB_PATH: A/B runs) has no such probe
+        lib.samrs_debug_gemm_choice.argtypes = [ip] * 10 + [C.POINTER(C.c_int32)]
+        lib.samrs_debug_gemm_choice.restype = None
     lib.samrs_get_slot_info.argtypes = [vp, ip, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     # checkpoint audit (samrs_hip.h samrs_audit_*; the two kernels alone: samrs_hip_internal.h)
     lib.samrs_audit_site_count.argtypes = [vp, C.POINTER(ip)]

@@ -1221,7 +1221,7 @@ def test_vit_h_odd_batches_equal_single_tile(batch):
 def test_operand_row_padding_is_bit_identical(split):
     """Round 5: at ViT-H the K = 1280 operands of the plain qkv / lin1 launches (the LayerNorm output, the weights) are stored with a row
     stride of 1408 elements instead of 1280 (option "operand_pad", engine field ldk; the persistent ET kernels take the stride:
-    gemm.hip tl_gemm_ld) -- a 2560-byte row is ten 256-byte units and lands the rows of a tile on half of the memory channels.  Where the
+    kernels.h GemmOpts::ld) -- a 2560-byte row is ten 256-byte units and lands the rows of a tile on half of the memory channels.  Where the
     bytes live cannot change what is computed: the embeddings of 4 and 8 tiles (the batches whose shapes fill whole rounds of tiles and
     therefore take the padded layout) must equal the dense layout's bit for bit, in the single-mask mode and in the multimask default
     (whose lin1, and qkv of the last blocks, run plain)."""
