@@ -65,6 +65,16 @@ struct DecLayer {
     uint16_t* i2t_ow_lo = nullptr;   // its split remainder
 };
 
+// The decoder's fp32 weights outside the transformer layers, resolved once (samrs_finalize_weights), like DecLayer / DecAttn.
+struct DecWeights {
+    PromptParams prompt{};         // its weight fields; the call fields are filled per call (prompt_call_fields)
+    MaskEmbedParams mask_embed{};
+    const float* no_mask_embed = nullptr;
+    const float *norm_final_w = nullptr, *norm_final_b = nullptr;      // transformer.norm_final_attn
+    const float *up_ln_w = nullptr, *up_ln_b = nullptr;                // output_upscaling.1 (LayerNorm2d), for the un-fused upscaler
+    const float *head_w[5][3] = {}, *head_b[5][3] = {};                // [0..3] hypernetwork MLPs, [4] the IoU head; 3 layers each
+};
+
 struct EncBlock {
     bool global = false;
     const float *ln1w, *ln1b, *ln2w, *ln2b, *qkv_b, *proj_b, *lin1_b, *lin2_b, *rel_h, *rel_w;
@@ -201,6 +211,7 @@ struct samrs_engine {
     // decoder weights
     std::vector<DecLayer> layers;
     DecAttn fin{};
+    DecWeights dec{};
     uint16_t* fin_kv_w = nullptr;  // ET [256][256] = [Wk; Wv]
     float *fin_kv_b = nullptr, *fin_pe = nullptr;
     uint16_t *up1_w = nullptr, *up2_w = nullptr, *up1_w_lo = nullptr, *up2_w_lo = nullptr;
@@ -389,6 +400,40 @@ DecAttn dec_attn(samrs_engine* e, const std::string& p) {
                    W(e, p + ".out_proj.weight"), W(e, p + ".out_proj.bias")};
 }
 
+DecWeights dec_weights(samrs_engine* e) {
+    DecWeights d;
+    d.prompt.gauss = W(e, "prompt_encoder.pe_layer.positional_encoding_gaussian_matrix");
+    for (int i = 0; i < 4; ++i) d.prompt.point_emb[i] = W(e, "prompt_encoder.point_embeddings." + std::to_string(i) + ".weight");
+    d.prompt.not_a_point = W(e, "prompt_encoder.not_a_point_embed.weight");
+    d.prompt.iou_token = W(e, "mask_decoder.iou_token.weight");
+    d.prompt.mask_tokens = W(e, "mask_decoder.mask_tokens.weight");
+    const std::string md = "prompt_encoder.mask_downscaling.";
+    d.mask_embed = MaskEmbedParams{W(e, md + "0.weight"), W(e, md + "0.bias"), W(e, md + "1.weight"), W(e, md + "1.bias"),
+                                   W(e, md + "3.weight"), W(e, md + "3.bias"), W(e, md + "4.weight"), W(e, md + "4.bias"),
+                                   W(e, md + "6.weight"), W(e, md + "6.bias")};
+    d.no_mask_embed = W(e, "prompt_encoder.no_mask_embed.weight");
+    d.norm_final_w = W(e, "mask_decoder.transformer.norm_final_attn.weight");
+    d.norm_final_b = W(e, "mask_decoder.transformer.norm_final_attn.bias");
+    d.up_ln_w = W(e, "mask_decoder.output_upscaling.1.weight");
+    d.up_ln_b = W(e, "mask_decoder.output_upscaling.1.bias");
+    for (int i = 0; i < 5; ++i) {
+        const std::string p = i < 4 ? "mask_decoder.output_hypernetworks_mlps." + std::to_string(i) + ".layers." : "mask_decoder.iou_prediction_head.layers.";
+        for (int k = 0; k < 3; ++k) {
+            d.head_w[i][k] = W(e, p + std::to_string(k) + ".weight");
+            d.head_b[i][k] = W(e, p + std::to_string(k) + ".bias");
+        }
+    }
+    return d;
+}
+
+// the call fields of a PromptParams; its weight fields are the caller's (DecWeights::prompt, or the kernel hook's arguments)
+void prompt_call_fields(PromptParams& pp, const float* boxes, const float* point_coords, const int32_t* point_labels, int n_prompts,
+                        int n_points, float img_size) {
+    pp.boxes = boxes; pp.point_coords = point_coords; pp.point_labels = point_labels;
+    pp.n_prompts = n_prompts; pp.n_points = point_coords ? n_points : 0;
+    pp.img_size = img_size;
+}
+
 // fp32 device tensor -> new ET device tensor (and, if asked for, the remainder of its two-term split); optionally frees the fp32 copy
 int to_et(samrs_engine* e, const std::string& name, uint16_t** out, bool free_f32, hipStream_t s, uint16_t** out_lo = nullptr) {
     DevTensor& t = e->w.at(name);
@@ -509,6 +554,9 @@ samrs_engine_t* samrs_create(const samrs_config* cfg, int device, char* err, int
     if (!cfg) return bad("null config");
     if (cfg->img_size != 1024 || cfg->patch_size != 16 || cfg->window_size != 14 || cfg->out_chans != 256)
         return bad("only img_size 1024 / patch 16 / window 14 / out_chans 256 are supported (build_sam.py:62-80)");
+    // What the decoder relies on from here on: grid 64, tokens 4096 in every engine that exists.  Its route (decode_route) therefore asks no
+    // shape question: 32-row key groups (i2t_fused), 16-token upscaler groups, 256-row GEMM tiles and 1024-row ConvT #2 blocks all divide
+    // these sizes, and each launcher refuses a shape it cannot take on its own.
     if (cfg->embed_dim % 128 || cfg->embed_dim % cfg->num_heads) return bad("embed_dim must be a multiple of 128 and of num_heads");
     const int hd = cfg->embed_dim / cfg->num_heads;
     if (hd != 64 && hd != 80) return bad("head_dim must be 64 or 80");
@@ -875,6 +923,7 @@ int samrs_finalize_weights(samrs_engine_t* e, void* stream) {
     CK(e, dalloc(e, &e->HYPER, Bb * 4 * (C / 8))); CK(e, dalloc(e, &e->IOU, Bb * 4));
     CK(e, dalloc(e, &e->LOW, Bb * 3 * 256 * 256));
     CK(e, hipStreamSynchronize(s));
+    e->dec = dec_weights(e);       // after every to_et(..., free_f32 = true): no freed tensor is resolved
     audit_build_sites(e);
     e->finalized = true;
     return SAMRS_OK;
@@ -1492,7 +1541,7 @@ static int prepare_slot_keys(samrs_engine_t* e, int slot0, int n, hipStream_t s)
     const DecLayer& L = e->layers[0];
     for (int i = 0; i < n; ++i) {
         const size_t o = (size_t)(slot0 + i) * tokens * C;
-        CK(e, launch_make_keys(prec, e->EMB + o, nullptr, W(e, "prompt_encoder.no_mask_embed.weight"), e->K0F + o, e->K0E + o, 1, tokens, C, s));
+        CK(e, launch_make_keys(prec, e->EMB + o, nullptr, e->dec.no_mask_embed, e->K0F + o, e->K0E + o, 1, tokens, C, s));
     }
     CK(e, launch_gemm_et(prec, e->K0E + (size_t)slot0 * tokens * C, L.kvq_w, e->KVQ0 + (size_t)slot0 * tokens * 3 * Ci, L.kvq_b, L.kvq_pe,
                          tokens, n * tokens, 3 * Ci, C, false, false, false, s));
@@ -1658,6 +1707,282 @@ int samrs_predict_multi(samrs_engine_t* e, int n_images, const int* slots, const
                           iou_out, lowres_out, stream);
 }
 
+// ---- the decoder pass: which launches a chunk takes, decided before anything is launched --------------------------------------------
+// decode_route reads engine fields and the call's shape only: it launches nothing, allocates nothing and touches no device memory.
+// run_prompt_side / run_dec_layer / run_final_attn / run_heads / run_upscaler / run_postprocess below do what the route says and decide
+// nothing.  The kernels rely on the one geometry samrs_create admits (grid 64, tokens 4096); a launcher refuses any other shape itself.
+namespace {
+
+// The form of a layer's image -> tokens step (attention, out-projection, residual, norm4).
+//   FUSED: attention + out_proj + residual + norm4 in one pass over the keys (layer 0 without a mask prompt: the residual
+//          is the shared image embedding, batch stride 0).
+// decoder_fusion = 0 (the fused-vs-unfused parity test, timing experiments) takes the separate attention, GEMM and LayerNorm launches:
+//   PER_SEGMENT: the shared layer 0 of a chunk that spans several images, attention + GEMM once per image segment (each segment's
+//          residual is its own slot's layer-0 keys);
+//   SHARED_RESIDUAL: the shared layer 0 of one image, the GEMM adds the slot's layer-0 keys (period = tokens);
+//   ACCUMULATE: per-prompt keys, the GEMM accumulates into KF.
+enum class I2T { FUSED, PER_SEGMENT, SHARED_RESIDUAL, ACCUMULATE };
+// The form of the upscaler (mask_decoder.py:53-59,154-155).
+//   ONE_KERNEL: both transposed convs, LayerNorm2d, both GELUs and the hypernetwork product in one kernel (upscaler_fused.hip): the
+//          [rows][256] intermediate never leaves the CU.
+//   GLN_SPLIT: ConvT #1 as a GEMM with LayerNorm2d(64) + GELU fused into its epilogue, on hi + lo operands, fp32 output in U1raw;
+//          then upscale2_masks on U1raw with the lo weights (it splits U1raw in registers).
+//   GLN:   the same on plain operands: the GEMM writes U1 in the operand type, upscale2_masks reads U1.
+//   UNFUSED: plain GEMM -> U1raw, group_ln_gelu -> U1, GEMM -> U2, mask_product.
+// Which of U1raw / U1 hands ConvT #1's output to ConvT #2 is a property of the form (run_upscaler).
+enum class Upscaler { ONE_KERNEL, GLN_SPLIT, GLN, UNFUSED };
+
+struct DecodeLayerRoute {
+    bool shared = false;           // image side still identical for every prompt of an image: the slot's K0F / KVQ0 rows (prepare_slot_keys), no kvq GEMM
+    long bstride = 0;              // batch stride, in rows, of the image-side operands: 0 = one image's rows for every prompt
+    bool tab = false;              // the kernels get the per-prompt slot table
+    I2T i2t = I2T::FUSED;
+    bool write_kf = false;         // FUSED: also writes the fp32 keys (KF)
+    bool write_ke_lo = false;      // FUSED: also writes the split remainder of the keys (KE_lo)
+    bool ow_lo = false;            // FUSED: reads the lo half of the out-projection weights
+};
+
+struct DecodeRoute {
+    // sizes
+    int T = 0, BT = 0, Mi = 0;     // tokens per prompt; token rows n T; image rows n tokens
+    int npt = 0;                   // point tokens per prompt, the pad point included
+    int sel0 = 0, nsel = 1;        // mask tokens the caller gets: [sel0, sel0 + nsel)  (mask_decoder.py:102-107)
+    // image side
+    bool shared0 = false;          // no mask prompt: layer 0 runs on the slots' prepared keys
+    bool slot_table = false;       // the chunk spans several images: SLOT_OF is filled and read
+    size_t slot0 = 0;              // one image: its slot; several: 0 (the table indexes the whole slot store)
+    DecodeLayerRoute layer[2];
+    // heads + upscaler
+    bool iou = false;              // the caller takes the IoU predictions
+    Upscaler up = Upscaler::ONE_KERNEL;
+    bool sp_up = false;            // the upscaler runs on hi + lo operands (ONE_KERNEL, GLN_SPLIT)
+    bool low_own = false;          // the low-res logits go to the engine's LOW (the caller gave no buffer)
+};
+
+// tokens per prompt: IoU token + 4 mask tokens, the points (+ the pad point when there is no box), two box corners
+static int point_token_count(bool boxes, int n_points) { return n_points ? n_points + (boxes ? 0 : 1) : 0; }
+static int prompt_token_count(bool boxes, int n_points) { return 5 + point_token_count(boxes, n_points) + (boxes ? 2 : 0); }
+
+// `slot_first`: the slot of the chunk's first image segment.  `n_points`: points per prompt, 0 = no point prompt.
+static DecodeRoute decode_route(const samrs_engine_t* e, int n, int n_seg, int slot_first, bool boxes, int n_points, bool mask,
+                                bool multimask, bool has_iou_out, bool has_lowres_out) {
+    DecodeRoute r;
+    r.npt = point_token_count(boxes, n_points);
+    r.T = prompt_token_count(boxes, n_points);
+    r.BT = n * r.T;
+    r.Mi = n * e->tokens;
+    r.sel0 = multimask ? 1 : 0; r.nsel = multimask ? 3 : 1;     // mask_decoder.py:102-107
+    r.shared0 = !mask;
+    // image side: one image -> its slot's rows with batch stride 0, as for every single-image call; several images ->
+    // the per-prompt slot table, and the slot stores with a stride of one slot (only the addressing differs)
+    r.slot_table = n_seg > 1;
+    r.slot0 = n_seg == 1 ? (size_t)slot_first : 0;
+    for (int li = 0; li < 2; ++li) {
+        DecodeLayerRoute& l = r.layer[li];
+        l.shared = r.shared0 && li == 0;     // image side still identical for every prompt
+        l.bstride = l.shared && !r.slot_table ? 0 : e->tokens;     // with the slot table: a stride of one slot
+        l.tab = l.shared && r.slot_table;
+        l.i2t = e->decoder_fusion ? I2T::FUSED : l.tab ? I2T::PER_SEGMENT : l.shared ? I2T::SHARED_RESIDUAL : I2T::ACCUMULATE;
+        // the fp32 copy of the keys is the NEXT layer's residual; after the last layer only the ET copy is read
+        // (final t2i projections, upscaler), so its 4 bytes per element are not written
+        l.write_kf = l.i2t == I2T::FUSED && li == 0;
+        // SPLIT_OI: attention output and out-projection weights as hi + lo; SPLIT_UP: the last layer also writes the split
+        // remainder of the final keys for the first transposed conv
+        l.ow_lo = l.i2t == I2T::FUSED && (e->split & SPLIT_OI);
+        l.write_ke_lo = l.i2t == I2T::FUSED && li == 1 && (e->split & SPLIT_UP);
+    }
+    r.iou = has_iou_out;
+    // A/B knob (timing experiments): SAMRS_DECODER_FUSION=0 runs the un-fused upscaler kernels
+    const bool fuse = e->decoder_fusion;
+    // SPLIT_UP (fused path only): both transposed convs on hi + lo operands -- ConvT #1 writes its LayerNorm2d + GELU output in
+    // fp32 (U1raw), ConvT #2 splits that in registers.  error_budget.py: 376 + 395 of the 899 class-map pixels at ViT-H.
+    r.sp_up = fuse && (e->split & SPLIT_UP);      // KE_lo exists (written by the fused i2t kernel)
+    r.up = !fuse ? Upscaler::UNFUSED : e->upscaler_fused ? Upscaler::ONE_KERNEL : r.sp_up ? Upscaler::GLN_SPLIT : Upscaler::GLN;
+    r.low_own = !has_lowres_out;
+    return r;
+}
+
+// (A + A2) W^T + b
+static hipError_t gemm_f32_sum(const float* A, const float* A2, int lda, const float* Wt, const float* b, float* Cout, int ldc, int M, int N,
+                               int K, hipStream_t s) {
+    F32Batch bt{};
+    bt.A[0] = A; bt.A2[0] = A2; bt.W[0] = Wt; bt.bias[0] = b; bt.C[0] = Cout;
+    return launch_gemm_f32_batch(bt, 1, lda, ldc, M, N, K, false, false, s);
+}
+
+// LayerNorm of the token stream Q, in place
+static hipError_t ln_tokens(samrs_engine_t* e, int BT, const float* gw, const float* gb, hipStream_t s) {
+    return launch_layernorm(e->prec, e->Q, gw, gb, 1e-5f, nullptr, e->Q, BT, e->C, 0, e->grid, 0, s);
+}
+
+}  // namespace
+
+// prompt encoder (prompt_encoder.py:128-173): tokens and (a copy) the initial queries; the slot table of a chunk that spans several
+// images; with a mask prompt its dense embedding and the per-prompt keys
+static int run_prompt_side(samrs_engine_t* e, const DecodeRoute& r, const PredictImage* seg, int n_seg, int n, const float* boxes,
+                           const float* point_coords, const int32_t* point_labels, int n_points, const float* mask_input, hipStream_t s) {
+    const samrs_config& c = e->cfg;
+    const int C = e->C, tokens = e->tokens;
+    PromptParams pp = e->dec.prompt;
+    prompt_call_fields(pp, boxes, point_coords, point_labels, n, n_points, (float)c.img_size);
+    CK(e, launch_prompt_tokens(pp, e->TOK0, e->Q, r.T, s));       // tokens and (a copy) the initial queries
+    if (r.slot_table) {
+        if (!e->SLOT_OF) CK(e, dalloc(e, &e->SLOT_OF, (size_t)c.max_prompts));
+        std::vector<int> start((size_t)n_seg + 1), slot((size_t)n_seg);
+        for (int k = 0; k < n_seg; ++k) { start[k] = seg[k].p0; slot[k] = seg[k].slot; }
+        start[n_seg] = seg[n_seg - 1].p1;
+        CK(e, launch_fill_slot_table(start.data(), slot.data(), n_seg, e->SLOT_OF, s));
+    }
+    if (!r.shared0) {
+        if (!e->DENSE) CK(e, dalloc(e, &e->DENSE, (size_t)c.max_prompts * tokens * C));
+        CK(e, launch_mask_embed(e->dec.mask_embed, mask_input, e->DENSE, n, e->grid, s));
+        CK(e, launch_make_keys(e->prec, e->EMB + r.slot0 * tokens * C, e->DENSE, nullptr, e->KF, e->KE, n, tokens, C, s,
+                               r.slot_table ? e->SLOT_OF : nullptr));
+    }
+    return SAMRS_OK;
+}
+
+// one layer of the two-way transformer (transformer.py:151-182)
+static int run_dec_layer(samrs_engine_t* e, const DecodeRoute& r, int li, const PredictImage* seg, int n_seg, int n, hipStream_t s) {
+    const int C = e->C, Ci = C / 2, tokens = e->tokens, prec = e->prec, g = e->grid, T = r.T, BT = r.BT, Mi = r.Mi;
+    const DecLayer& L = e->layers[li];
+    const DecodeLayerRoute& l = r.layer[li];
+    // layer-0 image side of the slot(s) (prepare_slot_keys, at set_image time)
+    const float* k0f = e->K0F + r.slot0 * tokens * C;
+    const uint16_t* kvq = l.shared ? e->KVQ0 + r.slot0 * tokens * 3 * Ci : e->KVQ;
+    const int* tab = l.tab ? e->SLOT_OF : nullptr;
+    // (1) token self attention: q/k from queries (+ prompt PE after layer 0), v from queries -- one launch
+    {
+        F32Batch bt{};
+        const float* pe = li > 0 ? e->TOK0 : nullptr;
+        bt.A[0] = e->Q; bt.A2[0] = pe; bt.W[0] = L.self.qw; bt.bias[0] = L.self.qb; bt.C[0] = e->TQ;
+        bt.A[1] = e->Q; bt.A2[1] = pe; bt.W[1] = L.self.kw; bt.bias[1] = L.self.kb; bt.C[1] = e->TK;
+        bt.A[2] = e->Q; bt.A2[2] = nullptr; bt.W[2] = L.self.vw; bt.bias[2] = L.self.vb; bt.C[2] = e->TV;
+        CK(e, launch_gemm_f32_batch(bt, 3, C, C, BT, C, C, false, false, s));
+    }
+    CK(e, launch_token_self_attn(e->TQ, e->TK, e->TV, e->TO, n, T, C, 8, s));
+    CK(e, launch_gemm_f32(e->TO, C, L.self.ow, L.self.ob, e->Q, C, BT, C, C, false, li > 0, s));
+    CK(e, ln_tokens(e, BT, L.n1w, L.n1b, s));
+    // image-side projections for this layer: K_t2i | V_t2i | Q_i2t  (PE folded in as add2d)
+    if (!l.shared) CK(e, launch_gemm_et(prec, e->KE, L.kvq_w, e->KVQ, L.kvq_b, L.kvq_pe, tokens, Mi, 3 * Ci, C, false, false, false, s));
+    // (2) tokens -> image
+    CK(e, gemm_f32_sum(e->Q, e->TOK0, C, L.t2i.qw, L.t2i.qb, e->QP, Ci, BT, Ci, C, s));
+    CK(e, launch_t2i_attention(prec, e->QP, kvq, kvq + Ci, 3 * Ci, l.bstride, e->O128, e->T2IW, n, T, tokens, Ci, 8, s, tab));
+    CK(e, launch_gemm_f32(e->O128, Ci, L.t2i.ow, L.t2i.ob, e->Q, C, BT, C, Ci, false, true, s));
+    CK(e, ln_tokens(e, BT, L.n2w, L.n2b, s));
+    // (3) MLP (ReLU)
+    CK(e, launch_gemm_f32(e->Q, C, L.m1w, L.m1b, e->MH, 2048, BT, 2048, C, true, false, s));
+    CK(e, launch_gemm_f32(e->MH, 2048, L.m2w, L.m2b, e->Q, C, BT, C, 2048, false, true, s));
+    CK(e, ln_tokens(e, BT, L.n3w, L.n3b, s));
+    // (4) image -> tokens
+    {
+        F32Batch bt{};
+        bt.A[0] = e->Q; bt.A2[0] = e->TOK0; bt.W[0] = L.i2t.kw; bt.bias[0] = L.i2t.kb; bt.C[0] = e->KT;
+        bt.A[1] = e->Q; bt.A2[1] = nullptr; bt.W[1] = L.i2t.vw; bt.bias[1] = L.i2t.vb; bt.C[1] = e->VT;
+        CK(e, launch_gemm_f32_batch(bt, 2, C, Ci, BT, Ci, C, false, false, s));
+    }
+    switch (l.i2t) {
+    case I2T::FUSED:
+        CK(e, launch_i2t_fused(prec, kvq + 2 * Ci, 3 * Ci, l.bstride, e->KT, e->VT, L.i2t_ow, l.ow_lo ? L.i2t_ow_lo : nullptr, L.i2t.ob,
+                               l.shared ? k0f : e->KF, l.bstride, L.n4w, L.n4b, 1e-5f, l.write_kf ? e->KF : nullptr, e->KE,
+                               l.write_ke_lo ? e->KE_lo : nullptr, n, T, tokens, Ci, C, s, tab));
+        return SAMRS_OK;
+    case I2T::PER_SEGMENT:
+        for (int k = 0; k < n_seg; ++k) {
+            const size_t p0 = (size_t)seg[k].p0, ns = (size_t)(seg[k].p1 - seg[k].p0), sl = (size_t)seg[k].slot;
+            CK(e, launch_i2t_attention(prec, e->KVQ0 + sl * tokens * 3 * Ci + 2 * Ci, 3 * Ci, 0, e->KT + p0 * T * Ci,
+                                       e->VT + p0 * T * Ci, e->OI + p0 * tokens * Ci, (int)ns, T, tokens, Ci, 8, s));
+            CK(e, launch_gemm_et(prec, e->OI + p0 * tokens * Ci, L.i2t_ow, e->KF + p0 * tokens * C, L.i2t.ob,
+                                 e->K0F + sl * tokens * C, tokens, (int)ns * tokens, C, Ci, true, false, false, s));
+        }
+        break;
+    case I2T::SHARED_RESIDUAL:
+        CK(e, launch_i2t_attention(prec, kvq + 2 * Ci, 3 * Ci, l.bstride, e->KT, e->VT, e->OI, n, T, tokens, Ci, 8, s));
+        CK(e, launch_gemm_et(prec, e->OI, L.i2t_ow, e->KF, L.i2t.ob, k0f, tokens, Mi, C, Ci, true, false, false, s));
+        break;
+    case I2T::ACCUMULATE:
+        CK(e, launch_i2t_attention(prec, kvq + 2 * Ci, 3 * Ci, l.bstride, e->KT, e->VT, e->OI, n, T, tokens, Ci, 8, s));
+        CK(e, launch_gemm_et(prec, e->OI, L.i2t_ow, e->KF, L.i2t.ob, nullptr, 0, Mi, C, Ci, true, false, true, s));
+        break;
+    }
+    CK(e, launch_layernorm(prec, e->KF, L.n4w, L.n4b, 1e-5f, e->KE, e->KF, Mi, C, 0, g, 0, s));
+    return SAMRS_OK;
+}
+
+// final tokens -> image attention (transformer.py:98-104)
+static int run_final_attn(samrs_engine_t* e, const DecodeRoute& r, int n, hipStream_t s) {
+    const int C = e->C, Ci = C / 2, tokens = e->tokens, BT = r.BT;
+    CK(e, gemm_f32_sum(e->Q, e->TOK0, C, e->fin.qw, e->fin.qb, e->QP, Ci, BT, Ci, C, s));
+    CK(e, launch_gemm_et(e->prec, e->KE, e->fin_kv_w, e->KVQ, e->fin_kv_b, e->fin_pe, tokens, r.Mi, 2 * Ci, C, false, false, false, s));
+    CK(e, launch_t2i_attention(e->prec, e->QP, e->KVQ, e->KVQ + Ci, 2 * Ci, tokens, e->O128, e->T2IW, n, r.T, tokens, Ci, 8, s));
+    CK(e, launch_gemm_f32(e->O128, Ci, e->fin.ow, e->fin.ob, e->Q, C, BT, C, Ci, false, true, s));
+    CK(e, ln_tokens(e, BT, e->dec.norm_final_w, e->dec.norm_final_b, s));
+    return SAMRS_OK;
+}
+
+// heads (mask_decoder.py:156-172): 4 hypernetwork MLPs + the IoU MLP, layer by layer in one launch each
+static int run_heads(samrs_engine_t* e, const DecodeRoute& r, int n, float* iou_out, hipStream_t s) {
+    const int C = e->C;
+    const DecWeights& w = e->dec;
+    const size_t hs = (size_t)e->cfg.max_prompts * C;
+    F32Batch l0{}, l1{}, l2{};
+    for (int i = 0; i < 5; ++i) {
+        l0.A[i] = i < 4 ? e->Q + (size_t)(1 + i) * C : e->Q;       // mask token i / IoU token of every prompt
+        l0.W[i] = w.head_w[i][0]; l0.bias[i] = w.head_b[i][0]; l0.C[i] = e->HY1 + i * hs;
+        l1.A[i] = e->HY1 + i * hs;
+        l1.W[i] = w.head_w[i][1]; l1.bias[i] = w.head_b[i][1]; l1.C[i] = e->HY2 + i * hs;
+        if (i < 4) {
+            l2.A[i] = e->HY2 + i * hs;
+            l2.W[i] = w.head_w[i][2]; l2.bias[i] = w.head_b[i][2]; l2.C[i] = e->HYPER + i * (C / 8);
+        }
+    }
+    CK(e, launch_gemm_f32_batch(l0, 5, r.T * C, C, n, C, C, true, false, s));
+    CK(e, launch_gemm_f32_batch(l1, 5, C, C, n, C, C, true, false, s));
+    CK(e, launch_gemm_f32_batch(l2, 4, C, 4 * (C / 8), n, C / 8, C, false, false, s));
+    // IoU head, last layer: only the columns the caller gets (mask_decoder.py:102-107), written straight into its buffer
+    if (r.iou)
+        CK(e, launch_gemm_f32(e->HY2 + 4 * hs, C, w.head_w[4][2] + (size_t)r.sel0 * C, w.head_b[4][2] + r.sel0, iou_out, r.nsel, n, r.nsel, C,
+                              false, false, s));
+    return SAMRS_OK;
+}
+
+// upscaler (mask_decoder.py:53-59,154-155) in the form the route names
+static int run_upscaler(samrs_engine_t* e, const DecodeRoute& r, int n, float* low, hipStream_t s) {
+    const int C = e->C, prec = e->prec, g = e->grid, Mi = r.Mi;
+    switch (r.up) {
+    case Upscaler::ONE_KERNEL:
+        CK(e, launch_upscaler_fused(prec, e->KE, r.sp_up ? e->KE_lo : nullptr, e->up1_w, r.sp_up ? e->up1_w_lo : nullptr, e->up1_b, e->up_ln,
+                                    e->up2_w, r.sp_up ? e->up2_w_lo : nullptr, e->up2_b, e->HYPER, low, n, g, 4, r.sel0, r.nsel, s));
+        break;
+    case Upscaler::GLN_SPLIT:
+        CK(e, launch_gemm_et_gln(prec, e->KE, e->up1_w, e->U1raw, e->up1_b, e->up_ln, Mi, C, C, s, e->KE_lo, e->up1_w_lo));
+        CK(e, launch_upscale2_masks(prec, e->U1raw, e->up2_w, e->up2_w_lo, e->up2_b, e->HYPER, low, n, g, 4, r.sel0, r.nsel, s));
+        break;
+    case Upscaler::GLN:
+        CK(e, launch_gemm_et_gln(prec, e->KE, e->up1_w, e->U1, e->up1_b, e->up_ln, Mi, C, C, s));
+        CK(e, launch_upscale2_masks(prec, e->U1, e->up2_w, nullptr, e->up2_b, e->HYPER, low, n, g, 4, r.sel0, r.nsel, s));
+        break;
+    case Upscaler::UNFUSED:
+        CK(e, launch_gemm_et(prec, e->KE, e->up1_w, e->U1raw, e->up1_b, nullptr, 0, Mi, C, C, true, false, false, s));
+        CK(e, launch_group_ln_gelu(prec, e->U1raw, e->dec.up_ln_w, e->dec.up_ln_b, 1e-6f, e->U1, (long)Mi, 4, C / 4, s));
+        CK(e, launch_gemm_et(prec, e->U1, e->up2_w, e->U2, e->up2_b, nullptr, 0, Mi * 4, C / 2, C / 4, false, true, false, s));
+        CK(e, launch_mask_product(prec, e->U2, e->HYPER, low, n, g, 4, r.sel0, r.nsel, s));
+        break;
+    }
+    return SAMRS_OK;
+}
+
+// postprocess (sam.py:133-162) + threshold (predictor.py:242-243)
+// one launch per image segment: sizes and output buffer are the image's
+static int run_postprocess(samrs_engine_t* e, const DecodeRoute& r, const PredictImage* seg, int n_seg, const float* low, int return_logits,
+                           hipStream_t s) {
+    for (int k = 0; k < n_seg; ++k)
+        if (seg[k].masks)
+            CK(e, launch_postprocess(low + (size_t)seg[k].p0 * r.nsel * 256 * 256, (seg[k].p1 - seg[k].p0) * r.nsel, seg[k].in_h, seg[k].in_w,
+                                     seg[k].orig_h, seg[k].orig_w, e->cfg.img_size, return_logits, seg[k].masks, s));
+    return SAMRS_OK;
+}
+
 static int predict_chunk(samrs_engine_t* e, const PredictImage* seg, int n_seg, int n, const float* boxes, const float* point_coords,
                          const int32_t* point_labels, int n_points, const float* mask_input, int multimask,
                          int return_logits, float* iou_out, float* lowres_out, void* stream) {
@@ -1665,202 +1990,18 @@ static int predict_chunk(samrs_engine_t* e, const PredictImage* seg, int n_seg, 
     if (n < 1 || n > c.max_prompts) return fail(e, SAMRS_ERR_CAPACITY, "n_prompts=%d exceeds max_prompts=%d", n, c.max_prompts);
     hipStream_t s = (hipStream_t)stream;
     ON_DEVICE(e);
-    const int C = e->C, Ci = C / 2, tokens = e->tokens, prec = e->prec, g = e->grid;
-    const int npt = point_coords ? n_points + (boxes ? 0 : 1) : 0;
-    const int T = 5 + npt + (boxes ? 2 : 0);
-    const int BT = n * T;
-    const int Mi = n * tokens;
-    auto lin = [&](const float* A, int lda, const float* Wt, const float* b, float* Cout, int ldc, int M, int N, int K,
-                   bool relu, bool acc) { return launch_gemm_f32(A, lda, Wt, b, Cout, ldc, M, N, K, relu, acc, s); };
-    auto lin2 = [&](const float* A, const float* A2, int lda, const float* Wt, const float* b, float* Cout, int ldc, int M,
-                    int N, int K) {     // (A + A2) W^T + b
-        F32Batch bt{};
-        bt.A[0] = A; bt.A2[0] = A2; bt.W[0] = Wt; bt.bias[0] = b; bt.C[0] = Cout;
-        return launch_gemm_f32_batch(bt, 1, lda, ldc, M, N, K, false, false, s);
-    };
-    auto ln_tok = [&](const float* gw, const float* gb) {
-        return launch_layernorm(prec, e->Q, gw, gb, 1e-5f, nullptr, e->Q, BT, C, 0, g, 0, s);
-    };
-
-    // ---- prompt encoder (prompt_encoder.py:128-173) ----
-    PromptParams pp{};
-    pp.boxes = boxes; pp.point_coords = point_coords; pp.point_labels = point_labels;
-    pp.n_prompts = n; pp.n_points = point_coords ? n_points : 0;
-    pp.img_size = (float)c.img_size;
-    pp.gauss = W(e, "prompt_encoder.pe_layer.positional_encoding_gaussian_matrix");
-    for (int i = 0; i < 4; ++i) pp.point_emb[i] = W(e, "prompt_encoder.point_embeddings." + std::to_string(i) + ".weight");
-    pp.not_a_point = W(e, "prompt_encoder.not_a_point_embed.weight");
-    pp.iou_token = W(e, "mask_decoder.iou_token.weight");
-    pp.mask_tokens = W(e, "mask_decoder.mask_tokens.weight");
-    CK(e, launch_prompt_tokens(pp, e->TOK0, e->Q, T, s));       // tokens and (a copy) the initial queries
-
-    const bool shared0 = (mask_input == nullptr);
-    // image side: one image -> its slot's rows with batch stride 0, as for every single-image call; several images ->
-    // the per-prompt slot table, and the slot stores with a stride of one slot (only the addressing differs)
-    const int* slot_tab = nullptr;
-    const size_t slot0 = n_seg == 1 ? (size_t)seg[0].slot : 0;
-    if (n_seg > 1) {
-        if (!e->SLOT_OF) CK(e, dalloc(e, &e->SLOT_OF, (size_t)c.max_prompts));
-        std::vector<int> start((size_t)n_seg + 1), slot((size_t)n_seg);
-        for (int k = 0; k < n_seg; ++k) { start[k] = seg[k].p0; slot[k] = seg[k].slot; }
-        start[n_seg] = seg[n_seg - 1].p1;
-        CK(e, launch_fill_slot_table(start.data(), slot.data(), n_seg, e->SLOT_OF, s));
-        slot_tab = e->SLOT_OF;
-    }
-    const float* emb = e->EMB + slot0 * tokens * C;
-    // layer-0 image side of the slot(s) (prepare_slot_keys, at set_image time)
-    const float* k0f = e->K0F + slot0 * tokens * C;
-    const uint16_t* kvq0 = e->KVQ0 + slot0 * tokens * 3 * Ci;
-    if (!shared0) {
-        if (!e->DENSE) CK(e, dalloc(e, &e->DENSE, (size_t)c.max_prompts * tokens * C));
-        MaskEmbedParams mp{W(e, "prompt_encoder.mask_downscaling.0.weight"), W(e, "prompt_encoder.mask_downscaling.0.bias"),
-                           W(e, "prompt_encoder.mask_downscaling.1.weight"), W(e, "prompt_encoder.mask_downscaling.1.bias"),
-                           W(e, "prompt_encoder.mask_downscaling.3.weight"), W(e, "prompt_encoder.mask_downscaling.3.bias"),
-                           W(e, "prompt_encoder.mask_downscaling.4.weight"), W(e, "prompt_encoder.mask_downscaling.4.bias"),
-                           W(e, "prompt_encoder.mask_downscaling.6.weight"), W(e, "prompt_encoder.mask_downscaling.6.bias")};
-        CK(e, launch_mask_embed(mp, mask_input, e->DENSE, n, g, s));
-        CK(e, launch_make_keys(prec, emb, e->DENSE, nullptr, e->KF, e->KE, n, tokens, C, s, slot_tab));
-    }
-
-    // ---- two-way transformer (transformer.py:62-106,151-182) ----
-    for (int li = 0; li < 2; ++li) {
-        const DecLayer& L = e->layers[li];
-        const bool sh = shared0 && li == 0;     // image side still identical for every prompt
-        // (1) token self attention: q/k from queries (+ prompt PE after layer 0), v from queries -- one launch
-        {
-            F32Batch bt{};
-            const float* pe = li > 0 ? e->TOK0 : nullptr;
-            bt.A[0] = e->Q; bt.A2[0] = pe; bt.W[0] = L.self.qw; bt.bias[0] = L.self.qb; bt.C[0] = e->TQ;
-            bt.A[1] = e->Q; bt.A2[1] = pe; bt.W[1] = L.self.kw; bt.bias[1] = L.self.kb; bt.C[1] = e->TK;
-            bt.A[2] = e->Q; bt.A2[2] = nullptr; bt.W[2] = L.self.vw; bt.bias[2] = L.self.vb; bt.C[2] = e->TV;
-            CK(e, launch_gemm_f32_batch(bt, 3, C, C, BT, C, C, false, false, s));
-        }
-        CK(e, launch_token_self_attn(e->TQ, e->TK, e->TV, e->TO, n, T, C, 8, s));
-        CK(e, lin(e->TO, C, L.self.ow, L.self.ob, e->Q, C, BT, C, C, false, li > 0));
-        CK(e, ln_tok(L.n1w, L.n1b));
-        // image-side projections for this layer: K_t2i | V_t2i | Q_i2t  (PE folded in as add2d)
-        const long bstride = sh && !slot_tab ? 0 : tokens;     // with the slot table: a stride of one slot
-        const int* tab = sh ? slot_tab : nullptr;
-        const uint16_t* kvq = sh ? kvq0 : e->KVQ;
-        if (!sh) CK(e, launch_gemm_et(prec, e->KE, L.kvq_w, e->KVQ, L.kvq_b, L.kvq_pe, tokens, Mi, 3 * Ci, C, false, false, false, s));
-        // (2) tokens -> image
-        CK(e, lin2(e->Q, e->TOK0, C, L.t2i.qw, L.t2i.qb, e->QP, Ci, BT, Ci, C));
-        CK(e, launch_t2i_attention(prec, e->QP, kvq, kvq + Ci, 3 * Ci, bstride, e->O128, e->T2IW, n, T, tokens, Ci, 8, s, tab));
-        CK(e, lin(e->O128, Ci, L.t2i.ow, L.t2i.ob, e->Q, C, BT, C, Ci, false, true));
-        CK(e, ln_tok(L.n2w, L.n2b));
-        // (3) MLP (ReLU)
-        CK(e, lin(e->Q, C, L.m1w, L.m1b, e->MH, 2048, BT, 2048, C, true, false));
-        CK(e, lin(e->MH, 2048, L.m2w, L.m2b, e->Q, C, BT, C, 2048, false, true));
-        CK(e, ln_tok(L.n3w, L.n3b));
-        // (4) image -> tokens
-        {
-            F32Batch bt{};
-            bt.A[0] = e->Q; bt.A2[0] = e->TOK0; bt.W[0] = L.i2t.kw; bt.bias[0] = L.i2t.kb; bt.C[0] = e->KT;
-            bt.A[1] = e->Q; bt.A2[1] = nullptr; bt.W[1] = L.i2t.vw; bt.bias[1] = L.i2t.vb; bt.C[1] = e->VT;
-            CK(e, launch_gemm_f32_batch(bt, 2, C, Ci, BT, Ci, C, false, false, s));
-        }
-        if (e->decoder_fusion && tokens % 32 == 0) {
-            // attention + out_proj + residual + norm4 in one pass over the keys (layer 0 without a mask prompt: the residual
-            // is the shared image embedding, batch stride 0)
-            // the fp32 copy of the keys is the NEXT layer's residual; after the last layer only the ET copy is read
-            // (final t2i projections, upscaler), so its 4 bytes per element are not written
-            // SPLIT_OI: attention output and out-projection weights as hi + lo; SPLIT_UP: the last layer also writes the split
-            // remainder of the final keys for the first transposed conv
-            CK(e, launch_i2t_fused(prec, kvq + 2 * Ci, 3 * Ci, bstride, e->KT, e->VT, L.i2t_ow,
-                                   (e->split & SPLIT_OI) ? L.i2t_ow_lo : nullptr, L.i2t.ob, sh ? k0f : e->KF,
-                                   bstride, L.n4w, L.n4b, 1e-5f, li == 1 ? nullptr : e->KF, e->KE,
-                                   (li == 1 && (e->split & SPLIT_UP)) ? e->KE_lo : nullptr, n, T, tokens, Ci, C, s, tab));
-        } else if (tab) {
-            // small test geometries only (tokens % 32 != 0) or decoder_fusion = 0: the shared layer 0 once per image segment
-            for (int k = 0; k < n_seg; ++k) {
-                const size_t p0 = (size_t)seg[k].p0, ns = (size_t)(seg[k].p1 - seg[k].p0), sl = (size_t)seg[k].slot;
-                CK(e, launch_i2t_attention(prec, e->KVQ0 + sl * tokens * 3 * Ci + 2 * Ci, 3 * Ci, 0, e->KT + p0 * T * Ci,
-                                           e->VT + p0 * T * Ci, e->OI + p0 * tokens * Ci, (int)ns, T, tokens, Ci, 8, s));
-                CK(e, launch_gemm_et(prec, e->OI + p0 * tokens * Ci, L.i2t_ow, e->KF + p0 * tokens * C, L.i2t.ob,
-                                     e->K0F + sl * tokens * C, tokens, (int)ns * tokens, C, Ci, true, false, false, s));
-            }
-            CK(e, launch_layernorm(prec, e->KF, L.n4w, L.n4b, 1e-5f, e->KE, e->KF, Mi, C, 0, g, 0, s));
-        } else {
-            CK(e, launch_i2t_attention(prec, kvq + 2 * Ci, 3 * Ci, bstride, e->KT, e->VT, e->OI, n, T, tokens, Ci, 8, s));
-            if (sh)
-                CK(e, launch_gemm_et(prec, e->OI, L.i2t_ow, e->KF, L.i2t.ob, k0f, tokens, Mi, C, Ci, true, false, false, s));
-            else
-                CK(e, launch_gemm_et(prec, e->OI, L.i2t_ow, e->KF, L.i2t.ob, nullptr, 0, Mi, C, Ci, true, false, true, s));
-            CK(e, launch_layernorm(prec, e->KF, L.n4w, L.n4b, 1e-5f, e->KE, e->KF, Mi, C, 0, g, 0, s));
-        }
-    }
-    // final tokens -> image attention (transformer.py:98-104)
-    CK(e, lin2(e->Q, e->TOK0, C, e->fin.qw, e->fin.qb, e->QP, Ci, BT, Ci, C));
-    CK(e, launch_gemm_et(prec, e->KE, e->fin_kv_w, e->KVQ, e->fin_kv_b, e->fin_pe, tokens, Mi, 2 * Ci, C, false, false, false, s));
-    CK(e, launch_t2i_attention(prec, e->QP, e->KVQ, e->KVQ + Ci, 2 * Ci, tokens, e->O128, e->T2IW, n, T, tokens, Ci, 8, s));
-    CK(e, lin(e->O128, Ci, e->fin.ow, e->fin.ob, e->Q, C, BT, C, Ci, false, true));
-    CK(e, ln_tok(W(e, "mask_decoder.transformer.norm_final_attn.weight"), W(e, "mask_decoder.transformer.norm_final_attn.bias")));
-
-    // ---- heads (mask_decoder.py:156-172): 4 hypernetwork MLPs + the IoU MLP, layer by layer in one launch each ----
-    {
-        const std::string hp = "mask_decoder.output_hypernetworks_mlps.", ip = "mask_decoder.iou_prediction_head.layers";
-        const size_t hs = (size_t)c.max_prompts * C;
-        F32Batch l0{}, l1{}, l2{};
-        for (int i = 0; i < 5; ++i) {
-            const std::string p = i < 4 ? hp + std::to_string(i) + ".layers" : ip;
-            l0.A[i] = i < 4 ? e->Q + (size_t)(1 + i) * C : e->Q;       // mask token i / IoU token of every prompt
-            l0.W[i] = W(e, p + ".0.weight"); l0.bias[i] = W(e, p + ".0.bias"); l0.C[i] = e->HY1 + i * hs;
-            l1.A[i] = e->HY1 + i * hs;
-            l1.W[i] = W(e, p + ".1.weight"); l1.bias[i] = W(e, p + ".1.bias"); l1.C[i] = e->HY2 + i * hs;
-            if (i < 4) {
-                l2.A[i] = e->HY2 + i * hs;
-                l2.W[i] = W(e, p + ".2.weight"); l2.bias[i] = W(e, p + ".2.bias"); l2.C[i] = e->HYPER + i * (C / 8);
-            }
-        }
-        CK(e, launch_gemm_f32_batch(l0, 5, T * C, C, n, C, C, true, false, s));
-        CK(e, launch_gemm_f32_batch(l1, 5, C, C, n, C, C, true, false, s));
-        CK(e, launch_gemm_f32_batch(l2, 4, C, 4 * (C / 8), n, C / 8, C, false, false, s));
-        // IoU head, last layer: only the columns the caller gets (mask_decoder.py:102-107), written straight into its buffer
-        if (iou_out) {
-            const int s0 = multimask ? 1 : 0, ns = multimask ? 3 : 1;
-            CK(e, lin(e->HY2 + 4 * hs, C, W(e, ip + ".2.weight") + (size_t)s0 * C, W(e, ip + ".2.bias") + s0, iou_out, ns, n, ns, C, false, false));
-        }
-    }
-    // ---- upscaler (mask_decoder.py:53-59,154-155) as two GEMMs + fused tail ----
-    // A/B knob (timing experiments): SAMRS_DECODER_FUSION=0 runs the un-fused upscaler kernels
-    const bool fuse = e->decoder_fusion;
-    // SPLIT_UP (fused path only): both transposed convs on hi + lo operands -- ConvT #1 writes its LayerNorm2d + GELU output in
-    // fp32 (U1raw), ConvT #2 splits that in registers.  error_budget.py: 376 + 395 of the 899 class-map pixels at ViT-H.
-    const bool sp_up = fuse && (e->split & SPLIT_UP) && tokens % 32 == 0;      // KE_lo exists (written by the fused i2t kernel)
-    const int sel0 = multimask ? 1 : 0, nsel = multimask ? 3 : 1;     // mask_decoder.py:102-107
-    float* low = lowres_out ? lowres_out : e->LOW;
-    const bool one_kernel = fuse && e->upscaler_fused && g % 16 == 0;
-    if (one_kernel) {
-        // both transposed convs, LayerNorm2d, both GELUs and the hypernetwork product in one kernel (upscaler_fused.hip): the
-        // [rows][256] intermediate never leaves the CU
-        CK(e, launch_upscaler_fused(prec, e->KE, sp_up ? e->KE_lo : nullptr, e->up1_w, sp_up ? e->up1_w_lo : nullptr, e->up1_b, e->up_ln,
-                                    e->up2_w, sp_up ? e->up2_w_lo : nullptr, e->up2_b, e->HYPER, low, n, g, 4, sel0, nsel, s));
-    } else if (sp_up && Mi % 256 == 0 && (g * g * 4) % 1024 == 0) {
-        CK(e, launch_gemm_et_gln(prec, e->KE, e->up1_w, e->U1raw, e->up1_b, e->up_ln, Mi, C, C, s, e->KE_lo, e->up1_w_lo));
-    } else if (fuse && Mi % 256 == 0) {   // ConvT #1 as a GEMM with LayerNorm2d(64) + GELU fused into its epilogue
-        CK(e, launch_gemm_et_gln(prec, e->KE, e->up1_w, e->U1, e->up1_b, e->up_ln, Mi, C, C, s));
-    } else {
-        CK(e, launch_gemm_et(prec, e->KE, e->up1_w, e->U1raw, e->up1_b, nullptr, 0, Mi, C, C, true, false, false, s));
-        CK(e, launch_group_ln_gelu(prec, e->U1raw, W(e, "mask_decoder.output_upscaling.1.weight"),
-                                   W(e, "mask_decoder.output_upscaling.1.bias"), 1e-6f, e->U1, (long)Mi, 4, C / 4, s));
-    }
-    if (one_kernel) {
-        // done above
-    } else if (sp_up && Mi % 256 == 0 && (g * g * 4) % 1024 == 0) {
-        CK(e, launch_upscale2_masks(prec, e->U1raw, e->up2_w, e->up2_w_lo, e->up2_b, e->HYPER, low, n, g, 4, sel0, nsel, s));
-    } else if (fuse && (g * g * 4) % 1024 == 0) {
-        CK(e, launch_upscale2_masks(prec, e->U1, e->up2_w, nullptr, e->up2_b, e->HYPER, low, n, g, 4, sel0, nsel, s));
-    } else {   // tiny grids (test configurations): GEMM + separate product
-        CK(e, launch_gemm_et(prec, e->U1, e->up2_w, e->U2, e->up2_b, nullptr, 0, Mi * 4, C / 2, C / 4, false, true, false, s));
-        CK(e, launch_mask_product(prec, e->U2, e->HYPER, low, n, g, 4, sel0, nsel, s));
-    }
-    // ---- postprocess (sam.py:133-162) + threshold (predictor.py:242-243) ----
-    // one launch per image segment: sizes and output buffer are the image's
-    for (int k = 0; k < n_seg; ++k)
-        if (seg[k].masks)
-            CK(e, launch_postprocess(low + (size_t)seg[k].p0 * nsel * 256 * 256, (seg[k].p1 - seg[k].p0) * nsel, seg[k].in_h, seg[k].in_w,
-                                     seg[k].orig_h, seg[k].orig_w, c.img_size, return_logits, seg[k].masks, s));
-    return SAMRS_OK;
+    const DecodeRoute r = decode_route(e, n, n_seg, seg[0].slot, boxes != nullptr, point_coords ? n_points : 0, mask_input != nullptr,
+                                       multimask != 0, iou_out != nullptr, lowres_out != nullptr);
+    float* low = r.low_own ? e->LOW : lowres_out;
+    int rc;
+    if ((rc = run_prompt_side(e, r, seg, n_seg, n, boxes, point_coords, point_labels, n_points, mask_input, s))) return rc;
+    // two-way transformer (transformer.py:62-106)
+    for (int li = 0; li < 2; ++li)
+        if ((rc = run_dec_layer(e, r, li, seg, n_seg, n, s))) return rc;
+    if ((rc = run_final_attn(e, r, n, s))) return rc;
+    if ((rc = run_heads(e, r, n, iou_out, s))) return rc;
+    if ((rc = run_upscaler(e, r, n, low, s))) return rc;
+    return run_postprocess(e, r, seg, n_seg, low, return_logits, s);
 }
 
 int samrs_paint(samrs_engine_t* e, const uint8_t* masks, const int32_t* labels, int n, int h, int w, uint8_t* seg,
@@ -2436,14 +2577,11 @@ int samrs_k_prompt_tokens(const float* boxes, const float* point_coords, const i
     if (!tokens || !gauss || !point_emb || !not_a_point || !iou_token || !mask_tokens || n_prompts < 1) return SAMRS_ERR_BAD_ARG;
     if ((point_coords != nullptr) != (point_labels != nullptr) || (point_coords && n_points < 1)) return SAMRS_ERR_BAD_ARG;
     PromptParams pp{};
-    pp.boxes = boxes; pp.point_coords = point_coords; pp.point_labels = point_labels;
-    pp.n_prompts = n_prompts; pp.n_points = point_coords ? n_points : 0;
-    pp.img_size = img_size;
+    prompt_call_fields(pp, boxes, point_coords, point_labels, n_prompts, n_points, img_size);
     pp.gauss = gauss;
     for (int i = 0; i < 4; ++i) pp.point_emb[i] = point_emb + i * 256;
     pp.not_a_point = not_a_point; pp.iou_token = iou_token; pp.mask_tokens = mask_tokens;
-    const int npt = point_coords ? n_points + (boxes ? 0 : 1) : 0;
-    if (T != 5 + npt + (boxes ? 2 : 0)) return SAMRS_ERR_BAD_SHAPE;
+    if (T != prompt_token_count(boxes != nullptr, pp.n_points)) return SAMRS_ERR_BAD_SHAPE;
     KRET(launch_prompt_tokens(pp, tokens, tokens2, T, (hipStream_t)stream));
 }
 int samrs_k_dense_pe(const float* gauss, float* pe, int grid, void* stream) {

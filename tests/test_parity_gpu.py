@@ -302,6 +302,45 @@ def test_decoder_alone_all_prompt_types(precision):
     assert not bad, bad
 
 
+@pytest.mark.parametrize("route", [dict(upscaler_fused=0, split=15), dict(upscaler_fused=0, split=3), dict(decoder_fusion=0)],
+                         ids=["gln_split", "gln", "unfused"])
+@pytest.mark.parametrize("precision", ["f16", "bf16"])
+def test_decoder_alone_every_route(precision, route):
+    """test_decoder_alone_all_prompt_types on the decoder's other three routes (decode_route, engine.hip): ConvT #1 as a GEMM with the
+    LayerNorm2d + GELU epilogue followed by upscale2_masks, on split operands (split 15) and on plain ones (split 3), and the
+    un-fused kernels (decoder_fusion = 0).  Same cases, same bounds: measured under the library of the commit before decode_route
+    existed, the worst route (bf16, un-fused) reaches rel L2 4.4e-3 of 1.2e-2, max err / std 2.7e-2 of 5e-2, IoU-prediction error
+    1.5e-4 of 2e-2; f16 5.7e-4 / 3.0e-3 / 2.3e-5 (profiles/r09_decoder_route.txt 3)."""
+    from oracle.make_golden import cases, run_predictor
+    so = _oracle()
+    name = "vit_tiny"
+    pred = get_predictor(name, precision)
+    orc = get_oracle(name)
+    img = synth.make_image(0)
+    orc.set_image(img)
+    pred.set_image(img)                              # sets sizes / state
+    pred.model.engine.set_embedding(orc.features.cuda(), pred.slot)
+    tol_l2, tol_max = (1.5e-3, 6e-3) if precision == "f16" else (1.2e-2, 5e-2)
+    bad = []
+    if ("decoder_alone_refs", name) not in _CACHE:   # the oracle's answers, once for the six parameter sets of this test
+        _CACHE[("decoder_alone_refs", name)] = [(tag, kw, run_predictor(orc, so.apply_boxes, so.apply_coords, img.shape[:2], kw))
+                                                for tag, kw, labels in cases(name)]
+    with pred.model.engine.options(**route):
+        for tag, kw, (m0, i0, l0) in _CACHE[("decoder_alone_refs", name)]:
+            m, i, l = run_predictor(pred, lambda b, s: pred.transform.apply_boxes_torch(b.cuda(), s),
+                                    lambda c, s: pred.transform.apply_coords_torch(c.cuda(), s), img.shape[:2], kw)
+            err = (l.cpu() - l0).abs().max().item() / l0.std().item()
+            l2 = ((l.cpu() - l0).norm() / l0.norm()).item()
+            ierr = (i.cpu() - i0).abs().max().item()
+            ious = iou_stats(m.cpu(), m0)
+            print(f"decoder {precision} {route} {tag}: low-res rel L2 {l2:.3e} max err / std {err:.3e}; iou-pred err {ierr:.3e}; "
+                  f"mask IoU min {ious.min():.5f}")
+            assert m.shape == m0.shape and l.shape == l0.shape and i.shape == i0.shape
+            if not (l2 < tol_l2 and err < tol_max and ierr < (2e-3 if precision == "f16" else 2e-2)):
+                bad.append(tag)
+    assert not bad, bad
+
+
 def _prompt_side_fp64(so, sd64, cfg, points, boxes, mask):
     """float64 statement of the three pure-fp32 stages (prompt tokens, dense embedding, layer-0 keys' addend) for the
     fp32 rule of tests/test_decoder_kernels_gpu.py: the oracle's own code on a float64 state dict; the mask path restated,
