@@ -249,6 +249,33 @@ enum samrs_region_mode { SAMRS_REGION_HOLES = 1, SAMRS_REGION_ISLANDS = 2, SAMRS
 int samrs_clean_masks(samrs_engine_t* e, uint8_t* masks, int n, int h, int w, int min_area, int mode,
                       int64_t* areas_out, int64_t* changed_out, void* stream);
 
+/* -- where a mask actually is: the tight horizontal box and the minimum-area rotated box of every mask, derived on the device from
+ * the masks themselves (the `bbox` the reference stores is the PROMPT box; its oriented annotations -- DOTA text form, `Generate
+ * Dataset/ann_transform.py:46` -- come from cv2.findContours + cv2.minAreaRect on the host).  masks uint8 [n][h][w] device (non-zero
+ * = set), decoded in a window whose origin is (x0, y0) in the frame the boxes are wanted in.
+ *   points      the set pixels as integer points (x0 + col, y0 + row): pixel CENTRES, cv2's convention;
+ *   hbox_out    int32 [n][4] = xmin, ymin, xmax, ymax, inclusive;
+ *   hull        the strict vertices of the convex hull (no collinear points), from v0 = the set pixel with the smallest (y, x), down
+ *               the left side, along the last non-empty row, up the right side, back to v0; m vertices (1 for one pixel, 2 for
+ *               collinear pixels);
+ *   candidates  edge k = vertex k -> vertex (k + 1) mod m with (dx, dy) their difference (not reduced); over the hull vertices
+ *               p = x dx + y dy, q = -x dy + y dx; area (pmax - pmin)(qmax - qmin) / (dx^2 + dy^2), an exact rational;
+ *   winner      the smallest area, compared exactly; ties go to the smallest k (this library's rule).  m = 1: (dx, dy) = (1, 0);
+ *   rbox_out    fp32 [n][4][2]: the corners (pmin, qmin), (pmax, qmin), (pmax, qmax), (pmin, qmax) as x = (p dx - q dy) / L,
+ *               y = (p dy + q dx) / L, L = dx^2 + dy^2: an exact integer numerator, one correctly rounded fp64 division, rounded
+ *               to fp32;
+ *   record_out  int64 [n][8]: dx, dy, pmin, pmax, qmin, qmax, m, twice the hull's area (shoelace sum over the ordered vertices):
+ *               convexity = mask area / hull area comes for free.
+ * An empty mask has m = 0 and all its outputs zero.  Any output may be NULL.  Not pinned against cv2 itself: cv2.minAreaRect works
+ * from the same hull, so it can differ only in float rounding and in which of several equal-area rectangles it returns.
+ * h, w <= 8192, x0, y0 >= 0, x0 + w <= 32768 and y0 + h <= 32768; outside these limits, n < 0 or masks == NULL:
+ * SAMRS_ERR_BAD_ARG and nothing is written.  n == 0 is a no-op.  Integer arithmetic up to the one division per coordinate,
+ * bitwise reproducible, no host synchronisation.  The row extents (12 bytes per mask row; a call whose extents would exceed 64 MiB
+ * runs as consecutive chunks on the stream) live in ONE scratch buffer per handle that grows on demand: all samrs_mask_boxes calls
+ * on a handle must be stream-ordered with each other (same stream, or an event between them); two handles never share it. */
+int samrs_mask_boxes(samrs_engine_t* e, const uint8_t* masks, int n, int h, int w, int x0, int y0,
+                     int32_t* hbox_out /*[n][4]*/, float* rbox_out /*[n][4][2]*/, int64_t* record_out /*[n][8]*/, void* stream);
+
 /* -- the generation CLI's class-map files (main_sam_hbox_semantic.py:212-215: gray/<stem>.png and color/<stem>.png), encoded on
  * the device.  maps: uint8 [n][h][w] (255 = unlabeled), lut: uint8 [256][3] (class id -> RGB), both on the device.  The two PNG
  * files of each map are byte-identical with what the host's samrs_io_png_write_label_pair (include/samrs_io.h) writes for

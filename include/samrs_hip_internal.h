@@ -219,6 +219,14 @@ int samrs_k_audit_rows_per_partial(void);
  * labels_out int32 [n][h][w] = the flattened root of every pixel, i.e. the smallest row-major pixel index of its 8-connected
  * component of the set pixels (complement != 0: of the unset pixels), -1 where the pixel is not in that working set */
 int samrs_k_region_labels(const uint8_t* masks, int n, int h, int w, int complement, int32_t* labels_out, void* stream);
+/* the two kernels of samrs_mask_boxes alone (box_kernels.hip).
+ *   samrs_k_mask_row_extents  ext_out int32 [n][h][3] = first set column, last set column, pixel count of every row (-1, -1, 0 for an
+ *                             empty row)
+ *   samrs_k_mask_hull         the ordered strict hull vertices: verts_out int32 [n][cap][2] = (x, y) of the first min(m, cap) vertices
+ *                             in the frame of (x0, y0), counts_out int32 [n] = m; ext_scratch: device int32 [n][h][3] */
+int samrs_k_mask_row_extents(const uint8_t* masks, int n, int h, int w, int32_t* ext_out, void* stream);
+int samrs_k_mask_hull(const uint8_t* masks, int n, int h, int w, int x0, int y0, int32_t* ext_scratch, int32_t* verts_out, int cap,
+                      int32_t* counts_out, void* stream);
 
 #ifdef __cplusplus
 }

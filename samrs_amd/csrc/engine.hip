@@ -245,6 +245,9 @@ struct samrs_engine {
     // labels + areas + counters of samrs_clean_masks, grown on demand
     void* region_scratch = nullptr;
     size_t region_scratch_bytes = 0;
+    // row extents of samrs_mask_boxes, grown on demand
+    void* box_scratch = nullptr;
+    size_t box_scratch_bytes = 0;
     // class-map PNG scratch (samrs_png_encode_labels), grown on demand
     void* png_scratch = nullptr;
     size_t png_scratch_bytes = 0;
@@ -624,6 +627,7 @@ void samrs_destroy(samrs_engine_t* e) {
     for (void* p : e->owned) (void)hipFree(p);
     if (e->rle_scratch) (void)hipFree(e->rle_scratch);
     if (e->region_scratch) (void)hipFree(e->region_scratch);
+    if (e->box_scratch) (void)hipFree(e->box_scratch);
     if (e->png_scratch) (void)hipFree(e->png_scratch);
     delete e;
 }
@@ -2266,6 +2270,38 @@ int samrs_clean_masks(samrs_engine_t* e, uint8_t* masks, int n, int h, int w, in
     return SAMRS_OK;
 }
 
+// tight hbox, minimum-area rbox and record of n masks (see samrs_hip.h)
+int samrs_mask_boxes(samrs_engine_t* e, const uint8_t* masks, int n, int h, int w, int x0, int y0, int32_t* hbox_out, float* rbox_out,
+                     int64_t* record_out, void* stream) {
+    if (!e || !masks || n < 0) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_mask_boxes: bad argument");
+    if (!mask_boxes_shape_ok(h, w, x0, y0))
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_mask_boxes: %d x %d masks at (%d, %d): h, w must be 1..8192 and x0 + w, y0 + h <= 32768",
+                    h, w, x0, y0);
+    if (n == 0 || (!hbox_out && !rbox_out && !record_out)) return SAMRS_OK;
+    ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    const int cap = (int)(((size_t)64 << 20) / mask_boxes_scratch_bytes(1, h));      // masks per pass: the scratch stays below 64 MiB
+    const int chunk = n < cap ? n : cap;
+    const size_t need = mask_boxes_scratch_bytes(chunk, h);
+    if (need > e->box_scratch_bytes) {
+        if (e->box_scratch) {
+            CK(e, hipStreamSynchronize(s));
+            CK(e, hipFree(e->box_scratch));               // device-synchronising: nothing still reads the old scratch
+            e->box_scratch = nullptr; e->box_scratch_bytes = 0;
+        }
+        CK(e, hipMalloc(&e->box_scratch, need));
+        e->box_scratch_bytes = need;
+    }
+    for (int off = 0; off < n; off += chunk) {
+        const int m = n - off < chunk ? n - off : chunk;
+        CK(e, launch_mask_row_extents(masks + (size_t)off * h * w, m, h, w, (int32_t*)e->box_scratch, s));
+        CK(e, launch_mask_hull_rect((const int32_t*)e->box_scratch, m, h, x0, y0, hbox_out ? hbox_out + (size_t)off * 4 : nullptr,
+                                    rbox_out ? rbox_out + (size_t)off * 8 : nullptr,
+                                    record_out ? (long long*)record_out + (size_t)off * 8 : nullptr, nullptr, 0, nullptr, s));
+    }
+    return SAMRS_OK;
+}
+
 // gray + colour PNG files of n class maps, packed behind *cursor into `out` (see samrs_hip.h)
 int samrs_png_encode_labels(samrs_engine_t* e, const uint8_t* maps, int n, int h, int w, const uint8_t* lut, uint8_t* out,
                             int64_t out_capacity, int64_t* cursor, int64_t* table, void* stream) {
@@ -2523,6 +2559,16 @@ int samrs_k_postprocess(const float* low, int n_masks, int in_h, int in_w, int o
 }
 int samrs_k_region_labels(const uint8_t* masks, int n, int h, int w, int complement, int32_t* labels_out, void* stream) {
     KRET(launch_region_labels(masks, n, h, w, complement, labels_out, (hipStream_t)stream));
+}
+int samrs_k_mask_row_extents(const uint8_t* masks, int n, int h, int w, int32_t* ext_out, void* stream) {
+    KRET(launch_mask_row_extents(masks, n, h, w, ext_out, (hipStream_t)stream));
+}
+int samrs_k_mask_hull(const uint8_t* masks, int n, int h, int w, int x0, int y0, int32_t* ext_scratch, int32_t* verts_out, int cap,
+                      int32_t* counts_out, void* stream) {
+    if (!verts_out || !counts_out || !mask_boxes_shape_ok(h, w, x0, y0)) return SAMRS_ERR_BAD_ARG;
+    hipError_t err = launch_mask_row_extents(masks, n, h, w, ext_scratch, (hipStream_t)stream);
+    if (err != hipSuccess) KRET(err);
+    KRET(launch_mask_hull_rect(ext_scratch, n, h, x0, y0, nullptr, nullptr, nullptr, verts_out, cap, counts_out, (hipStream_t)stream));
 }
 int samrs_k_gemm_gln(int prec, const void* A, const void* B, void* C, const float* bias, const float* gamma_beta, int M, int N,
                      int K, const void* A_lo, const void* B_lo, void* stream) {

@@ -287,3 +287,15 @@ hipError_t launch_clean_masks(uint8_t* masks, int n, int h, int w, int min_area,
 // the labelling alone (any n): labels_out int32 [n][h][w] = the smallest row-major pixel index of the pixel's 8-connected component
 // of the set pixels (complement != 0: of the unset pixels), -1 outside that working set.  Needs no scratch.
 hipError_t launch_region_labels(const uint8_t* masks, int n, int h, int w, int complement, int32_t* labels_out, hipStream_t s);
+
+// ---- box_kernels.hip ------------------------------------------------------------------------
+// Mask-derived boxes (definition: the header comment of box_kernels.hip).  ext: int32 [n][h][3] = first set column, last set column
+// and pixel count of every row of masks uint8 [n][h][w] (-1, -1, 0 for an empty row); it is the scratch between the two launches,
+// mask_boxes_scratch_bytes(n, h).  hbox_out int32 [n][4], rbox_out fp32 [n][4][2], record_out int64 [n][8], verts_out int32
+// [n][cap][2] (the ordered hull vertices, the first min(m, cap) of them) and counts_out int32 [n] (m) may each be null.
+// h, w <= 8192, x0, y0 >= 0, x0 + w, y0 + h <= 32768 (mask_boxes_shape_ok).
+bool mask_boxes_shape_ok(int h, int w, int x0, int y0);
+size_t mask_boxes_scratch_bytes(int n, int h);
+hipError_t launch_mask_row_extents(const uint8_t* masks, int n, int h, int w, int32_t* ext, hipStream_t s);
+hipError_t launch_mask_hull_rect(const int32_t* ext, int n, int h, int x0, int y0, int32_t* hbox_out, float* rbox_out,
+                                 long long* record_out, int32_t* verts_out, int cap, int32_t* counts_out, hipStream_t s);

@@ -324,6 +324,11 @@ class TileResult:
     png_table: Optional[np.ndarray] = None  # int64 [2, 2] (offset, length) of the gray and the colour PNG in png_data (png_lut)
     png_data: Optional[np.ndarray] = None   # uint8 view of the batch's pinned PNG byte buffer
     changed: Optional[np.ndarray] = None    # int64 [n_boxes] pixels the small-region clean-up changed (min_region_area > 0)
+    # mask_boxes=True (samrs_mask_boxes, in the image's own frame; an empty mask has mask_record[j, 6] == 0 and zeros everywhere):
+    mask_hbox: Optional[np.ndarray] = None  # int32 [n_boxes, 4] xmin, ymin, xmax, ymax (inclusive) of the set pixels
+    mask_rbox: Optional[np.ndarray] = None  # fp32 [n_boxes, 4, 2] corners of the minimum-area rotated rectangle of the pixel centres
+    mask_record: Optional[np.ndarray] = None    # int64 [n_boxes, 8] dx, dy, pmin, pmax, qmin, qmax, hull vertices m, 2 x hull area
+    gt_hbox: Optional[np.ndarray] = None    # int32 [n_boxes, 4] the same hbox of the ground-truth masks (gt=True, rle=True, mask_boxes=True)
     windows: Optional[List[Tuple[int, int, int, int]]] = None   # scene mode (scene.ScenePipeline): the planned (x0, y0, w, h) windows
     window_of: Optional[List[int]] = None   # scene mode: window_of[j] = index into `windows` of the window box j was decoded in
 
@@ -334,6 +339,13 @@ class TileResult:
             raise ValueError("no device PNG files: the pipeline ran without png_lut")
         off, n = (int(v) for v in self.png_table[{"gray": 0, "color": 1}[kind]])
         return memoryview(self.png_data[off:off + n])
+
+    def mask_bbox(self, j: int) -> Optional[List[int]]:
+        """COCO ``[x, y, w, h]`` of instance j's mask (w = xmax - xmin + 1: whole pixels), None for an empty mask."""
+        if int(self.mask_record[j, 6]) == 0:
+            return None
+        x0, y0, x1, y1 = (int(v) for v in self.mask_hbox[j])
+        return [x0, y0, x1 - x0 + 1, y1 - y0 + 1]
 
     def rle(self, j: int) -> dict:
         """COCO RLE of instance j exactly as the reference stores it (main_sam_hbox_semantic.py:201-202):
@@ -351,10 +363,14 @@ class TileResult:
 
 
 class _OutBuf:
-    def __init__(self, batch: int, side: int, max_boxes: int, rle: bool = False, png: bool = False, changed: bool = False):
+    def __init__(self, batch: int, side: int, max_boxes: int, rle: bool = False, png: bool = False, changed: bool = False,
+                 boxes: bool = False):
         self.seg = torch.empty(batch, side, side, dtype=torch.uint8).pin_memory()
         self.areas = torch.empty(batch, max_boxes, dtype=torch.int64).pin_memory()
         self.changed = torch.empty(batch, max_boxes, dtype=torch.int64).pin_memory() if changed else None
+        self.hbox = torch.empty(batch, max_boxes, 4, dtype=torch.int32).pin_memory() if boxes else None
+        self.rbox = torch.empty(batch, max_boxes, 4, 2, dtype=torch.float32).pin_memory() if boxes else None
+        self.record = torch.empty(batch, max_boxes, 8, dtype=torch.int64).pin_memory() if boxes else None
         self.done = torch.cuda.Event()
         self.masks: List[Optional[torch.Tensor]] = [None] * batch     # keep_masks: host copies of the full masks
         self.odd: dict = {}                                           # tiles that are not side x side: their class maps
@@ -395,7 +411,7 @@ class TilePipeline:
                  out_depth: int = 3, max_boxes: int = 512, device_inputs: bool = False, rle: bool = False,
                  rle_buffer_mb: int = 256, precision="auto", _multimask: bool = False, png_lut: Optional[np.ndarray] = None,
                  png_buffer_mb: Optional[int] = None, batch_decode: bool = False, min_region_area: int = 0,
-                 region_mode: str = "both"):
+                 region_mode: str = "both", mask_boxes: bool = False):
         """precision: the operand-split mode (engine option "split") THIS PIPELINE'S OWN CALLS run in.  The option is set around
         each of the pipeline's encode / decode calls and restored afterwards (``Engine.options``), so the mode never outlives
         them: a ``SamPredictor`` built on the same model keeps the engine's own default (round 3 changed the engine's option for
@@ -415,7 +431,10 @@ class TilePipeline:
         (region_mode "islands"), hole ("holes") or both ("both": holes first) of fewer than that many pixels
         (``Engine.clean_masks`` = segment_anything's ``remove_small_regions``): class map, areas, class statistics, RLE strings,
         device PNGs and kept masks all see the cleaned masks, and ``TileResult.changed`` counts the pixels changed per
-        instance.  0 (default) issues no call at all."""
+        instance.  0 (default) issues no call at all.
+        mask_boxes: derive, on the decode stream and from the masks that become the output (after the clean-up where that is
+        on), each mask's tight hbox, its minimum-area rotated box and the record behind it (``Engine.mask_boxes``):
+        ``TileResult.mask_hbox`` / ``mask_rbox`` / ``mask_record``.  False (default) launches and allocates nothing."""
         from .transforms import ResizeLongestSide
         from .engine import REGION_MODES
         if int(min_region_area) < 0:
@@ -482,13 +501,18 @@ class TilePipeline:
         self.area_dev = [torch.zeros(batch, max_boxes, dtype=torch.int64, device=dev) for _ in range(2)]
         if self.min_region_area:
             self.chg_dev = [torch.zeros(batch, max_boxes, dtype=torch.int64, device=dev) for _ in range(2)]
+        self.mask_boxes = bool(mask_boxes)
+        if self.mask_boxes:
+            self.hbox_dev = [torch.zeros(batch, max_boxes, 4, dtype=torch.int32, device=dev) for _ in range(2)]
+            self.rbox_dev = [torch.zeros(batch, max_boxes, 4, 2, dtype=torch.float32, device=dev) for _ in range(2)]
+            self.rec_dev = [torch.zeros(batch, max_boxes, 8, dtype=torch.int64, device=dev) for _ in range(2)]
         self.ev_h2d = [torch.cuda.Event() for _ in range(2)]
         self.ev_enc = [torch.cuda.Event() for _ in range(2)]
         self.ev_dec = [torch.cuda.Event() for _ in range(2)]
         self.ev_in_free = [torch.cuda.Event() for _ in range(2)]     # encoder has consumed input set b
         self.free_out: "queue.Queue[_OutBuf]" = queue.Queue()
         for _ in range(out_depth):
-            self.free_out.put(_OutBuf(batch, side, max_boxes, rle, self.png, self.min_region_area > 0))
+            self.free_out.put(_OutBuf(batch, side, max_boxes, rle, self.png, self.min_region_area > 0, self.mask_boxes))
 
     @staticmethod
     def _choose_split(sam, precision, multimask: bool) -> Optional[int]:
@@ -612,6 +636,8 @@ class TilePipeline:
             if self.min_region_area:                                              # before anything else reads the masks
                 eng.clean_masks(masks[:, 0], self.min_region_area, self.region_mode, areas_out=False,     # paint counts them
                                 changed_out=self.chg_dev[b][i, s:e])
+            if self.mask_boxes:
+                eng.mask_boxes(masks[:, 0], (0, 0), self.hbox_dev[b][i, s:e], self.rbox_dev[b][i, s:e], self.rec_dev[b][i, s:e])
             eng.paint(masks[:, 0], self.dev_lab[b][off + s:off + e], seg, self.class_pixels, self.class_instances,
                       areas_out=self.area_dev[b][i, s:e])
             if self.rle:                                                          # :201-202, on the device
@@ -652,6 +678,10 @@ class TilePipeline:
             out.areas.copy_(self.area_dev[b], non_blocking=True)
             if self.min_region_area:
                 out.changed.copy_(self.chg_dev[b], non_blocking=True)
+            if self.mask_boxes:
+                out.hbox.copy_(self.hbox_dev[b], non_blocking=True)
+                out.rbox.copy_(self.rbox_dev[b], non_blocking=True)
+                out.record.copy_(self.rec_dev[b], non_blocking=True)
             if self.rle:
                 out.rle_tab.copy_(self.rle_tab[b], non_blocking=True)
                 out.rle_cur.copy_(self.rle_cur[b], non_blocking=True)
@@ -741,6 +771,9 @@ class TilePipeline:
                 r.png_table, r.png_data = ptab[i], pdat
             if self.min_region_area:
                 r.changed = out.changed[i, :nb].numpy().copy()
+            if self.mask_boxes:
+                r.mask_hbox, r.mask_rbox = out.hbox[i, :nb].numpy().copy(), out.rbox[i, :nb].numpy().copy()
+                r.mask_record = out.record[i, :nb].numpy().copy()
             self._extra_result(r, i, off, nb, out, extra)
             res.append(r)
         out.odd = {}
@@ -855,6 +888,8 @@ class InstancePipeline(TilePipeline):
                 self.gt_rle_dev = [torch.empty_like(t) for t in self.rle_dev]
                 self.gt_rle_cur = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(2)]
                 self.gt_rle_tab = [torch.zeros(B * M, 3, dtype=torch.int64, device=dev) for _ in range(2)]
+                if self.mask_boxes:
+                    self.gt_hbox_dev = [torch.zeros(B, M, 4, dtype=torch.int32, device=dev) for _ in range(2)]
             for _ in range(self.free_out.qsize()):
                 o = self.free_out.get()
                 o.inter = torch.empty(B, M, dtype=torch.int64).pin_memory()
@@ -863,6 +898,8 @@ class InstancePipeline(TilePipeline):
                     o.gt_rle_tab = torch.zeros(B * M, 3, dtype=torch.int64).pin_memory()
                     o.gt_rle_cur = torch.zeros(1, dtype=torch.int64).pin_memory()
                     o.gt_rle_bytes = torch.empty(1 << 20, dtype=torch.uint8).pin_memory()
+                    if self.mask_boxes:
+                        o.gt_hbox = torch.empty(B, M, 4, dtype=torch.int32).pin_memory()
                 self.free_out.put(o)
 
     def _stage(self, b: int, items: List[WorkItem]):
@@ -947,6 +984,8 @@ class InstancePipeline(TilePipeline):
             if self.min_region_area:                      # the area table then holds the cleaned areas (select_best's are stale)
                 eng.clean_masks(mk, self.min_region_area, self.region_mode, areas_out=self.area_dev[b][i, s:e],
                                 changed_out=self.chg_dev[b][i, s:e])
+            if self.mask_boxes:                           # of the kept mask, as it goes out
+                eng.mask_boxes(mk, (0, 0), self.hbox_dev[b][i, s:e], self.rbox_dev[b][i, s:e], self.rec_dev[b][i, s:e])
             if self.rle:
                 eng.rle_encode(mk, self.rle_dev[b], self.rle_cur[b], self.rle_tab[b][off + s:off + e])
             if self.gt:                                   # main_sam_rhbox_mask_instance.py:204-238, on the device
@@ -955,6 +994,8 @@ class InstancePipeline(TilePipeline):
                              self.gta_dev[b][i, s:e], gm)
                 if self.rle:                              # instance_to_json.py:44-45
                     eng.rle_encode(gm, self.gt_rle_dev[b], self.gt_rle_cur[b], self.gt_rle_tab[b][off + s:off + e])
+                    if self.mask_boxes:                   # the ground-truth masks are on the device here: their hbox too
+                        eng.mask_boxes(gm, (0, 0), self.gt_hbox_dev[b][i, s:e], False, False)
             kept.append(mk)
         self.last_masks = kept[-1].view(torch.bool) if kept else None
         out.masks[i] = torch.cat(kept).cpu() if (self.keep_masks and kept) else None
@@ -968,6 +1009,8 @@ class InstancePipeline(TilePipeline):
             if self.rle:
                 out.gt_rle_tab.copy_(self.gt_rle_tab[b], non_blocking=True)
                 out.gt_rle_cur.copy_(self.gt_rle_cur[b], non_blocking=True)
+                if self.mask_boxes:
+                    out.gt_hbox.copy_(self.gt_hbox_dev[b], non_blocking=True)
 
     def _fetch_extra(self, b: int, out: _OutBuf, n_boxes: int):
         if not (self.gt and self.rle):
@@ -981,3 +1024,5 @@ class InstancePipeline(TilePipeline):
         r.inter, r.gt_area = out.inter[i, :nb].numpy().copy(), out.gt_area[i, :nb].numpy().copy()
         if extra is not None:
             r.gt_rle_table, r.gt_rle_data = extra[0][off:off + nb], extra[1]
+            if self.mask_boxes:
+                r.gt_hbox = out.gt_hbox[i, :nb].numpy().copy()

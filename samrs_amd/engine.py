@@ -114,6 +114,11 @@ def load_library() -> C.CDLL:
     lib.samrs_clean_masks.restype = ip
     lib.samrs_k_region_labels.argtypes = [vp, ip, ip, ip, ip, vp, vp]
     lib.samrs_k_region_labels.restype = ip
+    lib.samrs_mask_boxes.argtypes = [vp, vp, ip, ip, ip, ip, ip, vp, vp, vp, vp]
+    lib.samrs_k_mask_row_extents.argtypes = [vp, ip, ip, ip, vp, vp]
+    lib.samrs_k_mask_hull.argtypes = [vp, ip, ip, ip, ip, ip, vp, vp, ip, vp, vp]
+    for name in ("samrs_mask_boxes", "samrs_k_mask_row_extents", "samrs_k_mask_hull"):
+        getattr(lib, name).restype = ip
     lib.samrs_png_encode_labels.argtypes = [vp, vp, ip, ip, ip, vp, vp, C.c_int64, vp, vp, vp]
     lib.samrs_k_upscaler_fused.argtypes = [ip, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, vp]
     lib.samrs_k_convert.argtypes = [ip, vp, vp, C.c_int64, vp]
@@ -655,6 +660,63 @@ class Engine:
         with torch.cuda.device(self.device):
             self._check(self.lib.samrs_k_region_labels(m.data_ptr(), n, h, w, int(bool(complement)), out.data_ptr(), _stream()))
         return out
+
+    def _masks_u8(self, masks: torch.Tensor) -> torch.Tensor:
+        m = masks.view(torch.uint8) if masks.dtype == torch.bool else masks
+        if m.dim() != 3 or m.dtype != torch.uint8:
+            raise ValueError(f"masks must be bool / uint8 [n, H, W], got {masks.dtype} {tuple(masks.shape)}")
+        if not (m.is_cuda and m.is_contiguous()):
+            raise ValueError("masks must be a contiguous tensor on the engine's device")
+        return m
+
+    def mask_boxes(self, masks: torch.Tensor, offset: Sequence[int] = (0, 0), hbox_out=None, rbox_out=None, record_out=None):
+        """Where each mask actually is, derived on the device (samrs_mask_boxes): masks [n, H, W] bool / uint8, contiguous, decoded
+        in a window whose origin is `offset` = (x0, y0) -> (hbox int32 [n, 4] = xmin, ymin, xmax, ymax inclusive; rbox fp32
+        [n, 4, 2] = the corners of the minimum-area rotated rectangle of the set pixels' centres; record int64 [n, 8] = dx, dy, pmin,
+        pmax, qmin, qmax, hull vertex count m, twice the hull's area).  The rectangle lies along a hull edge; of several
+        equal-area ones the edge that comes first from the top-left set pixel, down the left side, wins.  An empty mask has m = 0
+        and all outputs zero.  Each output: None = a new tensor, a caller-owned contiguous slice of that shape and type, or False =
+        not wanted (the library gets NULL and the tuple holds None there).  Asynchronous on the current stream."""
+        m = self._masks_u8(masks)
+        n, h, w = m.shape
+        outs = []
+        for name, t, shape, dt in (("hbox_out", hbox_out, (n, 4), torch.int32), ("rbox_out", rbox_out, (n, 4, 2), torch.float32),
+                                   ("record_out", record_out, (n, 8), torch.int64)):
+            if t is False:
+                t = None
+            elif t is None:
+                t = torch.empty(shape, dtype=dt, device=self.device)
+            elif not (isinstance(t, torch.Tensor) and t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shape):
+                raise ValueError(f"{name} must be a contiguous {dt} {list(shape)} tensor on the engine's device, None or False")
+            outs.append(t)
+        if n:
+            with torch.cuda.device(self.device):
+                self._check(self.lib.samrs_mask_boxes(self.handle, m.data_ptr(), n, h, w, int(offset[0]), int(offset[1]), _ptr(outs[0]),
+                                                      _ptr(outs[1]), _ptr(outs[2]), _stream()))
+        return outs[0], outs[1], outs[2]
+
+    def mask_row_extents(self, masks: torch.Tensor) -> torch.Tensor:
+        """Test hook (samrs_k_mask_row_extents): int32 [n, H, 3] = first set column, last set column and pixel count of every row,
+        (-1, -1, 0) for an empty row."""
+        m = self._masks_u8(masks)
+        n, h, w = m.shape
+        out = torch.empty(n, h, 3, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.samrs_k_mask_row_extents(m.data_ptr(), n, h, w, out.data_ptr(), _stream()))
+        return out
+
+    def mask_hull(self, masks: torch.Tensor, offset: Sequence[int] = (0, 0), cap: int = 2048):
+        """Test hook (samrs_k_mask_hull): (vertices int32 [n, cap, 2], counts int32 [n]): the ordered strict hull vertices (x, y) of
+        every mask in the frame of `offset`; rows past a mask's count are not written."""
+        m = self._masks_u8(masks)
+        n, h, w = m.shape
+        ext = torch.empty(n, h, 3, dtype=torch.int32, device=self.device)
+        verts = torch.zeros(n, cap, 2, dtype=torch.int32, device=self.device)
+        counts = torch.zeros(n, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.samrs_k_mask_hull(m.data_ptr(), n, h, w, int(offset[0]), int(offset[1]), ext.data_ptr(),
+                                                   verts.data_ptr(), int(cap), counts.data_ptr(), _stream()))
+        return verts, counts
 
     def gt_match(self, masks: torch.Tensor, label_rgb: torch.Tensor, colors: torch.Tensor, inter_out: Optional[torch.Tensor] = None,
                  gt_area_out: Optional[torch.Tensor] = None, gt_masks_out: Optional[torch.Tensor] = None):

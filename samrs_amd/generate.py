@@ -59,11 +59,15 @@ class StageClock:
 def write_outputs(out_dir: str, stem: str, seg: np.ndarray, masks: Optional[np.ndarray], boxes: np.ndarray,
                   labels: np.ndarray, areas: np.ndarray, palette: np.ndarray, class_names: Sequence[str],
                   rles: Optional[Sequence[dict]] = None, clock: Optional[StageClock] = None, png_level: int = tile_io.LEVEL_LABELS,
-                  png_files: Optional[Tuple[bytes, bytes]] = None) -> None:
+                  png_files: Optional[Tuple[bytes, bytes]] = None, mask_bboxes: Optional[Sequence] = None,
+                  mask_rboxes: Optional[Sequence] = None, dota_txt: bool = False) -> None:
     """`rles`: the per-instance COCO RLE dicts when they were encoded on the device (driver.TileResult.rle); otherwise they are
     encoded here from `masks` (host restatement), or left out when both are None (--no-rle).  `png_files`: the complete
     (gray, color) PNG files when they were encoded on the device (--png-device: driver.TileResult.png, byte-identical with the
-    LEVEL_LABELS encoder); they are written as they are and `seg` / `png_level` are not used for them."""
+    LEVEL_LABELS encoder); they are written as they are and `seg` / `png_level` are not used for them.  `mask_bboxes` /
+    `mask_rboxes` (--mask-boxes): per instance the COCO ``[x, y, w, h]`` and the fp32 [4, 2] minimum-area rotated box derived from
+    the mask on the device (driver.TileResult.mask_bbox / mask_rbox), None for an empty mask; they become the pickle entries'
+    ``"mask_bbox"`` / ``"mask_rbox"``.  `dota_txt` (--dota-txt): also ``rbox/<stem>.txt``, one DOTA line per non-empty instance."""
     import time
     t0 = time.perf_counter()
     for sub in ("gray", "color", "ins"):
@@ -95,13 +99,31 @@ def write_outputs(out_dir: str, stem: str, seg: np.ndarray, masks: Optional[np.n
             entry["mask"] = rles[j]
         elif masks is not None:
             entry["mask"] = rle.encode(masks[j])
+        if mask_bboxes is not None:
+            entry["mask_bbox"], entry["mask_rbox"] = mask_bboxes[j], mask_rboxes[j]
         info.append(entry)
+    if dota_txt:
+        # before the pickle, whose presence says "this image is complete" (--resume)
+        os.makedirs(os.path.join(out_dir, "rbox"), exist_ok=True)
+        _write_atomic(os.path.join(out_dir, "rbox", stem + ".txt"), "".join(dota_lines(mask_rboxes, labels, class_names)).encode())
     # the pickle goes last and through a rename: --resume takes its presence as "this image is complete"
     tmp = os.path.join(out_dir, "ins", f"{stem}.pkl.tmp.{os.getpid()}")     # per process: two ranks can never share a tmp file
     with open(tmp, "wb") as f:
         pickle.dump(info, f)                                                                # :216
     os.replace(tmp, os.path.join(out_dir, "ins", stem + ".pkl"))
     if clock: clock.add("write.pickle", t0)
+
+
+def dota_lines(mask_rboxes: Sequence, labels: Sequence[int], class_names: Sequence[str]) -> List[str]:
+    """One line per non-empty instance in the reference's oriented-box text form, ``x1 y1 x2 y2 x3 y3 x4 y4 category label``
+    (Generate Dataset/ann_transform.py:46), the coordinates printed as %.1f."""
+    lines = []
+    for j, rb in enumerate(mask_rboxes):
+        if rb is None:
+            continue
+        xy = " ".join("%.1f" % float(v) for v in np.asarray(rb, dtype=np.float32).reshape(8))
+        lines.append(f"{xy} {class_names[int(labels[j])]} {int(labels[j])}\n")
+    return lines
 
 
 def _write_atomic(path: str, data) -> None:
@@ -286,20 +308,25 @@ def run(args) -> Dict[str, List[int]]:
     # --scene-window: images larger than the window are decoded window by window and composited in their own frame on the device
     # (scene.ScenePipeline); the files written per image stem are the same, at the scene's size
     scene_window = int(getattr(args, "scene_window", 0) or 0)
+    # --mask-boxes / --dota-txt: each mask's tight hbox and minimum-area rotated box, derived on the device (samrs_mask_boxes)
+    dota_txt = bool(getattr(args, "dota_txt", False))
+    mask_boxes = bool(getattr(args, "mask_boxes", False)) or dota_txt
     if scene_window > 0:
         from . import scene
         pipe = scene.ScenePipeline(sam, n_classes, window=scene_window, overlap=getattr(args, "scene_overlap", 256),
                                    context=getattr(args, "scene_context", 2.0), batch=batch, box_batch=args.box_batch,
                                    rle=not args.no_rle, rle_buffer_mb=getattr(args, "rle_buffer_mb", 256),
                                    png_lut=tile_io.class_lut(palette) if png_device else None,
-                                   min_region_area=min_region_area, region_mode=getattr(args, "region_mode", "both"))
+                                   min_region_area=min_region_area, region_mode=getattr(args, "region_mode", "both"),
+                                   mask_boxes=mask_boxes)
     else:
         pipe = driver.TilePipeline(sam, n_classes, batch=batch, box_batch=args.box_batch, rle=not args.no_rle,
                                    rle_buffer_mb=getattr(args, "rle_buffer_mb", 256), max_boxes=max_boxes,
                                    out_depth=getattr(args, "out_depth", 4), png_lut=tile_io.class_lut(palette) if png_device else None,
                                    png_buffer_mb=getattr(args, "png_buffer_mb", None),
                                    batch_decode=bool(getattr(args, "batch_decode", False)),
-                                   min_region_area=min_region_area, region_mode=getattr(args, "region_mode", "both"))
+                                   min_region_area=min_region_area, region_mode=getattr(args, "region_mode", "both"),
+                                   mask_boxes=mask_boxes)
     # rank r takes chunks of `batch` consecutive stems: statically (r, r + world, ...) or from the shared counter (whose
     # store key must be unique per work list: a second run() in the same process group must not find a spent counter)
     import zlib
@@ -392,7 +419,12 @@ def run(args) -> Dict[str, List[int]]:
                 rles = [r.rle(j) for j in range(len(r.labels))] if r.rle_table is not None else None
                 if clock: clock.add("write.rle_dicts", t0)
                 files = (r.png("gray"), r.png("color")) if r.png_table is not None else None
-                write_outputs(args.out, r.key, r.seg_mask, None, r.boxes, r.labels, r.areas, palette, names, rles, clock, png_level, files)
+                bbs = rbs = None
+                if r.mask_record is not None:
+                    bbs = [r.mask_bbox(j) for j in range(len(r.labels))]
+                    rbs = [None if bb is None else r.mask_rbox[j].copy() for j, bb in enumerate(bbs)]
+                write_outputs(args.out, r.key, r.seg_mask, None, r.boxes, r.labels, r.areas, palette, names, rles, clock, png_level, files,
+                              bbs, rbs, dota_txt)
             finally:
                 with lock:
                     left[0] -= 1
@@ -484,6 +516,8 @@ class _Parser(argparse.ArgumentParser):
             self.error("--batch-decode does not apply with --scene-window: scene mode decodes each window's boxes on their own")
         if ns.scene_window > 0 and not 0 <= ns.scene_overlap < ns.scene_window:
             self.error("--scene-overlap must satisfy 0 <= overlap < --scene-window")
+        if ns.dota_txt:
+            ns.mask_boxes = True
         return ns
 
 
@@ -540,6 +574,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--scene-context", type=float, default=2.0,
                     help="with --scene-window: a box no grid window holds gets a window of its own, this many times its longer side")
     add_region_arguments(ap, " Under --resume the totals cover the images processed in this run only.")
+    add_mask_box_arguments(ap, "every ins/<stem>.pkl entry gains \"mask_bbox\" (COCO [x, y, w, h]) and \"mask_rbox\" (float32 [4, 2]), "
+                               "None for an empty mask")
+    ap.add_argument("--dota-txt", action="store_true",
+                    help="also write rbox/<stem>.txt, one line per non-empty instance in DOTA's oriented-box form "
+                         "'x1 y1 x2 y2 x3 y3 x4 y4 category label' (coordinates %%.1f); implies --mask-boxes")
     return ap
 
 
@@ -551,6 +590,12 @@ def add_region_arguments(ap: argparse.ArgumentParser, resume_note: str = "") -> 
                          "total changed pixels and changed instances go into the statistics output." + resume_note)
     ap.add_argument("--region-mode", default="both", choices=["holes", "islands", "both"],
                     help="with --min-region-area: fill small holes, remove small islands, or both (holes first)")
+
+
+def add_mask_box_arguments(ap: argparse.ArgumentParser, what: str) -> None:
+    """--mask-boxes, shared by this CLI and samrs_amd.instances."""
+    ap.add_argument("--mask-boxes", action="store_true",
+                    help="derive each mask's tight box (and minimum-area rotated box) from the mask itself on the GPU: " + what)
 
 
 def main(argv=None):

@@ -139,13 +139,24 @@ def write_fragment(out_dir: str, stem: str, frag: dict) -> None:
 
 
 def make_fragment(height: int, width: int, scores, rles: Sequence[str], pred_area=None, inter=None, gt_area=None,
-                  gt_rles: Optional[Sequence[str]] = None) -> dict:
-    """scores: fp32 qualities (stored as float(fp32), instance_to_json.py:103); rles / gt_rles: the COCO counts strings."""
+                  gt_rles: Optional[Sequence[str]] = None, bboxes=None, gt_bboxes=None) -> dict:
+    """scores: fp32 qualities (stored as float(fp32), instance_to_json.py:103); rles / gt_rles: the COCO counts strings; bboxes /
+    gt_bboxes (--mask-boxes): COCO [x, y, w, h] per prediction / ground-truth mask."""
     frag = {"height": int(height), "width": int(width), "scores": [float(np.float32(s)) for s in scores], "rles": list(rles)}
     if gt_rles is not None:
         frag.update(pred_area=[int(v) for v in pred_area], inter=[int(v) for v in inter], gt_area=[int(v) for v in gt_area],
                     gt_rles=list(gt_rles))
+    if bboxes is not None:
+        frag["bboxes"] = [[int(v) for v in b] for b in bboxes]
+    if gt_bboxes is not None:
+        frag["gt_bboxes"] = [[int(v) for v in b] for b in gt_bboxes]
     return frag
+
+
+def coco_bboxes(hbox: np.ndarray, areas) -> List[List[int]]:
+    """int32 [n, 4] inclusive xmin, ymin, xmax, ymax -> COCO [x, y, w, h] in whole pixels; [0, 0, 0, 0] for an empty mask."""
+    return [[int(b[0]), int(b[1]), int(b[2] - b[0] + 1), int(b[3] - b[1] + 1)] if int(a) > 0 else [0, 0, 0, 0]
+            for b, a in zip(hbox, areas)]
 
 
 def pending_stems(out_dir: str, stems: Sequence[str]) -> List[str]:
@@ -184,6 +195,8 @@ def merge_fragments(out_dir: str, stems: Sequence[str], tag: str, with_gt: bool)
         size = [fr["height"], fr["width"]]
         for c, (counts, score) in enumerate(zip(fr["rles"], fr["scores"])):
             pred.append({"image_id": int(n), "category_id": 0, "segmentation": {"size": size, "counts": counts}, "score": float(score)})
+            if "bboxes" in fr:                                     # --mask-boxes (the reference left it out: instance_to_json.py:63)
+                pred[-1]["bbox"] = fr["bboxes"][c]
     with open(os.path.join(out_dir, f"sam_ins_{tag}.json"), "w") as f:
         json.dump(pred, f)
     if not with_gt:
@@ -197,6 +210,8 @@ def merge_fragments(out_dir: str, stems: Sequence[str], tag: str, with_gt: bool)
         for c, counts in enumerate(fr["gt_rles"]):
             gt["annotations"].append({"id": c, "image_id": n, "category_id": 0, "area": int(fr["gt_area"][c]), "iscrowd": 0,
                                       "segmentation": {"size": size, "counts": counts}, "attributes": {}})
+            if "gt_bboxes" in fr:
+                gt["annotations"][-1]["bbox"] = fr["gt_bboxes"][c]
         inter += fr["inter"]
         parea += fr["pred_area"]
         garea += fr["gt_area"]
@@ -258,7 +273,8 @@ def run(args) -> Optional[dict]:
                                    rle_buffer_mb=getattr(args, "rle_buffer_mb", 256), keep_masks=False,
                                    batch_decode=bool(getattr(args, "batch_decode", False)),
                                    min_region_area=int(getattr(args, "min_region_area", 0) or 0),
-                                   region_mode=getattr(args, "region_mode", "both"))
+                                   region_mode=getattr(args, "region_mode", "both"),
+                                   mask_boxes=bool(getattr(args, "mask_boxes", False)))
     os.makedirs(os.path.join(args.out, "parts"), exist_ok=True)
     import zlib
     wq_name = "samrs_ins/%08x" % zlib.crc32(("\n".join(todo) + "|" + args.out).encode())
@@ -290,11 +306,13 @@ def run(args) -> Optional[dict]:
             for r in results:
                 n = len(r.labels)
                 rles = [r.rle(j)["counts"] for j in range(n)]
+                bbs = coco_bboxes(r.mask_hbox, r.areas) if r.mask_hbox is not None else None
                 if with_gt:
+                    gbs = coco_bboxes(r.gt_hbox, r.gt_area) if r.gt_hbox is not None else None
                     frag = make_fragment(r.size[0], r.size[1], r.quality, rles, r.areas, r.inter, r.gt_area,
-                                         [r.gt_rle(j)["counts"] for j in range(n)])
+                                         [r.gt_rle(j)["counts"] for j in range(n)], bbs, gbs)
                 else:
-                    frag = make_fragment(r.size[0], r.size[1], r.quality, rles)
+                    frag = make_fragment(r.size[0], r.size[1], r.quality, rles, bboxes=bbs)
                 write_fragment(args.out, r.key, frag)
         finally:
             release()
@@ -345,6 +363,8 @@ def build_parser() -> argparse.ArgumentParser:
                     help="decode the prompts of all images of a batch in one decoder chain (Engine.predict_multi); same outputs")
     from . import generate
     generate.add_region_arguments(ap)
+    generate.add_mask_box_arguments(ap, "every prediction of sam_ins_<tag>.json gains \"bbox\" (COCO [x, y, w, h]), and so does every "
+                                        "ground-truth annotation with --gt-labels")
     return ap
 
 

@@ -107,11 +107,13 @@ class ScenePipeline:
     on a stream of its own beside the decoding and compositing of the current ones when the engine has two sets of embedding slots
     (``max_images >= 2 * batch``).  The results do not depend on `batch` (windows per encoder pass) or `box_batch` (prompts per
     decoder call).  A scene no larger than `window` is one window, and every
-    output equals ``TilePipeline``'s for the same item byte for byte."""
+    output equals ``TilePipeline``'s for the same item byte for byte.  `mask_boxes`: each mask's tight hbox, minimum-area rotated
+    box and record (``Engine.mask_boxes``) with its window's origin as the offset, so they are in the scene's frame, exactly:
+    ``TileResult.mask_hbox`` / ``mask_rbox`` / ``mask_record``; off (default) launches and allocates nothing."""
 
     def __init__(self, sam, n_classes: int, window: int = 1024, overlap: int = 256, context: float = 2.0, batch: int = 8,
                  box_batch: int = 64, rle: bool = False, png_lut: Optional[np.ndarray] = None, min_region_area: int = 0,
-                 region_mode: str = "both", precision="auto", rle_buffer_mb: int = 256):
+                 region_mode: str = "both", precision="auto", rle_buffer_mb: int = 256, mask_boxes: bool = False):
         import torch
         from .driver import TilePipeline
         from .engine import REGION_MODES
@@ -133,6 +135,7 @@ class ScenePipeline:
         self.window, self.overlap, self.context = int(window), int(overlap), float(context)
         self.batch, self.box_batch, self.rle = int(batch), int(box_batch), bool(rle)
         self.min_region_area, self.region_mode = int(min_region_area), region_mode
+        self.mask_boxes = bool(mask_boxes)
         # the operand-split mode of this pipeline's own calls: TilePipeline's rule and TilePipeline's scoping
         self.split_mode = TilePipeline._choose_split(sam, precision, multimask=False)
         self.allow_reduced = False
@@ -222,6 +225,10 @@ class ScenePipeline:
         order = torch.full((H, W), -1, dtype=torch.int32, device=dev)
         w_areas = torch.zeros(n, dtype=torch.int64, device=dev)
         w_changed = torch.zeros(n, dtype=torch.int64, device=dev) if self.min_region_area else None
+        if self.mask_boxes:
+            w_hbox = torch.zeros(n, 4, dtype=torch.int32, device=dev)
+            w_rbox = torch.zeros(n, 4, 2, dtype=torch.float32, device=dev)
+            w_rec = torch.zeros(n, 8, dtype=torch.int64, device=dev)
         if self.rle:
             w_tab = torch.zeros(n, 3, dtype=torch.int64, device=dev)
             rle_cur = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -261,6 +268,8 @@ class ScenePipeline:
                     m = masks[:, 0]
                     if self.min_region_area:                                      # before anything else reads the masks
                         eng.clean_masks(m, self.min_region_area, self.region_mode, areas_out=False, changed_out=w_changed[s:e])
+                    if self.mask_boxes:                                           # in the scene's frame: the window's origin
+                        eng.mask_boxes(m, (x0, y0), w_hbox[s:e], w_rbox[s:e], w_rec[s:e])
                     eng.scene_claim(m, w_rank[s:e], win, order, w_lab[s:e], self.class_pixels, self.class_instances,
                                     areas_out=w_areas[s:e])
                     if self.rle:
@@ -294,6 +303,9 @@ class ScenePipeline:
         r.windows, r.window_of = windows, window_of
         if w_changed is not None:
             r.changed = unpermute(w_changed.cpu().numpy())
+        if self.mask_boxes:
+            r.mask_hbox, r.mask_rbox = unpermute(w_hbox.cpu().numpy()), unpermute(w_rbox.cpu().numpy())
+            r.mask_record = unpermute(w_rec.cpu().numpy())
         if self.rle:
             tab = unpermute(w_tab.cpu().numpy())
             total = int(rle_cur.item())
