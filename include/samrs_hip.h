@@ -276,6 +276,35 @@ int samrs_clean_masks(samrs_engine_t* e, uint8_t* masks, int n, int h, int w, in
 int samrs_mask_boxes(samrs_engine_t* e, const uint8_t* masks, int n, int h, int w, int x0, int y0,
                      int32_t* hbox_out /*[n][4]*/, float* rbox_out /*[n][4][2]*/, int64_t* record_out /*[n][8]*/, void* stream);
 
+/* -- mask quality before the masks become labels: the three signals a box-prompted mask carries, counted on the device straight
+ * from the 256^2 logits (`calculate_stability_score`, utils/amg.py:156-176, and the `pred_iou_thresh` / `stability_score_thresh`
+ * gate of automatic_mask_generator.py:295-304; the box fit is this library's own).  lowres fp32 [n][256][256]: the lowres_out of
+ * samrs_predict with C flattened into n (for C = 3 the caller repeats the boxes).  v(p) = the value samrs_predict's postprocess
+ * computes at output pixel p for (in_h, in_w, orig_h, orig_w) -- the very same arithmetic, so the second count equals the number of
+ * set bytes of the uint8 mask samrs_predict writes for the same logits, exactly.  counts_out int64 [n][4], overwritten:
+ *   n_hi  = #{v > +offset}      n_mid = #{v > 0} (SAM's mask_threshold)      n_lo = #{v > -offset}
+ *   n_in  = #{v > 0 and bx0 <= (float)x <= bx1 and by0 <= (float)y <= by1}: boxes fp32 [n][4] xyxy in the ORIGINAL frame, or
+ *           NULL (n_in = 0).
+ * stability = n_hi / n_lo, share inside the box = n_in / n_mid.  The full-resolution logits are never materialised: 256 KiB read
+ * and 32 bytes written per mask.  offset >= 0 and finite (0: three equal counts); orig_h * orig_w < 2^31; in_h, in_w <= img_size
+ * with max(in_h, in_w) == img_size.  n < 0, a null lowres / counts_out, a bad offset or size: SAMRS_ERR_BAD_ARG and nothing is
+ * written.  n == 0 is a no-op.  Integer atomics only: bitwise reproducible; no host synchronisation, no scratch on the handle. */
+int samrs_score_masks(samrs_engine_t* e, const float* lowres, int n, int in_h, int in_w, int orig_h, int orig_w,
+                      float offset, const float* boxes /* [n][4] or NULL */, int64_t* counts_out /* [n][4] */, void* stream);
+/* The gate itself: keep_out[j] = 1 iff every enabled criterion holds, else 0 and mask j (uint8 [n][h][w], in / out) is zeroed in
+ * place; a kept mask is not touched.  A threshold <= 0 disables its criterion (amg.py:295,303).  Compared in fp64 from the fp32
+ * arguments and the integer counts of samrs_score_masks (counts int64 [n][4]):
+ *   stability      n_lo > 0 && (double)n_hi >= (double)min_stability * (double)n_lo   (>=, as the reference; an empty low-threshold
+ *                  mask fails -- the reference's 0 / 0 is NaN, which fails too; that reading is this library's rule);
+ *   predicted IoU  iou[j] > min_pred_iou   (strict, as the reference; iou fp32 [n], NULL with the criterion on: SAMRS_ERR_BAD_ARG);
+ *   box fit        n_mid == 0 || (double)n_in >= (double)min_inside * (double)n_mid   (an empty mask passes: this library's rule).
+ * A dropped mask is an empty mask to everything downstream: samrs_paint paints nothing and counts area 0 (no class statistics),
+ * samrs_mask_boxes reports m = 0.  16-byte stores when masks is 16-byte aligned and h * w % 16 == 0, byte stores otherwise.
+ * n < 0, h or w < 1, a null masks / counts / keep_out: SAMRS_ERR_BAD_ARG and nothing is written.  n == 0 is a no-op. */
+int samrs_filter_masks(samrs_engine_t* e, uint8_t* masks, int n, int h, int w, const int64_t* counts /* [n][4] */,
+                       const float* iou /* [n] or NULL */, float min_stability, float min_pred_iou, float min_inside,
+                       uint8_t* keep_out /* [n] */, void* stream);
+
 /* -- the generation CLI's class-map files (main_sam_hbox_semantic.py:212-215: gray/<stem>.png and color/<stem>.png), encoded on
  * the device.  maps: uint8 [n][h][w] (255 = unlabeled), lut: uint8 [256][3] (class id -> RGB), both on the device.  The two PNG
  * files of each map are byte-identical with what the host's samrs_io_png_write_label_pair (include/samrs_io.h) writes for

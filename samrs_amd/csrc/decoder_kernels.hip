@@ -11,6 +11,7 @@
 //   painting / stats   : Generate Dataset/main_sam_hbox_semantic.py:195-206, statistic.py:15-21
 #include "common.h"
 #include "kernels.h"
+#include "postprocess_value.h"
 
 namespace {
 
@@ -834,31 +835,7 @@ __global__ __launch_bounds__(256) void upscale2_mask_kernel(const void* __restri
 }
 
 // ---- postprocess ------------------------------------------------------------------------
-// PyTorch upsample_bilinear2d, align_corners=False: src = scale*(dst+0.5)-0.5 clamped at 0,
-// scale = in/out; out = wy0*(wx0*v00 + wx1*v01) + wy1*(wx0*v10 + wx1*v11).
-struct Lin {
-    int i0, i1;
-    float w0, w1;
-};
-__device__ __forceinline__ Lin lin_coord(int dst, float scale, int in_size) {
-    float src = scale * ((float)dst + 0.5f) - 0.5f;
-    src = src < 0.f ? 0.f : src;
-    Lin r;
-    r.i0 = (int)src;
-    r.i0 = r.i0 < in_size - 1 ? r.i0 : in_size - 1;
-    r.i1 = r.i0 + (r.i0 < in_size - 1 ? 1 : 0);
-    r.w1 = src - (float)r.i0;
-    r.w0 = 1.0f - r.w1;
-    return r;
-}
-// stage 1: value of the img_size^2 upsampled map at integer (Y1, X1), from the 256^2 logits
-__device__ __forceinline__ float stage1(const float* __restrict__ low, int LS, float s1, int Y1, int X1) {
-    const Lin ly = lin_coord(Y1, s1, LS), lx = lin_coord(X1, s1, LS);
-    const float* r0 = low + (size_t)ly.i0 * LS;
-    const float* r1 = low + (size_t)ly.i1 * LS;
-    return ly.w0 * (lx.w0 * r0[lx.i0] + lx.w1 * r0[lx.i1]) + ly.w1 * (lx.w0 * r1[lx.i0] + lx.w1 * r1[lx.i1]);
-}
-
+// Lin / lin_coord / stage1 / SAMRS_POSTPROCESS_VALUES: postprocess_value.h (shared with score_masks_kernel, quality_kernels.hip)
 // One thread = 4 horizontally adjacent output pixels.  grid (ceil(W/4 * H / 256), n_masks).
 __global__ __launch_bounds__(256) void postprocess_kernel(const float* __restrict__ low_all, int LS, int in_h, int in_w,
                                                           int H, int W, int img_size, int return_logits,
@@ -869,41 +846,7 @@ __global__ __launch_bounds__(256) void postprocess_kernel(const float* __restric
     const int Y = (int)(t / W4), X0 = (int)(t % W4) * 4;
     const int mi = blockIdx.y;
     const float* low = low_all + (size_t)mi * LS * LS;
-    const float s1 = (float)LS / (float)img_size;
-    const bool identity = (H == in_h) && (W == in_w);
-    float v[4];
-    if (identity && 4 * LS == img_size && X0 + 3 < W) {
-        // the case of every 1024^2 tile: scale exactly 1/4, so output columns 4k, 4k+1 interpolate between the same two
-        // logits columns, and 4k+2, 4k+3 between the next pair; one row pair serves all four.  Same expression per
-        // pixel as stage1 (bit-identical), 8 loads and 5 coordinate computations instead of 16 and 8.
-        const Lin ly = lin_coord(Y, s1, LS);
-        const float* r0 = low + (size_t)ly.i0 * LS;
-        const float* r1 = low + (size_t)ly.i1 * LS;
-        const Lin la = lin_coord(X0, s1, LS), lb = lin_coord(X0 + 1, s1, LS), lc = lin_coord(X0 + 2, s1, LS), ld = lin_coord(X0 + 3, s1, LS);
-        const float a00 = r0[la.i0], a01 = r0[la.i1], a10 = r1[la.i0], a11 = r1[la.i1];
-        const float c00 = r0[lc.i0], c01 = r0[lc.i1], c10 = r1[lc.i0], c11 = r1[lc.i1];
-        v[0] = ly.w0 * (la.w0 * a00 + la.w1 * a01) + ly.w1 * (la.w0 * a10 + la.w1 * a11);
-        v[1] = ly.w0 * (lb.w0 * a00 + lb.w1 * a01) + ly.w1 * (lb.w0 * a10 + lb.w1 * a11);
-        v[2] = ly.w0 * (lc.w0 * c00 + lc.w1 * c01) + ly.w1 * (lc.w0 * c10 + lc.w1 * c11);
-        v[3] = ly.w0 * (ld.w0 * c00 + ld.w1 * c01) + ly.w1 * (ld.w0 * c10 + ld.w1 * c11);
-    } else if (identity) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = (X0 + e < W) ? stage1(low, LS, s1, Y, X0 + e) : 0.f;
-    } else {
-        const float sy = (float)in_h / (float)H, sx = (float)in_w / (float)W;
-        const Lin ly = lin_coord(Y, sy, in_h);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if (X0 + e < W) {
-                const Lin lx = lin_coord(X0 + e, sx, in_w);
-                const float a = lx.w0 * stage1(low, LS, s1, ly.i0, lx.i0) + lx.w1 * stage1(low, LS, s1, ly.i0, lx.i1);
-                const float b = lx.w0 * stage1(low, LS, s1, ly.i1, lx.i0) + lx.w1 * stage1(low, LS, s1, ly.i1, lx.i1);
-                v[e] = ly.w0 * a + ly.w1 * b;
-            } else {
-                v[e] = 0.f;
-            }
-        }
-    }
+    SAMRS_POSTPROCESS_VALUES();
     const size_t obase = ((size_t)mi * H + Y) * W + X0;
     if (return_logits) {
         float* o = reinterpret_cast<float*>(out) + obase;

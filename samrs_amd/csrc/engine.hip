@@ -2302,6 +2302,38 @@ int samrs_mask_boxes(samrs_engine_t* e, const uint8_t* masks, int n, int h, int 
     return SAMRS_OK;
 }
 
+// threshold counts of n masks straight from their 256^2 logits (see samrs_hip.h)
+int samrs_score_masks(samrs_engine_t* e, const float* lowres, int n, int in_h, int in_w, int orig_h, int orig_w, float offset,
+                      const float* boxes, int64_t* counts_out, void* stream) {
+    if (!e || !lowres || !counts_out || n < 0) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_score_masks: bad argument");
+    if (!(offset >= 0.f) || !std::isfinite(offset))
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_score_masks: offset must be finite and >= 0");
+    const int img = e->cfg.img_size;
+    if (in_h < 1 || in_w < 1 || in_h > img || in_w > img || (in_h != img && in_w != img) || orig_h < 1 || orig_w < 1 ||
+        (long long)orig_h * orig_w >= (1ll << 31))
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_score_masks: input %d x %d (long side must be %d), output %d x %d (h * w < 2^31)", in_h,
+                    in_w, img, orig_h, orig_w);
+    if (n == 0) return SAMRS_OK;
+    ON_DEVICE(e);
+    CK(e, launch_score_masks(lowres, n, in_h, in_w, orig_h, orig_w, img, offset, boxes, (unsigned long long*)counts_out,
+                             (hipStream_t)stream));
+    return SAMRS_OK;
+}
+
+// the quality gate: keep flags from the counts, dropped masks zeroed in place (see samrs_hip.h)
+int samrs_filter_masks(samrs_engine_t* e, uint8_t* masks, int n, int h, int w, const int64_t* counts, const float* iou,
+                       float min_stability, float min_pred_iou, float min_inside, uint8_t* keep_out, void* stream) {
+    if (!e || !masks || !counts || !keep_out || n < 0 || h < 1 || w < 1) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_filter_masks: bad argument");
+    if (min_pred_iou > 0.f && !iou) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_filter_masks: min_pred_iou > 0 needs iou");
+    if (std::isnan(min_stability) || std::isnan(min_pred_iou) || std::isnan(min_inside))
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_filter_masks: a threshold is NaN");
+    if (n == 0) return SAMRS_OK;
+    ON_DEVICE(e);
+    CK(e, launch_filter_masks(masks, n, (long)h * w, (const long long*)counts, iou, min_stability, min_pred_iou, min_inside, keep_out,
+                              (hipStream_t)stream));
+    return SAMRS_OK;
+}
+
 // gray + colour PNG files of n class maps, packed behind *cursor into `out` (see samrs_hip.h)
 int samrs_png_encode_labels(samrs_engine_t* e, const uint8_t* maps, int n, int h, int w, const uint8_t* lut, uint8_t* out,
                             int64_t out_capacity, int64_t* cursor, int64_t* table, void* stream) {

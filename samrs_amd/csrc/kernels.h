@@ -299,3 +299,14 @@ size_t mask_boxes_scratch_bytes(int n, int h);
 hipError_t launch_mask_row_extents(const uint8_t* masks, int n, int h, int w, int32_t* ext, hipStream_t s);
 hipError_t launch_mask_hull_rect(const int32_t* ext, int n, int h, int x0, int y0, int32_t* hbox_out, float* rbox_out,
                                  long long* record_out, int32_t* verts_out, int cap, int32_t* counts_out, hipStream_t s);
+
+// ---- quality_kernels.hip --------------------------------------------------------------------
+// counts [n][4] (zeroed on the stream, then counted) = #{v > +offset}, #{v > 0}, #{v > -offset}, #{v > 0 inside the mask's box} over
+// the orig_h x orig_w values v that postprocess_kernel computes from low [n][img_size / 4][img_size / 4] (postprocess_value.h);
+// boxes fp32 [n][4] xyxy in the output frame (inclusive on both sides) or null (the fourth count is then 0).  Integer atomics only.
+hipError_t launch_score_masks(const float* low, int n, int in_h, int in_w, int orig_h, int orig_w, int img_size, float offset,
+                              const float* boxes, unsigned long long* counts, hipStream_t s);
+// keep[j] = every enabled criterion holds for counts[j] / iou[j] (a threshold <= 0 disables its criterion; the rule: samrs_hip.h,
+// samrs_filter_masks); masks uint8 [n][hw] of dropped rows are zeroed (16-byte stores when masks is 16-byte aligned and hw % 16 == 0)
+hipError_t launch_filter_masks(uint8_t* masks, int n, long hw, const long long* counts, const float* iou, float min_stability,
+                               float min_pred_iou, float min_inside, uint8_t* keep, hipStream_t s);

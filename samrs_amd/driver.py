@@ -313,7 +313,7 @@ class TileResult:
     boxes: np.ndarray
     labels: np.ndarray
     masks: Optional[np.ndarray] = None      # uint8 [n_boxes, H, W] host when keep_masks
-    quality: Optional[np.ndarray] = None    # fp32 [n_boxes] predicted IoU of the kept mask (instance pipelines)
+    quality: Optional[np.ndarray] = None    # fp32 [n_boxes] predicted IoU of the kept mask (instance pipelines; TilePipeline(quality=True))
     rle_table: Optional[np.ndarray] = None  # int64 [n_boxes, 3] (offset, length, n_counts) into rle_data when rle=True
     rle_data: Optional[np.ndarray] = None   # uint8 view of the batch's pinned RLE byte buffer
     size: Optional[Tuple[int, int]] = None  # (H, W) of the tile
@@ -329,6 +329,9 @@ class TileResult:
     mask_rbox: Optional[np.ndarray] = None  # fp32 [n_boxes, 4, 2] corners of the minimum-area rotated rectangle of the pixel centres
     mask_record: Optional[np.ndarray] = None    # int64 [n_boxes, 8] dx, dy, pmin, pmax, qmin, qmax, hull vertices m, 2 x hull area
     gt_hbox: Optional[np.ndarray] = None    # int32 [n_boxes, 4] the same hbox of the ground-truth masks (gt=True, rle=True, mask_boxes=True)
+    # TilePipeline(quality=True) (samrs_score_masks / samrs_filter_masks; helpers in samrs_amd/quality.py):
+    score_counts: Optional[np.ndarray] = None   # int64 [n_boxes, 4] pixels with logit > +1, > 0, > -1, and > 0 inside the prompt box
+    kept: Optional[np.ndarray] = None       # bool [n_boxes] the instance passed the thresholds (all true without thresholds)
     windows: Optional[List[Tuple[int, int, int, int]]] = None   # scene mode (scene.ScenePipeline): the planned (x0, y0, w, h) windows
     window_of: Optional[List[int]] = None   # scene mode: window_of[j] = index into `windows` of the window box j was decoded in
 
@@ -364,13 +367,16 @@ class TileResult:
 
 class _OutBuf:
     def __init__(self, batch: int, side: int, max_boxes: int, rle: bool = False, png: bool = False, changed: bool = False,
-                 boxes: bool = False):
+                 boxes: bool = False, quality: bool = False):
         self.seg = torch.empty(batch, side, side, dtype=torch.uint8).pin_memory()
         self.areas = torch.empty(batch, max_boxes, dtype=torch.int64).pin_memory()
         self.changed = torch.empty(batch, max_boxes, dtype=torch.int64).pin_memory() if changed else None
         self.hbox = torch.empty(batch, max_boxes, 4, dtype=torch.int32).pin_memory() if boxes else None
         self.rbox = torch.empty(batch, max_boxes, 4, 2, dtype=torch.float32).pin_memory() if boxes else None
         self.record = torch.empty(batch, max_boxes, 8, dtype=torch.int64).pin_memory() if boxes else None
+        self.counts = torch.empty(batch, max_boxes, 4, dtype=torch.int64).pin_memory() if quality else None
+        self.kept = torch.empty(batch, max_boxes, dtype=torch.uint8).pin_memory() if quality else None
+        self.quality = torch.empty(batch, max_boxes, dtype=torch.float32).pin_memory() if quality else None
         self.done = torch.cuda.Event()
         self.masks: List[Optional[torch.Tensor]] = [None] * batch     # keep_masks: host copies of the full masks
         self.odd: dict = {}                                           # tiles that are not side x side: their class maps
@@ -382,6 +388,17 @@ class _OutBuf:
         self.png_tab = torch.zeros(batch, 2, 2, dtype=torch.int64).pin_memory() if png else None
         self.png_cur = torch.zeros(1, dtype=torch.int64).pin_memory() if png else None
         self.png_bytes = torch.empty(1 << 20, dtype=torch.uint8).pin_memory() if png else None
+
+
+QUALITY_OPTIONS = ("quality", "min_stability", "min_pred_iou", "min_inside_box")
+
+
+def refuse_quality_options(who: str, why: str, **opts) -> None:
+    """ValueError naming the mask-quality options of TilePipeline that `who` was handed (a pipeline that does not score masks)."""
+    given = [k for k in QUALITY_OPTIONS if opts.get(k)]
+    if given:
+        raise ValueError(f"{who} does not score masks ({why}): {', '.join(given)} "
+                         f"{'is a' if len(given) == 1 else 'are'} TilePipeline option{'' if len(given) == 1 else 's'}")
 
 
 class TilePipeline:
@@ -411,7 +428,8 @@ class TilePipeline:
                  out_depth: int = 3, max_boxes: int = 512, device_inputs: bool = False, rle: bool = False,
                  rle_buffer_mb: int = 256, precision="auto", _multimask: bool = False, png_lut: Optional[np.ndarray] = None,
                  png_buffer_mb: Optional[int] = None, batch_decode: bool = False, min_region_area: int = 0,
-                 region_mode: str = "both", mask_boxes: bool = False):
+                 region_mode: str = "both", mask_boxes: bool = False, quality: bool = False, min_stability: float = 0.0,
+                 min_pred_iou: float = 0.0, min_inside_box: float = 0.0):
         """precision: the operand-split mode (engine option "split") THIS PIPELINE'S OWN CALLS run in.  The option is set around
         each of the pipeline's encode / decode calls and restored afterwards (``Engine.options``), so the mode never outlives
         them: a ``SamPredictor`` built on the same model keeps the engine's own default (round 3 changed the engine's option for
@@ -434,7 +452,15 @@ class TilePipeline:
         instance.  0 (default) issues no call at all.
         mask_boxes: derive, on the decode stream and from the masks that become the output (after the clean-up where that is
         on), each mask's tight hbox, its minimum-area rotated box and the record behind it (``Engine.mask_boxes``):
-        ``TileResult.mask_hbox`` / ``mask_rbox`` / ``mask_record``.  False (default) launches and allocates nothing."""
+        ``TileResult.mask_hbox`` / ``mask_rbox`` / ``mask_record``.  False (default) launches and allocates nothing.
+        quality: score every mask on the decode stream, before anything else reads it (``Engine.score_masks``, offset 1.0, the
+        box in the original frame as it was staged): ``TileResult.score_counts`` (``quality.stability`` /
+        ``quality.inside_fraction`` turn them into the two scores), ``TileResult.quality`` = the decoder's predicted IoU, and
+        ``TileResult.kept``.  min_stability / min_pred_iou / min_inside_box: a threshold > 0 implies `quality` and drops the
+        instances that fail it (``Engine.filter_masks``; the rule: ``quality.keep_rule``): a dropped mask is zeroed on the device
+        before the clean-up, the mask boxes, the painting and the RLE encoding, so it paints nothing, has area 0, counts in no
+        class statistic and ``kept`` is False for it.  Without a threshold every output but the three new fields is byte for byte
+        what quality=False gives.  quality=False with no threshold (default) launches and allocates nothing new."""
         from .transforms import ResizeLongestSide
         from .engine import REGION_MODES
         if int(min_region_area) < 0:
@@ -442,6 +468,11 @@ class TilePipeline:
         if region_mode not in REGION_MODES:
             raise ValueError(f"region_mode must be one of {sorted(REGION_MODES)}, got {region_mode!r}")
         self.min_region_area, self.region_mode = int(min_region_area), region_mode
+        self.thresholds = (float(min_stability), float(min_pred_iou), float(min_inside_box))
+        if any(t != t or t < 0 for t in self.thresholds):
+            raise ValueError("min_stability, min_pred_iou and min_inside_box must be >= 0 (0 = off)")
+        self.filter = any(t > 0 for t in self.thresholds)
+        self.quality = bool(quality) or self.filter
         eng = sam.engine
         if eng is None:
             raise RuntimeError("move the model to the GPU first: sam.to('cuda')")
@@ -506,13 +537,17 @@ class TilePipeline:
             self.hbox_dev = [torch.zeros(batch, max_boxes, 4, dtype=torch.int32, device=dev) for _ in range(2)]
             self.rbox_dev = [torch.zeros(batch, max_boxes, 4, 2, dtype=torch.float32, device=dev) for _ in range(2)]
             self.rec_dev = [torch.zeros(batch, max_boxes, 8, dtype=torch.int64, device=dev) for _ in range(2)]
+        if self.quality:
+            self.cnt_dev = [torch.zeros(batch, max_boxes, 4, dtype=torch.int64, device=dev) for _ in range(2)]
+            self.keep_dev = [torch.ones(batch, max_boxes, dtype=torch.uint8, device=dev) for _ in range(2)]
+            self.qual_dev = [torch.zeros(batch, max_boxes, dtype=torch.float32, device=dev) for _ in range(2)]
         self.ev_h2d = [torch.cuda.Event() for _ in range(2)]
         self.ev_enc = [torch.cuda.Event() for _ in range(2)]
         self.ev_dec = [torch.cuda.Event() for _ in range(2)]
         self.ev_in_free = [torch.cuda.Event() for _ in range(2)]     # encoder has consumed input set b
         self.free_out: "queue.Queue[_OutBuf]" = queue.Queue()
         for _ in range(out_depth):
-            self.free_out.put(_OutBuf(batch, side, max_boxes, rle, self.png, self.min_region_area > 0, self.mask_boxes))
+            self.free_out.put(_OutBuf(batch, side, max_boxes, rle, self.png, self.min_region_area > 0, self.mask_boxes, self.quality))
 
     @staticmethod
     def _choose_split(sam, precision, multimask: bool) -> Optional[int]:
@@ -611,17 +646,17 @@ class TilePipeline:
         return self._input_frame_boxes(self.dev_box[b][off:off + nb], hw, in_size), None, None, None
 
     def _decode_multi(self, b: int, tiles, offs):
-        """batch_decode: the prompts of every tile of batch b in one predict_multi call -> per tile (masks, iou)."""
+        """batch_decode: the prompts of every tile of batch b in one predict_multi call -> per tile (masks, iou, low)."""
         per = [self._tile_prompts(b, t, hw, off, nb) for (t, hw), (off, nb) in zip(tiles, offs)]
         args = [None if per[0][j] is None else torch.cat([p[j] for p in per]) for j in range(4)]
-        masks, iou, _ = self.eng.predict_multi([b * self.batch + i for i in range(len(tiles))], [nb for _, nb in offs], *args,
+        masks, iou, low = self.eng.predict_multi([b * self.batch + i for i in range(len(tiles))], [nb for _, nb in offs], *args,
                                                self.multimask, False, [(int(t.shape[0]), int(t.shape[1])) for t, _ in tiles],
                                                [tuple(hw) for _, hw in tiles])
-        return list(zip(masks, iou))
+        return list(zip(masks, iou, low))
 
     def _decode_tile(self, b: int, i: int, tile, hw, off: int, nb: int, out: _OutBuf, pre=None) -> None:
         """Everything the reference does per image after set_image (main_sam_hbox_semantic.py:157-206), on s_dec.  pre: the
-        tile's (masks, iou) from _decode_multi (batch_decode), or None to predict here, chunk by chunk."""
+        tile's (masks, iou, low) from _decode_multi (batch_decode), or None to predict here, chunk by chunk."""
         eng, (H, W) = self.eng, hw
         in_size = (int(tile.shape[0]), int(tile.shape[1]))
         native = (H, W) == (self.side, self.side)
@@ -629,10 +664,12 @@ class TilePipeline:
         kept = []
         for s, e in box_chunks(nb, self.box_batch):                          # :157-181
             if pre is not None:
-                masks = pre[0][s:e]
+                masks, iou, low = pre[0][s:e], pre[1][s:e], pre[2][s:e]
             else:
                 tb = self._input_frame_boxes(self.dev_box[b][off + s:off + e], (H, W), in_size)   # :174
-                masks, _, _ = eng.predict(b * self.batch + i, tb, None, None, None, False, False, in_size, (H, W))
+                masks, iou, low = eng.predict(b * self.batch + i, tb, None, None, None, False, False, in_size, (H, W))
+            if self.quality:                                                      # score, then filter: before anything reads the masks
+                self._score(b, i, off, s, e, masks[:, 0], iou, low, in_size, (H, W))
             if self.min_region_area:                                              # before anything else reads the masks
                 eng.clean_masks(masks[:, 0], self.min_region_area, self.region_mode, areas_out=False,     # paint counts them
                                 changed_out=self.chg_dev[b][i, s:e])
@@ -653,6 +690,18 @@ class TilePipeline:
         # keep_masks: the full-resolution masks themselves (n MiB per tile instead of 1 MiB, copied synchronously) -- a
         # debugging / evaluation mode; the reference's pkl contract needs only their RLE (rle=True, encoded on the device)
         out.masks[i] = torch.cat(kept).cpu() if (self.keep_masks and kept) else None
+
+    STABILITY_OFFSET = 1.0     # the reference's stability_score_offset (automatic_mask_generator.py:43)
+
+    def _score(self, b: int, i: int, off: int, s: int, e: int, masks, iou, low, in_size, hw) -> None:
+        """quality: the counts of one chunk's masks from their low-resolution logits into the batch's table (the boxes as staged:
+        original frame), the predicted IoU beside them, and with a threshold the gate, which zeroes the dropped masks in place."""
+        eng = self.eng
+        counts = eng.score_masks(low[:, 0], in_size, hw, self.STABILITY_OFFSET, boxes=self.dev_box[b][off + s:off + e],
+                                 counts_out=self.cnt_dev[b][i, s:e])
+        self.qual_dev[b][i, s:e].copy_(iou[:, 0])
+        if self.filter:
+            eng.filter_masks(masks, counts, self.qual_dev[b][i, s:e], *self.thresholds, keep_out=self.keep_dev[b][i, s:e])
 
     def _input_frame_boxes(self, boxes: torch.Tensor, hw, in_size) -> torch.Tensor:
         """apply_boxes_torch (utils/transforms.py:83-91).  When the tile already has the encoder's input size both scale
@@ -682,6 +731,10 @@ class TilePipeline:
                 out.hbox.copy_(self.hbox_dev[b], non_blocking=True)
                 out.rbox.copy_(self.rbox_dev[b], non_blocking=True)
                 out.record.copy_(self.rec_dev[b], non_blocking=True)
+            if self.quality:
+                out.counts.copy_(self.cnt_dev[b], non_blocking=True)
+                out.kept.copy_(self.keep_dev[b], non_blocking=True)
+                out.quality.copy_(self.qual_dev[b], non_blocking=True)
             if self.rle:
                 out.rle_tab.copy_(self.rle_tab[b], non_blocking=True)
                 out.rle_cur.copy_(self.rle_cur[b], non_blocking=True)
@@ -759,7 +812,7 @@ class TilePipeline:
         for i, (it, (off, nb)) in enumerate(zip(items, offs)):
             seg = (odd[i].numpy() if odd[i] is not None else None) if i in odd else out.seg[i].numpy()
             m = out.masks[i].numpy() if out.masks[i] is not None else None
-            q = out.quality[i, :nb].numpy().copy() if getattr(out, "quality", None) is not None else None
+            q = out.quality[i, :nb].numpy().copy() if out.quality is not None else None      # instance pipelines; quality=True
             r = TileResult(it.key, seg, out.areas[i, :nb].numpy().copy(), np.asarray(it.boxes), np.asarray(it.labels), m, q)
             if seg is not None:
                 r.size = (int(seg.shape[0]), int(seg.shape[1]))
@@ -774,6 +827,9 @@ class TilePipeline:
             if self.mask_boxes:
                 r.mask_hbox, r.mask_rbox = out.hbox[i, :nb].numpy().copy(), out.rbox[i, :nb].numpy().copy()
                 r.mask_record = out.record[i, :nb].numpy().copy()
+            if self.quality:
+                r.score_counts = out.counts[i, :nb].numpy().copy()
+                r.kept = out.kept[i, :nb].numpy().astype(bool)
             self._extra_result(r, i, off, nb, out, extra)
             res.append(r)
         out.odd = {}
@@ -861,6 +917,7 @@ class InstancePipeline(TilePipeline):
         that driver uses multimask_output=False: pass multimask=False)."""
         if prompt not in ("box", "rbox_mask", "point"):
             raise ValueError("prompt must be 'box', 'rbox_mask' or 'point'")
+        refuse_quality_options("InstancePipeline", "scoring the best-of-3 path is not built", **kw)
         if prompt == "point":
             self.BOX_WIDTH = 2
         from . import transforms

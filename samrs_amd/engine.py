@@ -119,6 +119,10 @@ def load_library() -> C.CDLL:
     lib.samrs_k_mask_hull.argtypes = [vp, ip, ip, ip, ip, ip, vp, vp, ip, vp, vp]
     for name in ("samrs_mask_boxes", "samrs_k_mask_row_extents", "samrs_k_mask_hull"):
         getattr(lib, name).restype = ip
+    lib.samrs_score_masks.argtypes = [vp, vp, ip, ip, ip, ip, ip, fp, vp, vp, vp]
+    lib.samrs_filter_masks.argtypes = [vp, vp, ip, ip, ip, vp, vp, fp, fp, fp, vp, vp]
+    for name in ("samrs_score_masks", "samrs_filter_masks"):
+        getattr(lib, name).restype = ip
     lib.samrs_png_encode_labels.argtypes = [vp, vp, ip, ip, ip, vp, vp, C.c_int64, vp, vp, vp]
     lib.samrs_k_upscaler_fused.argtypes = [ip, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, vp]
     lib.samrs_k_convert.argtypes = [ip, vp, vp, C.c_int64, vp]
@@ -694,6 +698,73 @@ class Engine:
                 self._check(self.lib.samrs_mask_boxes(self.handle, m.data_ptr(), n, h, w, int(offset[0]), int(offset[1]), _ptr(outs[0]),
                                                       _ptr(outs[1]), _ptr(outs[2]), _stream()))
         return outs[0], outs[1], outs[2]
+
+    def score_masks(self, low: torch.Tensor, input_size: Sequence[int], original_size: Sequence[int], offset: float = 1.0,
+                    boxes: Optional[torch.Tensor] = None, counts_out=None) -> torch.Tensor:
+        """Threshold counts of every mask at the full output resolution, straight from the low-resolution logits
+        (samrs_score_masks): low fp32 [n, 256, 256] or [n, C, 256, 256] (the third output of ``predict``; C is flattened into n),
+        contiguous -> counts int64 [n, 4] = n_hi, n_mid, n_lo, n_in: the output pixels whose postprocessed logit is > +offset, > 0,
+        > -offset, and > 0 inside the mask's box.  n_mid equals the number of set pixels of the mask ``predict`` returns for the
+        same logits and sizes, exactly; stability = n_hi / n_lo (``quality.stability``), share inside the box = n_in / n_mid
+        (``quality.inside_fraction``).  `boxes`: fp32 [n, 4] xyxy in the ORIGINAL frame (both corners inclusive), or None (n_in =
+        0); for C = 3 repeat each box three times.  `counts_out`: None = a new tensor, or a caller-owned contiguous int64 [n, 4]
+        slice.  Nothing of full resolution is written.  Asynchronous on the current stream."""
+        if not (isinstance(low, torch.Tensor) and low.dtype == torch.float32 and low.dim() in (3, 4) and tuple(low.shape[-2:]) == (256, 256)):
+            raise ValueError("low must be fp32 [n, 256, 256] or [n, C, 256, 256] (the low-resolution logits of predict)")
+        if not (low.is_cuda and low.is_contiguous()):
+            raise ValueError("low must be a contiguous tensor on the engine's device")
+        n = int(low.numel() // (256 * 256))
+        offset = float(offset)
+        if not (offset >= 0.0 and offset != float("inf")):
+            raise ValueError(f"offset must be finite and >= 0, got {offset}")
+        if boxes is not None:
+            if not (isinstance(boxes, torch.Tensor) and boxes.dtype == torch.float32 and boxes.is_cuda and boxes.is_contiguous()
+                    and tuple(boxes.shape) == (n, 4)):
+                raise ValueError(f"boxes must be a contiguous fp32 [{n}, 4] tensor on the engine's device, or None")
+        if counts_out is None:
+            counts_out = torch.empty(n, 4, dtype=torch.int64, device=self.device)
+        elif not (isinstance(counts_out, torch.Tensor) and counts_out.dtype == torch.int64 and counts_out.is_cuda
+                  and counts_out.is_contiguous() and tuple(counts_out.shape) == (n, 4)):
+            raise ValueError(f"counts_out must be a contiguous int64 [{n}, 4] tensor on the engine's device, or None")
+        if n:
+            with torch.cuda.device(self.device):
+                self._check(self.lib.samrs_score_masks(self.handle, low.data_ptr(), n, int(input_size[0]), int(input_size[1]),
+                                                       int(original_size[0]), int(original_size[1]), offset, _ptr(boxes),
+                                                       counts_out.data_ptr(), _stream()))
+        return counts_out
+
+    def filter_masks(self, masks: torch.Tensor, counts: torch.Tensor, iou: Optional[torch.Tensor] = None, min_stability: float = 0.0,
+                     min_pred_iou: float = 0.0, min_inside_box: float = 0.0, keep_out=None) -> torch.Tensor:
+        """The quality gate on the device (samrs_filter_masks): masks [n, H, W] bool / uint8, contiguous, in / out; counts int64
+        [n, 4] from :meth:`score_masks`; iou fp32 [n] (the predicted IoU; needed when min_pred_iou > 0) -> keep uint8 [n].  A
+        mask is kept iff every enabled criterion holds (a threshold <= 0 disables its criterion; ``quality.keep_rule`` restates
+        the rule): stability n_hi / n_lo >= min_stability (an empty low-threshold mask fails), iou > min_pred_iou, share inside
+        the box n_in / n_mid >= min_inside_box (an empty mask passes).  A dropped mask is zeroed in place -- to painting, areas,
+        class statistics, ``mask_boxes`` and RLE it is an empty mask --, a kept one is not touched.  `keep_out`: None = a new
+        tensor, or a caller-owned contiguous uint8 [n] slice.  Asynchronous on the current stream."""
+        m = self._masks_u8(masks)
+        n, h, w = m.shape
+        if not (isinstance(counts, torch.Tensor) and counts.dtype == torch.int64 and counts.is_cuda and counts.is_contiguous()
+                and tuple(counts.shape) == (n, 4)):
+            raise ValueError(f"counts must be a contiguous int64 [{n}, 4] tensor on the engine's device")
+        thr = [float(min_stability), float(min_pred_iou), float(min_inside_box)]
+        if any(t != t for t in thr):
+            raise ValueError("a threshold is NaN")
+        if iou is None:
+            if thr[1] > 0:
+                raise ValueError("min_pred_iou > 0 needs iou")
+        elif not (isinstance(iou, torch.Tensor) and iou.dtype == torch.float32 and iou.is_cuda and iou.is_contiguous() and iou.numel() == n):
+            raise ValueError(f"iou must be a contiguous fp32 [{n}] tensor on the engine's device, or None")
+        if keep_out is None:
+            keep_out = torch.empty(n, dtype=torch.uint8, device=self.device)
+        elif not (isinstance(keep_out, torch.Tensor) and keep_out.dtype == torch.uint8 and keep_out.is_cuda and keep_out.is_contiguous()
+                  and tuple(keep_out.shape) == (n,)):
+            raise ValueError(f"keep_out must be a contiguous uint8 [{n}] tensor on the engine's device, or None")
+        if n:
+            with torch.cuda.device(self.device):
+                self._check(self.lib.samrs_filter_masks(self.handle, m.data_ptr(), n, h, w, counts.data_ptr(), _ptr(iou), thr[0], thr[1],
+                                                        thr[2], keep_out.data_ptr(), _stream()))
+        return keep_out
 
     def mask_row_extents(self, masks: torch.Tensor) -> torch.Tensor:
         """Test hook (samrs_k_mask_row_extents): int32 [n, H, 3] = first set column, last set column and pixel count of every row,

@@ -27,7 +27,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import driver, rle, tile_io
+from . import driver, quality, rle, tile_io
 
 
 def default_palette(n_classes: int) -> np.ndarray:
@@ -60,14 +60,17 @@ def write_outputs(out_dir: str, stem: str, seg: np.ndarray, masks: Optional[np.n
                   labels: np.ndarray, areas: np.ndarray, palette: np.ndarray, class_names: Sequence[str],
                   rles: Optional[Sequence[dict]] = None, clock: Optional[StageClock] = None, png_level: int = tile_io.LEVEL_LABELS,
                   png_files: Optional[Tuple[bytes, bytes]] = None, mask_bboxes: Optional[Sequence] = None,
-                  mask_rboxes: Optional[Sequence] = None, dota_txt: bool = False) -> None:
+                  mask_rboxes: Optional[Sequence] = None, dota_txt: bool = False, scores: Optional[dict] = None) -> None:
     """`rles`: the per-instance COCO RLE dicts when they were encoded on the device (driver.TileResult.rle); otherwise they are
     encoded here from `masks` (host restatement), or left out when both are None (--no-rle).  `png_files`: the complete
     (gray, color) PNG files when they were encoded on the device (--png-device: driver.TileResult.png, byte-identical with the
     LEVEL_LABELS encoder); they are written as they are and `seg` / `png_level` are not used for them.  `mask_bboxes` /
     `mask_rboxes` (--mask-boxes): per instance the COCO ``[x, y, w, h]`` and the fp32 [4, 2] minimum-area rotated box derived from
     the mask on the device (driver.TileResult.mask_bbox / mask_rbox), None for an empty mask; they become the pickle entries'
-    ``"mask_bbox"`` / ``"mask_rbox"``.  `dota_txt` (--dota-txt): also ``rbox/<stem>.txt``, one DOTA line per non-empty instance."""
+    ``"mask_bbox"`` / ``"mask_rbox"``.  `dota_txt` (--dota-txt): also ``rbox/<stem>.txt``, one DOTA line per non-empty instance.
+    `scores` (--quality): per-instance arrays "pred_iou", "stability", "inside_box" -- they become float pickle entries of those
+    names -- and "kept" (bool): an instance that failed a threshold gets no pickle entry (its mask was zeroed on the device, so it
+    painted nothing and, being empty, has no DOTA line either)."""
     import time
     t0 = time.perf_counter()
     for sub in ("gray", "color", "ins"):
@@ -94,7 +97,12 @@ def write_outputs(out_dir: str, stem: str, seg: np.ndarray, masks: Optional[np.n
         if clock: t0 = clock.add("write.color_png", t0)
     info = []
     for j in range(len(labels)):                                                            # :200-206
+        if scores is not None and not scores["kept"][j]:
+            continue
         entry = {"bbox": boxes[j], "category": class_names[int(labels[j])], "label": int(labels[j]), "size": int(areas[j])}
+        if scores is not None:
+            for key in ("pred_iou", "stability", "inside_box"):
+                entry[key] = float(scores[key][j])
         if rles is not None:
             entry["mask"] = rles[j]
         elif masks is not None:
@@ -311,6 +319,10 @@ def run(args) -> Dict[str, List[int]]:
     # --mask-boxes / --dota-txt: each mask's tight hbox and minimum-area rotated box, derived on the device (samrs_mask_boxes)
     dota_txt = bool(getattr(args, "dota_txt", False))
     mask_boxes = bool(getattr(args, "mask_boxes", False)) or dota_txt
+    # --quality / --min-stability / --min-pred-iou / --min-inside-box: every mask scored on the device (samrs_score_masks) and, with a
+    # threshold, the doubtful ones zeroed there before they are painted (samrs_filter_masks)
+    thresholds = {k: float(getattr(args, k, 0.0) or 0.0) for k in ("min_stability", "min_pred_iou", "min_inside_box")}
+    want_quality = bool(getattr(args, "quality", False)) or any(t > 0 for t in thresholds.values())
     if scene_window > 0:
         from . import scene
         pipe = scene.ScenePipeline(sam, n_classes, window=scene_window, overlap=getattr(args, "scene_overlap", 256),
@@ -318,7 +330,7 @@ def run(args) -> Dict[str, List[int]]:
                                    rle=not args.no_rle, rle_buffer_mb=getattr(args, "rle_buffer_mb", 256),
                                    png_lut=tile_io.class_lut(palette) if png_device else None,
                                    min_region_area=min_region_area, region_mode=getattr(args, "region_mode", "both"),
-                                   mask_boxes=mask_boxes)
+                                   mask_boxes=mask_boxes, quality=want_quality, **thresholds)     # refused there, by name
     else:
         pipe = driver.TilePipeline(sam, n_classes, batch=batch, box_batch=args.box_batch, rle=not args.no_rle,
                                    rle_buffer_mb=getattr(args, "rle_buffer_mb", 256), max_boxes=max_boxes,
@@ -326,7 +338,7 @@ def run(args) -> Dict[str, List[int]]:
                                    png_buffer_mb=getattr(args, "png_buffer_mb", None),
                                    batch_decode=bool(getattr(args, "batch_decode", False)),
                                    min_region_area=min_region_area, region_mode=getattr(args, "region_mode", "both"),
-                                   mask_boxes=mask_boxes)
+                                   mask_boxes=mask_boxes, quality=want_quality, **thresholds)
     # rank r takes chunks of `batch` consecutive stems: statically (r, r + world, ...) or from the shared counter (whose
     # store key must be unique per work list: a second run() in the same process group must not find a spent counter)
     import zlib
@@ -394,6 +406,7 @@ def run(args) -> Dict[str, List[int]]:
         return items
 
     done = [0]
+    dropped = [0]                    # --min-stability / --min-pred-iou / --min-inside-box: instances left unlabeled (this run's images)
     cleaned = [0, 0]                 # --min-region-area: pixels changed, instances with a changed pixel (this run's images)
     sizes: List[int] = []
     writers = ThreadPoolExecutor(max_workers=n_writers)
@@ -423,8 +436,12 @@ def run(args) -> Dict[str, List[int]]:
                 if r.mask_record is not None:
                     bbs = [r.mask_bbox(j) for j in range(len(r.labels))]
                     rbs = [None if bb is None else r.mask_rbox[j].copy() for j, bb in enumerate(bbs)]
+                scores = None
+                if r.score_counts is not None:
+                    scores = {"pred_iou": r.quality, "stability": quality.stability(r.score_counts),
+                              "inside_box": quality.inside_fraction(r.score_counts), "kept": r.kept}
                 write_outputs(args.out, r.key, r.seg_mask, None, r.boxes, r.labels, r.areas, palette, names, rles, clock, png_level, files,
-                              bbs, rbs, dota_txt)
+                              bbs, rbs, dota_txt, scores)
             finally:
                 with lock:
                     left[0] -= 1
@@ -435,8 +452,12 @@ def run(args) -> Dict[str, List[int]]:
             release()
         pending.extend(writers.submit(job, r) for r in results)
         if run_log is not None:                                  # one JSON line per batch handed to the writers (per-run log)
-            run_log.write(json.dumps({"t": round(time.perf_counter() - t_run, 4), "rank": rank, "images": [str(r.key) for r in results],
-                                      "boxes": [int(len(r.labels)) for r in results], "done": done[0] + len(results)}) + "\n")
+            line = {"t": round(time.perf_counter() - t_run, 4), "rank": rank, "images": [str(r.key) for r in results],
+                    "boxes": [int(len(r.labels)) for r in results], "done": done[0] + len(results)}
+            if want_quality:                                     # per image: instances that failed a threshold and were left unlabeled
+                line["dropped"] = [int((~r.kept).sum()) for r in results]
+                line["dropped_total"] = dropped[0] + sum(line["dropped"])
+            run_log.write(json.dumps(line) + "\n")
             run_log.flush()
         for r in results:
             buf = loaned.pop(r.key, None)
@@ -445,6 +466,8 @@ def run(args) -> Dict[str, List[int]]:
         reap(block=False)
         for r in results:
             sizes.extend(int(a) for a in r.areas if a > 0)                                           # statistic.py:44-49
+            if r.kept is not None:
+                dropped[0] += int((~r.kept).sum())
             if r.changed is not None:
                 cleaned[0] += int(r.changed.sum())
                 cleaned[1] += int((r.changed > 0).sum())
@@ -491,6 +514,14 @@ def run(args) -> Dict[str, List[int]]:
                                             torch.tensor([cleaned[1]], dtype=torch.int64, device=dev))
         stats["region_cleanup"] = {"min_region_area": min_region_area, "region_mode": getattr(args, "region_mode", "both"),
                                    "changed_pixel_num": int(cpx.item()), "changed_instance_num": int(cin.item())}
+    if want_quality:                 # over the images processed in THIS run, like region_cleanup
+        dev = pipe.class_pixels.device
+        dn, _ = driver.reduce_statistics(torch.tensor([dropped[0]], dtype=torch.int64, device=dev),
+                                         torch.zeros(1, dtype=torch.int64, device=dev))
+        stats["quality"] = dict(thresholds, stability_offset=driver.TilePipeline.STABILITY_OFFSET, dropped_instance_num=int(dn.item()))
+        if rank == 0:
+            print(f"[rank 0] quality: {int(dn.item())} instances dropped and left unlabeled "
+                  f"({', '.join(f'{k}={v:g}' for k, v in thresholds.items())})", flush=True)
     if clock:
         stats["timing"] = {"images": done[0], "loop_seconds": wall, "stage_thread_seconds": dict(clock.t),   # this rank's loop
                            "readers": n_readers, "writers": n_writers, "cpu_budget": round(host_cpu_budget(), 1)}
@@ -518,6 +549,13 @@ class _Parser(argparse.ArgumentParser):
             self.error("--scene-overlap must satisfy 0 <= overlap < --scene-window")
         if ns.dota_txt:
             ns.mask_boxes = True
+        for flag, on in (("--quality", ns.quality), ("--min-stability", ns.min_stability > 0), ("--min-pred-iou", ns.min_pred_iou > 0),
+                         ("--min-inside-box", ns.min_inside_box > 0)):
+            if on and ns.scene_window > 0:
+                self.error(f"{flag} does not apply with --scene-window: masks are not scored across scene windows")
+        for flag, v in (("--min-stability", ns.min_stability), ("--min-pred-iou", ns.min_pred_iou), ("--min-inside-box", ns.min_inside_box)):
+            if not v >= 0:
+                self.error(f"{flag} must be >= 0 (0 = off)")
         return ns
 
 
@@ -576,6 +614,17 @@ def build_parser() -> argparse.ArgumentParser:
     add_region_arguments(ap, " Under --resume the totals cover the images processed in this run only.")
     add_mask_box_arguments(ap, "every ins/<stem>.pkl entry gains \"mask_bbox\" (COCO [x, y, w, h]) and \"mask_rbox\" (float32 [4, 2]), "
                                "None for an empty mask")
+    ap.add_argument("--quality", action="store_true",
+                    help="score every mask on the GPU: each ins/<stem>.pkl entry gains \"pred_iou\" (the decoder's predicted IoU), "
+                         "\"stability\" (segment_anything's calculate_stability_score, offset 1.0, at the full resolution) and "
+                         "\"inside_box\" (the share of the mask inside its prompt box)")
+    ap.add_argument("--min-stability", type=float, default=0.0, metavar="S",
+                    help="leave instances with stability < S unlabeled: no pickle entry, no DOTA line, their pixels stay at what earlier "
+                         "boxes painted or 255; the --log lines and the statistics carry the dropped counts.  Implies --quality; 0 = off")
+    ap.add_argument("--min-pred-iou", type=float, default=0.0, metavar="Q",
+                    help="the same for instances whose predicted IoU is not > Q (segment_anything's pred_iou_thresh); 0 = off")
+    ap.add_argument("--min-inside-box", type=float, default=0.0, metavar="F",
+                    help="the same for instances with less than the share F of their mask inside their prompt box; 0 = off")
     ap.add_argument("--dota-txt", action="store_true",
                     help="also write rbox/<stem>.txt, one line per non-empty instance in DOTA's oriented-box form "
                          "'x1 y1 x2 y2 x3 y3 x4 y4 category label' (coordinates %%.1f); implies --mask-boxes")

@@ -91,6 +91,22 @@ class SamPredictor:
         return self.model.engine.predict(self.slot, boxes, point_coords, point_labels, mask_input,
                                          multimask_output, return_logits, self.input_size, self.original_size)
 
+    @torch.no_grad()
+    def stability_score(self, low_res_masks: torch.Tensor, offset: float = 1.0) -> torch.Tensor:
+        """``calculate_stability_score`` (utils/amg.py:156-176) of the masks behind `low_res_masks` ([n, C, 256, 256], the third
+        output of :meth:`predict_torch`) at the set image's ``original_size``: fp32 [n, C] = |logit > +offset| / |logit > -offset|
+        over the full-resolution logits, which are never materialised (``Engine.score_masks`` counts on the device).  0 / 0 (the
+        reference's NaN) is 0.0 here."""
+        if not self.is_image_set:
+            raise RuntimeError("An image must be set with .set_image(...) before mask prediction.")
+        if low_res_masks.dim() != 4:
+            raise ValueError(f"low_res_masks must be [n, C, 256, 256], got {tuple(low_res_masks.shape)}")
+        low = low_res_masks.to(device=self.device, dtype=torch.float32).contiguous()
+        counts = self.model.engine.score_masks(low, self.input_size, self.original_size, offset)
+        hi, lo = counts[:, 0].double(), counts[:, 2].double()
+        score = torch.where(lo > 0, hi / lo.clamp(min=1), torch.zeros_like(hi))
+        return score.to(torch.float32).reshape(low.shape[0], low.shape[1])
+
     def get_image_embedding(self) -> torch.Tensor:
         if not self.is_image_set:
             raise RuntimeError("An image must be set with .set_image(...) to generate an embedding.")

@@ -113,9 +113,12 @@ class ScenePipeline:
 
     def __init__(self, sam, n_classes: int, window: int = 1024, overlap: int = 256, context: float = 2.0, batch: int = 8,
                  box_batch: int = 64, rle: bool = False, png_lut: Optional[np.ndarray] = None, min_region_area: int = 0,
-                 region_mode: str = "both", precision="auto", rle_buffer_mb: int = 256, mask_boxes: bool = False):
+                 region_mode: str = "both", precision="auto", rle_buffer_mb: int = 256, mask_boxes: bool = False,
+                 quality: bool = False, min_stability: float = 0.0, min_pred_iou: float = 0.0, min_inside_box: float = 0.0):
         import torch
-        from .driver import TilePipeline
+        from .driver import TilePipeline, refuse_quality_options
+        refuse_quality_options("ScenePipeline", "scoring across scene windows is not built", quality=quality,
+                               min_stability=min_stability, min_pred_iou=min_pred_iou, min_inside_box=min_inside_box)
         from .engine import REGION_MODES
         from .transforms import ResizeLongestSide
         if not 0 <= int(overlap) < int(window):
