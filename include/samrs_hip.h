@@ -276,6 +276,45 @@ int samrs_clean_masks(samrs_engine_t* e, uint8_t* masks, int n, int h, int w, in
 int samrs_mask_boxes(samrs_engine_t* e, const uint8_t* masks, int n, int h, int w, int x0, int y0,
                      int32_t* hbox_out /*[n][4]*/, float* rbox_out /*[n][4][2]*/, int64_t* record_out /*[n][8]*/, void* stream);
 
+/* -- a mask's outline as polygons: outer rings and holes of every mask, traced on the device (annotation tools, iSAID-style
+ * instance files and DOTA-style oriented annotations consume polygons; the reference goes through cv2.findContours on the host, one
+ * mask at a time).  masks uint8 [n][h][w] device (non-zero = set; outside the image counts as unset), decoded in a window whose
+ * origin is (x0, y0).  All geometry is on the pixel LATTICE: vertex (x, y), 0 <= x <= w, 0 <= y <= h, is the top-left CORNER of pixel
+ * (row y, col x) -- deliberately NOT the pixel centres of samrs_mask_boxes: the polygon encloses exactly the set pixels' squares.
+ *   crack edge  a unit lattice segment between a set pixel and an unset one, directed so that the set pixel is on the right hand of
+ *               travel (y down).  Set pixel p = y w + x owns id = 4 p + d: d = 0 top, (x, y) -> (x + 1, y); 1 right, (x + 1, y) ->
+ *               (x + 1, y + 1); 2 bottom, (x + 1, y + 1) -> (x, y + 1); 3 left, (x, y + 1) -> (x, y);
+ *   successor   at the end vertex of pixel P's edge d, with R the pixel straight ahead of P and L the pixel ahead on the left: L set:
+ *               L's edge (d + 3) % 4 (a saddle vertex joins the diagonal pixels: the foreground is 8-connected, the regions of
+ *               samrs_clean_masks); else R set: R's edge d; else P's own edge (d + 1) % 4.  A bijection: the edges fall into rings;
+ *   ring        ranked from its smallest edge id (a top edge for an outer ring, a bottom edge for a hole) along the successor; an
+ *               edge is a corner when its direction differs from its predecessor's; the polygon is the start vertices of the corner
+ *               edges in rank order (collinear lattice points dropped, no other simplification; a hole's polygon starts at the first
+ *               corner behind its rank-0 edge; a ring may touch itself at a saddle vertex).  Outer rings run clockwise on screen;
+ *   order       the rings of a mask by ascending smallest edge id, masks in call order;
+ *   vertices    int32 [vertex_capacity][2] = (x0 + x, y0 + y);
+ *   rings       int32 [ring_capacity][4] = first vertex relative to the mask's first vertex, vertex count, twice the signed area
+ *               (shoelace; > 0 outer ring, < 0 hole; over a mask's rings it sums to twice the set pixels), the pixel index y w + x
+ *               of the ring's smallest edge (a set pixel of the ring's component);
+ *   table       int64 [n][5] = first ring, ring count, first vertex, vertex count, edge count; the firsts are absolute indices into
+ *               the two buffers; an empty mask has counts 0;
+ *   cursor      int64 [2] device, in / out: first free vertex, first free ring.  Masks are placed in order behind it, so several
+ *               calls append to one pair of buffers (as samrs_rle_encode does with its buffer).
+ * A mask that does not fit either capacity is skipped and takes no space: first ring = first vertex = -1, ring count = -1 - rings
+ * needed, vertex count = -1 - vertices needed; later masks are still placed if they fit.  A mask with edge count > max_edges is not
+ * traced: ring count = vertex count = -1, firsts -1; edge count is always the true number.  max_edges bounds the scratch (about 73
+ * bytes per edge and mask in flight) and the ceil(log2(min(max_edges, 4 h w))) ranking rounds (pointer doubling on the cycles).
+ * h, w, x0, y0 within samrs_mask_boxes's limits and h * w < 2^30; outside them, n < 0, max_edges < 4 or a null masks / vertices /
+ * rings / cursor / table: SAMRS_ERR_BAD_ARG and nothing is written.  n == 0 is a no-op.  Integer arithmetic only, bitwise
+ * reproducible, no host synchronisation.  ONE scratch buffer per handle grows on demand (a big call runs as consecutive chunks on the
+ * stream so that it stays at or below 256 MiB, or one mask's worth): all samrs_mask_polygons calls on a handle must be stream-ordered
+ * with each other; two handles never share it. */
+int samrs_mask_polygons(samrs_engine_t* e, const uint8_t* masks, int n, int h, int w, int x0, int y0, int max_edges,
+                        int32_t* vertices /* [vertex_capacity][2] */, int64_t vertex_capacity,
+                        int32_t* rings /* [ring_capacity][4] */, int64_t ring_capacity,
+                        int64_t* cursor /* device [2], in / out: first free vertex, first free ring */,
+                        int64_t* table /* device [n][5] */, void* stream);
+
 /* -- mask quality before the masks become labels: the three signals a box-prompted mask carries, counted on the device straight
  * from the 256^2 logits (`calculate_stability_score`, utils/amg.py:156-176, and the `pred_iou_thresh` / `stability_score_thresh`
  * gate of automatic_mask_generator.py:295-304; the box fit is this library's own).  lowres fp32 [n][256][256]: the lowres_out of

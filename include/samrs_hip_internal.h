@@ -227,6 +227,21 @@ int samrs_k_region_labels(const uint8_t* masks, int n, int h, int w, int complem
 int samrs_k_mask_row_extents(const uint8_t* masks, int n, int h, int w, int32_t* ext_out, void* stream);
 int samrs_k_mask_hull(const uint8_t* masks, int n, int h, int w, int x0, int y0, int32_t* ext_scratch, int32_t* verts_out, int cap,
                       int32_t* counts_out, void* stream);
+/* the stages of samrs_mask_polygons alone (polygon_kernels.hip), for one chunk of n <= 65535 masks.  scratch: a device buffer of
+ * samrs_k_polygon_scratch_bytes(n, h, w, max_edges) bytes; the per-edge outputs of mask j start at entry j * stride with
+ * stride = samrs_k_polygon_edge_stride(h, w, max_edges) = min(max_edges, 4 h w); counts_out int32 [n] = edges per mask; a mask
+ * with more than max_edges edges has its count and no entries.
+ *   samrs_k_polygon_edges  the compact edge list: ids_out uint32 [n][stride] = the edge ids 4 p + d in ascending order, succ_out
+ *                          int32 [n][stride] = the compact index of each edge's successor, corner_out uint8 [n][stride] = 1 where
+ *                          the edge's direction differs from its predecessor's
+ *   samrs_k_polygon_ranks  after the doubling rounds: leader_out int32 [n][stride] = the compact index of the smallest edge of the
+ *                          edge's ring, rank_out int32 [n][stride] = the edge's distance from it along the successor */
+int64_t samrs_k_polygon_scratch_bytes(int n, int h, int w, int max_edges);
+int64_t samrs_k_polygon_edge_stride(int h, int w, int max_edges);
+int samrs_k_polygon_edges(const uint8_t* masks, int n, int h, int w, int max_edges, void* scratch, uint32_t* ids_out, int32_t* succ_out,
+                          uint8_t* corner_out, int32_t* counts_out, void* stream);
+int samrs_k_polygon_ranks(const uint8_t* masks, int n, int h, int w, int max_edges, void* scratch, int32_t* leader_out,
+                          int32_t* rank_out, int32_t* counts_out, void* stream);
 
 #ifdef __cplusplus
 }

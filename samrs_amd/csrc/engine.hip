@@ -248,6 +248,9 @@ struct samrs_engine {
     // row extents of samrs_mask_boxes, grown on demand
     void* box_scratch = nullptr;
     size_t box_scratch_bytes = 0;
+    // edge lists and ranking state of samrs_mask_polygons, grown on demand
+    void* poly_scratch = nullptr;
+    size_t poly_scratch_bytes = 0;
     // class-map PNG scratch (samrs_png_encode_labels), grown on demand
     void* png_scratch = nullptr;
     size_t png_scratch_bytes = 0;
@@ -628,6 +631,7 @@ void samrs_destroy(samrs_engine_t* e) {
     if (e->rle_scratch) (void)hipFree(e->rle_scratch);
     if (e->region_scratch) (void)hipFree(e->region_scratch);
     if (e->box_scratch) (void)hipFree(e->box_scratch);
+    if (e->poly_scratch) (void)hipFree(e->poly_scratch);
     if (e->png_scratch) (void)hipFree(e->png_scratch);
     delete e;
 }
@@ -2302,6 +2306,40 @@ int samrs_mask_boxes(samrs_engine_t* e, const uint8_t* masks, int n, int h, int 
     return SAMRS_OK;
 }
 
+// the outlines of n masks as polygons behind a device-side cursor (see samrs_hip.h)
+int samrs_mask_polygons(samrs_engine_t* e, const uint8_t* masks, int n, int h, int w, int x0, int y0, int max_edges, int32_t* vertices,
+                        int64_t vertex_capacity, int32_t* rings, int64_t ring_capacity, int64_t* cursor, int64_t* table, void* stream) {
+    if (!e || !masks || !table || !cursor || !vertices || !rings || n < 0 || max_edges < 4 || vertex_capacity < 0 || ring_capacity < 0)
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_mask_polygons: bad argument");
+    if (!mask_polygons_shape_ok(h, w, x0, y0))
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_mask_polygons: %d x %d masks at (%d, %d): h, w must be 1..8192, x0 + w, y0 + h <= 32768 "
+                    "and h * w < 2^30", h, w, x0, y0);
+    if (n == 0) return SAMRS_OK;
+    ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    // masks per pass: as many as keep the scratch at or below 256 MiB (n masks need at most n times one mask's bytes), one at least
+    size_t cap = ((size_t)256 << 20) / mask_polygons_scratch_bytes(1, h, w, max_edges);
+    cap = cap < 1 ? 1 : (cap > 4096 ? 4096 : cap);
+    const int step = (size_t)n < cap ? n : (int)cap;
+    const size_t need = mask_polygons_scratch_bytes(step, h, w, max_edges);
+    if (need > e->poly_scratch_bytes) {
+        if (e->poly_scratch) {
+            CK(e, hipStreamSynchronize(s));
+            CK(e, hipFree(e->poly_scratch));              // device-synchronising: nothing still reads the old scratch
+            e->poly_scratch = nullptr; e->poly_scratch_bytes = 0;
+        }
+        CK(e, hipMalloc(&e->poly_scratch, need));
+        e->poly_scratch_bytes = need;
+    }
+    for (int off = 0; off < n; off += step) {
+        const int m = n - off < step ? n - off : step;
+        CK(e, launch_mask_polygons(masks + (size_t)off * h * w, m, h, w, x0, y0, max_edges, e->poly_scratch, vertices,
+                                   (long long)vertex_capacity, rings, (long long)ring_capacity, (long long*)cursor,
+                                   (long long*)table + (size_t)off * 5, s));
+    }
+    return SAMRS_OK;
+}
+
 // threshold counts of n masks straight from their 256^2 logits (see samrs_hip.h)
 int samrs_score_masks(samrs_engine_t* e, const float* lowres, int n, int in_h, int in_w, int orig_h, int orig_w, float offset,
                       const float* boxes, int64_t* counts_out, void* stream) {
@@ -2601,6 +2639,22 @@ int samrs_k_mask_hull(const uint8_t* masks, int n, int h, int w, int x0, int y0,
     hipError_t err = launch_mask_row_extents(masks, n, h, w, ext_scratch, (hipStream_t)stream);
     if (err != hipSuccess) KRET(err);
     KRET(launch_mask_hull_rect(ext_scratch, n, h, x0, y0, nullptr, nullptr, nullptr, verts_out, cap, counts_out, (hipStream_t)stream));
+}
+int64_t samrs_k_polygon_scratch_bytes(int n, int h, int w, int max_edges) {
+    if (n < 1 || max_edges < 4 || !mask_polygons_shape_ok(h, w, 0, 0)) return -1;
+    return (int64_t)mask_polygons_scratch_bytes(n, h, w, max_edges);
+}
+int64_t samrs_k_polygon_edge_stride(int h, int w, int max_edges) {
+    if (max_edges < 4 || !mask_polygons_shape_ok(h, w, 0, 0)) return -1;
+    return (int64_t)mask_polygons_edge_stride(h, w, max_edges);
+}
+int samrs_k_polygon_edges(const uint8_t* masks, int n, int h, int w, int max_edges, void* scratch, uint32_t* ids_out, int32_t* succ_out,
+                          uint8_t* corner_out, int32_t* counts_out, void* stream) {
+    KRET(launch_polygon_edges(masks, n, h, w, max_edges, scratch, ids_out, succ_out, corner_out, counts_out, (hipStream_t)stream));
+}
+int samrs_k_polygon_ranks(const uint8_t* masks, int n, int h, int w, int max_edges, void* scratch, int32_t* leader_out, int32_t* rank_out,
+                          int32_t* counts_out, void* stream) {
+    KRET(launch_polygon_ranks(masks, n, h, w, max_edges, scratch, leader_out, rank_out, counts_out, (hipStream_t)stream));
 }
 int samrs_k_gemm_gln(int prec, const void* A, const void* B, void* C, const float* bias, const float* gamma_beta, int M, int N,
                      int K, const void* A_lo, const void* B_lo, void* stream) {

@@ -310,3 +310,21 @@ hipError_t launch_score_masks(const float* low, int n, int in_h, int in_w, int o
 // samrs_filter_masks); masks uint8 [n][hw] of dropped rows are zeroed (16-byte stores when masks is 16-byte aligned and hw % 16 == 0)
 hipError_t launch_filter_masks(uint8_t* masks, int n, long hw, const long long* counts, const float* iou, float min_stability,
                                float min_pred_iou, float min_inside, uint8_t* keep, hipStream_t s);
+
+// ---- polygon_kernels.hip --------------------------------------------------------------------
+// Mask outlines as polygons on the pixel lattice (definition: the header comment of polygon_kernels.hip; contract: samrs_hip.h
+// samrs_mask_polygons).  One chunk of n <= 65535 masks per call; scratch: mask_polygons_scratch_bytes(n, h, w, max_edges).  The
+// per-edge arrays of a mask are mask_polygons_edge_stride(h, w, max_edges) = min(max_edges, 4 h w) entries apart.
+// launch_polygon_edges / launch_polygon_ranks: the stages alone -- ids_out uint32 / succ_out int32 / corner_out uint8 [n][stride]
+// (ascending edge ids, the successor's compact index, the corner flag), leader_out / rank_out int32 [n][stride], counts_out int32 [n]
+// = edges per mask; a mask over max_edges has its count and no entries.
+bool mask_polygons_shape_ok(int h, int w, int x0, int y0);
+long long mask_polygons_edge_stride(int h, int w, int max_edges);
+size_t mask_polygons_scratch_bytes(int n, int h, int w, int max_edges);
+hipError_t launch_mask_polygons(const uint8_t* masks, int n, int h, int w, int x0, int y0, int max_edges, void* scratch,
+                                int32_t* vertices, long long vertex_capacity, int32_t* rings, long long ring_capacity,
+                                long long* cursor, long long* table, hipStream_t s);
+hipError_t launch_polygon_edges(const uint8_t* masks, int n, int h, int w, int max_edges, void* scratch, uint32_t* ids_out,
+                                int32_t* succ_out, uint8_t* corner_out, int32_t* counts_out, hipStream_t s);
+hipError_t launch_polygon_ranks(const uint8_t* masks, int n, int h, int w, int max_edges, void* scratch, int32_t* leader_out,
+                                int32_t* rank_out, int32_t* counts_out, hipStream_t s);

@@ -332,6 +332,10 @@ class TileResult:
     # TilePipeline(quality=True) (samrs_score_masks / samrs_filter_masks; helpers in samrs_amd/quality.py):
     score_counts: Optional[np.ndarray] = None   # int64 [n_boxes, 4] pixels with logit > +1, > 0, > -1, and > 0 inside the prompt box
     kept: Optional[np.ndarray] = None       # bool [n_boxes] the instance passed the thresholds (all true without thresholds)
+    # polygons=True (samrs_mask_polygons; vertices are corners of the pixel lattice, in the image's / scene's own frame):
+    polygon_table: Optional[np.ndarray] = None      # int64 [n_boxes, 5] first ring, ring count, first vertex, vertex count, edge count
+    polygon_rings: Optional[np.ndarray] = None      # int32 [R, 4] the batch's ring records (the table's firsts index them)
+    polygon_vertices: Optional[np.ndarray] = None   # int32 [V, 2] the batch's vertices
     windows: Optional[List[Tuple[int, int, int, int]]] = None   # scene mode (scene.ScenePipeline): the planned (x0, y0, w, h) windows
     window_of: Optional[List[int]] = None   # scene mode: window_of[j] = index into `windows` of the window box j was decoded in
 
@@ -350,6 +354,13 @@ class TileResult:
         x0, y0, x1, y1 = (int(v) for v in self.mask_hbox[j])
         return [x0, y0, x1 - x0 + 1, y1 - y0 + 1]
 
+    def polygons(self, j: int) -> Optional[list]:
+        """Instance j's outline as a list of (int32 [k, 2] lattice vertices, is_hole), outer rings and holes in the library's order
+        (``samrs_amd.polygons.rings_of``; ``polygons.nest`` groups them); [] for an empty or dropped mask, None for a mask with more
+        edges than the pipeline's polygon_max_edges (not traced; polygon_table[j, 4] holds its edge count)."""
+        from .polygons import rings_of
+        return rings_of(self.polygon_table, self.polygon_rings, self.polygon_vertices, j)
+
     def rle(self, j: int) -> dict:
         """COCO RLE of instance j exactly as the reference stores it (main_sam_hbox_semantic.py:201-202):
         ``{"size": [H, W], "counts": str}``; encoded on the device (samrs_rle_encode)."""
@@ -367,7 +378,7 @@ class TileResult:
 
 class _OutBuf:
     def __init__(self, batch: int, side: int, max_boxes: int, rle: bool = False, png: bool = False, changed: bool = False,
-                 boxes: bool = False, quality: bool = False):
+                 boxes: bool = False, quality: bool = False, polygons: bool = False):
         self.seg = torch.empty(batch, side, side, dtype=torch.uint8).pin_memory()
         self.areas = torch.empty(batch, max_boxes, dtype=torch.int64).pin_memory()
         self.changed = torch.empty(batch, max_boxes, dtype=torch.int64).pin_memory() if changed else None
@@ -377,6 +388,11 @@ class _OutBuf:
         self.counts = torch.empty(batch, max_boxes, 4, dtype=torch.int64).pin_memory() if quality else None
         self.kept = torch.empty(batch, max_boxes, dtype=torch.uint8).pin_memory() if quality else None
         self.quality = torch.empty(batch, max_boxes, dtype=torch.float32).pin_memory() if quality else None
+        # polygons: per-box table, the cursor (vertices, rings used), and the batch's vertices and ring records (grown on demand)
+        self.poly_tab = torch.zeros(batch * max_boxes, 5, dtype=torch.int64).pin_memory() if polygons else None
+        self.poly_cur = torch.zeros(2, dtype=torch.int64).pin_memory() if polygons else None
+        self.poly_vert = torch.empty(1 << 16, 2, dtype=torch.int32).pin_memory() if polygons else None
+        self.poly_ring = torch.empty(1 << 14, 4, dtype=torch.int32).pin_memory() if polygons else None
         self.done = torch.cuda.Event()
         self.masks: List[Optional[torch.Tensor]] = [None] * batch     # keep_masks: host copies of the full masks
         self.odd: dict = {}                                           # tiles that are not side x side: their class maps
@@ -429,7 +445,8 @@ class TilePipeline:
                  rle_buffer_mb: int = 256, precision="auto", _multimask: bool = False, png_lut: Optional[np.ndarray] = None,
                  png_buffer_mb: Optional[int] = None, batch_decode: bool = False, min_region_area: int = 0,
                  region_mode: str = "both", mask_boxes: bool = False, quality: bool = False, min_stability: float = 0.0,
-                 min_pred_iou: float = 0.0, min_inside_box: float = 0.0):
+                 min_pred_iou: float = 0.0, min_inside_box: float = 0.0, polygons: bool = False, polygon_buffer_mb: int = 64,
+                 polygon_max_edges: int = 65536):
         """precision: the operand-split mode (engine option "split") THIS PIPELINE'S OWN CALLS run in.  The option is set around
         each of the pipeline's encode / decode calls and restored afterwards (``Engine.options``), so the mode never outlives
         them: a ``SamPredictor`` built on the same model keeps the engine's own default (round 3 changed the engine's option for
@@ -460,7 +477,14 @@ class TilePipeline:
         instances that fail it (``Engine.filter_masks``; the rule: ``quality.keep_rule``): a dropped mask is zeroed on the device
         before the clean-up, the mask boxes, the painting and the RLE encoding, so it paints nothing, has area 0, counts in no
         class statistic and ``kept`` is False for it.  Without a threshold every output but the three new fields is byte for byte
-        what quality=False gives.  quality=False with no threshold (default) launches and allocates nothing new."""
+        what quality=False gives.  quality=False with no threshold (default) launches and allocates nothing new.
+        polygons: trace, on the decode stream and from the masks as they go out (after the quality gate and the clean-up), each
+        mask's outline as polygons on the pixel lattice -- outer rings and holes (``Engine.mask_polygons``):
+        ``TileResult.polygons(j)`` / ``polygon_table`` / ``polygon_rings`` / ``polygon_vertices``.  A dropped or empty mask has no
+        rings.  `polygon_buffer_mb`: the device buffer for one batch's vertices and ring records (two of them; 12 bytes per vertex
+        with its share of ring records); a batch that overflows it raises, naming the option.  `polygon_max_edges`: a mask with
+        more crack edges is not traced and yields None.  Every other output is byte for byte what polygons=False gives, and
+        False (default) launches and allocates nothing."""
         from .transforms import ResizeLongestSide
         from .engine import REGION_MODES
         if int(min_region_area) < 0:
@@ -507,7 +531,7 @@ class TilePipeline:
         self.pin_in = None
         if not device_inputs:
             self.pin_in = [torch.empty(batch, side, side, 3, dtype=torch.uint8).pin_memory() for _ in range(2)]
-        if rle or self.png:
+        if rle or self.png or polygons:
             self.s_d2h = torch.cuda.Stream(dev)
         if rle:      # per input set: the batch's RLE strings (packed, 16-byte aligned), a cursor, (offset, length, n_counts) per box
             self.rle_dev = [torch.empty(rle_buffer_mb << 20, dtype=torch.uint8, device=dev) for _ in range(2)]
@@ -537,6 +561,16 @@ class TilePipeline:
             self.hbox_dev = [torch.zeros(batch, max_boxes, 4, dtype=torch.int32, device=dev) for _ in range(2)]
             self.rbox_dev = [torch.zeros(batch, max_boxes, 4, 2, dtype=torch.float32, device=dev) for _ in range(2)]
             self.rec_dev = [torch.zeros(batch, max_boxes, 8, dtype=torch.int64, device=dev) for _ in range(2)]
+        self.polygons = bool(polygons)
+        if self.polygons:
+            if int(polygon_buffer_mb) < 1 or int(polygon_max_edges) < 4:
+                raise ValueError("polygon_buffer_mb must be >= 1 and polygon_max_edges >= 4")
+            self.polygon_buffer_mb, self.polygon_max_edges = int(polygon_buffer_mb), int(polygon_max_edges)
+            nv = (self.polygon_buffer_mb << 20) // 12              # 8 bytes per vertex + 16 per ring, a ring has >= 4 vertices
+            self.poly_vert_dev = [torch.empty(nv, 2, dtype=torch.int32, device=dev) for _ in range(2)]
+            self.poly_ring_dev = [torch.empty(nv // 4, 4, dtype=torch.int32, device=dev) for _ in range(2)]
+            self.poly_cur = [torch.zeros(2, dtype=torch.int64, device=dev) for _ in range(2)]
+            self.poly_tab = [torch.zeros(batch * max_boxes, 5, dtype=torch.int64, device=dev) for _ in range(2)]
         if self.quality:
             self.cnt_dev = [torch.zeros(batch, max_boxes, 4, dtype=torch.int64, device=dev) for _ in range(2)]
             self.keep_dev = [torch.ones(batch, max_boxes, dtype=torch.uint8, device=dev) for _ in range(2)]
@@ -547,7 +581,8 @@ class TilePipeline:
         self.ev_in_free = [torch.cuda.Event() for _ in range(2)]     # encoder has consumed input set b
         self.free_out: "queue.Queue[_OutBuf]" = queue.Queue()
         for _ in range(out_depth):
-            self.free_out.put(_OutBuf(batch, side, max_boxes, rle, self.png, self.min_region_area > 0, self.mask_boxes, self.quality))
+            self.free_out.put(_OutBuf(batch, side, max_boxes, rle, self.png, self.min_region_area > 0, self.mask_boxes, self.quality,
+                                      self.polygons))
 
     @staticmethod
     def _choose_split(sam, precision, multimask: bool) -> Optional[int]:
@@ -675,6 +710,9 @@ class TilePipeline:
                                 changed_out=self.chg_dev[b][i, s:e])
             if self.mask_boxes:
                 eng.mask_boxes(masks[:, 0], (0, 0), self.hbox_dev[b][i, s:e], self.rbox_dev[b][i, s:e], self.rec_dev[b][i, s:e])
+            if self.polygons:                                                     # of the masks as they go out
+                eng.mask_polygons(masks[:, 0], (0, 0), self.polygon_max_edges, self.poly_vert_dev[b], self.poly_ring_dev[b],
+                                  self.poly_cur[b], self.poly_tab[b][off + s:off + e])
             eng.paint(masks[:, 0], self.dev_lab[b][off + s:off + e], seg, self.class_pixels, self.class_instances,
                       areas_out=self.area_dev[b][i, s:e])
             if self.rle:                                                          # :201-202, on the device
@@ -718,6 +756,8 @@ class TilePipeline:
                 self.rle_cur[b].zero_()
             if self.png:
                 self.png_cur[b].zero_()
+            if self.polygons:
+                self.poly_cur[b].zero_()
             with self._mode():
                 pre = self._decode_multi(b, tiles, offs) if self.batch_decode and sum(nb for _, nb in offs) else None
                 for i, ((t, hw), (off, nb)) in enumerate(zip(tiles, offs)):
@@ -735,6 +775,9 @@ class TilePipeline:
                 out.counts.copy_(self.cnt_dev[b], non_blocking=True)
                 out.kept.copy_(self.keep_dev[b], non_blocking=True)
                 out.quality.copy_(self.qual_dev[b], non_blocking=True)
+            if self.polygons:
+                out.poly_tab.copy_(self.poly_tab[b], non_blocking=True)
+                out.poly_cur.copy_(self.poly_cur[b], non_blocking=True)
             if self.rle:
                 out.rle_tab.copy_(self.rle_tab[b], non_blocking=True)
                 out.rle_cur.copy_(self.rle_cur[b], non_blocking=True)
@@ -780,6 +823,26 @@ class TilePipeline:
                                                  what="PNG buffer too small: a file", knob="png_buffer_mb")
         return tab.reshape(-1, 2, 2), out.png_bytes.numpy()
 
+    def _fetch_polygons(self, b: int, out: _OutBuf, n_boxes: int):
+        """The batch's polygons, fetched like the RLE strings: table + cursor on the host, then exact-size D2H of the vertices and
+        the ring records.  A mask that did not fit raises, naming polygon_buffer_mb; a mask over the edge cap stays (-1, -1)."""
+        tab = out.poly_tab[:n_boxes].numpy().copy()
+        nv, nr = int(out.poly_cur[0]), int(out.poly_cur[1])
+        if n_boxes and int(tab[:, 1].min()) < -1:
+            j = int(np.argmin(tab[:, 1]))
+            raise RuntimeError(f"polygon buffer too small: a mask needs {int(-tab[j, 3] - 1)} vertices and {int(-tab[j, 1] - 1)} rings and "
+                               f"the batch already holds {nv} and {nr}; raise polygon_buffer_mb (now {self.polygon_buffer_mb})")
+        if out.poly_vert.shape[0] < nv:
+            out.poly_vert = torch.empty(max(nv, 2 * out.poly_vert.shape[0]), 2, dtype=torch.int32).pin_memory()
+        if out.poly_ring.shape[0] < nr:
+            out.poly_ring = torch.empty(max(nr, 2 * out.poly_ring.shape[0]), 4, dtype=torch.int32).pin_memory()
+        if nv or nr:
+            with torch.cuda.stream(self.s_d2h):
+                out.poly_vert[:nv].copy_(self.poly_vert_dev[b][:nv], non_blocking=True)
+                out.poly_ring[:nr].copy_(self.poly_ring_dev[b][:nr], non_blocking=True)
+            self.s_d2h.synchronize()
+        return tab, out.poly_ring[:nr].numpy(), out.poly_vert[:nv].numpy()
+
     def _fetch_strings(self, dev: torch.Tensor, cur: torch.Tensor, tab_host: torch.Tensor, host: torch.Tensor, n_boxes: int,
                        what: str = "RLE buffer too small: a mask", knob: str = "rle_buffer_mb"):
         """(table, pinned host bytes) of one packed string buffer (samrs_rle_encode's layout); `host` grows when too small."""
@@ -808,6 +871,9 @@ class TilePipeline:
         ptab = pdat = None
         if self.png:
             ptab, pdat = self._fetch_png(b, out, len(items))
+        gtab = gring = gvert = None
+        if self.polygons:
+            gtab, gring, gvert = self._fetch_polygons(b, out, sum(nb for _, nb in offs))
         extra = self._fetch_extra(b, out, sum(nb for _, nb in offs))
         for i, (it, (off, nb)) in enumerate(zip(items, offs)):
             seg = (odd[i].numpy() if odd[i] is not None else None) if i in odd else out.seg[i].numpy()
@@ -827,6 +893,8 @@ class TilePipeline:
             if self.mask_boxes:
                 r.mask_hbox, r.mask_rbox = out.hbox[i, :nb].numpy().copy(), out.rbox[i, :nb].numpy().copy()
                 r.mask_record = out.record[i, :nb].numpy().copy()
+            if self.polygons:
+                r.polygon_table, r.polygon_rings, r.polygon_vertices = gtab[off:off + nb], gring, gvert
             if self.quality:
                 r.score_counts = out.counts[i, :nb].numpy().copy()
                 r.kept = out.kept[i, :nb].numpy().astype(bool)
@@ -924,6 +992,8 @@ class InstancePipeline(TilePipeline):
         self.fill_rule = transforms.resolve_fill_rule(fill_rule)       # prompt="rbox_mask": the cv2.fillPoly span rule to reproduce
         if kw.get("png_lut") is not None:
             raise ValueError("InstancePipeline paints no class map: png_lut is a TilePipeline option")
+        if kw.get("polygons"):
+            raise ValueError("InstancePipeline does not trace polygons: polygons is a TilePipeline / ScenePipeline option")
         super().__init__(sam, n_classes, precision=kw.pop("precision", "auto"), _multimask=bool(multimask), **kw)
         self.prompt, self.multimask = prompt, bool(multimask)
         self.qual_dev = [torch.zeros(self.batch, self.max_boxes, dtype=torch.float32, device=self.dev) for _ in range(2)]

@@ -119,6 +119,15 @@ def load_library() -> C.CDLL:
     lib.samrs_k_mask_hull.argtypes = [vp, ip, ip, ip, ip, ip, vp, vp, ip, vp, vp]
     for name in ("samrs_mask_boxes", "samrs_k_mask_row_extents", "samrs_k_mask_hull"):
         getattr(lib, name).restype = ip
+    lib.samrs_mask_polygons.argtypes = [vp, vp, ip, ip, ip, ip, ip, ip, vp, C.c_int64, vp, C.c_int64, vp, vp, vp]
+    lib.samrs_k_polygon_edges.argtypes = [vp, ip, ip, ip, ip, vp, vp, vp, vp, vp, vp]
+    lib.samrs_k_polygon_ranks.argtypes = [vp, ip, ip, ip, ip, vp, vp, vp, vp, vp]
+    lib.samrs_k_polygon_scratch_bytes.argtypes = [ip, ip, ip, ip]
+    lib.samrs_k_polygon_edge_stride.argtypes = [ip, ip, ip]
+    for name in ("samrs_mask_polygons", "samrs_k_polygon_edges", "samrs_k_polygon_ranks"):
+        getattr(lib, name).restype = ip
+    lib.samrs_k_polygon_scratch_bytes.restype = C.c_int64
+    lib.samrs_k_polygon_edge_stride.restype = C.c_int64
     lib.samrs_score_masks.argtypes = [vp, vp, ip, ip, ip, ip, ip, fp, vp, vp, vp]
     lib.samrs_filter_masks.argtypes = [vp, vp, ip, ip, ip, vp, vp, fp, fp, fp, vp, vp]
     for name in ("samrs_score_masks", "samrs_filter_masks"):
@@ -699,6 +708,47 @@ class Engine:
                                                       _ptr(outs[1]), _ptr(outs[2]), _stream()))
         return outs[0], outs[1], outs[2]
 
+    def mask_polygons(self, masks: torch.Tensor, offset: Sequence[int] = (0, 0), max_edges: int = 65536, vertices=None, rings=None,
+                      cursor=None, table=None):
+        """Each mask's outline as polygons, traced on the device (samrs_mask_polygons): masks [n, H, W] bool / uint8, contiguous,
+        decoded in a window whose origin is `offset` = (x0, y0) -> (vertices int32 [V, 2], rings int32 [R, 4], cursor int64 [2],
+        table int64 [n, 5]), all on the device.  Vertices are corners of the pixel LATTICE ((x, y) = the top-left corner of pixel
+        (row y, col x)), not the pixel centres of ``mask_boxes``: a polygon encloses exactly its pixels' squares.  A ring record is
+        (first vertex relative to the mask's first vertex, vertex count, twice the signed area: > 0 outer ring, < 0 hole, the pixel
+        index y * W + x of the ring's smallest edge); table[j] = (first ring, ring count, first vertex, vertex count, edge count) with
+        absolute firsts.  The masks are placed in order behind `cursor` (first free vertex, first free ring), which moves on: pass
+        the same `vertices`, `rings` and `cursor` again to append.  A mask that does not fit either buffer takes no space and has
+        firsts -1, ring count -1 - rings needed, vertex count -1 - vertices needed; a mask with more than `max_edges` edges is not
+        traced (ring count = vertex count = -1; the edge count is always true).  ``samrs_amd.polygons.rings_of`` reads the result on
+        the host.  Omitted buffers are allocated for the worst case (min(max_edges, 2 H W + 4) vertices and a quarter of that in rings
+        per mask: 24 bytes per edge of the cap), a fresh cursor is (0, 0).  Asynchronous on the current stream."""
+        m = self._masks_u8(masks)
+        n, h, w = m.shape
+        if int(max_edges) < 4:
+            raise ValueError(f"max_edges must be at least 4, got {max_edges}")
+        if vertices is None:
+            vertices = torch.empty(max(1, n) * min(int(max_edges), 2 * h * w + 4), 2, dtype=torch.int32, device=self.device)
+        if rings is None:
+            rings = torch.empty(max(1, n) * (min(int(max_edges), 2 * h * w + 4) // 4), 4, dtype=torch.int32, device=self.device)
+        if cursor is None:
+            cursor = torch.zeros(2, dtype=torch.int64, device=self.device)
+        if table is None:
+            table = torch.empty(n, 5, dtype=torch.int64, device=self.device)
+        for name, t, dt, last in (("vertices", vertices, torch.int32, 2), ("rings", rings, torch.int32, 4)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.is_cuda and t.is_contiguous() and t.dim() == 2 and t.shape[1] == last):
+                raise ValueError(f"{name} must be a contiguous {dt} [k, {last}] tensor on the engine's device")
+        if not (isinstance(cursor, torch.Tensor) and cursor.dtype == torch.int64 and cursor.is_cuda and cursor.is_contiguous() and cursor.numel() == 2):
+            raise ValueError("cursor must be a contiguous int64 [2] tensor on the engine's device")
+        if not (isinstance(table, torch.Tensor) and table.dtype == torch.int64 and table.is_cuda and table.is_contiguous()
+                and tuple(table.shape) == (n, 5)):
+            raise ValueError(f"table must be a contiguous int64 [{n}, 5] tensor on the engine's device")
+        if n:
+            with torch.cuda.device(self.device):
+                self._check(self.lib.samrs_mask_polygons(self.handle, m.data_ptr(), n, h, w, int(offset[0]), int(offset[1]), int(max_edges),
+                                                         vertices.data_ptr(), vertices.shape[0], rings.data_ptr(), rings.shape[0],
+                                                         cursor.data_ptr(), table.data_ptr(), _stream()))
+        return vertices, rings, cursor, table
+
     def score_masks(self, low: torch.Tensor, input_size: Sequence[int], original_size: Sequence[int], offset: float = 1.0,
                     boxes: Optional[torch.Tensor] = None, counts_out=None) -> torch.Tensor:
         """Threshold counts of every mask at the full output resolution, straight from the low-resolution logits
@@ -775,6 +825,31 @@ class Engine:
         with torch.cuda.device(self.device):
             self._check(self.lib.samrs_k_mask_row_extents(m.data_ptr(), n, h, w, out.data_ptr(), _stream()))
         return out
+
+    def polygon_stages(self, masks: torch.Tensor, max_edges: int = 65536):
+        """Test hook (samrs_k_polygon_edges, samrs_k_polygon_ranks): the stages of ``mask_polygons`` alone, for one chunk of masks ->
+        (counts int32 [n] = edges per mask, ids uint32-as-int64 [n, stride], succ int32 [n, stride], corner uint8 [n, stride],
+        leader int32 [n, stride], rank int32 [n, stride]) with stride = min(max_edges, 4 H W); only the first counts[j] entries of mask
+        j mean anything, and none where counts[j] > max_edges."""
+        m = self._masks_u8(masks)
+        n, h, w = m.shape
+        stride = int(self.lib.samrs_k_polygon_edge_stride(h, w, int(max_edges)))
+        nbytes = int(self.lib.samrs_k_polygon_scratch_bytes(n, h, w, int(max_edges)))
+        if stride < 0 or nbytes < 0:
+            raise ValueError(f"{n} masks of {h} x {w} with max_edges {max_edges}: outside the limits of samrs_mask_polygons")
+        dev = self.device
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ids = torch.zeros(n, stride, dtype=torch.int32, device=dev)
+        succ, leader, rank = (torch.zeros(n, stride, dtype=torch.int32, device=dev) for _ in range(3))
+        corner = torch.zeros(n, stride, dtype=torch.uint8, device=dev)
+        counts, counts2 = (torch.zeros(n, dtype=torch.int32, device=dev) for _ in range(2))
+        with torch.cuda.device(dev):
+            self._check(self.lib.samrs_k_polygon_edges(m.data_ptr(), n, h, w, int(max_edges), scratch.data_ptr(), ids.data_ptr(),
+                                                       succ.data_ptr(), corner.data_ptr(), counts.data_ptr(), _stream()))
+            self._check(self.lib.samrs_k_polygon_ranks(m.data_ptr(), n, h, w, int(max_edges), scratch.data_ptr(), leader.data_ptr(),
+                                                       rank.data_ptr(), counts2.data_ptr(), _stream()))
+        assert torch.equal(counts, counts2)
+        return counts, ids.to(torch.int64) & 0xFFFFFFFF, succ, corner, leader, rank
 
     def mask_hull(self, masks: torch.Tensor, offset: Sequence[int] = (0, 0), cap: int = 2048):
         """Test hook (samrs_k_mask_hull): (vertices int32 [n, cap, 2], counts int32 [n]): the ordered strict hull vertices (x, y) of

@@ -60,7 +60,8 @@ def write_outputs(out_dir: str, stem: str, seg: np.ndarray, masks: Optional[np.n
                   labels: np.ndarray, areas: np.ndarray, palette: np.ndarray, class_names: Sequence[str],
                   rles: Optional[Sequence[dict]] = None, clock: Optional[StageClock] = None, png_level: int = tile_io.LEVEL_LABELS,
                   png_files: Optional[Tuple[bytes, bytes]] = None, mask_bboxes: Optional[Sequence] = None,
-                  mask_rboxes: Optional[Sequence] = None, dota_txt: bool = False, scores: Optional[dict] = None) -> None:
+                  mask_rboxes: Optional[Sequence] = None, dota_txt: bool = False, scores: Optional[dict] = None,
+                  polygons: Optional[Sequence] = None) -> None:
     """`rles`: the per-instance COCO RLE dicts when they were encoded on the device (driver.TileResult.rle); otherwise they are
     encoded here from `masks` (host restatement), or left out when both are None (--no-rle).  `png_files`: the complete
     (gray, color) PNG files when they were encoded on the device (--png-device: driver.TileResult.png, byte-identical with the
@@ -70,7 +71,9 @@ def write_outputs(out_dir: str, stem: str, seg: np.ndarray, masks: Optional[np.n
     ``"mask_bbox"`` / ``"mask_rbox"``.  `dota_txt` (--dota-txt): also ``rbox/<stem>.txt``, one DOTA line per non-empty instance.
     `scores` (--quality): per-instance arrays "pred_iou", "stability", "inside_box" -- they become float pickle entries of those
     names -- and "kept" (bool): an instance that failed a threshold gets no pickle entry (its mask was zeroed on the device, so it
-    painted nothing and, being empty, has no DOTA line either)."""
+    painted nothing and, being empty, has no DOTA line either).  `polygons` (--polygons): per instance the rings of its outline as
+    (int32 [k, 2] lattice vertices, is_hole) pairs (driver.TileResult.polygons), or None for a mask over the edge cap; they become
+    the pickle entries' ``"polygons"`` (the list of vertex arrays, or None) and ``"polygon_holes"`` (the list of bool, or None)."""
     import time
     t0 = time.perf_counter()
     for sub in ("gray", "color", "ins"):
@@ -109,6 +112,10 @@ def write_outputs(out_dir: str, stem: str, seg: np.ndarray, masks: Optional[np.n
             entry["mask"] = rle.encode(masks[j])
         if mask_bboxes is not None:
             entry["mask_bbox"], entry["mask_rbox"] = mask_bboxes[j], mask_rboxes[j]
+        if polygons is not None:
+            pl = polygons[j]
+            entry["polygons"] = None if pl is None else [np.array(p[0], dtype=np.int32) for p in pl]
+            entry["polygon_holes"] = None if pl is None else [bool(p[1]) for p in pl]
         info.append(entry)
     if dota_txt:
         # before the pickle, whose presence says "this image is complete" (--resume)
@@ -323,6 +330,10 @@ def run(args) -> Dict[str, List[int]]:
     # threshold, the doubtful ones zeroed there before they are painted (samrs_filter_masks)
     thresholds = {k: float(getattr(args, k, 0.0) or 0.0) for k in ("min_stability", "min_pred_iou", "min_inside_box")}
     want_quality = bool(getattr(args, "quality", False)) or any(t > 0 for t in thresholds.values())
+    # --polygons: each mask's outline traced to polygons on the device (samrs_mask_polygons): outer rings and holes on the pixel lattice
+    want_polygons = bool(getattr(args, "polygons", False))
+    poly_kw = dict(polygons=True, polygon_buffer_mb=int(getattr(args, "polygon_buffer_mb", 64) or 64),
+                   polygon_max_edges=int(getattr(args, "polygon_max_edges", 65536) or 65536)) if want_polygons else {}
     if scene_window > 0:
         from . import scene
         pipe = scene.ScenePipeline(sam, n_classes, window=scene_window, overlap=getattr(args, "scene_overlap", 256),
@@ -330,7 +341,7 @@ def run(args) -> Dict[str, List[int]]:
                                    rle=not args.no_rle, rle_buffer_mb=getattr(args, "rle_buffer_mb", 256),
                                    png_lut=tile_io.class_lut(palette) if png_device else None,
                                    min_region_area=min_region_area, region_mode=getattr(args, "region_mode", "both"),
-                                   mask_boxes=mask_boxes, quality=want_quality, **thresholds)     # refused there, by name
+                                   mask_boxes=mask_boxes, quality=want_quality, **thresholds, **poly_kw)     # quality: refused there, by name
     else:
         pipe = driver.TilePipeline(sam, n_classes, batch=batch, box_batch=args.box_batch, rle=not args.no_rle,
                                    rle_buffer_mb=getattr(args, "rle_buffer_mb", 256), max_boxes=max_boxes,
@@ -338,7 +349,7 @@ def run(args) -> Dict[str, List[int]]:
                                    png_buffer_mb=getattr(args, "png_buffer_mb", None),
                                    batch_decode=bool(getattr(args, "batch_decode", False)),
                                    min_region_area=min_region_area, region_mode=getattr(args, "region_mode", "both"),
-                                   mask_boxes=mask_boxes, quality=want_quality, **thresholds)
+                                   mask_boxes=mask_boxes, quality=want_quality, **thresholds, **poly_kw)
     # rank r takes chunks of `batch` consecutive stems: statically (r, r + world, ...) or from the shared counter (whose
     # store key must be unique per work list: a second run() in the same process group must not find a spent counter)
     import zlib
@@ -440,8 +451,9 @@ def run(args) -> Dict[str, List[int]]:
                 if r.score_counts is not None:
                     scores = {"pred_iou": r.quality, "stability": quality.stability(r.score_counts),
                               "inside_box": quality.inside_fraction(r.score_counts), "kept": r.kept}
+                polys = [r.polygons(j) for j in range(len(r.labels))] if r.polygon_table is not None else None
                 write_outputs(args.out, r.key, r.seg_mask, None, r.boxes, r.labels, r.areas, palette, names, rles, clock, png_level, files,
-                              bbs, rbs, dota_txt, scores)
+                              bbs, rbs, dota_txt, scores, polys)
             finally:
                 with lock:
                     left[0] -= 1
@@ -457,6 +469,8 @@ def run(args) -> Dict[str, List[int]]:
             if want_quality:                                     # per image: instances that failed a threshold and were left unlabeled
                 line["dropped"] = [int((~r.kept).sum()) for r in results]
                 line["dropped_total"] = dropped[0] + sum(line["dropped"])
+            if want_polygons:                                    # per image: masks with more edges than --polygon-max-edges (no polygons)
+                line["polygons_over_cap"] = [int((r.polygon_table[:, 1] == -1).sum()) for r in results]
             run_log.write(json.dumps(line) + "\n")
             run_log.flush()
         for r in results:
@@ -628,6 +642,14 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--dota-txt", action="store_true",
                     help="also write rbox/<stem>.txt, one line per non-empty instance in DOTA's oriented-box form "
                          "'x1 y1 x2 y2 x3 y3 x4 y4 category label' (coordinates %%.1f); implies --mask-boxes")
+    ap.add_argument("--polygons", action="store_true",
+                    help="trace each mask's outline to polygons on the GPU (outer rings and holes, vertices on the pixel lattice): the "
+                         "ins/<stem>.pkl entries gain 'polygons' (a list of int32 [k, 2] arrays, or None for a mask over "
+                         "--polygon-max-edges) and 'polygon_holes' (a list of bool)")
+    ap.add_argument("--polygon-buffer-mb", type=int, default=64, metavar="N",
+                    help="device buffer for one batch's (one scene's) polygon vertices and ring records (default 64)")
+    ap.add_argument("--polygon-max-edges", type=int, default=65536, metavar="E",
+                    help="masks with more boundary edges than this are not traced (default 65536; counted in the --log lines)")
     return ap
 
 

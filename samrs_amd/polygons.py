@@ -1,0 +1,97 @@
+"""Reading the result of ``Engine.mask_polygons`` (samrs_mask_polygons) on the host: numpy only.
+
+Vertices are corners of the pixel lattice: (x, y) is the top-left corner of pixel (row y, col x), so a ring encloses exactly the squares
+of its pixels.  Outer rings have a positive signed area (clockwise on screen, y down), holes a negative one."""
+from __future__ import annotations
+
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+
+Ring = Tuple[np.ndarray, bool]
+
+
+def _np(t) -> np.ndarray:
+    return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+
+
+def rings_of(table, rings, vertices, j: int) -> Optional[List[Ring]]:
+    """The rings of mask `j` as a list of (int32 [k, 2] vertices, is_hole), in the order the library wrote them (ascending smallest
+    edge).  None when the mask was not traced or placed (a negative ring count: over the edge cap, or a full buffer)."""
+    t = _np(table)[j]
+    first_ring, n_rings, first_vertex = int(t[0]), int(t[1]), int(t[2])
+    if n_rings < 0:
+        return None
+    rec = _np(rings)[first_ring:first_ring + n_rings]
+    v = _np(vertices)
+    out = []
+    for r in rec:
+        a = first_vertex + int(r[0])
+        out.append((np.ascontiguousarray(v[a:a + int(r[1])], dtype=np.int32), bool(r[2] < 0)))
+    return out
+
+
+def hole_pixel(pts: np.ndarray) -> Tuple[int, int]:
+    """(x, y) of the pixel a hole's ring record names -- the pixel that owns the ring's smallest edge --, in the vertices' frame: the
+    ring's topmost lattice line carries only bottom edges, of pixels in the row above it, and the smallest of them is the leftmost.
+    A set pixel of the component the hole lies in."""
+    p = np.asarray(pts, np.int64)
+    top = p[:, 1].min()
+    return int(p[p[:, 1] == top, 0].min()), int(top) - 1
+
+
+def signed_area2(pts: np.ndarray) -> int:
+    """twice the signed shoelace area of a closed ring [k, 2] (positive: an outer ring of this library)"""
+    p = np.asarray(pts, np.int64)
+    q = np.roll(p, -1, axis=0)
+    return int((p[:, 0] * q[:, 1] - q[:, 0] * p[:, 1]).sum())
+
+
+def _contains(pts: np.ndarray, x2: int, y2: int) -> bool:
+    """even-odd: is the point (x2 / 2, y2 / 2) -- a pixel centre, never on a lattice line -- inside the rectilinear ring"""
+    p = np.asarray(pts, np.int64) * 2
+    q = np.roll(p, -1, axis=0)
+    vert = p[:, 0] == q[:, 0]                                      # vertical edges cross the horizontal ray to the right
+    lo = np.minimum(p[:, 1], q[:, 1])
+    hi = np.maximum(p[:, 1], q[:, 1])
+    return bool((vert & (p[:, 0] > x2) & (lo < y2) & (y2 < hi)).sum() & 1)
+
+
+def nest(rings_list: Sequence[Ring]) -> List[Tuple[np.ndarray, List[np.ndarray]]]:
+    """[(outer, [holes])] from ``rings_of``, the outer rings in their order.  A hole's parent is the smallest-area outer ring that
+    contains the centre of the pixel recorded in the hole's ring record (``hole_pixel`` finds the same pixel from the vertices): a set
+    pixel of the component the hole lies in.  What GeoJSON / labelme writers need."""
+    outers = [(r[0], []) for r in rings_list if not r[1]]
+    areas = [signed_area2(o[0]) for o in outers]
+    for r in rings_list:
+        if not r[1]:
+            continue
+        x, y = hole_pixel(r[0])
+        best = None
+        for k, (o, _) in enumerate(outers):
+            if _contains(o, 2 * x + 1, 2 * y + 1) and (best is None or areas[k] < areas[best]):
+                best = k
+        if best is None:
+            raise ValueError("a hole lies in no outer ring: the rings are not those of one mask")
+        outers[best][1].append(r[0])
+    return outers
+
+
+def coco_segmentation(rings_list: Sequence) -> Tuple[List[List[int]], bool]:
+    """(polygons, has_holes): the OUTER rings as COCO flat [x0, y0, x1, y1, ...] lists.  COCO's polygon form cannot carry holes, so
+    the holes are DROPPED here and `has_holes` says whether there were any; use the RLE form where they matter."""
+    polys = [[int(c) for c in r[0].reshape(-1)] for r in rings_list if not r[1]]
+    return polys, any(r[1] for r in rings_list)
+
+
+def rasterize(rings_list: Sequence, h: int, w: int, origin: Sequence[int] = (0, 0)) -> np.ndarray:
+    """uint8 [h, w]: the even-odd fill of the rings -- the inverse of the tracing.  Every vertical ring edge toggles the pixels to its
+    right in the rows it spans."""
+    d = np.zeros((h, w + 1), np.int32)
+    for r in rings_list:
+        p = np.asarray(r[0], np.int64) - np.asarray(origin, np.int64)
+        q = np.roll(p, -1, axis=0)
+        for (xa, ya), (xb, yb) in zip(p.tolist(), q.tolist()):
+            if xa == xb and ya != yb:
+                d[min(ya, yb):max(ya, yb), xa] += 1
+    return (np.cumsum(d, axis=1)[:, :w] & 1).astype(np.uint8)

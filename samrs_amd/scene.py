@@ -109,12 +109,16 @@ class ScenePipeline:
     decoder call).  A scene no larger than `window` is one window, and every
     output equals ``TilePipeline``'s for the same item byte for byte.  `mask_boxes`: each mask's tight hbox, minimum-area rotated
     box and record (``Engine.mask_boxes``) with its window's origin as the offset, so they are in the scene's frame, exactly:
-    ``TileResult.mask_hbox`` / ``mask_rbox`` / ``mask_record``; off (default) launches and allocates nothing."""
+    ``TileResult.mask_hbox`` / ``mask_rbox`` / ``mask_record``; off (default) launches and allocates nothing.  `polygons`: each
+    mask's outline as polygons on the pixel lattice (``Engine.mask_polygons``), again with the window's origin as the offset, so the
+    vertices are in the scene's frame exactly: ``TileResult.polygons(j)``; `polygon_buffer_mb` holds one scene's vertices and ring
+    records (an overflow raises, naming it), a mask over `polygon_max_edges` edges yields None; off launches and allocates nothing."""
 
     def __init__(self, sam, n_classes: int, window: int = 1024, overlap: int = 256, context: float = 2.0, batch: int = 8,
                  box_batch: int = 64, rle: bool = False, png_lut: Optional[np.ndarray] = None, min_region_area: int = 0,
                  region_mode: str = "both", precision="auto", rle_buffer_mb: int = 256, mask_boxes: bool = False,
-                 quality: bool = False, min_stability: float = 0.0, min_pred_iou: float = 0.0, min_inside_box: float = 0.0):
+                 quality: bool = False, min_stability: float = 0.0, min_pred_iou: float = 0.0, min_inside_box: float = 0.0,
+                 polygons: bool = False, polygon_buffer_mb: int = 64, polygon_max_edges: int = 65536):
         import torch
         from .driver import TilePipeline, refuse_quality_options
         refuse_quality_options("ScenePipeline", "scoring across scene windows is not built", quality=quality,
@@ -139,6 +143,14 @@ class ScenePipeline:
         self.batch, self.box_batch, self.rle = int(batch), int(box_batch), bool(rle)
         self.min_region_area, self.region_mode = int(min_region_area), region_mode
         self.mask_boxes = bool(mask_boxes)
+        self.polygons = bool(polygons)
+        if self.polygons:
+            if int(polygon_buffer_mb) < 1 or int(polygon_max_edges) < 4:
+                raise ValueError("polygon_buffer_mb must be >= 1 and polygon_max_edges >= 4")
+            self.polygon_buffer_mb, self.polygon_max_edges = int(polygon_buffer_mb), int(polygon_max_edges)
+            nv = (self.polygon_buffer_mb << 20) // 12              # 8 bytes per vertex + 16 per ring, a ring has >= 4 vertices
+            self.poly_vert_dev = torch.empty(nv, 2, dtype=torch.int32, device=eng.device)
+            self.poly_ring_dev = torch.empty(nv // 4, 4, dtype=torch.int32, device=eng.device)
         # the operand-split mode of this pipeline's own calls: TilePipeline's rule and TilePipeline's scoping
         self.split_mode = TilePipeline._choose_split(sam, precision, multimask=False)
         self.allow_reduced = False
@@ -232,6 +244,9 @@ class ScenePipeline:
             w_hbox = torch.zeros(n, 4, dtype=torch.int32, device=dev)
             w_rbox = torch.zeros(n, 4, 2, dtype=torch.float32, device=dev)
             w_rec = torch.zeros(n, 8, dtype=torch.int64, device=dev)
+        if self.polygons:
+            w_ptab = torch.zeros(n, 5, dtype=torch.int64, device=dev)
+            poly_cur = torch.zeros(2, dtype=torch.int64, device=dev)
         if self.rle:
             w_tab = torch.zeros(n, 3, dtype=torch.int64, device=dev)
             rle_cur = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -273,6 +288,9 @@ class ScenePipeline:
                         eng.clean_masks(m, self.min_region_area, self.region_mode, areas_out=False, changed_out=w_changed[s:e])
                     if self.mask_boxes:                                           # in the scene's frame: the window's origin
                         eng.mask_boxes(m, (x0, y0), w_hbox[s:e], w_rbox[s:e], w_rec[s:e])
+                    if self.polygons:                                             # lattice vertices in the scene's frame
+                        eng.mask_polygons(m, (x0, y0), self.polygon_max_edges, self.poly_vert_dev, self.poly_ring_dev, poly_cur,
+                                          w_ptab[s:e])
                     eng.scene_claim(m, w_rank[s:e], win, order, w_lab[s:e], self.class_pixels, self.class_instances,
                                     areas_out=w_areas[s:e])
                     if self.rle:
@@ -309,6 +327,15 @@ class ScenePipeline:
         if self.mask_boxes:
             r.mask_hbox, r.mask_rbox = unpermute(w_hbox.cpu().numpy()), unpermute(w_rbox.cpu().numpy())
             r.mask_record = unpermute(w_rec.cpu().numpy())
+        if self.polygons:
+            ptab = unpermute(w_ptab.cpu().numpy())
+            nv, nr = (int(v) for v in poly_cur.cpu().tolist())
+            if n and int(ptab[:, 1].min()) < -1:
+                j = int(np.argmin(ptab[:, 1]))
+                raise RuntimeError(f"polygon buffer too small: a mask needs {int(-ptab[j, 3] - 1)} vertices and {int(-ptab[j, 1] - 1)} "
+                                   f"rings and the scene already holds {nv} and {nr}; raise polygon_buffer_mb (now {self.polygon_buffer_mb})")
+            r.polygon_table = ptab
+            r.polygon_rings, r.polygon_vertices = self.poly_ring_dev[:nr].cpu().numpy(), self.poly_vert_dev[:nv].cpu().numpy()
         if self.rle:
             tab = unpermute(w_tab.cpu().numpy())
             total = int(rle_cur.item())
