@@ -62,7 +62,9 @@ typedef struct samrs_config {
     int32_t window_size;             /* 14                                                    */
     int32_t out_chans;               /* 256 (== prompt / decoder width)                       */
     int32_t max_images;              /* encoder batch == number of embedding slots            */
-    int32_t max_prompts;             /* prompts (boxes) decoded per pass: workspace size      */
+    int32_t max_prompts;             /* prompts (boxes) of one samrs_predict pass; the decoder
+                                        workspaces hold this many unless option "decode_prompts"
+                                        raises it                                             */
     int32_t max_points;              /* max points per prompt                                 */
     int32_t precision;               /* enum samrs_precision                                  */
 } samrs_config;
@@ -155,8 +157,8 @@ int samrs_predict(samrs_engine_t* e, int slot, int n_prompts,
  *                 NULL (the array or an entry) to skip
  *  iou_out [total, C] / lowres_out [total, C, 256, 256]: contiguous over all prompts of the call, or NULL
  * Validation is that of samrs_predict for every image (SAMRS_ERR_NOT_SET names the slot; the multimask grade is checked per
- * slot).  Calls larger than max_prompts run as consecutive chunks that may cross image boundaries; every output byte equals
- * what samrs_predict(slots[i], ...) gives for image i alone. */
+ * slot).  One chain holds option "decode_prompts" prompts (default: max_prompts); larger calls run as consecutive chunks of that
+ * size that may cross image boundaries; every output byte equals what samrs_predict(slots[i], ...) gives for image i alone. */
 int samrs_predict_multi(samrs_engine_t* e, int n_images, const int* slots, const int* prompt_offsets,
                         const float* boxes, const float* point_coords, const int32_t* point_labels, int n_points,
                         const float* mask_input, int multimask, int return_logits,
@@ -387,6 +389,20 @@ int samrs_resample_pass_u8(const uint8_t* in, uint8_t* out, const int32_t* bound
  *                    GEMMs.  Measured slower on MI355X.  Must be on before samrs_finalize_weights for the folded weights to
  *                    exist; can be flipped afterwards.
  *   "gemm_variant"   [default -1 = automatic] GEMM tile variant for this handle's launches (tools/gemm_bench.py lists them).
+ *   "decode_prompts" [default max_prompts] prompts ONE decoder chain of samrs_predict_multi may hold: every per-prompt decoder workspace
+ *                    is sized by it.  Accepted: max_prompts <= value <= min(max_images x max_prompts, 512), anything else is
+ *                    SAMRS_ERR_BAD_ARG.  512 is what the index types carry: up to there every element index and byte offset of a chain
+ *                    stays below 2^31 (n x 4096 x 384 key-projection elements pass it at n = 1366, n x 2^22 bytes of fp32 keys at 512).
+ *                    Set before samrs_finalize_weights it sizes the first allocation; set later it reallocates the workspaces at
+ *                    once, on the calling thread: the device is synchronised before a replaced buffer is released, an allocation
+ *                    that fails leaves the engine as it was (SAMRS_ERR_HIP), and no chain may be running on another thread.  The
+ *                    workspaces never shrink; a lower value only shortens the chains.  Memory per prompt at 16 tokens x 4096 x
+ *                    256: 12 bytes per key element (fp32 keys 4, operand keys 2, their split remainder 2, projections 3, attention
+ *                    output 1) = 12.6 MB, 0.8 MB of low-res logits, 0.2 MB on the token side: 13.5 MB, 3.5 GB at 256 prompts.  A
+ *                    mask prompt adds 4.2 MB per prompt, the upscaler forms other than the one-kernel one 10.5 MB (first use).
+ *                    samrs_predict is not affected: it decodes max_prompts per pass, as it always did.  Results do not depend on
+ *                    the chain length, bit for bit.
+ *   "decode_kbytes"  read-only: KiB of per-prompt decoder workspace allocated now (the byte count does not fit an int).
  *   "upscaler_fused" [SAMRS_UPSCALER_FUSED, default 1] 1 = the mask upscaler as ONE kernel (samrs_k_upscaler_fused); 0 = ConvT #1 as a GEMM with a
  *                    LayerNorm2d + GELU epilogue, then the ConvT #2 + GELU + product kernel (A/B runs, tests).
  *   "split_passes"   [SAMRS_SPLIT_PASSES, default 0] reference-grade bits of "split" only: 1 = the three terms of a split block GEMM as

@@ -227,6 +227,11 @@ struct samrs_engine {
     float *K0F = nullptr;          // layer-0 keys fp32 [max_images][tokens][C]
     uint16_t* K0E = nullptr;       // ... in the operand type
     uint16_t* KVQ0 = nullptr;      // their K_t2i | V_t2i | Q_i2t projections [max_images][tokens][3 C / 2]
+    // The per-prompt workspaces (the token buffers above included) hold decode_alloc prompts: Bb below.  They are listed once, in
+    // decode_buffers(), and allocated / grown by grow_decode_workspaces() only.
+    int decode_prompts = 0;        // option "decode_prompts": prompts one decoder chain may hold (samrs_create: max_prompts)
+    int decode_alloc = 0;          // prompts the workspaces hold now: the largest decode_prompts so far (they never shrink)
+    size_t decode_bytes = 0;       // bytes of the per-prompt workspaces allocated now (option "decode_kbytes")
     float* KF = nullptr;           // per-prompt keys fp32 [Bb*tokens][C]
     uint16_t* KE = nullptr;
     uint16_t* KE_lo = nullptr;     // split remainder of the final keys (operand of the first transposed conv)
@@ -234,7 +239,7 @@ struct samrs_engine {
     int* SLOT_OF = nullptr;        // [Bb] slot of every prompt of a chunk that spans several images (samrs_predict_multi; first use)
     uint16_t* KVQ = nullptr;       // [Bb*tokens][384]
     uint16_t* OI = nullptr;        // [Bb*tokens][128]
-    float* U1raw = nullptr;        // [Bb*tokens][256]
+    float* U1raw = nullptr;        // [Bb*tokens][256]      U1raw / U1 / U2: the upscaler forms other than ONE_KERNEL; first use
     uint16_t* U1 = nullptr;        // [Bb*tokens][256]
     uint16_t* U2 = nullptr;        // [Bb*tokens*4][128]
     float *HY1 = nullptr, *HY2 = nullptr, *HYPER = nullptr, *IOU = nullptr, *LOW = nullptr;
@@ -585,6 +590,7 @@ samrs_engine_t* samrs_create(const samrs_config* cfg, int device, char* err, int
     e->hd = hd;
     e->nwin = (e->grid + cfg->window_size - 1) / cfg->window_size;
     e->T_max = 5 + cfg->max_points + 1 + 2;
+    e->decode_prompts = cfg->max_prompts;
     e->slot_set.assign(cfg->max_images, 0);
     e->slot_split.assign(cfg->max_images, 0);
     e->slot_depth.assign(cfg->max_images, 0);
@@ -675,6 +681,97 @@ int samrs_load_weight(samrs_engine_t* e, const char* name, const float* host, co
 }
 
 static void audit_build_sites(samrs_engine_t* e);      // the checkpoint audit's site table (defined with the audit helpers below)
+
+// ---- the per-prompt decoder workspaces ------------------------------------------------------------------------------------------------
+// Every buffer of the decoder pass whose size is a number of prompts, with its bytes per prompt, listed ONCE: samrs_finalize_weights
+// (capacity = max_prompts unless option "decode_prompts" was set before it) and a later growth of "decode_prompts" both go through
+// grow_decode_workspaces, so the two cannot drift apart.  `lazy`: allocated by the first pass that needs the buffer (need_decode_buffer),
+// at the capacity of that moment, and grown with the others from then on.
+// The largest element index on the pass is KVQ's n x 4096 x 384 (U2: n x 2^21), the largest byte offset n x 2^22 (KF, U1raw, U2):
+// up to DECODE_PROMPTS_LIMIT prompts every index AND byte offset of a chain stays below 2^31, whatever type a kernel counts in;
+// every launcher's blockIdx.y = n stays far below 65536.
+constexpr int DECODE_PROMPTS_LIMIT = 512;
+
+struct DecodeBuf {
+    const char* name;
+    size_t per_prompt;             // bytes
+    bool lazy;
+    void* (*get)(const samrs_engine_t*);
+    void (*set)(samrs_engine_t*, void*);
+};
+#define DECODE_BUF(field, elems, lazy)                                                             \
+    DecodeBuf{#field, sizeof(*static_cast<samrs_engine_t*>(nullptr)->field) * (size_t)(elems), lazy, \
+              [](const samrs_engine_t* e) -> void* { return e->field; },                           \
+              [](samrs_engine_t* e, void* p) { e->field = static_cast<decltype(e->field)>(p); }}
+
+static std::vector<DecodeBuf> decode_buffers(const samrs_engine_t* e) {
+    const size_t T = (size_t)e->T_max, tokens = (size_t)e->tokens, C = (size_t)e->C, Ci = C / 2;
+    return {
+        // token side: [Bb * T_max] rows
+        DECODE_BUF(TOK0, T * C, false), DECODE_BUF(Q, T * C, false), DECODE_BUF(TA, T * C, false), DECODE_BUF(TQ, T * C, false),
+        DECODE_BUF(TK, T * C, false), DECODE_BUF(TV, T * C, false), DECODE_BUF(TO, T * C, false), DECODE_BUF(MH, T * 2048, false),
+        DECODE_BUF(QP, T * Ci, false), DECODE_BUF(KT, T * Ci, false), DECODE_BUF(VT, T * Ci, false), DECODE_BUF(O128, T * Ci, false),
+        DECODE_BUF(T2IW, t2i_workspace_floats(1, e->T_max), false),        // linear in the prompt count (T2I_MAX_SPLITS partial states each)
+        // image side: [Bb * tokens] rows
+        DECODE_BUF(KF, tokens * C, false), DECODE_BUF(KE, tokens * C, false), DECODE_BUF(KE_lo, tokens * C, false),
+        DECODE_BUF(KVQ, tokens * 3 * Ci, false), DECODE_BUF(OI, tokens * Ci, false),
+        DECODE_BUF(DENSE, tokens * C, true), DECODE_BUF(SLOT_OF, 1, true),
+        DECODE_BUF(U1raw, tokens * C, true), DECODE_BUF(U1, tokens * C, true), DECODE_BUF(U2, tokens * 4 * Ci, true),
+        // heads and outputs
+        DECODE_BUF(HY1, 5 * C, false), DECODE_BUF(HY2, 5 * C, false), DECODE_BUF(HYPER, 4 * (C / 8), false), DECODE_BUF(IOU, 4, false),
+        DECODE_BUF(LOW, 3 * 256 * 256, false),
+    };
+}
+#undef DECODE_BUF
+
+// The buffers hold at least `cap` prompts afterwards.  Contents are not carried over: everything listed is scratch of one chain.  No
+// chain may be running on another host thread (an engine is driven by one thread at a time).  Old buffers are released only after
+// every stream of the device has drained -- the chains that used them may have run on any -- and a failed allocation leaves the
+// engine as it was.  Never shrinks.
+static int grow_decode_workspaces(samrs_engine_t* e, int cap) {
+    if (cap <= e->decode_alloc) return SAMRS_OK;
+    const std::vector<DecodeBuf> bufs = decode_buffers(e);
+    std::vector<void*> fresh(bufs.size(), nullptr);
+    size_t bytes = 0;
+    for (size_t i = 0; i < bufs.size(); ++i) {
+        if (bufs[i].lazy && !bufs[i].get(e)) continue;
+        const hipError_t r = hipMalloc(&fresh[i], bufs[i].per_prompt * (size_t)cap);
+        if (r != hipSuccess) {
+            for (void* p : fresh) if (p) (void)hipFree(p);
+            return fail(e, SAMRS_ERR_HIP, "decoder workspaces for %d prompts: %s (%zu bytes for %s)", cap, hipGetErrorString(r),
+                        bufs[i].per_prompt * (size_t)cap, bufs[i].name);
+        }
+        bytes += bufs[i].per_prompt * (size_t)cap;
+    }
+    if (e->decode_alloc > 0) CK(e, hipDeviceSynchronize());
+    for (size_t i = 0; i < bufs.size(); ++i) {
+        if (!fresh[i]) continue;
+        if (void* old = bufs[i].get(e)) {
+            e->owned.erase(std::find(e->owned.begin(), e->owned.end(), old));
+            (void)hipFree(old);
+        }
+        e->owned.push_back(fresh[i]);
+        bufs[i].set(e, fresh[i]);
+    }
+    e->decode_alloc = cap;
+    e->decode_bytes = bytes;
+    return SAMRS_OK;
+}
+
+// a lazy buffer of the list, by its field name, at the current capacity
+static int need_decode_buffer(samrs_engine_t* e, const char* name) {
+    for (const DecodeBuf& b : decode_buffers(e)) {
+        if (strcmp(b.name, name)) continue;
+        if (b.get(e)) return SAMRS_OK;
+        void* p = nullptr;
+        CK(e, hipMalloc(&p, b.per_prompt * (size_t)e->decode_alloc));
+        e->owned.push_back(p);
+        b.set(e, p);
+        e->decode_bytes += b.per_prompt * (size_t)e->decode_alloc;
+        return SAMRS_OK;
+    }
+    return fail(e, SAMRS_ERR_BAD_ARG, "no decoder workspace named %s", name);
+}
 
 int samrs_finalize_weights(samrs_engine_t* e, void* stream) {
     if (!e) return SAMRS_ERR_BAD_ARG;
@@ -867,7 +964,7 @@ int samrs_finalize_weights(samrs_engine_t* e, void* stream) {
     }
 
     // ---- workspaces ----
-    const size_t Bi = c.max_images, Bb = c.max_prompts;
+    const size_t Bi = c.max_images;
     const size_t M = Bi * tokens;
     const size_t Mmax = M;
     CK(e, dalloc(e, &e->X, M * D));
@@ -913,23 +1010,9 @@ int samrs_finalize_weights(samrs_engine_t* e, void* stream) {
     CK(e, dalloc(e, &e->N1, M * C));
     CK(e, dalloc(e, &e->N1e, M * C));
     CK(e, dalloc(e, &e->EMB, M * C));
-    const size_t BT = Bb * e->T_max;
-    CK(e, dalloc(e, &e->TOK0, BT * C)); CK(e, dalloc(e, &e->Q, BT * C)); CK(e, dalloc(e, &e->TA, BT * C));
-    CK(e, dalloc(e, &e->TQ, BT * C)); CK(e, dalloc(e, &e->TK, BT * C)); CK(e, dalloc(e, &e->TV, BT * C));
-    CK(e, dalloc(e, &e->TO, BT * C)); CK(e, dalloc(e, &e->MH, BT * 2048));
-    CK(e, dalloc(e, &e->QP, BT * Ci)); CK(e, dalloc(e, &e->KT, BT * Ci)); CK(e, dalloc(e, &e->VT, BT * Ci));
-    CK(e, dalloc(e, &e->O128, BT * Ci));
-    CK(e, dalloc(e, &e->T2IW, t2i_workspace_floats(c.max_prompts, e->T_max)));
     CK(e, dalloc(e, &e->K0F, (size_t)c.max_images * tokens * C)); CK(e, dalloc(e, &e->K0E, (size_t)c.max_images * tokens * C));
     CK(e, dalloc(e, &e->KVQ0, (size_t)c.max_images * tokens * 3 * (C / 2)));
-    CK(e, dalloc(e, &e->KF, Bb * tokens * C)); CK(e, dalloc(e, &e->KE, Bb * tokens * C));
-    CK(e, dalloc(e, &e->KE_lo, Bb * tokens * C));
-    CK(e, dalloc(e, &e->KVQ, Bb * tokens * 3 * Ci)); CK(e, dalloc(e, &e->OI, Bb * tokens * Ci));
-    CK(e, dalloc(e, &e->U1raw, Bb * tokens * C)); CK(e, dalloc(e, &e->U1, Bb * tokens * C));
-    CK(e, dalloc(e, &e->U2, Bb * tokens * 4 * (C / 2)));
-    CK(e, dalloc(e, &e->HY1, 5 * Bb * C)); CK(e, dalloc(e, &e->HY2, 5 * Bb * C));
-    CK(e, dalloc(e, &e->HYPER, Bb * 4 * (C / 8))); CK(e, dalloc(e, &e->IOU, Bb * 4));
-    CK(e, dalloc(e, &e->LOW, Bb * 3 * 256 * 256));
+    if ((rc = grow_decode_workspaces(e, e->decode_prompts))) return rc;      // every per-prompt decoder workspace
     CK(e, hipStreamSynchronize(s));
     e->dec = dec_weights(e);       // after every to_et(..., free_f32 = true): no freed tensor is resolved
     audit_build_sites(e);
@@ -1643,14 +1726,16 @@ static int check_predict(samrs_engine_t* e, const PredictImage* im, int n_img, b
 }
 
 // The reference takes any number of prompts per call (its instance drivers pass every object of an image at once,
-// main_sam_rbox_mask_instance.py:159-164).  The engine's workspaces hold max_prompts prompts, so a larger call is
-// run as consecutive chunks of max_prompts on the same stream, each writing its slice of the caller's buffers;
-// results do not depend on the chunking (no cross-prompt arithmetic, no atomics anywhere on the path).  A chunk may
-// span several images (samrs_predict_multi): every prompt reads its own image's slot, nothing else changes.
-static int predict_images(samrs_engine_t* e, const PredictImage* im, int n_img, const float* boxes, const float* point_coords,
+// main_sam_rbox_mask_instance.py:159-164).  The engine's workspaces hold decode_prompts prompts (option "decode_prompts";
+// max_prompts unless the caller raised it), so a larger call is run as consecutive chunks of that many on the same stream, each
+// writing its slice of the caller's buffers; results do not depend on the chunking (no cross-prompt arithmetic, no atomics
+// anywhere on the path, and no launcher picks a summation order by the prompt count).  A chunk may span several images
+// (samrs_predict_multi): every prompt reads its own image's slot, nothing else changes.
+// `cap`: prompts per chunk -- max_prompts for samrs_predict (the caller's per-image contract: its launches are what they always were),
+// decode_prompts for samrs_predict_multi.
+static int predict_images(samrs_engine_t* e, int cap, const PredictImage* im, int n_img, const float* boxes, const float* point_coords,
                           const int32_t* point_labels, int n_points, const float* mask_input, int multimask, int return_logits,
                           float* iou_out, float* lowres_out, void* stream) {
-    const int cap = e->cfg.max_prompts;
     const size_t nsel = multimask ? 3 : 1;
     const int np = point_coords ? n_points : 0;
     const int n = n_img ? im[n_img - 1].p1 : 0;
@@ -1688,7 +1773,7 @@ int samrs_predict(samrs_engine_t* e, int slot, int n, const float* boxes, const 
     if (multimask) { const int rc = check_multimask_grade(e, slot, false); if (rc != SAMRS_OK) return rc; }
     const PredictImage im{slot, 0, n, in_h, in_w, orig_h, orig_w, masks_out};
     { const int rc = check_predict(e, &im, 1, false, boxes, point_coords, point_labels, n_points, mask_input); if (rc != SAMRS_OK) return rc; }
-    return predict_images(e, &im, 1, boxes, point_coords, point_labels, n_points, mask_input, multimask, return_logits, iou_out,
+    return predict_images(e, e->cfg.max_prompts, &im, 1, boxes, point_coords, point_labels, n_points, mask_input, multimask, return_logits, iou_out,
                           lowres_out, stream);
 }
 
@@ -1711,7 +1796,7 @@ int samrs_predict_multi(samrs_engine_t* e, int n_images, const int* slots, const
     if (multimask)
         for (int i = 0; i < n_images; ++i) { const int rc = check_multimask_grade(e, slots[i], true); if (rc != SAMRS_OK) return rc; }
     { const int rc = check_predict(e, im.data(), n_images, true, boxes, point_coords, point_labels, n_points, mask_input); if (rc != SAMRS_OK) return rc; }
-    return predict_images(e, im.data(), n_images, boxes, point_coords, point_labels, n_points, mask_input, multimask, return_logits,
+    return predict_images(e, e->decode_prompts, im.data(), n_images, boxes, point_coords, point_labels, n_points, mask_input, multimask, return_logits,
                           iou_out, lowres_out, stream);
 }
 
@@ -1835,14 +1920,14 @@ static int run_prompt_side(samrs_engine_t* e, const DecodeRoute& r, const Predic
     prompt_call_fields(pp, boxes, point_coords, point_labels, n, n_points, (float)c.img_size);
     CK(e, launch_prompt_tokens(pp, e->TOK0, e->Q, r.T, s));       // tokens and (a copy) the initial queries
     if (r.slot_table) {
-        if (!e->SLOT_OF) CK(e, dalloc(e, &e->SLOT_OF, (size_t)c.max_prompts));
+        if (!e->SLOT_OF) { const int rc = need_decode_buffer(e, "SLOT_OF"); if (rc != SAMRS_OK) return rc; }
         std::vector<int> start((size_t)n_seg + 1), slot((size_t)n_seg);
         for (int k = 0; k < n_seg; ++k) { start[k] = seg[k].p0; slot[k] = seg[k].slot; }
         start[n_seg] = seg[n_seg - 1].p1;
         CK(e, launch_fill_slot_table(start.data(), slot.data(), n_seg, e->SLOT_OF, s));
     }
     if (!r.shared0) {
-        if (!e->DENSE) CK(e, dalloc(e, &e->DENSE, (size_t)c.max_prompts * tokens * C));
+        if (!e->DENSE) { const int rc = need_decode_buffer(e, "DENSE"); if (rc != SAMRS_OK) return rc; }
         CK(e, launch_mask_embed(e->dec.mask_embed, mask_input, e->DENSE, n, e->grid, s));
         CK(e, launch_make_keys(e->prec, e->EMB + r.slot0 * tokens * C, e->DENSE, nullptr, e->KF, e->KE, n, tokens, C, s,
                                r.slot_table ? e->SLOT_OF : nullptr));
@@ -1932,7 +2017,7 @@ static int run_final_attn(samrs_engine_t* e, const DecodeRoute& r, int n, hipStr
 static int run_heads(samrs_engine_t* e, const DecodeRoute& r, int n, float* iou_out, hipStream_t s) {
     const int C = e->C;
     const DecWeights& w = e->dec;
-    const size_t hs = (size_t)e->cfg.max_prompts * C;
+    const size_t hs = (size_t)e->decode_alloc * C;        // HY1 / HY2: [5][Bb][C]
     F32Batch l0{}, l1{}, l2{};
     for (int i = 0; i < 5; ++i) {
         l0.A[i] = i < 4 ? e->Q + (size_t)(1 + i) * C : e->Q;       // mask token i / IoU token of every prompt
@@ -1957,6 +2042,12 @@ static int run_heads(samrs_engine_t* e, const DecodeRoute& r, int n, float* iou_
 // upscaler (mask_decoder.py:53-59,154-155) in the form the route names
 static int run_upscaler(samrs_engine_t* e, const DecodeRoute& r, int n, float* low, hipStream_t s) {
     const int C = e->C, prec = e->prec, g = e->grid, Mi = r.Mi;
+    // the intermediates of the forms that keep them in memory: allocated by the first pass that takes such a form
+    for (const char* name : {"U1raw", "U1", "U2"}) {
+        const bool used = !strcmp(name, "U1raw") ? (r.up == Upscaler::GLN_SPLIT || r.up == Upscaler::UNFUSED)
+                        : !strcmp(name, "U1")    ? (r.up == Upscaler::GLN || r.up == Upscaler::UNFUSED) : r.up == Upscaler::UNFUSED;
+        if (used) { const int rc = need_decode_buffer(e, name); if (rc != SAMRS_OK) return rc; }
+    }
     switch (r.up) {
     case Upscaler::ONE_KERNEL:
         CK(e, launch_upscaler_fused(prec, e->KE, r.sp_up ? e->KE_lo : nullptr, e->up1_w, r.sp_up ? e->up1_w_lo : nullptr, e->up1_b, e->up_ln,
@@ -1994,8 +2085,8 @@ static int run_postprocess(samrs_engine_t* e, const DecodeRoute& r, const Predic
 static int predict_chunk(samrs_engine_t* e, const PredictImage* seg, int n_seg, int n, const float* boxes, const float* point_coords,
                          const int32_t* point_labels, int n_points, const float* mask_input, int multimask,
                          int return_logits, float* iou_out, float* lowres_out, void* stream) {
-    const samrs_config& c = e->cfg;
-    if (n < 1 || n > c.max_prompts) return fail(e, SAMRS_ERR_CAPACITY, "n_prompts=%d exceeds max_prompts=%d", n, c.max_prompts);
+    if (n < 1 || n > e->decode_prompts || n > e->decode_alloc)
+        return fail(e, SAMRS_ERR_CAPACITY, "a decoder chain of %d prompts exceeds decode_prompts=%d", n, e->decode_prompts);
     hipStream_t s = (hipStream_t)stream;
     ON_DEVICE(e);
     const DecodeRoute r = decode_route(e, n, n_seg, seg[0].slot, boxes != nullptr, point_coords ? n_points : 0, mask_input != nullptr,
@@ -2065,6 +2156,19 @@ int samrs_set_option(samrs_engine_t* e, const char* name, int value) {
         e->split = value & SPLIT_ALL;
     }
     else if (n == "gemm_variant") e->gemm_variant = value;
+    else if (n == "decode_prompts") {
+        const long long prod = (long long)e->cfg.max_images * e->cfg.max_prompts;
+        const int lo = e->cfg.max_prompts, lim = prod < DECODE_PROMPTS_LIMIT ? (int)prod : DECODE_PROMPTS_LIMIT, hi = lim > lo ? lim : lo;
+        if (value < lo || value > hi)
+            return fail(e, SAMRS_ERR_BAD_ARG, "decode_prompts=%d is outside [%d, %d]: from max_prompts to max_images x max_prompts = %lld, "
+                                              "at most %d (the index range of the decoder kernels)", value, lo, hi, prod, DECODE_PROMPTS_LIMIT);
+        if (e->finalized) {          // before that, samrs_finalize_weights allocates at the value set here
+            ON_DEVICE(e);
+            const int rc = grow_decode_workspaces(e, value);
+            if (rc != SAMRS_OK) return rc;
+        }
+        e->decode_prompts = value;
+    }
     else if (n == "upscaler_fused") e->upscaler_fused = value != 0;
     else if (n == "split_passes") e->split_passes = value != 0;
     else if (n == "split_depth") e->split_depth = value > 0 ? value : 0;
@@ -2133,6 +2237,8 @@ int samrs_get_option(const samrs_engine_t* e, const char* name, int* value) {
     else if (n == "ln_fold") *value = e->ln_fold;
     else if (n == "split") *value = e->split;
     else if (n == "gemm_variant") *value = e->gemm_variant;
+    else if (n == "decode_prompts") *value = e->decode_prompts;
+    else if (n == "decode_kbytes") *value = (int)((e->decode_bytes + 1023) / 1024);     // read-only; KiB: the bytes do not fit an int
     else if (n == "upscaler_fused") *value = e->upscaler_fused;
     else if (n == "split_passes") *value = e->split_passes;
     else if (n == "split_depth") *value = e->split_depth;

@@ -417,6 +417,33 @@ def refuse_quality_options(who: str, why: str, **opts) -> None:
                          f"{'is a' if len(given) == 1 else 'are'} TilePipeline option{'' if len(given) == 1 else 's'}")
 
 
+DECODE_PROMPTS_LIMIT = 512      # the engine's cap on option "decode_prompts" (samrs_hip.h)
+
+
+def resolve_batch_decode(batch_decode, batch: int, box_batch: int, max_boxes: int, max_prompts: int, max_images: int,
+                         capacity: int) -> Tuple[bool, Optional[int], str]:
+    """What a pipeline's ``batch_decode`` argument becomes: (on, the "decode_prompts" to ask the engine for or None, why).  Pure.
+
+    True / False stand as they are and ask for nothing.  "auto" is on when
+      * box_batch >= max_boxes: no tile is decoded in several chunks (the c2 / c4 shape).  A long-tailed batch (c3: up to 400 boxes
+        in 64-box chunks) keeps the per-tile chains it has; nothing was measured to gain there; and
+      * one chain holds the whole batch, batch x max_boxes prompts: the engine's capacity as it stands (`capacity`), or a value it
+        accepts -- [max_prompts, min(max_images x max_prompts, DECODE_PROMPTS_LIMIT)] -- which is then the value to set.
+    No output option is part of the rule: min_region_area, quality, mask_boxes and polygons give byte for byte the same outputs
+    under batch_decode=True as without it (tests/test_clean_masks_gpu.py, test_quality_gpu.py, test_polygons_gpu.py)."""
+    if batch_decode != "auto":
+        return bool(batch_decode), None, "explicit"
+    if box_batch < max_boxes:
+        return False, None, f"box_batch={box_batch} < max_boxes={max_boxes}: tiles are decoded in several chunks"
+    need = batch * max_boxes
+    if need <= capacity:
+        return True, None, f"a chain of {need} prompts fits the engine's decode_prompts={capacity}"
+    hi = min(max_images * max_prompts, DECODE_PROMPTS_LIMIT)
+    if need > hi:
+        return False, None, f"a chain of {need} prompts exceeds what the engine accepts ({hi})"
+    return True, need, f"decode_prompts raised from {capacity} to {need}"
+
+
 class TilePipeline:
     """hbox -> semantic labels for a stream of tiles (main_sam_hbox_semantic.py:110-216), restructured for the GPU:
 
@@ -443,7 +470,7 @@ class TilePipeline:
     def __init__(self, sam, n_classes: int, batch: int = 8, box_batch: int = 20, keep_masks: bool = False,
                  out_depth: int = 3, max_boxes: int = 512, device_inputs: bool = False, rle: bool = False,
                  rle_buffer_mb: int = 256, precision="auto", _multimask: bool = False, png_lut: Optional[np.ndarray] = None,
-                 png_buffer_mb: Optional[int] = None, batch_decode: bool = False, min_region_area: int = 0,
+                 png_buffer_mb: Optional[int] = None, batch_decode="auto", min_region_area: int = 0,
                  region_mode: str = "both", mask_boxes: bool = False, quality: bool = False, min_stability: float = 0.0,
                  min_pred_iou: float = 0.0, min_inside_box: float = 0.0, polygons: bool = False, polygon_buffer_mb: int = 64,
                  polygon_max_edges: int = 65536):
@@ -461,7 +488,11 @@ class TilePipeline:
         caller's consent to run its multimask predicts in it: option "allow_reduced").
         batch_decode: decode the prompts of every tile of a batch in one ``Engine.predict_multi`` call (one decoder chain per
         batch instead of one per tile and box chunk); painting, RLE and PNG encoding then run per tile as before, and every
-        output is the same byte for byte.
+        output is the same byte for byte.  True / False: on / off; a chain holds the engine's "decode_prompts" prompts (its
+        max_prompts unless somebody raised it) and a longer batch is cut into chunks of that size again.  "auto" (default): on
+        where a whole batch fits ONE chain and no tile is decoded in several chunks (``resolve_batch_decode``), raising the
+        engine's "decode_prompts" to batch x max_boxes once, here, when it is smaller (13.5 MB of workspace per prompt); off
+        otherwise, and off when the engine refuses the capacity.  ``batch_decode_on`` / ``batch_decode_reason`` say what it became.
         min_region_area: > 0 removes, on the device and before anything else reads the masks, every 8-connected island
         (region_mode "islands"), hole ("holes") or both ("both": holes first) of fewer than that many pixels
         (``Engine.clean_masks`` = segment_anything's ``remove_small_regions``): class map, areas, class statistics, RLE strings,
@@ -517,7 +548,8 @@ class TilePipeline:
         self.sam, self.eng, self.dev = sam, eng, eng.device
         self.batch, self.box_batch, self.keep_masks, self.max_boxes = batch, box_batch, keep_masks, max_boxes
         self.rle = rle
-        self.batch_decode = bool(batch_decode)
+        self.batch_decode, self.batch_decode_reason = self._resolve_batch_decode(batch_decode)
+        self.batch_decode_on = self.batch_decode
         self.png = png_lut is not None
         self.side = sam.cfg.img_size
         self.transform = ResizeLongestSide(sam.image_encoder.img_size)
@@ -583,6 +615,24 @@ class TilePipeline:
         for _ in range(out_depth):
             self.free_out.put(_OutBuf(batch, side, max_boxes, rle, self.png, self.min_region_area > 0, self.mask_boxes, self.quality,
                                       self.polygons))
+
+    def _resolve_batch_decode(self, batch_decode) -> Tuple[bool, str]:
+        """(on, why).  "auto": the pure rule, then the engine's own answer to the capacity it asks for."""
+        from .engine import EngineError
+        if batch_decode != "auto":
+            return bool(batch_decode), "explicit"
+        eng = self.eng
+        try:
+            capacity = eng.get_option("decode_prompts")
+        except (AssertionError, EngineError):                    # a library without the option: chains of max_prompts
+            capacity = eng.max_prompts
+        on, want, why = resolve_batch_decode("auto", self.batch, self.box_batch, self.max_boxes, eng.max_prompts, eng.max_images, capacity)
+        if on and want is not None:
+            try:
+                eng.set_option("decode_prompts", want)
+            except (AssertionError, EngineError) as exc:         # refused (range, memory): the engine is as it was
+                return False, f"the engine refused decode_prompts={want}: {exc}"
+        return on, why
 
     @staticmethod
     def _choose_split(sam, precision, multimask: bool) -> Optional[int]:

@@ -347,7 +347,7 @@ def run(args) -> Dict[str, List[int]]:
                                    rle_buffer_mb=getattr(args, "rle_buffer_mb", 256), max_boxes=max_boxes,
                                    out_depth=getattr(args, "out_depth", 4), png_lut=tile_io.class_lut(palette) if png_device else None,
                                    png_buffer_mb=getattr(args, "png_buffer_mb", None),
-                                   batch_decode=bool(getattr(args, "batch_decode", False)),
+                                   batch_decode=True if getattr(args, "batch_decode", False) else "auto",
                                    min_region_area=min_region_area, region_mode=getattr(args, "region_mode", "both"),
                                    mask_boxes=mask_boxes, quality=want_quality, **thresholds, **poly_kw)
     # rank r takes chunks of `batch` consecutive stems: statically (r, r + world, ...) or from the shared counter (whose

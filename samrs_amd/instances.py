@@ -271,7 +271,7 @@ def run(args) -> Optional[dict]:
     pipe = driver.InstancePipeline(sam, 1, prompt=args.prompt, multimask=multimask, fill_rule=getattr(args, "fill_rule", "auto"),
                                    gt=with_gt, batch=batch, box_batch=args.box_batch, max_boxes=max_boxes, rle=True,
                                    rle_buffer_mb=getattr(args, "rle_buffer_mb", 256), keep_masks=False,
-                                   batch_decode=bool(getattr(args, "batch_decode", False)),
+                                   batch_decode=True if getattr(args, "batch_decode", False) else "auto",
                                    min_region_area=int(getattr(args, "min_region_area", 0) or 0),
                                    region_mode=getattr(args, "region_mode", "both"),
                                    mask_boxes=bool(getattr(args, "mask_boxes", False)))
