@@ -26,7 +26,7 @@ import os
 import queue
 import threading
 from dataclasses import dataclass, field
-from typing import Callable, Iterable, Iterator, List, Optional, Sequence, Tuple
+from typing import Callable, Iterable, Iterator, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -376,34 +376,146 @@ class TileResult:
         return {"size": [int(self.size[0]), int(self.size[1])], "counts": self.gt_rle_data[off:off + n].tobytes().decode("ascii")}
 
 
+class OutputTable(NamedTuple):
+    """One fixed-size per-box output, declared once (``output_tables``): per input set a device table [batch, max_boxes, *tail] that
+    the decode chain fills, per output buffer a pinned mirror, per tile the ``TileResult`` field of its [n_boxes, *tail] rows."""
+    field: str                      # the TileResult field
+    dev: str                        # the pipeline attribute that holds the two device tables
+    tail: Tuple[int, ...]           # shape of one box's row
+    dtype: torch.dtype
+    fill: Optional[str] = "zeros"   # the device tables start as "zeros" / "ones" / None: uninitialised
+    as_bool: bool = False           # the host rows: a copy, or astype(bool)
+
+    def alloc(self, batch: int, max_boxes: int, device=None) -> torch.Tensor:
+        """The device table (filled) on `device`; without one, its pinned host mirror."""
+        shape = (batch, max_boxes, *self.tail)
+        if device is None:
+            return torch.empty(shape, dtype=self.dtype).pin_memory()
+        return {"zeros": torch.zeros, "ones": torch.ones, None: torch.empty}[self.fill](shape, dtype=self.dtype, device=device)
+
+    def rows(self, host: torch.Tensor) -> np.ndarray:
+        a = host.numpy()
+        return a.astype(bool) if self.as_bool else a.copy()
+
+
+def output_tables(min_region_area: int = 0, mask_boxes: bool = False, quality: bool = False, gt: bool = False, rle: bool = False,
+                  instance: bool = False) -> List[OutputTable]:
+    """The per-box tables a pipeline with these (resolved) options allocates, copies to the host and hands out, in that order.
+    Pure.  An option that is off contributes nothing: no allocation, no copy, and its TileResult fields stay None.  `instance`: an
+    InstancePipeline, which always reports the predicted IoU of the mask it kept."""
+    T, i64, i32 = OutputTable, torch.int64, torch.int32
+    tabs = [T("areas", "area_dev", (), i64)]
+    if min_region_area:
+        tabs.append(T("changed", "chg_dev", (), i64))
+    if mask_boxes:
+        tabs += [T("mask_hbox", "hbox_dev", (4,), i32), T("mask_rbox", "rbox_dev", (4, 2), torch.float32),
+                 T("mask_record", "rec_dev", (8,), i64)]
+    if quality:
+        tabs += [T("score_counts", "cnt_dev", (4,), i64), T("kept", "keep_dev", (), torch.uint8, "ones", True)]
+    if quality or instance:
+        tabs.append(T("quality", "qual_dev", (), torch.float32))
+    if gt:
+        tabs += [T("inter", "inter_dev", (), i64), T("gt_area", "gta_dev", (), i64)]
+        if rle and mask_boxes:      # the ground-truth masks are only materialised for their RLE
+            tabs.append(T("gt_hbox", "gt_hbox_dev", (4,), i32))
+    return tabs
+
+
+def check_packed(tab: np.ndarray, total: int, holder: str, now: int, what: str = "RLE buffer too small: a mask",
+                 knob: str = "rle_buffer_mb") -> None:
+    """Raises for a packed string table (rows of (offset, length, ...)) with an entry that did not fit: its length is
+    -1 - the bytes it needs.  `holder`: "batch" / "scene", whatever shares the buffer; `now`: the buffer's size in MiB."""
+    if len(tab) and int(tab[:, 1].min()) < 0:
+        raise RuntimeError(f"{what} needs {int((-tab[:, 1] - 1).max())} bytes and the {holder} already holds {total}; raise "
+                           f"{knob} (now {now})")
+
+
+def check_polygons(tab: np.ndarray, nv: int, nr: int, holder: str, now: int) -> None:
+    """Raises for a polygon table with a mask that did not fit (ring count -1 - rings needed, vertex count -1 - vertices needed);
+    a mask over the edge cap stays (-1, -1)."""
+    if len(tab) and int(tab[:, 1].min()) < -1:
+        j = int(np.argmin(tab[:, 1]))
+        raise RuntimeError(f"polygon buffer too small: a mask needs {int(-tab[j, 3] - 1)} vertices and {int(-tab[j, 1] - 1)} rings and "
+                           f"the {holder} already holds {nv} and {nr}; raise polygon_buffer_mb (now {now})")
+
+
+def validate_output_options(min_region_area: int = 0, region_mode: str = "both", polygons: bool = False, polygon_buffer_mb: int = 64,
+                            polygon_max_edges: int = 65536, png_lut=None):
+    """The output options TilePipeline and ScenePipeline share, checked in one place -> (png_lut as contiguous uint8 [256, 3] or
+    None, the vertices one polygon buffer holds or None).  Touches no device."""
+    from .engine import REGION_MODES
+    if int(min_region_area) < 0:
+        raise ValueError("min_region_area must be >= 0 (0 = off)")
+    if region_mode not in REGION_MODES:
+        raise ValueError(f"region_mode must be one of {sorted(REGION_MODES)}, got {region_mode!r}")
+    lut = nv = None
+    if png_lut is not None:
+        lut = np.ascontiguousarray(png_lut, dtype=np.uint8)
+        if lut.shape != (256, 3):
+            raise ValueError("png_lut must be uint8 [256, 3] (tile_io.class_lut)")
+    if polygons:
+        if int(polygon_buffer_mb) < 1 or int(polygon_max_edges) < 4:
+            raise ValueError("polygon_buffer_mb must be >= 1 and polygon_max_edges >= 4")
+        nv = (int(polygon_buffer_mb) << 20) // 12              # 8 bytes per vertex + 16 per ring, a ring has >= 4 vertices
+    return lut, nv
+
+
+class PackedStream:
+    """One variable-length output of a batch, packed on the device behind a cursor (samrs_rle_encode's layout).  Per input set:
+    the payload buffers, a cursor (int64, one count of rows used per payload) and a table of `rows` x `tail` int64 that says where
+    each entry lies.  Per output buffer (``pinned``): mirrors of the table and the cursor, and payloads that grow on demand.
+    The device payloads are attributes of the pipeline, two tensors each, named in `payloads` as (attribute, row tail, dtype, pinned
+    rows to begin with) and read at each use.  `check(table, used)` raises for a table with an entry that did not fit.
+    RLE, ground-truth RLE and PNG have one byte payload; polygons have two (vertices, ring records) and fit without a special case."""
+
+    def __init__(self, pipe, name: str, rows: int, tail: Tuple[int, ...], payloads, check):
+        self.pipe, self.name, self.shape, self.payloads, self.check = pipe, name, (rows, *tail), payloads, check
+        self.cur = [torch.zeros(len(payloads), dtype=torch.int64, device=pipe.dev) for _ in range(2)]
+        self.tab = [torch.zeros(self.shape, dtype=torch.int64, device=pipe.dev) for _ in range(2)]
+
+    def pinned(self) -> list:
+        """[table, cursor, [payloads]] on the host, for one _OutBuf."""
+        return [torch.zeros(self.shape, dtype=torch.int64).pin_memory(), torch.zeros(len(self.payloads), dtype=torch.int64).pin_memory(),
+                [torch.empty(n, *tail, dtype=dtype).pin_memory() for _, tail, dtype, n in self.payloads]]
+
+    def reset(self, b: int) -> None:
+        self.cur[b].zero_()
+
+    def copy_table(self, b: int, out: "_OutBuf") -> None:
+        tab, cur, _ = out.packed[self.name]
+        tab.copy_(self.tab[b], non_blocking=True)
+        cur.copy_(self.cur[b], non_blocking=True)
+
+    def fetch(self, b: int, out: "_OutBuf", n: int):
+        """(the first n table rows, the pinned payloads, the rows used of each) of a batch whose table and cursor are on the host
+        (out.done), so the payloads can be copied with their exact size -- on a copy stream, while the GPU works on the batches
+        already queued."""
+        tab, cur, host = out.packed[self.name]
+        tab = tab.view(-1, tab.shape[-1])[:n].numpy()
+        used = cur.tolist()
+        self.check(tab, used)
+        for k, (_, tail, dtype, _) in enumerate(self.payloads):
+            if host[k].shape[0] < used[k]:
+                host[k] = torch.empty(max(used[k], 2 * host[k].shape[0]), *tail, dtype=dtype).pin_memory()
+        if any(used):
+            with torch.cuda.stream(self.pipe.s_d2h):
+                for k, (attr, _, _, _) in enumerate(self.payloads):
+                    host[k][:used[k]].copy_(getattr(self.pipe, attr)[b][:used[k]], non_blocking=True)
+            self.pipe.s_d2h.synchronize()
+        return tab, host, used
+
+
 class _OutBuf:
-    def __init__(self, batch: int, side: int, max_boxes: int, rle: bool = False, png: bool = False, changed: bool = False,
-                 boxes: bool = False, quality: bool = False, polygons: bool = False):
+    """One batch's results in pinned host memory: the class maps, a mirror of each active per-box table (by TileResult field) and
+    of each packed stream (by its name)."""
+
+    def __init__(self, batch: int, side: int, max_boxes: int, tables: Sequence[OutputTable], streams: Sequence[PackedStream] = ()):
         self.seg = torch.empty(batch, side, side, dtype=torch.uint8).pin_memory()
-        self.areas = torch.empty(batch, max_boxes, dtype=torch.int64).pin_memory()
-        self.changed = torch.empty(batch, max_boxes, dtype=torch.int64).pin_memory() if changed else None
-        self.hbox = torch.empty(batch, max_boxes, 4, dtype=torch.int32).pin_memory() if boxes else None
-        self.rbox = torch.empty(batch, max_boxes, 4, 2, dtype=torch.float32).pin_memory() if boxes else None
-        self.record = torch.empty(batch, max_boxes, 8, dtype=torch.int64).pin_memory() if boxes else None
-        self.counts = torch.empty(batch, max_boxes, 4, dtype=torch.int64).pin_memory() if quality else None
-        self.kept = torch.empty(batch, max_boxes, dtype=torch.uint8).pin_memory() if quality else None
-        self.quality = torch.empty(batch, max_boxes, dtype=torch.float32).pin_memory() if quality else None
-        # polygons: per-box table, the cursor (vertices, rings used), and the batch's vertices and ring records (grown on demand)
-        self.poly_tab = torch.zeros(batch * max_boxes, 5, dtype=torch.int64).pin_memory() if polygons else None
-        self.poly_cur = torch.zeros(2, dtype=torch.int64).pin_memory() if polygons else None
-        self.poly_vert = torch.empty(1 << 16, 2, dtype=torch.int32).pin_memory() if polygons else None
-        self.poly_ring = torch.empty(1 << 14, 4, dtype=torch.int32).pin_memory() if polygons else None
+        self.tables = {t.field: t.alloc(batch, max_boxes) for t in tables}
+        self.packed = {s.name: s.pinned() for s in streams}
         self.done = torch.cuda.Event()
         self.masks: List[Optional[torch.Tensor]] = [None] * batch     # keep_masks: host copies of the full masks
         self.odd: dict = {}                                           # tiles that are not side x side: their class maps
-        # rle: per-box (offset, length, n_counts), the number of bytes used, and the strings themselves (grown on demand)
-        self.rle_tab = torch.zeros(batch * max_boxes, 3, dtype=torch.int64).pin_memory() if rle else None
-        self.rle_cur = torch.zeros(1, dtype=torch.int64).pin_memory() if rle else None
-        self.rle_bytes = torch.empty(1 << 20, dtype=torch.uint8).pin_memory() if rle else None
-        # png: per tile (offset, length) of its gray and colour file, the number of bytes used, and the files (grown on demand)
-        self.png_tab = torch.zeros(batch, 2, 2, dtype=torch.int64).pin_memory() if png else None
-        self.png_cur = torch.zeros(1, dtype=torch.int64).pin_memory() if png else None
-        self.png_bytes = torch.empty(1 << 20, dtype=torch.uint8).pin_memory() if png else None
 
 
 QUALITY_OPTIONS = ("quality", "min_stability", "min_pred_iou", "min_inside_box")
@@ -517,11 +629,7 @@ class TilePipeline:
         more crack edges is not traced and yields None.  Every other output is byte for byte what polygons=False gives, and
         False (default) launches and allocates nothing."""
         from .transforms import ResizeLongestSide
-        from .engine import REGION_MODES
-        if int(min_region_area) < 0:
-            raise ValueError("min_region_area must be >= 0 (0 = off)")
-        if region_mode not in REGION_MODES:
-            raise ValueError(f"region_mode must be one of {sorted(REGION_MODES)}, got {region_mode!r}")
+        lut, poly_vertices = validate_output_options(min_region_area, region_mode, polygons, polygon_buffer_mb, polygon_max_edges, png_lut)
         self.min_region_area, self.region_mode = int(min_region_area), region_mode
         self.thresholds = (float(min_stability), float(min_pred_iou), float(min_inside_box))
         if any(t != t or t < 0 for t in self.thresholds):
@@ -563,21 +671,7 @@ class TilePipeline:
         self.pin_in = None
         if not device_inputs:
             self.pin_in = [torch.empty(batch, side, side, 3, dtype=torch.uint8).pin_memory() for _ in range(2)]
-        if rle or self.png or polygons:
-            self.s_d2h = torch.cuda.Stream(dev)
-        if rle:      # per input set: the batch's RLE strings (packed, 16-byte aligned), a cursor, (offset, length, n_counts) per box
-            self.rle_dev = [torch.empty(rle_buffer_mb << 20, dtype=torch.uint8, device=dev) for _ in range(2)]
-            self.rle_cur = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(2)]
-            self.rle_tab = [torch.zeros(batch * max_boxes, 3, dtype=torch.int64, device=dev) for _ in range(2)]
-        if self.png:   # the LUT once; per input set: the batch's PNG files (packed, 16-byte aligned), a cursor, (offset, length) per file
-            lut = np.ascontiguousarray(png_lut, dtype=np.uint8)
-            if lut.shape != (256, 3):
-                raise ValueError("png_lut must be uint8 [256, 3] (tile_io.class_lut)")
-            self.png_lut = torch.from_numpy(lut).to(dev)
-            self.png_buffer_mb = int(png_buffer_mb) if png_buffer_mb else 6 * batch
-            self.png_dev = [torch.empty(self.png_buffer_mb << 20, dtype=torch.uint8, device=dev) for _ in range(2)]
-            self.png_cur = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(2)]
-            self.png_tab = [torch.zeros(batch, 2, 2, dtype=torch.int64, device=dev) for _ in range(2)]
+        self.mask_boxes, self.polygons = bool(mask_boxes), bool(polygons)
         self.dev_in = [torch.empty(batch, side, side, 3, dtype=torch.uint8, device=dev) for _ in range(2)]
         bw = self.BOX_WIDTH
         self.pin_box = [torch.empty(batch * max_boxes, bw, dtype=torch.float32).pin_memory() for _ in range(2)]
@@ -585,36 +679,48 @@ class TilePipeline:
         self.dev_box = [torch.empty(batch * max_boxes, bw, dtype=torch.float32, device=dev) for _ in range(2)]
         self.dev_lab = [torch.empty(batch * max_boxes, dtype=torch.int32, device=dev) for _ in range(2)]
         self.seg_dev = [torch.empty(batch, side, side, dtype=torch.uint8, device=dev) for _ in range(2)]
-        self.area_dev = [torch.zeros(batch, max_boxes, dtype=torch.int64, device=dev) for _ in range(2)]
-        if self.min_region_area:
-            self.chg_dev = [torch.zeros(batch, max_boxes, dtype=torch.int64, device=dev) for _ in range(2)]
-        self.mask_boxes = bool(mask_boxes)
-        if self.mask_boxes:
-            self.hbox_dev = [torch.zeros(batch, max_boxes, 4, dtype=torch.int32, device=dev) for _ in range(2)]
-            self.rbox_dev = [torch.zeros(batch, max_boxes, 4, 2, dtype=torch.float32, device=dev) for _ in range(2)]
-            self.rec_dev = [torch.zeros(batch, max_boxes, 8, dtype=torch.int64, device=dev) for _ in range(2)]
-        self.polygons = bool(polygons)
-        if self.polygons:
-            if int(polygon_buffer_mb) < 1 or int(polygon_max_edges) < 4:
-                raise ValueError("polygon_buffer_mb must be >= 1 and polygon_max_edges >= 4")
+        # the fixed per-box outputs: one declaration each (output_tables), two device tables per entry under the entry's name
+        self.tables = output_tables(self.min_region_area, self.mask_boxes, self.quality, self.gt, rle, self.INSTANCE)
+        for t in self.tables:
+            setattr(self, t.dev, [t.alloc(batch, max_boxes, dev) for _ in range(2)])
+        # the packed outputs, per input set: the payload (16-byte aligned entries) here, cursor and table in the stream
+        self.streams: List[PackedStream] = []
+        if rle or self.png or polygons:
+            self.s_d2h = torch.cuda.Stream(dev)
+        nbm = batch * max_boxes
+        if rle:      # the batch's RLE strings; (offset, length, n_counts) per box
+            self.rle_dev = [torch.empty(rle_buffer_mb << 20, dtype=torch.uint8, device=dev) for _ in range(2)]
+            self.rle_out = PackedStream(self, "rle", nbm, (3,), [("rle_dev", (), torch.uint8, 1 << 20)],
+                                        lambda tab, used: check_packed(tab, used[0], "batch", self.rle_dev[0].numel() >> 20))
+            self.streams.append(self.rle_out)
+            if self.gt:      # InstancePipeline(gt=True): the ground-truth masks' strings beside them
+                self.gt_rle_dev = [torch.empty_like(t) for t in self.rle_dev]
+                self.gt_rle_out = PackedStream(self, "gt_rle", nbm, (3,), [("gt_rle_dev", (), torch.uint8, 1 << 20)],
+                                               lambda tab, used: check_packed(tab, used[0], "batch", self.gt_rle_dev[0].numel() >> 20))
+                self.streams.append(self.gt_rle_out)
+        if self.png:   # the LUT once; the batch's PNG files; (offset, length) of the gray and the colour file per tile
+            self.png_lut = torch.from_numpy(lut).to(dev)
+            self.png_buffer_mb = int(png_buffer_mb) if png_buffer_mb else 6 * batch
+            self.png_dev = [torch.empty(self.png_buffer_mb << 20, dtype=torch.uint8, device=dev) for _ in range(2)]
+            self.png_out = PackedStream(self, "png", batch, (2, 2), [("png_dev", (), torch.uint8, 1 << 20)],
+                                        lambda tab, used: check_packed(tab, used[0], "batch", self.png_dev[0].numel() >> 20,
+                                                                       what="PNG buffer too small: a file", knob="png_buffer_mb"))
+            self.streams.append(self.png_out)
+        if self.polygons:   # the batch's vertices and ring records; the cursor counts both; five table columns per box
             self.polygon_buffer_mb, self.polygon_max_edges = int(polygon_buffer_mb), int(polygon_max_edges)
-            nv = (self.polygon_buffer_mb << 20) // 12              # 8 bytes per vertex + 16 per ring, a ring has >= 4 vertices
-            self.poly_vert_dev = [torch.empty(nv, 2, dtype=torch.int32, device=dev) for _ in range(2)]
-            self.poly_ring_dev = [torch.empty(nv // 4, 4, dtype=torch.int32, device=dev) for _ in range(2)]
-            self.poly_cur = [torch.zeros(2, dtype=torch.int64, device=dev) for _ in range(2)]
-            self.poly_tab = [torch.zeros(batch * max_boxes, 5, dtype=torch.int64, device=dev) for _ in range(2)]
-        if self.quality:
-            self.cnt_dev = [torch.zeros(batch, max_boxes, 4, dtype=torch.int64, device=dev) for _ in range(2)]
-            self.keep_dev = [torch.ones(batch, max_boxes, dtype=torch.uint8, device=dev) for _ in range(2)]
-            self.qual_dev = [torch.zeros(batch, max_boxes, dtype=torch.float32, device=dev) for _ in range(2)]
+            self.poly_vert_dev = [torch.empty(poly_vertices, 2, dtype=torch.int32, device=dev) for _ in range(2)]
+            self.poly_ring_dev = [torch.empty(poly_vertices // 4, 4, dtype=torch.int32, device=dev) for _ in range(2)]
+            self.poly_out = PackedStream(self, "polygons", nbm, (5,), [("poly_vert_dev", (2,), torch.int32, 1 << 16),
+                                                                        ("poly_ring_dev", (4,), torch.int32, 1 << 14)],
+                                         lambda tab, used: check_polygons(tab, used[0], used[1], "batch", self.polygon_buffer_mb))
+            self.streams.append(self.poly_out)
         self.ev_h2d = [torch.cuda.Event() for _ in range(2)]
         self.ev_enc = [torch.cuda.Event() for _ in range(2)]
         self.ev_dec = [torch.cuda.Event() for _ in range(2)]
         self.ev_in_free = [torch.cuda.Event() for _ in range(2)]     # encoder has consumed input set b
         self.free_out: "queue.Queue[_OutBuf]" = queue.Queue()
         for _ in range(out_depth):
-            self.free_out.put(_OutBuf(batch, side, max_boxes, rle, self.png, self.min_region_area > 0, self.mask_boxes, self.quality,
-                                      self.polygons))
+            self.free_out.put(_OutBuf(batch, side, max_boxes, self.tables, self.streams))
 
     def _resolve_batch_decode(self, batch_decode) -> Tuple[bool, str]:
         """(on, why).  "auto": the pure rule, then the engine's own answer to the capacity it asks for."""
@@ -723,12 +829,15 @@ class TilePipeline:
             self.ev_enc[b].record(self.s_enc)
             self.ev_in_free[b].record(self.s_enc)
 
-    multimask = False
+    multimask = False      # InstancePipeline sets these three
+    gt = False
+    INSTANCE = False
 
     def _tile_prompts(self, b: int, tile, hw, off: int, nb: int):
-        """(boxes, point_coords, point_labels, mask_input) of a tile's nb prompts, as _decode_tile issues them per chunk."""
+        """(boxes, point_coords, point_labels, mask_input) of the nb staged annotations from row `off` of input set b: a tile's
+        (batch_decode) or a chunk's.  The only place that turns annotations into prompts."""
         in_size = (int(tile.shape[0]), int(tile.shape[1]))
-        return self._input_frame_boxes(self.dev_box[b][off:off + nb], hw, in_size), None, None, None
+        return self._input_frame_boxes(self.dev_box[b][off:off + nb], hw, in_size), None, None, None           # :174
 
     def _decode_multi(self, b: int, tiles, offs):
         """batch_decode: the prompts of every tile of batch b in one predict_multi call -> per tile (masks, iou, low)."""
@@ -739,6 +848,15 @@ class TilePipeline:
                                                [tuple(hw) for _, hw in tiles])
         return list(zip(masks, iou, low))
 
+    def _chunk_masks(self, b: int, i: int, tile, hw, off: int, s: int, e: int, pre):
+        """(masks, iou, low) of prompts s..e of tile i: rows of `pre`, the tile's output of _decode_multi (batch_decode), or with
+        pre None one predict call of its own."""
+        if pre is not None:
+            return pre[0][s:e], pre[1][s:e], pre[2][s:e]
+        in_size = (int(tile.shape[0]), int(tile.shape[1]))
+        return self.eng.predict(b * self.batch + i, *self._tile_prompts(b, tile, hw, off + s, e - s), self.multimask, False, in_size,
+                                tuple(hw))
+
     def _decode_tile(self, b: int, i: int, tile, hw, off: int, nb: int, out: _OutBuf, pre=None) -> None:
         """Everything the reference does per image after set_image (main_sam_hbox_semantic.py:157-206), on s_dec.  pre: the
         tile's (masks, iou, low) from _decode_multi (batch_decode), or None to predict here, chunk by chunk."""
@@ -748,11 +866,7 @@ class TilePipeline:
         seg = self.seg_dev[b][i] if native else torch.full((H, W), 255, dtype=torch.uint8, device=self.dev)
         kept = []
         for s, e in box_chunks(nb, self.box_batch):                          # :157-181
-            if pre is not None:
-                masks, iou, low = pre[0][s:e], pre[1][s:e], pre[2][s:e]
-            else:
-                tb = self._input_frame_boxes(self.dev_box[b][off + s:off + e], (H, W), in_size)   # :174
-                masks, iou, low = eng.predict(b * self.batch + i, tb, None, None, None, False, False, in_size, (H, W))
+            masks, iou, low = self._chunk_masks(b, i, tile, hw, off, s, e, pre)
             if self.quality:                                                      # score, then filter: before anything reads the masks
                 self._score(b, i, off, s, e, masks[:, 0], iou, low, in_size, (H, W))
             if self.min_region_area:                                              # before anything else reads the masks
@@ -762,15 +876,15 @@ class TilePipeline:
                 eng.mask_boxes(masks[:, 0], (0, 0), self.hbox_dev[b][i, s:e], self.rbox_dev[b][i, s:e], self.rec_dev[b][i, s:e])
             if self.polygons:                                                     # of the masks as they go out
                 eng.mask_polygons(masks[:, 0], (0, 0), self.polygon_max_edges, self.poly_vert_dev[b], self.poly_ring_dev[b],
-                                  self.poly_cur[b], self.poly_tab[b][off + s:off + e])
+                                  self.poly_out.cur[b], self.poly_out.tab[b][off + s:off + e])
             eng.paint(masks[:, 0], self.dev_lab[b][off + s:off + e], seg, self.class_pixels, self.class_instances,
                       areas_out=self.area_dev[b][i, s:e])
             if self.rle:                                                          # :201-202, on the device
-                eng.rle_encode(masks[:, 0], self.rle_dev[b], self.rle_cur[b], self.rle_tab[b][off + s:off + e])
+                eng.rle_encode(masks[:, 0], self.rle_dev[b], self.rle_out.cur[b], self.rle_out.tab[b][off + s:off + e])
             if self.keep_masks:
                 kept.append(masks[:, 0].view(torch.uint8))
         if self.png and not native:                                              # an odd-sized tile: its own call
-            eng.png_encode(seg, self.png_lut, self.png_dev[b], self.png_cur[b], self.png_tab[b][i:i + 1])
+            eng.png_encode(seg, self.png_lut, self.png_dev[b], self.png_out.cur[b], self.png_out.tab[b][i:i + 1])
         if native:
             out.seg[i].copy_(seg, non_blocking=True)
         else:
@@ -802,39 +916,18 @@ class TilePipeline:
         with torch.cuda.stream(self.s_dec):
             self.s_dec.wait_event(self.ev_enc[b])
             self.seg_dev[b].fill_(255)                                               # main_sam_hbox_semantic.py:162
-            if self.rle:
-                self.rle_cur[b].zero_()
-            if self.png:
-                self.png_cur[b].zero_()
-            if self.polygons:
-                self.poly_cur[b].zero_()
+            for st in self.streams:
+                st.reset(b)
             with self._mode():
                 pre = self._decode_multi(b, tiles, offs) if self.batch_decode and sum(nb for _, nb in offs) else None
                 for i, ((t, hw), (off, nb)) in enumerate(zip(tiles, offs)):
                     self._decode_tile(b, i, t, hw, off, nb, out, None if pre is None else pre[i])
             if self.png:
                 self._encode_png(b, tiles)
-            out.areas.copy_(self.area_dev[b], non_blocking=True)
-            if self.min_region_area:
-                out.changed.copy_(self.chg_dev[b], non_blocking=True)
-            if self.mask_boxes:
-                out.hbox.copy_(self.hbox_dev[b], non_blocking=True)
-                out.rbox.copy_(self.rbox_dev[b], non_blocking=True)
-                out.record.copy_(self.rec_dev[b], non_blocking=True)
-            if self.quality:
-                out.counts.copy_(self.cnt_dev[b], non_blocking=True)
-                out.kept.copy_(self.keep_dev[b], non_blocking=True)
-                out.quality.copy_(self.qual_dev[b], non_blocking=True)
-            if self.polygons:
-                out.poly_tab.copy_(self.poly_tab[b], non_blocking=True)
-                out.poly_cur.copy_(self.poly_cur[b], non_blocking=True)
-            if self.rle:
-                out.rle_tab.copy_(self.rle_tab[b], non_blocking=True)
-                out.rle_cur.copy_(self.rle_cur[b], non_blocking=True)
-            if self.png:
-                out.png_tab.copy_(self.png_tab[b], non_blocking=True)
-                out.png_cur.copy_(self.png_cur[b], non_blocking=True)
-            self._extra_outputs(b, out)
+            for t in self.tables:
+                out.tables[t.field].copy_(getattr(self, t.dev)[b], non_blocking=True)
+            for st in self.streams:
+                st.copy_table(b, out)
             self.ev_dec[b].record(self.s_dec)
             out.done.record(self.s_dec)
 
@@ -850,105 +943,41 @@ class TilePipeline:
                 runs.append([i])
         for r in runs:
             i0, i1 = r[0], r[-1] + 1
-            self.eng.png_encode(self.seg_dev[b][i0:i1], self.png_lut, self.png_dev[b], self.png_cur[b], self.png_tab[b][i0:i1])
-
-    def _extra_outputs(self, b: int, out: _OutBuf) -> None:
-        pass
-
-    def _fetch_extra(self, b: int, out: _OutBuf, n_boxes: int):
-        return None
-
-    def _extra_result(self, r: TileResult, i: int, off: int, nb: int, out: _OutBuf, extra) -> None:
-        pass
-
-    def _fetch_rle(self, b: int, out: _OutBuf, n_boxes: int):
-        """The batch's RLE strings: the table and the byte count are on the host (out.done), so the strings can be copied
-        with their exact size -- on a copy stream, while the GPU works on the batches already queued."""
-        tab, out.rle_bytes = self._fetch_strings(self.rle_dev[b], out.rle_cur, out.rle_tab, out.rle_bytes, n_boxes)
-        return tab, out.rle_bytes.numpy()
-
-    def _fetch_png(self, b: int, out: _OutBuf, n_tiles: int):
-        """The batch's PNG files, fetched like the RLE strings: table + exact byte count on the host, then one exact-size D2H."""
-        tab, out.png_bytes = self._fetch_strings(self.png_dev[b], out.png_cur, out.png_tab.view(-1, 2), out.png_bytes, 2 * n_tiles,
-                                                 what="PNG buffer too small: a file", knob="png_buffer_mb")
-        return tab.reshape(-1, 2, 2), out.png_bytes.numpy()
-
-    def _fetch_polygons(self, b: int, out: _OutBuf, n_boxes: int):
-        """The batch's polygons, fetched like the RLE strings: table + cursor on the host, then exact-size D2H of the vertices and
-        the ring records.  A mask that did not fit raises, naming polygon_buffer_mb; a mask over the edge cap stays (-1, -1)."""
-        tab = out.poly_tab[:n_boxes].numpy().copy()
-        nv, nr = int(out.poly_cur[0]), int(out.poly_cur[1])
-        if n_boxes and int(tab[:, 1].min()) < -1:
-            j = int(np.argmin(tab[:, 1]))
-            raise RuntimeError(f"polygon buffer too small: a mask needs {int(-tab[j, 3] - 1)} vertices and {int(-tab[j, 1] - 1)} rings and "
-                               f"the batch already holds {nv} and {nr}; raise polygon_buffer_mb (now {self.polygon_buffer_mb})")
-        if out.poly_vert.shape[0] < nv:
-            out.poly_vert = torch.empty(max(nv, 2 * out.poly_vert.shape[0]), 2, dtype=torch.int32).pin_memory()
-        if out.poly_ring.shape[0] < nr:
-            out.poly_ring = torch.empty(max(nr, 2 * out.poly_ring.shape[0]), 4, dtype=torch.int32).pin_memory()
-        if nv or nr:
-            with torch.cuda.stream(self.s_d2h):
-                out.poly_vert[:nv].copy_(self.poly_vert_dev[b][:nv], non_blocking=True)
-                out.poly_ring[:nr].copy_(self.poly_ring_dev[b][:nr], non_blocking=True)
-            self.s_d2h.synchronize()
-        return tab, out.poly_ring[:nr].numpy(), out.poly_vert[:nv].numpy()
-
-    def _fetch_strings(self, dev: torch.Tensor, cur: torch.Tensor, tab_host: torch.Tensor, host: torch.Tensor, n_boxes: int,
-                       what: str = "RLE buffer too small: a mask", knob: str = "rle_buffer_mb"):
-        """(table, pinned host bytes) of one packed string buffer (samrs_rle_encode's layout); `host` grows when too small."""
-        total = int(cur[0])
-        tab = tab_host[:n_boxes].numpy()
-        if n_boxes and int(tab[:, 1].min()) < 0:
-            need = int((-tab[:, 1] - 1).max())
-            raise RuntimeError(f"{what} needs {need} bytes and the batch already holds {total}; raise "
-                               f"{knob} (now {dev.numel() >> 20})")
-        if host.numel() < total:
-            host = torch.empty(max(total, 2 * host.numel()), dtype=torch.uint8).pin_memory()
-        if total:
-            with torch.cuda.stream(self.s_d2h):
-                host[:total].copy_(dev[:total], non_blocking=True)
-            self.s_d2h.synchronize()
-        return tab, host
+            self.eng.png_encode(self.seg_dev[b][i0:i1], self.png_lut, self.png_dev[b], self.png_out.cur[b], self.png_out.tab[b][i0:i1])
 
     def _finish(self, pending, sink):
         items, offs, out, b = pending
         out.done.synchronize()
         odd = out.odd
         res = []
-        rtab = rdat = None
+        n_boxes = sum(nb for _, nb in offs)
         if self.rle:
-            rtab, rdat = self._fetch_rle(b, out, sum(nb for _, nb in offs))
-        ptab = pdat = None
-        if self.png:
-            ptab, pdat = self._fetch_png(b, out, len(items))
-        gtab = gring = gvert = None
+            rtab, (rdat,), _ = self.rle_out.fetch(b, out, n_boxes)
+            if self.gt:
+                ttab, (tdat,), _ = self.gt_rle_out.fetch(b, out, n_boxes)
+        if self.png:                                        # two table rows per tile: its gray and its colour file
+            ptab, (pdat,), _ = self.png_out.fetch(b, out, 2 * len(items))
+            ptab = ptab.reshape(-1, 2, 2)
         if self.polygons:
-            gtab, gring, gvert = self._fetch_polygons(b, out, sum(nb for _, nb in offs))
-        extra = self._fetch_extra(b, out, sum(nb for _, nb in offs))
+            gtab, (gvert, gring), (nv, nr) = self.poly_out.fetch(b, out, n_boxes)
+            gtab, gvert, gring = gtab.copy(), gvert[:nv].numpy(), gring[:nr].numpy()
         for i, (it, (off, nb)) in enumerate(zip(items, offs)):
             seg = (odd[i].numpy() if odd[i] is not None else None) if i in odd else out.seg[i].numpy()
             m = out.masks[i].numpy() if out.masks[i] is not None else None
-            q = out.quality[i, :nb].numpy().copy() if out.quality is not None else None      # instance pipelines; quality=True
-            r = TileResult(it.key, seg, out.areas[i, :nb].numpy().copy(), np.asarray(it.boxes), np.asarray(it.labels), m, q)
+            r = TileResult(it.key, seg, boxes=np.asarray(it.boxes), labels=np.asarray(it.labels), masks=m,
+                           **{t.field: t.rows(out.tables[t.field][i, :nb]) for t in self.tables})
             if seg is not None:
                 r.size = (int(seg.shape[0]), int(seg.shape[1]))
             else:
                 r.size = (int(it.image.shape[0]), int(it.image.shape[1]))
             if self.rle:
-                r.rle_table, r.rle_data = rtab[off:off + nb], rdat
+                r.rle_table, r.rle_data = rtab[off:off + nb], rdat.numpy()
+                if self.gt:
+                    r.gt_rle_table, r.gt_rle_data = ttab[off:off + nb], tdat.numpy()
             if self.png:
-                r.png_table, r.png_data = ptab[i], pdat
-            if self.min_region_area:
-                r.changed = out.changed[i, :nb].numpy().copy()
-            if self.mask_boxes:
-                r.mask_hbox, r.mask_rbox = out.hbox[i, :nb].numpy().copy(), out.rbox[i, :nb].numpy().copy()
-                r.mask_record = out.record[i, :nb].numpy().copy()
+                r.png_table, r.png_data = ptab[i], pdat.numpy()
             if self.polygons:
                 r.polygon_table, r.polygon_rings, r.polygon_vertices = gtab[off:off + nb], gring, gvert
-            if self.quality:
-                r.score_counts = out.counts[i, :nb].numpy().copy()
-                r.kept = out.kept[i, :nb].numpy().astype(bool)
-            self._extra_result(r, i, off, nb, out, extra)
             res.append(r)
         out.odd = {}
         release = lambda o=out: self.free_out.put(o)
@@ -1026,6 +1055,7 @@ class InstancePipeline(TilePipeline):
     gt_area - inter); with ``rle=True`` the ground-truth masks are RLE-encoded on the device too (``TileResult.gt_rle``)."""
 
     BOX_WIDTH = 8          # four (x, y) corners
+    INSTANCE = True
 
     def __init__(self, sam, n_classes: int, prompt: str = "box", multimask: bool = True, fill_rule: str = "auto", gt: bool = False,
                  **kw):
@@ -1044,40 +1074,16 @@ class InstancePipeline(TilePipeline):
             raise ValueError("InstancePipeline paints no class map: png_lut is a TilePipeline option")
         if kw.get("polygons"):
             raise ValueError("InstancePipeline does not trace polygons: polygons is a TilePipeline / ScenePipeline option")
+        self.gt = bool(gt)             # read by TilePipeline.__init__: the ground-truth tables and stream are allocated with the rest
         super().__init__(sam, n_classes, precision=kw.pop("precision", "auto"), _multimask=bool(multimask), **kw)
         self.prompt, self.multimask = prompt, bool(multimask)
-        self.qual_dev = [torch.zeros(self.batch, self.max_boxes, dtype=torch.float32, device=self.dev) for _ in range(2)]
-        for _ in range(self.free_out.qsize()):
-            o = self.free_out.get()
-            o.quality = torch.empty(self.batch, self.max_boxes, dtype=torch.float32).pin_memory()
-            self.free_out.put(o)
         self.last_masks = None
-        self.gt = bool(gt)
         if self.gt:
             dev, B, M = self.dev, self.batch, self.max_boxes
             self.pin_col = [torch.empty(B * M, 3, dtype=torch.uint8).pin_memory() for _ in range(2)]
             self.dev_col = [torch.empty(B * M, 3, dtype=torch.uint8, device=dev) for _ in range(2)]
             self.gt_lab: List[List[torch.Tensor]] = [[], []]          # per input set: the label images on the device
             self.ev_gt = [torch.cuda.Event() for _ in range(2)]
-            self.inter_dev = [torch.zeros(B, M, dtype=torch.int64, device=dev) for _ in range(2)]
-            self.gta_dev = [torch.zeros(B, M, dtype=torch.int64, device=dev) for _ in range(2)]
-            if self.rle:
-                self.gt_rle_dev = [torch.empty_like(t) for t in self.rle_dev]
-                self.gt_rle_cur = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(2)]
-                self.gt_rle_tab = [torch.zeros(B * M, 3, dtype=torch.int64, device=dev) for _ in range(2)]
-                if self.mask_boxes:
-                    self.gt_hbox_dev = [torch.zeros(B, M, 4, dtype=torch.int32, device=dev) for _ in range(2)]
-            for _ in range(self.free_out.qsize()):
-                o = self.free_out.get()
-                o.inter = torch.empty(B, M, dtype=torch.int64).pin_memory()
-                o.gt_area = torch.empty(B, M, dtype=torch.int64).pin_memory()
-                if self.rle:
-                    o.gt_rle_tab = torch.zeros(B * M, 3, dtype=torch.int64).pin_memory()
-                    o.gt_rle_cur = torch.zeros(1, dtype=torch.int64).pin_memory()
-                    o.gt_rle_bytes = torch.empty(1 << 20, dtype=torch.uint8).pin_memory()
-                    if self.mask_boxes:
-                        o.gt_hbox = torch.empty(B, M, 4, dtype=torch.int32).pin_memory()
-                self.free_out.put(o)
 
     def _stage(self, b: int, items: List[WorkItem]):
         if not self.gt:
@@ -1114,19 +1120,14 @@ class InstancePipeline(TilePipeline):
         self.gt_lab[b] = labs
         return out
 
-    def _decode(self, b, items, tiles, offs, out):
-        if self.gt and self.rle:
-            with torch.cuda.stream(self.s_dec):
-                self.gt_rle_cur[b].zero_()
-        super()._decode(b, items, tiles, offs, out)
-
     def _tile_prompts(self, b: int, tile, hw, off: int, nb: int):
         from . import transforms
         in_size = (int(tile.shape[0]), int(tile.shape[1]))
         ann = self.dev_box[b][off:off + nb]
         if self.prompt == "box":
             polys = ann.view(-1, 4, 2)
-            return self._input_frame_boxes(torch.cat([polys.amin(1), polys.amax(1)], dim=1), hw, in_size), None, None, None
+            hb = torch.cat([polys.amin(1), polys.amax(1)], dim=1)                                   # :125-130
+            return self._input_frame_boxes(hb, hw, in_size), None, None, None
         if self.prompt == "rbox_mask":
             side = 4 * self.sam.cfg.grid
             pr = (transforms.rbox_mask_prompts_device(ann.view(-1, 4, 2), hw, self.side, device=self.dev, fill_rule=self.fill_rule)
@@ -1135,27 +1136,12 @@ class InstancePipeline(TilePipeline):
         return None, ann.view(-1, 1, 2), torch.ones(nb, 1, dtype=torch.int32, device=self.dev), None
 
     def _decode_tile(self, b, i, tile, hw, off, nb, out, pre=None) -> None:
-        from . import transforms
-        eng, (H, W) = self.eng, hw
-        in_size = (int(tile.shape[0]), int(tile.shape[1]))
-        slot, mm = b * self.batch + i, self.multimask
+        eng = self.eng
         kept = []
         if self.gt:
             self.s_dec.wait_event(self.ev_gt[b])
         for s, e in box_chunks(nb, self.box_batch):
-            ann = self.dev_box[b][off + s:off + e]
-            if pre is not None:
-                m, q = pre[0][s:e], pre[1][s:e]
-            elif self.prompt == "box":
-                polys = ann.view(-1, 4, 2)
-                hb = torch.cat([polys.amin(1), polys.amax(1)], dim=1)                                   # :125-130
-                m, q, _ = eng.predict(slot, self._input_frame_boxes(hb, (H, W), in_size), None, None, None, mm, False, in_size, (H, W))
-            elif self.prompt == "rbox_mask":
-                pr = transforms.rbox_mask_prompts_device(ann.view(-1, 4, 2), (H, W), self.side, device=self.dev, fill_rule=self.fill_rule)
-                m, q, _ = eng.predict(slot, None, None, None, pr[:, None], mm, False, in_size, (H, W))
-            else:
-                pl = torch.ones(e - s, 1, dtype=torch.int32, device=self.dev)
-                m, q, _ = eng.predict(slot, None, ann.view(-1, 1, 2), pl, None, mm, False, in_size, (H, W))
+            m, q, _ = self._chunk_masks(b, i, tile, hw, off, s, e, pre)
             # best of the C masks by predicted IoU, its quality and area: one pass on the device, straight into the tables
             mk, _, _ = eng.select_best(m, q, None, self.qual_dev[b][i, s:e], self.area_dev[b][i, s:e])
             if self.min_region_area:                      # the area table then holds the cleaned areas (select_best's are stale)
@@ -1164,42 +1150,16 @@ class InstancePipeline(TilePipeline):
             if self.mask_boxes:                           # of the kept mask, as it goes out
                 eng.mask_boxes(mk, (0, 0), self.hbox_dev[b][i, s:e], self.rbox_dev[b][i, s:e], self.rec_dev[b][i, s:e])
             if self.rle:
-                eng.rle_encode(mk, self.rle_dev[b], self.rle_cur[b], self.rle_tab[b][off + s:off + e])
+                eng.rle_encode(mk, self.rle_dev[b], self.rle_out.cur[b], self.rle_out.tab[b][off + s:off + e])
             if self.gt:                                   # main_sam_rhbox_mask_instance.py:204-238, on the device
                 gm = torch.empty_like(mk) if self.rle else None
                 eng.gt_match(mk, self.gt_lab[b][i], self.dev_col[b][off + s:off + e], self.inter_dev[b][i, s:e],
                              self.gta_dev[b][i, s:e], gm)
                 if self.rle:                              # instance_to_json.py:44-45
-                    eng.rle_encode(gm, self.gt_rle_dev[b], self.gt_rle_cur[b], self.gt_rle_tab[b][off + s:off + e])
+                    eng.rle_encode(gm, self.gt_rle_dev[b], self.gt_rle_out.cur[b], self.gt_rle_out.tab[b][off + s:off + e])
                     if self.mask_boxes:                   # the ground-truth masks are on the device here: their hbox too
                         eng.mask_boxes(gm, (0, 0), self.gt_hbox_dev[b][i, s:e], False, False)
             kept.append(mk)
         self.last_masks = kept[-1].view(torch.bool) if kept else None
         out.masks[i] = torch.cat(kept).cpu() if (self.keep_masks and kept) else None
         out.odd[i] = None                      # instance pipelines paint no class map
-
-    def _extra_outputs(self, b: int, out: _OutBuf) -> None:
-        out.quality.copy_(self.qual_dev[b], non_blocking=True)
-        if self.gt:
-            out.inter.copy_(self.inter_dev[b], non_blocking=True)
-            out.gt_area.copy_(self.gta_dev[b], non_blocking=True)
-            if self.rle:
-                out.gt_rle_tab.copy_(self.gt_rle_tab[b], non_blocking=True)
-                out.gt_rle_cur.copy_(self.gt_rle_cur[b], non_blocking=True)
-                if self.mask_boxes:
-                    out.gt_hbox.copy_(self.gt_hbox_dev[b], non_blocking=True)
-
-    def _fetch_extra(self, b: int, out: _OutBuf, n_boxes: int):
-        if not (self.gt and self.rle):
-            return None
-        tab, out.gt_rle_bytes = self._fetch_strings(self.gt_rle_dev[b], out.gt_rle_cur, out.gt_rle_tab, out.gt_rle_bytes, n_boxes)
-        return tab, out.gt_rle_bytes.numpy()
-
-    def _extra_result(self, r: TileResult, i: int, off: int, nb: int, out: _OutBuf, extra) -> None:
-        if not self.gt:
-            return
-        r.inter, r.gt_area = out.inter[i, :nb].numpy().copy(), out.gt_area[i, :nb].numpy().copy()
-        if extra is not None:
-            r.gt_rle_table, r.gt_rle_data = extra[0][off:off + nb], extra[1]
-            if self.mask_boxes:
-                r.gt_hbox = out.gt_hbox[i, :nb].numpy().copy()

@@ -120,17 +120,13 @@ class ScenePipeline:
                  quality: bool = False, min_stability: float = 0.0, min_pred_iou: float = 0.0, min_inside_box: float = 0.0,
                  polygons: bool = False, polygon_buffer_mb: int = 64, polygon_max_edges: int = 65536):
         import torch
-        from .driver import TilePipeline, refuse_quality_options
+        from .driver import TilePipeline, output_tables, refuse_quality_options, validate_output_options
         refuse_quality_options("ScenePipeline", "scoring across scene windows is not built", quality=quality,
                                min_stability=min_stability, min_pred_iou=min_pred_iou, min_inside_box=min_inside_box)
-        from .engine import REGION_MODES
         from .transforms import ResizeLongestSide
         if not 0 <= int(overlap) < int(window):
             raise ValueError(f"overlap must satisfy 0 <= overlap < window, got overlap={overlap}, window={window}")
-        if int(min_region_area) < 0:
-            raise ValueError("min_region_area must be >= 0 (0 = off)")
-        if region_mode not in REGION_MODES:
-            raise ValueError(f"region_mode must be one of {sorted(REGION_MODES)}, got {region_mode!r}")
+        lut, nv = validate_output_options(min_region_area, region_mode, polygons, polygon_buffer_mb, polygon_max_edges, png_lut)
         eng = sam.engine
         if eng is None:
             raise RuntimeError("move the model to the GPU first: sam.to('cuda')")
@@ -144,11 +140,9 @@ class ScenePipeline:
         self.min_region_area, self.region_mode = int(min_region_area), region_mode
         self.mask_boxes = bool(mask_boxes)
         self.polygons = bool(polygons)
+        self.tables = output_tables(self.min_region_area, self.mask_boxes)      # per scene: one device table of n rows each
         if self.polygons:
-            if int(polygon_buffer_mb) < 1 or int(polygon_max_edges) < 4:
-                raise ValueError("polygon_buffer_mb must be >= 1 and polygon_max_edges >= 4")
             self.polygon_buffer_mb, self.polygon_max_edges = int(polygon_buffer_mb), int(polygon_max_edges)
-            nv = (self.polygon_buffer_mb << 20) // 12              # 8 bytes per vertex + 16 per ring, a ring has >= 4 vertices
             self.poly_vert_dev = torch.empty(nv, 2, dtype=torch.int32, device=eng.device)
             self.poly_ring_dev = torch.empty(nv // 4, 4, dtype=torch.int32, device=eng.device)
         # the operand-split mode of this pipeline's own calls: TilePipeline's rule and TilePipeline's scoping
@@ -171,9 +165,6 @@ class ScenePipeline:
         # for tools/scene_bench.py's attribution run only -- the synchronises cost throughput
         self.stage_seconds: Optional[dict] = None
         if self.png:
-            lut = np.ascontiguousarray(png_lut, dtype=np.uint8)
-            if lut.shape != (256, 3):
-                raise ValueError("png_lut must be uint8 [256, 3] (tile_io.class_lut)")
             self.png_lut = torch.from_numpy(lut).to(self.dev)
             self.png_dev = None
         if self.rle:
@@ -206,7 +197,7 @@ class ScenePipeline:
 
     def _run_scene(self, it):
         import torch
-        from .driver import TileResult, box_chunks
+        from .driver import TileResult, box_chunks, check_packed, check_polygons
         eng, dev = self.eng, self.dev
         t_stage = [time.perf_counter()]
 
@@ -238,12 +229,7 @@ class ScenePipeline:
         w_lab = torch.from_numpy(labels[perm]).to(dev)
         w_rank = dev_perm.to(torch.int32)
         order = torch.full((H, W), -1, dtype=torch.int32, device=dev)
-        w_areas = torch.zeros(n, dtype=torch.int64, device=dev)
-        w_changed = torch.zeros(n, dtype=torch.int64, device=dev) if self.min_region_area else None
-        if self.mask_boxes:
-            w_hbox = torch.zeros(n, 4, dtype=torch.int32, device=dev)
-            w_rbox = torch.zeros(n, 4, 2, dtype=torch.float32, device=dev)
-            w_rec = torch.zeros(n, 8, dtype=torch.int64, device=dev)
+        tabs = {t.field: t.alloc(1, n, dev)[0] for t in self.tables}        # the per-box tables, rows in window order
         if self.polygons:
             w_ptab = torch.zeros(n, 5, dtype=torch.int64, device=dev)
             poly_cur = torch.zeros(2, dtype=torch.int64, device=dev)
@@ -285,14 +271,14 @@ class ScenePipeline:
                         masks, _, _ = eng.predict(b * self.batch + i, tb, None, None, None, False, False, in_sizes[g][i], (h, w))
                     m = masks[:, 0]
                     if self.min_region_area:                                      # before anything else reads the masks
-                        eng.clean_masks(m, self.min_region_area, self.region_mode, areas_out=False, changed_out=w_changed[s:e])
+                        eng.clean_masks(m, self.min_region_area, self.region_mode, areas_out=False, changed_out=tabs["changed"][s:e])
                     if self.mask_boxes:                                           # in the scene's frame: the window's origin
-                        eng.mask_boxes(m, (x0, y0), w_hbox[s:e], w_rbox[s:e], w_rec[s:e])
+                        eng.mask_boxes(m, (x0, y0), tabs["mask_hbox"][s:e], tabs["mask_rbox"][s:e], tabs["mask_record"][s:e])
                     if self.polygons:                                             # lattice vertices in the scene's frame
                         eng.mask_polygons(m, (x0, y0), self.polygon_max_edges, self.poly_vert_dev, self.poly_ring_dev, poly_cur,
                                           w_ptab[s:e])
                     eng.scene_claim(m, w_rank[s:e], win, order, w_lab[s:e], self.class_pixels, self.class_instances,
-                                    areas_out=w_areas[s:e])
+                                    areas_out=tabs["areas"][s:e])
                     if self.rle:
                         eng.rle_encode_placed(m, win, (H, W), self.rle_dev, rle_cur, w_tab[s:e])
             self.ev_dec[b].record(cur)
@@ -319,29 +305,20 @@ class ScenePipeline:
                 self._png_warned = True
                 warnings.warn(f"scene {it.key!r} ({H} x {W}) exceeds the device PNG encoder's limit; this and any later such scene "
                               "carry no device PNG (TileResult.png_table is None): write them with tile_io.write_label_pair")
-        r = TileResult(it.key, seg.cpu().numpy(), unpermute(w_areas.cpu().numpy()), np.asarray(it.boxes), np.asarray(it.labels))
+        r = TileResult(it.key, seg.cpu().numpy(), boxes=np.asarray(it.boxes), labels=np.asarray(it.labels),
+                       **{f: unpermute(t.cpu().numpy()) for f, t in tabs.items()})
         r.size = (H, W)
         r.windows, r.window_of = windows, window_of
-        if w_changed is not None:
-            r.changed = unpermute(w_changed.cpu().numpy())
-        if self.mask_boxes:
-            r.mask_hbox, r.mask_rbox = unpermute(w_hbox.cpu().numpy()), unpermute(w_rbox.cpu().numpy())
-            r.mask_record = unpermute(w_rec.cpu().numpy())
         if self.polygons:
             ptab = unpermute(w_ptab.cpu().numpy())
             nv, nr = (int(v) for v in poly_cur.cpu().tolist())
-            if n and int(ptab[:, 1].min()) < -1:
-                j = int(np.argmin(ptab[:, 1]))
-                raise RuntimeError(f"polygon buffer too small: a mask needs {int(-ptab[j, 3] - 1)} vertices and {int(-ptab[j, 1] - 1)} "
-                                   f"rings and the scene already holds {nv} and {nr}; raise polygon_buffer_mb (now {self.polygon_buffer_mb})")
+            check_polygons(ptab, nv, nr, "scene", self.polygon_buffer_mb)
             r.polygon_table = ptab
             r.polygon_rings, r.polygon_vertices = self.poly_ring_dev[:nr].cpu().numpy(), self.poly_vert_dev[:nv].cpu().numpy()
         if self.rle:
             tab = unpermute(w_tab.cpu().numpy())
             total = int(rle_cur.item())
-            if n and int(tab[:, 1].min()) < 0:
-                raise RuntimeError(f"RLE buffer too small: a mask needs {int((-tab[:, 1] - 1).max())} bytes and the scene already holds "
-                                   f"{total}; raise rle_buffer_mb (now {self.rle_buffer_mb})")
+            check_packed(tab, total, "scene", self.rle_buffer_mb)
             r.rle_table, r.rle_data = tab, self.rle_dev[:total].cpu().numpy()
         if png_tab is not None:
             t = png_tab.cpu().numpy()[0]

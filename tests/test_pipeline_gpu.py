@@ -344,3 +344,89 @@ def test_multimask_after_a_single_mask_pipeline_keeps_its_precision(golden_dir):
     assert i79.min() >= 0.999
     assert i15.min() >= 0.998 and m1.shape[1] == 1
     eng.close()
+
+
+# ---- every output at once against each output alone ---------------------------------------------------------------------------
+_every_output = {}
+
+
+def _every_output_setup():
+    """(sam, items, lut, threshold), made once for both cases: vit_tiny with the seeded weights of a checkpoint-like logit spread
+    (as test_quality_gpu._weights: with the plain ones every stability is 0), one native and one 600 x 800 tile of 4 boxes each, and
+    as threshold the median stability of the eight instances (scored before anything changes the masks), so that half of them drop."""
+    if not _every_output:
+        import samrs_amd
+        from samrs_amd import driver, quality, tile_io
+        weights = synth.make_state_dict(synth.CONFIGS["vit_tiny"], 0, logit_scale=synth.MARGIN_LOGIT_SCALE)
+        sam = samrs_amd.sam_model_registry["vit_tiny"](state_dict=weights, max_images=4, max_prompts=20, precision="f16").to("cuda")
+        items = []
+        for i, (h, w) in enumerate([(1024, 1024), (600, 800)]):
+            boxes, labels = synth.make_boxes(60 + i, 4, h, w)
+            items.append(driver.WorkItem(f"B{i:04d}", synth.make_image(60 + i, h, w), boxes, labels))
+        stab = []
+
+        def sink(results, release):
+            stab.extend(quality.stability(r.score_counts) for r in results)
+            release()
+        driver.TilePipeline(sam, 18, batch=2, box_batch=3, max_boxes=8, quality=True).run(driver.batched(items, 2), sink)
+        lut = tile_io.class_lut(np.random.default_rng(2).integers(0, 256, (18, 3), dtype=np.uint8))
+        _every_output.update(sam=sam, items=items, lut=lut, threshold=float(np.median(np.concatenate(stab))))
+    return (_every_output[k] for k in ("sam", "items", "lut", "threshold"))
+
+
+def _frozen_fields(r) -> dict:
+    """Every non-None field of a TileResult in a form that compares byte for byte and outlives release(): arrays as (dtype, shape,
+    bytes); the packed byte buffers (whole pinned buffers, with alignment gaps) as the strings / files their tables cut out."""
+    import dataclasses
+    out = {}
+    for f in dataclasses.fields(r):
+        v = getattr(r, f.name)
+        if v is None or f.name == "key":
+            continue
+        if f.name == "rle_data":
+            v = [r.rle(j)["counts"] for j in range(len(r.labels))]
+        elif f.name == "png_data":
+            v = [bytes(r.png("gray")), bytes(r.png("color"))]
+        elif isinstance(v, np.ndarray):
+            v = (str(v.dtype), v.shape, v.tobytes())
+        out[f.name] = v
+    return out
+
+
+@pytest.mark.parametrize("batch_decode", [False, True])
+def test_every_output_at_once_equals_each_output_alone(batch_decode):
+    """The outputs are allocated, copied and handed out by loops over one list of declarations (driver.output_tables, the packed
+    streams): a field wired to its neighbour's table would show here.  A TilePipeline with RLE, device PNG, clean-up, mask boxes,
+    quality with a threshold and polygons all on must give, field by field and byte for byte, what a pipeline with that output
+    alone gives (each with the same threshold and clean-up, which change the masks)."""
+    from samrs_amd import driver
+    sam, items, lut, thr = _every_output_setup()
+    common = dict(batch=2, box_batch=3, max_boxes=8, batch_decode=batch_decode, min_region_area=16, min_stability=thr)
+    alone = {"rle": dict(rle=True, rle_buffer_mb=64), "png_lut": dict(png_lut=lut), "mask_boxes": dict(mask_boxes=True),
+             "quality, min_region_area": dict(quality=True), "polygons": dict(polygons=True, polygon_buffer_mb=64, polygon_max_edges=1 << 21)}
+
+    def collect(**kw):
+        pipe, got = driver.TilePipeline(sam, 18, **common, **kw), {}
+
+        def sink(results, release):
+            got.update({r.key: _frozen_fields(r) for r in results})
+            release()
+        assert pipe.run(driver.batched(items, 2), sink) == len(items)
+        return got, pipe.class_pixels.cpu().tolist(), pipe.class_instances.cpu().tolist()
+
+    every, pixels, instances = collect(**{k: v for kw in alone.values() for k, v in kw.items()})
+    kept = np.concatenate([np.frombuffer(every[it.key]["kept"][2], dtype=bool) for it in items])
+    print(f"threshold {thr:.6f}: kept {kept.astype(int).tolist()}")
+    assert kept.any() and not kept.all()                                  # the threshold drops some instances and keeps some
+    want_fields = {"seg_mask", "areas", "boxes", "labels", "size", "changed", "score_counts", "kept", "quality", "rle_table", "rle_data",
+                   "png_table", "png_data", "mask_hbox", "mask_rbox", "mask_record", "polygon_table", "polygon_rings", "polygon_vertices"}
+    covered = set()
+    for name, kw in alone.items():
+        one, pix1, ins1 = collect(**kw)
+        assert (pix1, ins1) == (pixels, instances), name
+        for it in items:
+            assert set(every[it.key]) == want_fields
+            for f, v in one[it.key].items():
+                assert every[it.key][f] == v, f"{it.key}.{f} differs from the pipeline with {name} alone"
+                covered.add(f)
+    assert covered == want_fields                                          # every field was compared with a pipeline that owns it

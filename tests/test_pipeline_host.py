@@ -163,3 +163,96 @@ def test_host_bound_warning_names_the_arithmetic(monkeypatch):
     assert w and "HOST-bound at ~97 images/s" in w and "2 reader + 2 writer threads on a share of 2.0 CPUs" in w
     monkeypatch.setattr(generate, "host_cpu_budget", lambda local_world=None: 16.0)
     assert generate.host_bound_warning(5, 11) is None
+
+
+# ---- the output declarations of the pipelines -----------------------------------------------------------------------------------
+# TileResult's own comments, restated: field -> (dtype of the host rows, shape of one box's row)
+DOCUMENTED = {"areas": (np.int64, ()), "changed": (np.int64, ()), "mask_hbox": (np.int32, (4,)), "mask_rbox": (np.float32, (4, 2)),
+              "mask_record": (np.int64, (8,)), "score_counts": (np.int64, (4,)), "kept": (np.bool_, ()), "quality": (np.float32, ()),
+              "inter": (np.int64, ()), "gt_area": (np.int64, ()), "gt_hbox": (np.int32, (4,))}
+
+
+def test_output_tables_for_every_combination_of_options():
+    """driver.output_tables: the exact set of TileResult fields per combination, all-off = areas (+ quality for an instance
+    pipeline), and each entry's dtype and row shape as TileResult documents them (kept reaches the host as bool)."""
+    import dataclasses
+    import itertools
+    import torch
+    result_fields = {f.name for f in dataclasses.fields(driver.TileResult)}
+    assert [t.field for t in driver.output_tables()] == ["areas"]
+    assert [t.field for t in driver.output_tables(instance=True)] == ["areas", "quality"]
+    for area, boxes, quality, gt, rle_, inst in itertools.product((0, 16), (False, True), (False, True), (False, True), (False, True),
+                                                                  (False, True)):
+        tabs = driver.output_tables(area, boxes, quality, gt, rle_, inst)
+        want = {"areas"}
+        want |= {"changed"} if area else set()
+        want |= {"mask_hbox", "mask_rbox", "mask_record"} if boxes else set()
+        want |= {"score_counts", "kept"} if quality else set()
+        want |= {"quality"} if quality or inst else set()
+        want |= {"inter", "gt_area"} if gt else set()
+        want |= {"gt_hbox"} if gt and rle_ and boxes else set()
+        names = [t.field for t in tabs]
+        assert set(names) == want and len(names) == len(want), (area, boxes, quality, gt, rle_, inst, names)
+        assert want <= result_fields
+        assert len({t.dev for t in tabs}) == len(tabs)                    # no two entries share a device table
+        for t in tabs:
+            dtype, tail = DOCUMENTED[t.field]
+            pinned = torch.zeros(2, 5, *t.tail, dtype=t.dtype)            # what alloc() makes, without the pinning
+            rows = t.rows(pinned[1, :3])
+            assert rows.dtype == dtype and rows.shape == (3, *tail), t.field
+            assert not np.shares_memory(rows, pinned.numpy())              # the result outlives the pinned ring buffer
+            assert t.fill == ("ones" if t.field == "kept" else "zeros")    # nothing is dropped until a threshold says so
+    kept = [t for t in driver.output_tables(quality=True) if t.field == "kept"][0]
+    assert kept.dtype == torch.uint8 and kept.rows(torch.tensor([1, 0, 1], dtype=torch.uint8)).tolist() == [True, False, True]
+
+
+def test_overflow_checks_name_the_option_and_the_holder():
+    """driver.check_packed / check_polygons on hand-built tables: an entry that did not fit (length = -1 - the size needed) raises
+    with the message the pipelines always had, for the batch (TilePipeline) and for the scene (ScenePipeline); a clean table and
+    the polygon "over the edge cap" marker (-1) pass."""
+    clean = np.array([[0, 37, 5], [48, 12, 3]], dtype=np.int64)
+    small = np.array([[0, 37, 5], [-1, -1 - 5000, 0], [-1, -1 - 123, 0]], dtype=np.int64)
+    for holder in ("batch", "scene"):
+        driver.check_packed(clean, 60, holder, 256)
+        driver.check_packed(clean[:0], 0, holder, 256)
+        with pytest.raises(RuntimeError) as e:
+            driver.check_packed(small, 48, holder, 256)
+        assert str(e.value) == (f"RLE buffer too small: a mask needs 5000 bytes and the {holder} already holds 48; raise "
+                                "rle_buffer_mb (now 256)")
+        with pytest.raises(RuntimeError) as e:
+            driver.check_packed(small[:, :2], 48, holder, 6, what="PNG buffer too small: a file", knob="png_buffer_mb")
+        assert str(e.value) == (f"PNG buffer too small: a file needs 5000 bytes and the {holder} already holds 48; raise "
+                                "png_buffer_mb (now 6)")
+        # polygons: (first ring, ring count, first vertex, vertex count, edge count)
+        ok = np.array([[0, 2, 0, 12, 12], [-1, -1, -1, -1, 99999], [2, 0, 12, 0, 0]], dtype=np.int64)      # traced, over the cap, empty
+        driver.check_polygons(ok, 12, 2, holder, 64)
+        driver.check_polygons(ok[:0], 0, 0, holder, 64)
+        full = np.array([[0, 2, 0, 12, 12], [-1, -1 - 3, -1, -1 - 40, 40], [-1, -1, -1, -1, 99999]], dtype=np.int64)
+        with pytest.raises(RuntimeError) as e:
+            driver.check_polygons(full, 12, 2, holder, 64)
+        assert str(e.value) == (f"polygon buffer too small: a mask needs 40 vertices and 3 rings and the {holder} already holds 12 "
+                                "and 2; raise polygon_buffer_mb (now 64)")
+
+
+def test_shared_output_option_validation():
+    """driver.validate_output_options (TilePipeline and ScenePipeline): the texts both always raised, and what it hands back."""
+    v = driver.validate_output_options
+    assert v() == (None, None)
+    with pytest.raises(ValueError) as e:
+        v(region_mode="neither")
+    assert str(e.value) == "region_mode must be one of ['both', 'holes', 'islands'], got 'neither'"
+    with pytest.raises(ValueError) as e:
+        v(min_region_area=-1)
+    assert str(e.value) == "min_region_area must be >= 0 (0 = off)"
+    for kw in (dict(polygon_buffer_mb=0), dict(polygon_max_edges=3)):
+        with pytest.raises(ValueError) as e:
+            v(polygons=True, **kw)
+        assert str(e.value) == "polygon_buffer_mb must be >= 1 and polygon_max_edges >= 4"
+        assert v(polygons=False, **kw) == (None, None)                     # off: its arguments are not read
+    for bad in (np.zeros((255, 3), np.uint8), np.zeros((256, 4), np.uint8), np.zeros(768, np.uint8)):
+        with pytest.raises(ValueError) as e:
+            v(png_lut=bad)
+        assert str(e.value) == "png_lut must be uint8 [256, 3] (tile_io.class_lut)"
+    lut, nv = v(16, "holes", True, 64, 65536, np.arange(768).reshape(256, 3) % 256)
+    assert lut.dtype == np.uint8 and lut.shape == (256, 3) and lut.flags.c_contiguous
+    assert nv == (64 << 20) // 12                                          # 8 bytes per vertex + a quarter of a 16-byte ring record

@@ -14,6 +14,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import samrs_amd  # noqa: E402
 from samrs_amd import driver, synth  # noqa: E402
+from decode_timer import decode_ms, time_decode  # noqa: E402
 
 BATCH, BOXES = 8, 32
 
@@ -29,24 +30,13 @@ def items(n):
 
 def run_arm(sam, work, batch_decode):
     pipe = driver.TilePipeline(sam, 18, batch=BATCH, box_batch=BOXES, max_boxes=BOXES, rle=True, batch_decode=batch_decode)
-    events = []
-    decode = pipe._decode
-
-    def timed(b, its, tiles, offs, out):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        pipe.s_dec.wait_event(pipe.ev_enc[b])          # the decode's own first wait: time the work, not the wait for the encoder
-        e0.record(pipe.s_dec)
-        decode(b, its, tiles, offs, out)
-        e1.record(pipe.s_dec)
-        events.append((e0, e1))
-
-    pipe._decode = timed
+    events = time_decode(pipe)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     n = pipe.run(driver.batched(work, BATCH), lambda res, rel: rel())
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    dec = [a.elapsed_time(b) for a, b in events]
+    dec = decode_ms(events)
     return {"arm": "batch_decode" if batch_decode else "per_tile", "max_prompts": sam.max_prompts, "images": n,
             "images_per_s": round(n / dt, 1), "decode_ms_per_step": round(sum(dec) / len(dec), 3),
             "decode_ms_per_step_min": round(min(dec), 3)}

@@ -21,6 +21,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(1, os.path.join(ROOT, "tests"))
 import samrs_amd  # noqa: E402
 from samrs_amd import driver, synth  # noqa: E402
+from decode_timer import decode_ms, time_decode  # noqa: E402
 import box_ref  # noqa: E402  (tests/box_ref.py: the host restatement)
 from region_ref import speckled_ellipse  # noqa: E402  (tests/region_ref.py: the blob-with-speckle recipe of the tests)
 
@@ -45,19 +46,7 @@ def items(n):
 
 def run_arm(sam, work, on):
     pipe = driver.TilePipeline(sam, 18, batch=BATCH, box_batch=BOXES, max_boxes=BOXES, rle=True, mask_boxes=on)
-    events = []
     nonempty = [0]
-    # timing events around TilePipeline._decode, behind the wait for the encoder that _decode itself begins with (a private
-    # method, as in tools/clean_masks_bench.py: if _decode's first wait changes, this wrapper has to follow)
-    decode = pipe._decode
-
-    def timed(b, its, tiles, offs, out):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        pipe.s_dec.wait_event(pipe.ev_enc[b])          # the decode's own first wait: time the work, not the wait for the encoder
-        e0.record(pipe.s_dec)
-        decode(b, its, tiles, offs, out)
-        e1.record(pipe.s_dec)
-        events.append((e0, e1))
 
     def sink(res, rel):
         for r in res:
@@ -65,13 +54,13 @@ def run_arm(sam, work, on):
                 nonempty[0] += int((r.mask_record[:, 6] > 0).sum())
         rel()
 
-    pipe._decode = timed
+    events = time_decode(pipe)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     n = pipe.run(driver.batched(work, BATCH), sink)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    dec = [a.elapsed_time(b) for a, b in events]
+    dec = decode_ms(events)
     return {"arm": "boxes_on" if on else "boxes_off", "images": n, "images_per_s": round(n / dt, 1),
             "decode_ms_per_step": round(sum(dec) / len(dec), 3), "decode_ms_per_step_min": round(min(dec), 3),
             "non_empty_masks": nonempty[0]}

@@ -17,6 +17,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import samrs_amd  # noqa: E402
 from samrs_amd import driver, synth  # noqa: E402
+from decode_timer import decode_ms, time_decode  # noqa: E402
 
 BATCH, BOXES = 8, 32
 ARMS = {"off": {}, "on": {"quality": True},
@@ -34,17 +35,7 @@ def items(n, pool=64):
 
 def run_arm(sam, work, arm):
     pipe = driver.TilePipeline(sam, 18, batch=BATCH, box_batch=BOXES, max_boxes=BOXES, device_inputs=True, rle_buffer_mb=512, **ARMS[arm])
-    events = []
-    decode = pipe._decode
     dropped = [0]
-
-    def timed(b, its, tiles, offs, out):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        pipe.s_dec.wait_event(pipe.ev_enc[b])          # the decode's own first wait: time the work, not the wait for the encoder
-        e0.record(pipe.s_dec)
-        decode(b, its, tiles, offs, out)
-        e1.record(pipe.s_dec)
-        events.append((e0, e1))
 
     def sink(res, rel):
         for r in res:
@@ -52,13 +43,13 @@ def run_arm(sam, work, arm):
                 dropped[0] += int((~r.kept).sum())
         rel()
 
-    pipe._decode = timed
+    events = time_decode(pipe)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     n = pipe.run(driver.batched(work, BATCH), sink)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    dec = [a.elapsed_time(b) for a, b in events]
+    dec = decode_ms(events)
     return {"arm": arm, "images": n, "images_per_s": round(n / dt, 2), "step_ms": round(1e3 * dt * BATCH / n, 3),
             "decode_ms_per_step": round(sum(dec) / len(dec), 3), "decode_ms_per_step_min": round(min(dec), 3),
             "dropped": dropped[0]}
