@@ -230,7 +230,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(
         out_et[(size_t)row * ld_out + D + 32 + lane] = hi;
     }
     // the rest of a padded row behind the extension: zero, so that a reader which walks whole rows (the side GEMM of lin2's
-    // outlier columns, engine.hip) meets nothing stale there
+    // outlier columns, engine_encode.hip run_block_mlp) meets nothing stale there
     if (n_oc > 0 && out_et)
         for (int c = D + 64 + lane; c < ld_out; c += 64) out_et[(size_t)row * ld_out + c] = 0;
 }
@@ -654,7 +654,7 @@ __global__ __launch_bounds__(512) void window_attention_kernel(
     const float* __restrict__ rel_w, uint16_t* __restrict__ out, int grid, int heads, int n_items,
     uint16_t* __restrict__ out_lo = nullptr /* LO == 1: the split remainder of out (reference-grade mode) */, MxOut mx = MxOut(),
     uint32_t lo_heads = 0xffffffffu /* LO == 1: bit h set = head h writes its remainder (the outlier extension of proj needs the
-                                       heads that hold its columns only: engine.hip EncBlock::oc_heads) */,
+                                       heads that hold its columns only: engine_state.h EncBlock::oc_heads) */,
     int dense = 1 /* 0: queries numbered in window order, 7 strips per item whatever the window's real extent */) {
     using C = WinCfg<HD>;
     constexpr int KS = HD / 16;

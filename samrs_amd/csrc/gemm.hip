@@ -983,7 +983,7 @@ struct LnTail {
     float eps = 0.f;
 };
 
-// EXT (round 6, the outlier-column extension of proj / lin2: engine.hip EncBlock::oc_*): ONE more pair stage behind the K axis whose
+// EXT (round 6, the outlier-column extension of proj / lin2: engine_state.h EncBlock::oc_*): ONE more pair stage behind the K axis whose
 // 64 k come from two dense side operands A_x [M][64], B_x [N][64] (the hi + lo split of up to 32 outlier columns: A_lo | A_hi against
 // B_hi | B_lo) -- the operand A is written by another kernel with its own row stride, so the extra columns cannot simply be appended
 // to its rows as for qkv / lin1.  Only the DMA source of that one stage differs (row stride 64 instead of K); passed in the A_lo /
@@ -2315,7 +2315,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(W4THREADS, W4THREADS), amd
         const uint16_t* nA = A + (size_t)m1 * LD;
         const uint16_t* nB = B + (size_t)n1 * LD;
         // (rd lives across tiles: with an EVEN number of stages per tile it is back at 0 here -- the round-5 behaviour, bit for bit --, with
-        // an odd number (K = 1344: the K = 1280 operands + the 64-column outlier extension, engine.hip) the next tile starts in buffer 1)
+        // an odd number (K = 1344: the K = 1280 operands + the 64-column outlier extension, engine_encode.hip block_route) the next tile starts in buffer 1)
         // stage t feeds stage t + 2 into its own buffer; past the end of this tile that is stage t + 2 - nst of the NEXT tile
         const uint16_t* pa = sA + 2 * XBK;
         const uint16_t* pb = sB + 2 * XBK;
@@ -2788,7 +2788,7 @@ hipError_t launch_gemm_k256(const void* A, const void* B, void* C, const float* 
     return hipGetLastError();
 }
 
-thread_local int tl_gemm_variant = -1;   // per-engine override, set around an engine's launches (engine.hip GemmVariantScope)
+thread_local int tl_gemm_variant = -1;   // per-engine override, set around an engine's launches (engine_state.h GemmVariantScope)
 int g_gemm_variant = 8;   // 0 reg-staged 128^2, 1 +LDS-DMA, 2 +grouped order, 3 reg+grouped, 4 256x128 3-stage pipe, 5 +staggered groups, 6 256x256, 7 2 blocks/CU, 8 auto(5|6|7)
 
 template <int PREC, bool GLDS, int GROUP_M>
@@ -2973,7 +2973,7 @@ __global__ __launch_bounds__(QTHREADS) void gemm_et_mx_kernel(
     const uint16_t* __restrict__ A, const uint16_t* __restrict__ B, void* __restrict__ Cv, const float* __restrict__ bias,
     int M, int N, int K, int accumulate, MxOperands mx, MxOut mxo = MxOut(),
     int ld = 0 /* row stride of A and B in elements, 0 = K */,
-    int ext = 0 /* round 6: the rows carry the 64-column outlier extension behind their K live columns (engine.hip EncBlock::oc_*): the tiles
+    int ext = 0 /* round 6: the rows carry the 64-column outlier extension behind their K live columns (engine_state.h EncBlock::oc_*): the tiles
                    that take NO lo terms (n0 < split_from_n: q and k of the v-third split) read it as one more f16 stage; the tiles that do
                    take them are covered by their fp4 correction segments, which span every column */) {
     constexpr int NI = 5;

@@ -47,7 +47,7 @@ hipError_t launch_gemm_et_lntail(int prec, const void* A, const void* B, float* 
                                  const float* gamma, const float* beta, float eps, void* out_et, unsigned int* counters, hipStream_t s);
 bool gemm_ld_ok(int M, int N, int K, bool gelu);     // a plain ET launch of this shape takes an operand row stride (GemmOpts::ld)
 // C (fp32 [M][N], the residual stream) += A B^T + A_x B_x^T + bias: proj / lin2 with ONE more 64-k stage read from two dense side operands
-// A_x [M][64], B_x [N][64] (hi + lo of the outlier columns, engine.hip EncBlock::oc_*).  gemm_ext_ok: the shapes of the 256 x 320
+// A_x [M][64], B_x [N][64] (hi + lo of the outlier columns, engine_state.h EncBlock::oc_*).  gemm_ext_ok: the shapes of the 256 x 320
 // pair-stage kernel (ViT-H at >= 2 tiles); other shapes add the side product with an accumulating launch of their own.
 bool gemm_ext_ok(int M, int N, int K);
 hipError_t launch_gemm_et_ext(int prec, const void* A, const void* B, const void* Ax, const void* Bx, float* C, const float* bias,

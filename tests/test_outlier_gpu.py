@@ -222,7 +222,7 @@ def test_heavy_tailed_statistical_sample():
     eng = sam.engine
     assert eng.get_option("outlier_cols") == 7 and eng.get_option("outlier_blocks") == cfg.depth
     # every block's qkv / proj operand error is dominated by its outlier columns: in mode 79 these blocks take the exact lo terms of those
-    # columns (plain launches + the extension) instead of the MXFP4 lo terms of all columns (engine.hip oc_dominant)
+    # columns (plain launches + the extension) instead of the MXFP4 lo terms of all columns (engine_encode.hip oc_dominant)
     assert eng.get_option("outlier_dominant_blocks") == cfg.depth
     eng.set_option("allow_reduced", 1)
     pred = samrs_amd.SamPredictor(sam)

@@ -306,7 +306,7 @@ def test_decoder_alone_all_prompt_types(precision):
                          ids=["gln_split", "gln", "unfused"])
 @pytest.mark.parametrize("precision", ["f16", "bf16"])
 def test_decoder_alone_every_route(precision, route):
-    """test_decoder_alone_all_prompt_types on the decoder's other three routes (decode_route, engine.hip): ConvT #1 as a GEMM with the
+    """test_decoder_alone_all_prompt_types on the decoder's other three routes (decode_route, engine_decode.hip): ConvT #1 as a GEMM with the
     LayerNorm2d + GELU epilogue followed by upscale2_masks, on split operands (split 15) and on plain ones (split 3), and the
     un-fused kernels (decoder_fusion = 0).  Same cases, same bounds: measured under the library of the commit before decode_route
     existed, the worst route (bf16, un-fused) reaches rel L2 4.4e-3 of 1.2e-2, max err / std 2.7e-2 of 5e-2, IoU-prediction error
@@ -369,7 +369,7 @@ def _prompt_side_fp64(so, sd64, cfg, points, boxes, mask):
 def test_decoder_stagewise(precision, fusion):
     """The decoder stage by stage (the counterpart of test_encoder_blockwise): oracle embedding installed, one predict per
     prompt kind (box; 8 points, which adds the pad point: T = 14; box + mask), then the engine's internal buffers against
-    the oracle's taps.  What each buffer holds when samrs_predict returns (predict_chunk, engine.hip):
+    the oracle's taps.  What each buffer holds when samrs_predict returns (predict_chunk, engine_decode.hip):
 
       buffer  stage                                                     tap            rule
       TOK0    prompt tokens [n, T, 256], fp32                           tokens         fp32
