@@ -346,6 +346,42 @@ int samrs_filter_masks(samrs_engine_t* e, uint8_t* masks, int n, int h, int w, c
                        const float* iou /* [n] or NULL */, float min_stability, float min_pred_iou, float min_inside,
                        uint8_t* keep_out /* [n] */, void* stream);
 
+/* -- one instance per pixel: where several masks of a call are set at the same pixel, the pixel is given to exactly one of them and
+ * cleared in the others, in place, so that everything downstream (samrs_paint, areas, class statistics, samrs_rle_encode,
+ * samrs_mask_boxes, samrs_mask_polygons) sees disjoint masks.  Without this stage the only overlap rule is samrs_paint's painting
+ * order -- a later box wins (main_sam_hbox_semantic.py:195-199) -- and it reaches the class map alone.
+ * masks uint8 [n][h][w] device, in / out (non-zero = set); (h, w) = the original size the masks were decoded at.
+ *   the rule  walk j = 0 .. n-1 and keep a holder per pixel.  Mask j is a candidate at p iff its byte is set.  It replaces holder b iff
+ *             there is no holder, or P[j] > P[b], or P[j] == P[b] and not v_j(p) < v_b(p).  Ties and non-comparable values (NaN)
+ *             therefore go to the LATER mask, as painting does.  P[j] is an int64 primary key per mask, v_j(p) the postprocessed
+ *             logit of mask j at p: the value samrs_predict's postprocess computes there for (in_h, in_w, h, w) from lowres fp32
+ *             [n][256][256] -- the very same arithmetic as samrs_score_masks, never materialised.  With lowres NULL the logit term is
+ *             absent (treated as equal: the later mask of equal key wins).
+ *   the gate  is the mask BYTE, not v > 0: a pixel that samrs_clean_masks filled competes, with its negative logit, and a pixel
+ *             that samrs_filter_masks or the clean-up cleared does not.
+ *   SAMRS_OVERLAP_LOGIT     P[j] = 0: the highest logit wins.  Needs lowres.
+ *   SAMRS_OVERLAP_SMALLEST  P[j] = -(set pixels of mask j on entry): the smaller instance wins (a ship inside a harbour); equal areas
+ *                           fall to the logit if lowres is given, then to the later mask.  The call counts the entry areas itself,
+ *                           in a first launch.
+ *   SAMRS_OVERLAP_PRIORITY  P[j] = priority[j], the caller's device int64 [n]; equal keys as above.
+ * Every loser's byte is set to 0; a winner's byte is not touched (a 0/1 mask stays 0/1, a 0/255 mask 0/255).  Optional outputs, each
+ * may be NULL: owner_out int32 [h][w] = index of the winner, -1 where no mask is set; before_out int64 [n] = set pixels on entry;
+ * removed_out int64 [n] = pixels cleared (before - removed = set pixels afterwards).
+ * (in_h, in_w): the input frame, in_h, in_w <= img_size with max(in_h, in_w) == img_size as samrs_score_masks; only read when
+ * lowres is given.  n < 0, a null masks, an unknown rule, LOGIT without lowres, PRIORITY without priority, h or w < 1, a bad input
+ * frame or h * w >= 2^31: SAMRS_ERR_BAD_ARG and nothing is written.  n == 0 is a no-op; n == 1 changes no mask and still fills the
+ * outputs.  A pixel has one owning thread and the counts use integer atomics only: bitwise reproducible; no host synchronisation.
+ * Cost: the n h w mask bytes are read once; only the threads with a contested pixel read them again and evaluate logits there.
+ * Rule SMALLEST with before_out NULL keeps its 8 n bytes of entry areas in ONE scratch buffer per handle that grows on demand: such
+ * calls on a handle must be stream-ordered with each other (same stream, or an event between them); two handles never share it.
+ * Every other form uses no scratch. */
+enum samrs_overlap_rule { SAMRS_OVERLAP_LOGIT = 1, SAMRS_OVERLAP_SMALLEST = 2, SAMRS_OVERLAP_PRIORITY = 3 };
+int samrs_resolve_overlaps(samrs_engine_t* e, uint8_t* masks, int n, int h, int w, int rule,
+                           const float* lowres /* [n][256][256] or NULL */, int in_h, int in_w,
+                           const int64_t* priority /* [n], rule PRIORITY */,
+                           int32_t* owner_out /* [h][w] or NULL */, int64_t* before_out /* [n] or NULL */,
+                           int64_t* removed_out /* [n] or NULL */, void* stream);
+
 /* -- the generation CLI's class-map files (main_sam_hbox_semantic.py:212-215: gray/<stem>.png and color/<stem>.png), encoded on
  * the device.  maps: uint8 [n][h][w] (255 = unlabeled), lut: uint8 [256][3] (class id -> RGB), both on the device.  The two PNG
  * files of each map are byte-identical with what the host's samrs_io_png_write_label_pair (include/samrs_io.h) writes for

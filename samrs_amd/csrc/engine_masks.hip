@@ -203,6 +203,35 @@ int samrs_filter_masks(samrs_engine_t* e, uint8_t* masks, int n, int h, int w, c
     return SAMRS_OK;
 }
 
+// one instance per pixel: contested pixels given to one mask, cleared in the others, in place (see samrs_hip.h)
+int samrs_resolve_overlaps(samrs_engine_t* e, uint8_t* masks, int n, int h, int w, int rule, const float* lowres, int in_h, int in_w,
+                           const int64_t* priority, int32_t* owner_out, int64_t* before_out, int64_t* removed_out, void* stream) {
+    if (!e || !masks || n < 0) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_resolve_overlaps: bad argument");
+    if (rule != SAMRS_OVERLAP_LOGIT && rule != SAMRS_OVERLAP_SMALLEST && rule != SAMRS_OVERLAP_PRIORITY)
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_resolve_overlaps: unknown rule %d", rule);
+    if (rule == SAMRS_OVERLAP_LOGIT && !lowres) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_resolve_overlaps: rule LOGIT needs lowres");
+    if (rule == SAMRS_OVERLAP_PRIORITY && !priority) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_resolve_overlaps: rule PRIORITY needs priority");
+    const int img = e->cfg.img_size;
+    if (h < 1 || w < 1 || (long long)h * w >= (1ll << 31))
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_resolve_overlaps: masks %d x %d (h, w >= 1, h * w < 2^31)", h, w);
+    if (lowres && (in_h < 1 || in_w < 1 || in_h > img || in_w > img || (in_h != img && in_w != img)))
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_resolve_overlaps: input %d x %d (long side must be %d)", in_h, in_w, img);
+    if (n == 0) return SAMRS_OK;
+    ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    unsigned long long* before = (unsigned long long*)before_out;
+    if (rule == SAMRS_OVERLAP_SMALLEST && !before) {
+        CK(e, scratch_reserve(e->overlap_scratch, sizeof(unsigned long long) * (size_t)n, s));
+        before = (unsigned long long*)e->overlap_scratch.p;
+    }
+    if (before) CK(e, launch_mask_areas(masks, n, h, w, before, s));
+    const long long* prim = rule == SAMRS_OVERLAP_PRIORITY ? (const long long*)priority
+                          : rule == SAMRS_OVERLAP_SMALLEST ? (const long long*)before : nullptr;
+    CK(e, launch_resolve_overlaps(masks, n, h, w, prim, rule == SAMRS_OVERLAP_SMALLEST ? 1 : 0, lowres, in_h, in_w, img, owner_out,
+                                  (unsigned long long*)removed_out, s));
+    return SAMRS_OK;
+}
+
 // gray + colour PNG files of n class maps, packed behind *cursor into `out` (see samrs_hip.h)
 int samrs_png_encode_labels(samrs_engine_t* e, const uint8_t* maps, int n, int h, int w, const uint8_t* lut, uint8_t* out,
                             int64_t out_capacity, int64_t* cursor, int64_t* table, void* stream) {

@@ -311,6 +311,17 @@ hipError_t launch_score_masks(const float* low, int n, int in_h, int in_w, int o
 hipError_t launch_filter_masks(uint8_t* masks, int n, long hw, const long long* counts, const float* iou, float min_stability,
                                float min_pred_iou, float min_inside, uint8_t* keep, hipStream_t s);
 
+// ---- overlap_kernels.hip --------------------------------------------------------------------
+// areas [n] (zeroed on the stream, then counted) = set bytes of masks uint8 [n][h][w].  h * w < 2^31.
+hipError_t launch_mask_areas(const uint8_t* masks, int n, int h, int w, unsigned long long* areas, hipStream_t s);
+// One instance per pixel, in place (the rule: samrs_hip.h samrs_resolve_overlaps): walking j = 0 .. n-1, mask j set at p takes p from
+// holder b iff there is none, or P[j] > P[b], or P[j] == P[b] and not v_j(p) < v_b(p).  P[j] = prim[j], or -prim[j] with prim_neg, or
+// 0 with prim null; v = the postprocessed logit from low [n][img_size / 4][img_size / 4] (postprocess_value.h), or equal with low
+// null.  Losers' bytes are zeroed; owner_out int32 [h][w] (the winner, -1 where no mask is set) and removed [n] (zeroed on the
+// stream, then counted) may each be null.  Integer atomics only.
+hipError_t launch_resolve_overlaps(uint8_t* masks, int n, int h, int w, const long long* prim, int prim_neg, const float* low, int in_h,
+                                   int in_w, int img_size, int32_t* owner_out, unsigned long long* removed, hipStream_t s);
+
 // ---- polygon_kernels.hip --------------------------------------------------------------------
 // Mask outlines as polygons on the pixel lattice (definition: the header comment of polygon_kernels.hip; contract: samrs_hip.h
 // samrs_mask_polygons).  One chunk of n <= 65535 masks per call; scratch: mask_polygons_scratch_bytes(n, h, w, max_edges).  The

@@ -324,6 +324,7 @@ class TileResult:
     png_table: Optional[np.ndarray] = None  # int64 [2, 2] (offset, length) of the gray and the colour PNG in png_data (png_lut)
     png_data: Optional[np.ndarray] = None   # uint8 view of the batch's pinned PNG byte buffer
     changed: Optional[np.ndarray] = None    # int64 [n_boxes] pixels the small-region clean-up changed (min_region_area > 0)
+    removed: Optional[np.ndarray] = None    # int64 [n_boxes] pixels the overlap stage took from the instance (overlap != "order")
     # mask_boxes=True (samrs_mask_boxes, in the image's own frame; an empty mask has mask_record[j, 6] == 0 and zeros everywhere):
     mask_hbox: Optional[np.ndarray] = None  # int32 [n_boxes, 4] xmin, ymin, xmax, ymax (inclusive) of the set pixels
     mask_rbox: Optional[np.ndarray] = None  # fp32 [n_boxes, 4, 2] corners of the minimum-area rotated rectangle of the pixel centres
@@ -399,7 +400,7 @@ class OutputTable(NamedTuple):
 
 
 def output_tables(min_region_area: int = 0, mask_boxes: bool = False, quality: bool = False, gt: bool = False, rle: bool = False,
-                  instance: bool = False) -> List[OutputTable]:
+                  instance: bool = False, overlap: str = "order") -> List[OutputTable]:
     """The per-box tables a pipeline with these (resolved) options allocates, copies to the host and hands out, in that order.
     Pure.  An option that is off contributes nothing: no allocation, no copy, and its TileResult fields stay None.  `instance`: an
     InstancePipeline, which always reports the predicted IoU of the mask it kept."""
@@ -407,6 +408,8 @@ def output_tables(min_region_area: int = 0, mask_boxes: bool = False, quality: b
     tabs = [T("areas", "area_dev", (), i64)]
     if min_region_area:
         tabs.append(T("changed", "chg_dev", (), i64))
+    if overlap != "order":
+        tabs.append(T("removed", "rem_dev", (), i64))
     if mask_boxes:
         tabs += [T("mask_hbox", "hbox_dev", (4,), i32), T("mask_rbox", "rbox_dev", (4, 2), torch.float32),
                  T("mask_record", "rec_dev", (8,), i64)]
@@ -439,11 +442,17 @@ def check_polygons(tab: np.ndarray, nv: int, nr: int, holder: str, now: int) -> 
                            f"the {holder} already holds {nv} and {nr}; raise polygon_buffer_mb (now {now})")
 
 
+OVERLAP_OPTIONS = ("order", "logit", "smallest")       # TilePipeline(overlap=...): "order" = painting order, nothing launched
+
+
 def validate_output_options(min_region_area: int = 0, region_mode: str = "both", polygons: bool = False, polygon_buffer_mb: int = 64,
-                            polygon_max_edges: int = 65536, png_lut=None):
+                            polygon_max_edges: int = 65536, png_lut=None, overlap: str = "order"):
     """The output options TilePipeline and ScenePipeline share, checked in one place -> (png_lut as contiguous uint8 [256, 3] or
-    None, the vertices one polygon buffer holds or None).  Touches no device."""
+    None, the vertices one polygon buffer holds or None).  `overlap` is TilePipeline's alone (ScenePipeline refuses it before it gets
+    here: ``refuse_overlap_option``).  Touches no device."""
     from .engine import REGION_MODES
+    if overlap not in OVERLAP_OPTIONS:
+        raise ValueError(f"overlap must be one of {list(OVERLAP_OPTIONS)}, got {overlap!r}")
     if int(min_region_area) < 0:
         raise ValueError("min_region_area must be >= 0 (0 = off)")
     if region_mode not in REGION_MODES:
@@ -529,6 +538,14 @@ def refuse_quality_options(who: str, why: str, **opts) -> None:
                          f"{'is a' if len(given) == 1 else 'are'} TilePipeline option{'' if len(given) == 1 else 's'}")
 
 
+def refuse_overlap_option(who: str, why: str, **opts) -> None:
+    """ValueError naming TilePipeline's `overlap` option when `who` (a pipeline that does not resolve overlapping masks) was handed
+    anything but "order"."""
+    value = opts.get("overlap", "order")
+    if value != "order":
+        raise ValueError(f"{who} does not resolve overlapping masks ({why}): overlap={value!r} is a TilePipeline option")
+
+
 DECODE_PROMPTS_LIMIT = 512      # the engine's cap on option "decode_prompts" (samrs_hip.h)
 
 
@@ -585,7 +602,7 @@ class TilePipeline:
                  png_buffer_mb: Optional[int] = None, batch_decode="auto", min_region_area: int = 0,
                  region_mode: str = "both", mask_boxes: bool = False, quality: bool = False, min_stability: float = 0.0,
                  min_pred_iou: float = 0.0, min_inside_box: float = 0.0, polygons: bool = False, polygon_buffer_mb: int = 64,
-                 polygon_max_edges: int = 65536):
+                 polygon_max_edges: int = 65536, overlap: str = "order"):
         """precision: the operand-split mode (engine option "split") THIS PIPELINE'S OWN CALLS run in.  The option is set around
         each of the pipeline's encode / decode calls and restored afterwards (``Engine.options``), so the mode never outlives
         them: a ``SamPredictor`` built on the same model keeps the engine's own default (round 3 changed the engine's option for
@@ -627,9 +644,22 @@ class TilePipeline:
         rings.  `polygon_buffer_mb`: the device buffer for one batch's vertices and ring records (two of them; 12 bytes per vertex
         with its share of ring records); a batch that overflows it raises, naming the option.  `polygon_max_edges`: a mask with
         more crack edges is not traced and yields None.  Every other output is byte for byte what polygons=False gives, and
-        False (default) launches and allocates nothing."""
+        False (default) launches and allocates nothing.
+        overlap: what becomes of a pixel at which several masks of a tile are set.  "order" (default): today's behaviour -- the
+        masks stay as they are and the class map follows the painting order, a later box wins; nothing is launched or allocated.
+        "logit" / "smallest": the pixel is given to exactly one instance on the device, in place (``Engine.resolve_overlaps``):
+        the mask with the highest postprocessed logit there, or the mask with the fewest set pixels (equal areas fall to the
+        logit); exact ties go to the later box, as painting does.  The stage runs after the quality gate and the clean-up and
+        before the mask boxes, the polygons, the painting and the RLE encoding, so areas, class statistics, class map, PNGs, RLE
+        strings, boxes, polygons and kept masks are all those of the disjoint masks, and the class map no longer depends on the
+        box order except at exact ties; ``TileResult.removed`` counts the pixels taken from each instance.  All masks of a tile
+        have to be on the device at once for this: a tile's boxes are decoded in ONE predict call whatever `box_batch` says (the
+        engine cuts it into chains of its own), so n_boxes x H x W mask bytes live at once (512 MiB for 512 boxes of a 1024^2
+        tile).  Under batch_decode the tile's rows of the batch's call are used as they are."""
         from .transforms import ResizeLongestSide
-        lut, poly_vertices = validate_output_options(min_region_area, region_mode, polygons, polygon_buffer_mb, polygon_max_edges, png_lut)
+        lut, poly_vertices = validate_output_options(min_region_area, region_mode, polygons, polygon_buffer_mb, polygon_max_edges, png_lut,
+                                                     overlap)
+        self.overlap = overlap
         self.min_region_area, self.region_mode = int(min_region_area), region_mode
         self.thresholds = (float(min_stability), float(min_pred_iou), float(min_inside_box))
         if any(t != t or t < 0 for t in self.thresholds):
@@ -680,7 +710,7 @@ class TilePipeline:
         self.dev_lab = [torch.empty(batch * max_boxes, dtype=torch.int32, device=dev) for _ in range(2)]
         self.seg_dev = [torch.empty(batch, side, side, dtype=torch.uint8, device=dev) for _ in range(2)]
         # the fixed per-box outputs: one declaration each (output_tables), two device tables per entry under the entry's name
-        self.tables = output_tables(self.min_region_area, self.mask_boxes, self.quality, self.gt, rle, self.INSTANCE)
+        self.tables = output_tables(self.min_region_area, self.mask_boxes, self.quality, self.gt, rle, self.INSTANCE, self.overlap)
         for t in self.tables:
             setattr(self, t.dev, [t.alloc(batch, max_boxes, dev) for _ in range(2)])
         # the packed outputs, per input set: the payload (16-byte aligned entries) here, cursor and table in the stream
@@ -865,13 +895,18 @@ class TilePipeline:
         native = (H, W) == (self.side, self.side)
         seg = self.seg_dev[b][i] if native else torch.full((H, W), 255, dtype=torch.uint8, device=self.dev)
         kept = []
-        for s, e in box_chunks(nb, self.box_batch):                          # :157-181
+        resolve = self.overlap != "order"
+        # :157-181; the overlap stage needs every mask of the tile at once: one chunk
+        for s, e in ([(0, nb)] if nb else []) if resolve else box_chunks(nb, self.box_batch):
             masks, iou, low = self._chunk_masks(b, i, tile, hw, off, s, e, pre)
             if self.quality:                                                      # score, then filter: before anything reads the masks
                 self._score(b, i, off, s, e, masks[:, 0], iou, low, in_size, (H, W))
             if self.min_region_area:                                              # before anything else reads the masks
                 eng.clean_masks(masks[:, 0], self.min_region_area, self.region_mode, areas_out=False,     # paint counts them
                                 changed_out=self.chg_dev[b][i, s:e])
+            if resolve:                                                           # of the masks as gated and cleaned; "smallest": low breaks ties
+                eng.resolve_overlaps(masks[:, 0], self.overlap, low=low, input_size=in_size, owner_out=False, before_out=False,
+                                     removed_out=self.rem_dev[b][i, s:e])
             if self.mask_boxes:
                 eng.mask_boxes(masks[:, 0], (0, 0), self.hbox_dev[b][i, s:e], self.rbox_dev[b][i, s:e], self.rec_dev[b][i, s:e])
             if self.polygons:                                                     # of the masks as they go out
@@ -1066,6 +1101,7 @@ class InstancePipeline(TilePipeline):
         if prompt not in ("box", "rbox_mask", "point"):
             raise ValueError("prompt must be 'box', 'rbox_mask' or 'point'")
         refuse_quality_options("InstancePipeline", "scoring the best-of-3 path is not built", **kw)
+        refuse_overlap_option("InstancePipeline", "resolving the best-of-3 masks is not built", **kw)
         if prompt == "point":
             self.BOX_WIDTH = 2
         from . import transforms

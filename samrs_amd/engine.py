@@ -24,6 +24,7 @@ PRECISIONS = {"bf16": PREC_BF16, "f16": PREC_F16, "fp16": PREC_F16}
 
 ABI_VERSION = 5
 REGION_MODES = {"holes": 1, "islands": 2, "both": 3}        # enum samrs_region_mode
+OVERLAP_RULES = {"logit": 1, "smallest": 2, "priority": 3}  # enum samrs_overlap_rule
 # "split" option bits (include/samrs_hip.h): rounding points that run as a two-term operand split
 SPLIT_PATCH, SPLIT_NECK, SPLIT_OI, SPLIT_UP, SPLIT_DEFAULT = 1, 2, 4, 8, 15
 SPLIT_ATTN, SPLIT_MLP, SPLIT_ATTN_V, SPLIT_LIN2, SPLIT_ALL = 16, 32, 64, 128, 255          # reference-grade bits: set before the weights are loaded
@@ -130,7 +131,8 @@ def load_library() -> C.CDLL:
     lib.samrs_k_polygon_edge_stride.restype = C.c_int64
     lib.samrs_score_masks.argtypes = [vp, vp, ip, ip, ip, ip, ip, fp, vp, vp, vp]
     lib.samrs_filter_masks.argtypes = [vp, vp, ip, ip, ip, vp, vp, fp, fp, fp, vp, vp]
-    for name in ("samrs_score_masks", "samrs_filter_masks"):
+    lib.samrs_resolve_overlaps.argtypes = [vp, vp, ip, ip, ip, ip, vp, ip, ip, vp, vp, vp, vp, vp]
+    for name in ("samrs_score_masks", "samrs_filter_masks", "samrs_resolve_overlaps"):
         getattr(lib, name).restype = ip
     lib.samrs_png_encode_labels.argtypes = [vp, vp, ip, ip, ip, vp, vp, C.c_int64, vp, vp, vp]
     lib.samrs_k_upscaler_fused.argtypes = [ip, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, vp]
@@ -815,6 +817,63 @@ class Engine:
                 self._check(self.lib.samrs_filter_masks(self.handle, m.data_ptr(), n, h, w, counts.data_ptr(), _ptr(iou), thr[0], thr[1],
                                                         thr[2], keep_out.data_ptr(), _stream()))
         return keep_out
+
+    def resolve_overlaps(self, masks: torch.Tensor, rule, low: Optional[torch.Tensor] = None, input_size: Optional[Sequence[int]] = None,
+                         original_size: Optional[Sequence[int]] = None, priority: Optional[torch.Tensor] = None, owner_out=None,
+                         before_out=None, removed_out=None):
+        """One instance per pixel, on the device and in place (samrs_resolve_overlaps): masks [n, H, W] bool / uint8, contiguous, in /
+        out -> (masks, owner int32 [H, W] = index of the mask that holds each pixel, -1 where none is set; before int64 [n] = set
+        pixels on entry; removed int64 [n] = pixels cleared).  Walking the masks in order, mask j takes a pixel it is set at from
+        its holder b iff there is no holder, or P[j] > P[b], or P[j] == P[b] and not v_j < v_b: ties go to the later mask, as
+        painting does.  v is the postprocessed logit at the pixel, from `low` fp32 [n, 256, 256] or [n, 1, 256, 256] (the third
+        output of ``predict``) for `input_size` -> the masks' size; without `low` the logit term is absent.  `rule`: "logit" (P = 0;
+        needs `low`), "smallest" (P = -(the mask's set pixels on entry): the smaller instance wins; `low` breaks equal areas) or
+        "priority" (P = `priority`, int64 [n] on the device; `low` breaks equal keys).  The gate is the mask byte, not v > 0: a pixel
+        the clean-up filled competes with its negative logit.  Losers' bytes become 0, winners' bytes are not touched.
+        `original_size`, when given, must be the masks' (H, W).  Each output: None = a new tensor, a caller-owned contiguous slice
+        of that shape and type, or False = not wanted (the library gets NULL and the tuple holds None there).  Asynchronous on the
+        current stream."""
+        m = self._masks_u8(masks)
+        n, h, w = m.shape
+        code = OVERLAP_RULES.get(rule) if isinstance(rule, str) else int(rule)
+        if code not in OVERLAP_RULES.values():
+            raise ValueError(f"rule must be one of {sorted(OVERLAP_RULES)}, got {rule!r}")
+        if original_size is not None and (int(original_size[0]), int(original_size[1])) != (h, w):
+            raise ValueError(f"original_size {tuple(original_size)} is not the masks' size {(h, w)}")
+        in_h = in_w = 0
+        if low is not None:
+            if not (isinstance(low, torch.Tensor) and low.dtype == torch.float32 and low.is_cuda and low.is_contiguous()
+                    and tuple(low.shape) in ((n, 256, 256), (n, 1, 256, 256))):
+                raise ValueError(f"low must be a contiguous fp32 [{n}, 256, 256] tensor on the engine's device (the low-resolution "
+                                 f"logits of predict), or None")
+            if input_size is None:
+                raise ValueError("low needs input_size, the (h, w) of the input frame the logits were decoded for")
+            in_h, in_w = int(input_size[0]), int(input_size[1])
+        elif code == OVERLAP_RULES["logit"]:
+            raise ValueError('rule "logit" needs low')
+        if code == OVERLAP_RULES["priority"]:
+            if not (isinstance(priority, torch.Tensor) and priority.dtype == torch.int64 and priority.is_cuda and priority.is_contiguous()
+                    and priority.numel() == n):
+                raise ValueError(f'rule "priority" needs priority, a contiguous int64 [{n}] tensor on the device')
+        else:
+            priority = None
+        outs = []
+        for name, t, shape, dt in (("owner_out", owner_out, (h, w), torch.int32), ("before_out", before_out, (n,), torch.int64),
+                                   ("removed_out", removed_out, (n,), torch.int64)):
+            if t is False:
+                t = None
+            elif t is None:
+                t = torch.empty(shape, dtype=dt, device=self.device)
+            elif not (isinstance(t, torch.Tensor) and t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shape):
+                raise ValueError(f"{name} must be a contiguous {dt} {list(shape)} tensor on the engine's device, None or False")
+            outs.append(t)
+        if n:
+            with torch.cuda.device(self.device):
+                self._check(self.lib.samrs_resolve_overlaps(self.handle, m.data_ptr(), n, h, w, code, _ptr(low), in_h, in_w, _ptr(priority),
+                                                            _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), _stream()))
+        elif outs[0] is not None:
+            outs[0].fill_(-1)
+        return masks, outs[0], outs[1], outs[2]
 
     def mask_row_extents(self, masks: torch.Tensor) -> torch.Tensor:
         """Test hook (samrs_k_mask_row_extents): int32 [n, H, 3] = first set column, last set column and pixel count of every row,

@@ -61,7 +61,7 @@ def write_outputs(out_dir: str, stem: str, seg: np.ndarray, masks: Optional[np.n
                   rles: Optional[Sequence[dict]] = None, clock: Optional[StageClock] = None, png_level: int = tile_io.LEVEL_LABELS,
                   png_files: Optional[Tuple[bytes, bytes]] = None, mask_bboxes: Optional[Sequence] = None,
                   mask_rboxes: Optional[Sequence] = None, dota_txt: bool = False, scores: Optional[dict] = None,
-                  polygons: Optional[Sequence] = None) -> None:
+                  polygons: Optional[Sequence] = None, removed: Optional[Sequence[int]] = None) -> None:
     """`rles`: the per-instance COCO RLE dicts when they were encoded on the device (driver.TileResult.rle); otherwise they are
     encoded here from `masks` (host restatement), or left out when both are None (--no-rle).  `png_files`: the complete
     (gray, color) PNG files when they were encoded on the device (--png-device: driver.TileResult.png, byte-identical with the
@@ -73,7 +73,9 @@ def write_outputs(out_dir: str, stem: str, seg: np.ndarray, masks: Optional[np.n
     names -- and "kept" (bool): an instance that failed a threshold gets no pickle entry (its mask was zeroed on the device, so it
     painted nothing and, being empty, has no DOTA line either).  `polygons` (--polygons): per instance the rings of its outline as
     (int32 [k, 2] lattice vertices, is_hole) pairs (driver.TileResult.polygons), or None for a mask over the edge cap; they become
-    the pickle entries' ``"polygons"`` (the list of vertex arrays, or None) and ``"polygon_holes"`` (the list of bool, or None)."""
+    the pickle entries' ``"polygons"`` (the list of vertex arrays, or None) and ``"polygon_holes"`` (the list of bool, or None).
+    `removed` (--overlap logit / smallest): per instance the pixels the overlap stage gave to another instance; the entries' ``"removed"``
+    (`areas` and `rles` are then those of the disjoint masks already)."""
     import time
     t0 = time.perf_counter()
     for sub in ("gray", "color", "ins"):
@@ -112,6 +114,8 @@ def write_outputs(out_dir: str, stem: str, seg: np.ndarray, masks: Optional[np.n
             entry["mask"] = rle.encode(masks[j])
         if mask_bboxes is not None:
             entry["mask_bbox"], entry["mask_rbox"] = mask_bboxes[j], mask_rboxes[j]
+        if removed is not None:
+            entry["removed"] = int(removed[j])
         if polygons is not None:
             pl = polygons[j]
             entry["polygons"] = None if pl is None else [np.array(p[0], dtype=np.int32) for p in pl]
@@ -334,8 +338,13 @@ def run(args) -> Dict[str, List[int]]:
     want_polygons = bool(getattr(args, "polygons", False))
     poly_kw = dict(polygons=True, polygon_buffer_mb=int(getattr(args, "polygon_buffer_mb", 64) or 64),
                    polygon_max_edges=int(getattr(args, "polygon_max_edges", 65536) or 65536)) if want_polygons else {}
+    # --overlap: a pixel several masks of an image are set at goes to one of them on the device (samrs_resolve_overlaps) before the masks
+    # are painted, counted and RLE-encoded; "order" = the reference's painting order, nothing launched
+    overlap = getattr(args, "overlap", "order") or "order"
     if scene_window > 0:
         from . import scene
+        if overlap != "order":
+            raise ValueError(f"--overlap {overlap} does not apply with --scene-window: overlaps are not resolved across scene windows")
         pipe = scene.ScenePipeline(sam, n_classes, window=scene_window, overlap=getattr(args, "scene_overlap", 256),
                                    context=getattr(args, "scene_context", 2.0), batch=batch, box_batch=args.box_batch,
                                    rle=not args.no_rle, rle_buffer_mb=getattr(args, "rle_buffer_mb", 256),
@@ -349,7 +358,7 @@ def run(args) -> Dict[str, List[int]]:
                                    png_buffer_mb=getattr(args, "png_buffer_mb", None),
                                    batch_decode=True if getattr(args, "batch_decode", False) else "auto",
                                    min_region_area=min_region_area, region_mode=getattr(args, "region_mode", "both"),
-                                   mask_boxes=mask_boxes, quality=want_quality, **thresholds, **poly_kw)
+                                   mask_boxes=mask_boxes, quality=want_quality, overlap=overlap, **thresholds, **poly_kw)
     # rank r takes chunks of `batch` consecutive stems: statically (r, r + world, ...) or from the shared counter (whose
     # store key must be unique per work list: a second run() in the same process group must not find a spent counter)
     import zlib
@@ -419,6 +428,7 @@ def run(args) -> Dict[str, List[int]]:
     done = [0]
     dropped = [0]                    # --min-stability / --min-pred-iou / --min-inside-box: instances left unlabeled (this run's images)
     cleaned = [0, 0]                 # --min-region-area: pixels changed, instances with a changed pixel (this run's images)
+    resolved = [0, 0]                # --overlap: pixels taken from an instance, instances that lost a pixel (this run's images)
     sizes: List[int] = []
     writers = ThreadPoolExecutor(max_workers=n_writers)
     pending: List = []
@@ -453,7 +463,7 @@ def run(args) -> Dict[str, List[int]]:
                               "inside_box": quality.inside_fraction(r.score_counts), "kept": r.kept}
                 polys = [r.polygons(j) for j in range(len(r.labels))] if r.polygon_table is not None else None
                 write_outputs(args.out, r.key, r.seg_mask, None, r.boxes, r.labels, r.areas, palette, names, rles, clock, png_level, files,
-                              bbs, rbs, dota_txt, scores, polys)
+                              bbs, rbs, dota_txt, scores, polys, r.removed)
             finally:
                 with lock:
                     left[0] -= 1
@@ -485,6 +495,9 @@ def run(args) -> Dict[str, List[int]]:
             if r.changed is not None:
                 cleaned[0] += int(r.changed.sum())
                 cleaned[1] += int((r.changed > 0).sum())
+            if r.removed is not None:
+                resolved[0] += int(r.removed.sum())
+                resolved[1] += int((r.removed > 0).sum())
         done[0] += len(results)
         if rank == 0 and (done[0] // batch) % 50 == 0:
             print(f"[rank 0] {done[0]} images", flush=True)
@@ -528,6 +541,11 @@ def run(args) -> Dict[str, List[int]]:
                                             torch.tensor([cleaned[1]], dtype=torch.int64, device=dev))
         stats["region_cleanup"] = {"min_region_area": min_region_area, "region_mode": getattr(args, "region_mode", "both"),
                                    "changed_pixel_num": int(cpx.item()), "changed_instance_num": int(cin.item())}
+    if overlap != "order":           # over the images processed in THIS run, like region_cleanup
+        dev = pipe.class_pixels.device
+        rpx, rin = driver.reduce_statistics(torch.tensor([resolved[0]], dtype=torch.int64, device=dev),
+                                            torch.tensor([resolved[1]], dtype=torch.int64, device=dev))
+        stats["overlap"] = {"rule": overlap, "removed_pixel_num": int(rpx.item()), "removed_instance_num": int(rin.item())}
     if want_quality:                 # over the images processed in THIS run, like region_cleanup
         dev = pipe.class_pixels.device
         dn, _ = driver.reduce_statistics(torch.tensor([dropped[0]], dtype=torch.int64, device=dev),
@@ -567,6 +585,8 @@ class _Parser(argparse.ArgumentParser):
                          ("--min-inside-box", ns.min_inside_box > 0)):
             if on and ns.scene_window > 0:
                 self.error(f"{flag} does not apply with --scene-window: masks are not scored across scene windows")
+        if ns.overlap != "order" and ns.scene_window > 0:
+            self.error(f"--overlap {ns.overlap} does not apply with --scene-window: overlaps are not resolved across scene windows")
         for flag, v in (("--min-stability", ns.min_stability), ("--min-pred-iou", ns.min_pred_iou), ("--min-inside-box", ns.min_inside_box)):
             if not v >= 0:
                 self.error(f"{flag} must be >= 0 (0 = off)")
@@ -639,6 +659,13 @@ def build_parser() -> argparse.ArgumentParser:
                     help="the same for instances whose predicted IoU is not > Q (segment_anything's pred_iou_thresh); 0 = off")
     ap.add_argument("--min-inside-box", type=float, default=0.0, metavar="F",
                     help="the same for instances with less than the share F of their mask inside their prompt box; 0 = off")
+    ap.add_argument("--overlap", default="order", choices=["order", "logit", "smallest"],
+                    help="what becomes of a pixel several masks of an image are set at.  order (default): the masks stay as they are and "
+                         "the class map follows the box order, a later box wins.  logit / smallest: the pixel goes to exactly one instance on "
+                         "the GPU -- the mask with the highest logit there, or the mask with the fewest pixels (equal areas: the logit; exact "
+                         "ties: the later box) -- before the masks are painted, counted and encoded: the ins/<stem>.pkl entries' \"size\" and "
+                         "\"mask\" are those of the disjoint masks and each entry gains \"removed\" (pixels given to another instance).  "
+                         "Decodes an image's boxes in one call: n_boxes x H x W mask bytes live at once.  Not with --scene-window")
     ap.add_argument("--dota-txt", action="store_true",
                     help="also write rbox/<stem>.txt, one line per non-empty instance in DOTA's oriented-box form "
                          "'x1 y1 x2 y2 x3 y3 x4 y4 category label' (coordinates %%.1f); implies --mask-boxes")

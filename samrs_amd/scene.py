@@ -120,7 +120,10 @@ class ScenePipeline:
                  quality: bool = False, min_stability: float = 0.0, min_pred_iou: float = 0.0, min_inside_box: float = 0.0,
                  polygons: bool = False, polygon_buffer_mb: int = 64, polygon_max_edges: int = 65536):
         import torch
-        from .driver import TilePipeline, output_tables, refuse_quality_options, validate_output_options
+        from .driver import TilePipeline, output_tables, refuse_overlap_option, refuse_quality_options, validate_output_options
+        if isinstance(overlap, str):        # TilePipeline's overlap rule; the name means the windows' overlap in pixels here
+            refuse_overlap_option("ScenePipeline", "resolving across scene windows is not built", overlap=overlap)
+            raise ValueError("ScenePipeline's overlap is the windows' overlap in pixels; masks always overlap in painting order here")
         refuse_quality_options("ScenePipeline", "scoring across scene windows is not built", quality=quality,
                                min_stability=min_stability, min_pred_iou=min_pred_iou, min_inside_box=min_inside_box)
         from .transforms import ResizeLongestSide
