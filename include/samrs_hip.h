@@ -382,6 +382,59 @@ int samrs_resolve_overlaps(samrs_engine_t* e, uint8_t* masks, int n, int h, int 
                            int32_t* owner_out /* [h][w] or NULL */, int64_t* before_out /* [n] or NULL */,
                            int64_t* removed_out /* [n] or NULL */, void* stream);
 
+/* -- COCO mask AP on the device: every prediction of an image against every ground truth of it (samrs_gt_match counts the diagonal
+ * only), and COCOeval.evaluateImg's greedy matching.  The two JSON files of the instance drivers exist for this number
+ * (main_sam_rhbox_mask_instance.py:246-255, "Obtain COCO format for AP calculation").
+ * Bit planes: uint64 [n][words], words = ceil(h * w / 64); pixel p (row-major) is bit p % 64 of word p / 64, the unused high bits of
+ * the last word are zero.  An eighth of the mask bytes, so a tile's planes can be kept while its masks are decoded chunk by chunk.
+ *   samrs_mask_pack_bits   masks uint8 [n][h][w] (non-zero = set) -> planes_out.  Any alignment; 16-byte loads where h * w % 16 == 0
+ *                          and masks is 16-byte aligned.
+ *   samrs_label_pack_bits  the ground truth straight from label_rgb uint8 [h][w][3] and colors uint8 [n][3]: instance j = the pixels
+ *                          whose RGB equals colors[j] (duplicate colours give equal planes, an absent colour an empty one).  The
+ *                          label image is read once per call, not once per instance; no mask bytes are materialised.
+ *   samrs_mask_pair_counts a uint64 [na][words], b uint64 [nb][words] -> inter_out int64 [na][nb] = popcount(a[i] & b[j]),
+ *                          area_a_out int64 [na] / area_b_out int64 [nb] = popcount of each plane (each may be NULL).  Integer
+ *                          atomics into outputs the call zeroes: exact and bitwise reproducible.  a == b is allowed.
+ * All on the device, no host synchronisation, no scratch.  h * w < 2^30 (words <= 2^24).  A null handle or pointer, a negative count,
+ * h, w or words < 1 or a size over the limit: SAMRS_ERR_BAD_ARG and nothing is launched.  n == 0 is a no-op; with na == 0 or nb == 0
+ * there are no pairs and the areas of the other side are still counted.
+ *
+ * samrs_coco_match: the matching of one image and one category, for n_ranges area ranges x n_thresholds IoU thresholds at once.
+ *   inputs   inter int64 [nd][ng], area_d int64 [nd], area_g int64 [ng] (the outputs of samrs_mask_pair_counts) and scores fp32 [nd]
+ *            on the device; thresholds double [n_thresholds] and area_ranges double [n_ranges][2] = (lo, hi) on the HOST (read
+ *            before the call returns).  scores_on_host != 0: scores is a host array; it is checked and copied to the device by
+ *            the call and must stay unchanged until the stream has passed the call.
+ *   order    detection d precedes e iff score[d] > score[e], or the scores are equal and d < e (a stable descending sort); the
+ *            first max_det are kept: n_kept = min(nd, max_det).
+ *   ignore   for range [lo, hi] ground truth g is ignored iff area_g < lo or area_g > hi (both ends inclusive); n_valid = the
+ *            ground truths not ignored.  Ground truths are visited non-ignored first, each group in index order.
+ *   IoU      inter / (area_d + area_g - inter) as a correctly rounded double (0 where the union is 0), so every comparison below
+ *            decides as IEEE double arithmetic on the host does, also for an IoU exactly on a threshold.
+ *   match    per threshold t, walking the kept detections in order, bar = min(t, 1 - 1e-10): among the not yet matched non-ignored
+ *            ground truths with IoU >= bar the one with the greatest IoU, the LAST in visiting order on a tie; only if there is
+ *            none, the same among the not yet matched ignored ones.  The match consumes the ground truth for that threshold.
+ *            dt_ignore = 1 iff the detection matched an ignored ground truth, or is unmatched and its own area is outside [lo, hi].
+ *   outputs  (device, all overwritten) order_out int32 [max_det] = detection index per rank; match_out int32
+ *            [n_ranges][n_thresholds][max_det] = matched ground-truth INDEX or -1; dt_ignore_out uint8 of the same shape;
+ *            n_valid_out int32 [n_ranges]; n_kept_out int32 [1].  Ranks >= n_kept hold -1 / -1 / 0.
+ * A match is a match by index: ground truth 0 can be matched like any other (pycocotools stores the annotation id and tests it for
+ * truth, which loses the matches to id 0 -- and gt_ins_<tag>.json restarts its ids at 0 per image).
+ * A null handle / output / needed input, nd or ng < 0, n_thresholds or n_ranges outside 1..16, max_det outside 1..4096, a NaN
+ * threshold or bound, or a NaN among host scores: SAMRS_ERR_BAD_ARG, nothing launched.  Device scores cannot be read without a
+ * synchronisation: a NaN among them makes the kernel write n_kept = -1 and match nothing.  nd == 0 or ng == 0 is a valid image.
+ * One block per area range, one wave per threshold; no host synchronisation.  Scratch: n_ranges * n_thresholds * ng bytes (+ 4 nd
+ * for host scores) in ONE buffer per handle that grows on demand: calls on a handle must be stream-ordered with each other (same
+ * stream, or an event between them); two handles never share it. */
+int samrs_mask_pack_bits(samrs_engine_t* e, const uint8_t* masks, int n, int h, int w, uint64_t* planes_out, void* stream);
+int samrs_label_pack_bits(samrs_engine_t* e, const uint8_t* label_rgb, const uint8_t* colors, int n, int h, int w, uint64_t* planes_out,
+                          void* stream);
+int samrs_mask_pair_counts(samrs_engine_t* e, const uint64_t* a, int na, const uint64_t* b, int nb, int64_t words, int64_t* inter_out,
+                           int64_t* area_a_out, int64_t* area_b_out, void* stream);
+int samrs_coco_match(samrs_engine_t* e, const int64_t* inter, const int64_t* area_d, const int64_t* area_g, const float* scores,
+                     int scores_on_host, int nd, int ng, const double* thresholds, int n_thresholds, const double* area_ranges,
+                     int n_ranges, int max_det, int32_t* order_out, int32_t* match_out, uint8_t* dt_ignore_out, int32_t* n_valid_out,
+                     int32_t* n_kept_out, void* stream);
+
 /* -- the generation CLI's class-map files (main_sam_hbox_semantic.py:212-215: gray/<stem>.png and color/<stem>.png), encoded on
  * the device.  maps: uint8 [n][h][w] (255 = unlabeled), lut: uint8 [256][3] (class id -> RGB), both on the device.  The two PNG
  * files of each map are byte-identical with what the host's samrs_io_png_write_label_pair (include/samrs_io.h) writes for

@@ -1,5 +1,6 @@
 // engine_masks.hip -- the entry points that work on finished masks, class maps and prompts' pixels and read no model weights: paint,
-// selection, ground-truth match, RLE, scene stitching, clean-up, boxes, polygons, quality gate, PNG, resampling, rbox mask prompts.
+// selection, ground-truth match, RLE, scene stitching, clean-up, boxes, polygons, quality gate, overlap, COCO AP (bit planes, pair counts,
+// matching), PNG, resampling, rbox mask prompts.
 #include <cmath>
 
 #include "engine_state.h"
@@ -229,6 +230,82 @@ int samrs_resolve_overlaps(samrs_engine_t* e, uint8_t* masks, int n, int h, int 
                           : rule == SAMRS_OVERLAP_SMALLEST ? (const long long*)before : nullptr;
     CK(e, launch_resolve_overlaps(masks, n, h, w, prim, rule == SAMRS_OVERLAP_SMALLEST ? 1 : 0, lowres, in_h, in_w, img, owner_out,
                                   (unsigned long long*)removed_out, s));
+    return SAMRS_OK;
+}
+
+// COCO mask AP (see samrs_hip.h): bit planes of masks / of a label image's instances, pairwise counts, the greedy matching
+int samrs_mask_pack_bits(samrs_engine_t* e, const uint8_t* masks, int n, int h, int w, uint64_t* planes_out, void* stream) {
+    if (!e || !masks || !planes_out || n < 0) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_mask_pack_bits: bad argument");
+    if (h < 1 || w < 1 || (long long)h * w >= (1ll << 30))
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_mask_pack_bits: masks %d x %d (h, w >= 1, h * w < 2^30)", h, w);
+    if (n == 0) return SAMRS_OK;
+    ON_DEVICE(e);
+    CK(e, launch_pack_bits(masks, n, h, w, (unsigned long long*)planes_out, (hipStream_t)stream));
+    return SAMRS_OK;
+}
+int samrs_label_pack_bits(samrs_engine_t* e, const uint8_t* label_rgb, const uint8_t* colors, int n, int h, int w, uint64_t* planes_out,
+                          void* stream) {
+    if (!e || !label_rgb || !colors || !planes_out || n < 0) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_label_pack_bits: bad argument");
+    if (h < 1 || w < 1 || (long long)h * w >= (1ll << 30))
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_label_pack_bits: label image %d x %d (h, w >= 1, h * w < 2^30)", h, w);
+    if (n == 0) return SAMRS_OK;
+    ON_DEVICE(e);
+    CK(e, launch_label_pack_bits(label_rgb, colors, n, h, w, (unsigned long long*)planes_out, (hipStream_t)stream));
+    return SAMRS_OK;
+}
+int samrs_mask_pair_counts(samrs_engine_t* e, const uint64_t* a, int na, const uint64_t* b, int nb, int64_t words, int64_t* inter_out,
+                           int64_t* area_a_out, int64_t* area_b_out, void* stream) {
+    if (!e || na < 0 || nb < 0 || (na > 0 && !a) || (nb > 0 && !b) || (na > 0 && nb > 0 && !inter_out))
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_mask_pair_counts: bad argument");
+    if (words < 1 || words > (1ll << 24))
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_mask_pair_counts: %lld words per plane (1 .. 2^24)", (long long)words);
+    if ((na + 63) / 64 > 65535 || (nb + 63) / 64 > 65535) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_mask_pair_counts: too many planes");
+    if (na == 0 && nb == 0) return SAMRS_OK;
+    ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    if (na > 0 && area_a_out) CK(e, launch_bit_areas((const unsigned long long*)a, na, (long)words, (unsigned long long*)area_a_out, s));
+    if (nb > 0 && area_b_out) CK(e, launch_bit_areas((const unsigned long long*)b, nb, (long)words, (unsigned long long*)area_b_out, s));
+    if (na > 0 && nb > 0)
+        CK(e, launch_pair_counts((const unsigned long long*)a, na, (const unsigned long long*)b, nb, (long)words,
+                                 (unsigned long long*)inter_out, s));
+    return SAMRS_OK;
+}
+int samrs_coco_match(samrs_engine_t* e, const int64_t* inter, const int64_t* area_d, const int64_t* area_g, const float* scores,
+                     int scores_on_host, int nd, int ng, const double* thresholds, int n_thresholds, const double* area_ranges,
+                     int n_ranges, int max_det, int32_t* order_out, int32_t* match_out, uint8_t* dt_ignore_out, int32_t* n_valid_out,
+                     int32_t* n_kept_out, void* stream) {
+    if (!e || nd < 0 || ng < 0 || !thresholds || !area_ranges || !order_out || !match_out || !dt_ignore_out || !n_valid_out || !n_kept_out ||
+        (nd > 0 && (!scores || !area_d)) || (ng > 0 && !area_g) || (nd > 0 && ng > 0 && !inter))
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_coco_match: bad argument");
+    if (n_thresholds < 1 || n_thresholds > COCO_MAX_THRESHOLDS || n_ranges < 1 || n_ranges > COCO_MAX_RANGES || max_det < 1 ||
+        max_det > COCO_MAX_DET)
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_coco_match: %d thresholds (1..%d), %d area ranges (1..%d), max_det %d (1..%d)", n_thresholds,
+                    COCO_MAX_THRESHOLDS, n_ranges, COCO_MAX_RANGES, max_det, COCO_MAX_DET);
+    CocoMatchParams P{};
+    for (int t = 0; t < n_thresholds; ++t) {
+        if (std::isnan(thresholds[t])) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_coco_match: threshold %d is NaN", t);
+        P.bar[t] = std::fmin(thresholds[t], 1.0 - 1e-10);
+    }
+    for (int a = 0; a < n_ranges; ++a) {
+        P.lo[a] = area_ranges[2 * a];
+        P.hi[a] = area_ranges[2 * a + 1];
+        if (std::isnan(P.lo[a]) || std::isnan(P.hi[a])) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_coco_match: area range %d is NaN", a);
+    }
+    if (scores_on_host)
+        for (int d = 0; d < nd; ++d)
+            if (std::isnan(scores[d])) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_coco_match: score %d is NaN", d);
+    ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t flags = coco_match_scratch_bytes(ng, n_thresholds, n_ranges);
+    CK(e, scratch_reserve(e->ap_scratch, flags + (scores_on_host ? sizeof(float) * (size_t)nd : 0), s));
+    const float* dev_scores = scores;
+    if (scores_on_host && nd > 0) {
+        float* staged = (float*)((char*)e->ap_scratch.p + flags);
+        CK(e, hipMemcpyAsync(staged, scores, sizeof(float) * (size_t)nd, hipMemcpyHostToDevice, s));
+        dev_scores = staged;
+    }
+    CK(e, launch_coco_match((const long long*)inter, (const long long*)area_d, (const long long*)area_g, dev_scores, nd, ng, P, n_thresholds,
+                            n_ranges, max_det, e->ap_scratch.p, order_out, match_out, dt_ignore_out, n_valid_out, n_kept_out, s));
     return SAMRS_OK;
 }
 

@@ -242,6 +242,7 @@ struct samrs_engine {
     DeviceScratch poly_scratch;    // edge lists and ranking state of samrs_mask_polygons
     DeviceScratch png_scratch;     // class-map PNG scratch (samrs_png_encode_labels)
     DeviceScratch overlap_scratch; // entry areas of samrs_resolve_overlaps (rule SMALLEST without before_out)
+    DeviceScratch ap_scratch;      // matched flags (+ host scores staged) of samrs_coco_match
 
     // optional in-situ timing of the dominant kernel (MLP lin1 + GELU GEMM) with HIP events
     bool timing = false;

@@ -322,6 +322,29 @@ hipError_t launch_mask_areas(const uint8_t* masks, int n, int h, int w, unsigned
 hipError_t launch_resolve_overlaps(uint8_t* masks, int n, int h, int w, const long long* prim, int prim_neg, const float* low, int in_h,
                                    int in_w, int img_size, int32_t* owner_out, unsigned long long* removed, hipStream_t s);
 
+// ---- ap_kernels.hip -------------------------------------------------------------------------
+// Bit planes: out uint64 [n][words], words = ceil(h w / 64), pixel p = bit p % 64 of word p / 64, tail bits zero; of masks uint8
+// [n][h][w] (non-zero = set; 16-byte loads where h w % 16 == 0 and the pointer allows), or of the instances of a label image
+// (label_rgb uint8 [h][w][3], colors uint8 [n][3]: instance j = the pixels whose RGB equals colors[j]; the image is read once).
+// h * w < 2^30, n >= 1.
+hipError_t launch_pack_bits(const uint8_t* masks, int n, int h, int w, unsigned long long* out, hipStream_t s);
+hipError_t launch_label_pack_bits(const uint8_t* label_rgb, const uint8_t* colors, int n, int h, int w, unsigned long long* out,
+                                  hipStream_t s);
+// area [n] (zeroed on the stream, then counted) = set bits of planes [n][words]; inter [na][nb] (likewise) = set bits of
+// a[i] & b[j].  1 <= words <= 2^24, na, nb >= 1.  Integer atomics only: exact and order-independent.
+hipError_t launch_bit_areas(const unsigned long long* planes, int n, long words, unsigned long long* area, hipStream_t s);
+hipError_t launch_pair_counts(const unsigned long long* a, int na, const unsigned long long* b, int nb, long words,
+                              unsigned long long* inter, hipStream_t s);
+// COCO matching of one image (the rule: samrs_hip.h samrs_coco_match).  bar[t] = min(threshold t, 1 - 1e-10); [lo, hi] per area
+// range.  scores fp32 [nd] on the device; a NaN among them: *n_kept_out = -1 and nothing is matched.  scratch:
+// coco_match_scratch_bytes(ng, T, A), zeroed here.  inter / area_d / scores may be null where nd == 0, inter / area_g where ng == 0.
+constexpr int COCO_MAX_THRESHOLDS = 16, COCO_MAX_RANGES = 16, COCO_MAX_DET = 4096;
+struct CocoMatchParams { double bar[COCO_MAX_THRESHOLDS], lo[COCO_MAX_RANGES], hi[COCO_MAX_RANGES]; };
+size_t coco_match_scratch_bytes(int ng, int n_thresholds, int n_ranges);
+hipError_t launch_coco_match(const long long* inter, const long long* area_d, const long long* area_g, const float* scores, int nd, int ng,
+                             const CocoMatchParams& P, int n_thresholds, int n_ranges, int max_det, void* scratch, int32_t* order_out,
+                             int32_t* match_out, uint8_t* ign_out, int32_t* n_valid_out, int32_t* n_kept_out, hipStream_t s);
+
 // ---- polygon_kernels.hip --------------------------------------------------------------------
 // Mask outlines as polygons on the pixel lattice (definition: the header comment of polygon_kernels.hip; contract: samrs_hip.h
 // samrs_mask_polygons).  One chunk of n <= 65535 masks per call; scratch: mask_polygons_scratch_bytes(n, h, w, max_edges).  The

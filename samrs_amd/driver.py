@@ -337,8 +337,23 @@ class TileResult:
     polygon_table: Optional[np.ndarray] = None      # int64 [n_boxes, 5] first ring, ring count, first vertex, vertex count, edge count
     polygon_rings: Optional[np.ndarray] = None      # int32 [R, 4] the batch's ring records (the table's firsts index them)
     polygon_vertices: Optional[np.ndarray] = None   # int32 [V, 2] the batch's vertices
+    # InstancePipeline(gt=True, ap=True) (samrs_coco_match on every prediction x every ground truth of the tile; per tile, not per box):
+    ap_order: Optional[np.ndarray] = None       # int32 [100] detection index per rank (score descending, stable), -1 past n_kept
+    ap_match: Optional[np.ndarray] = None       # int32 [4, 10, 100] matched ground-truth INDEX per area range, IoU threshold and rank, -1 = none
+    ap_dt_ignore: Optional[np.ndarray] = None   # uint8 [4, 10, 100] the detection does not count at that range / threshold
+    ap_n_valid: Optional[np.ndarray] = None     # int32 [4] ground truths inside each area range
+    ap_n_kept: Optional[np.ndarray] = None      # int32 [1] ranks in use = min(n_boxes, 100)
     windows: Optional[List[Tuple[int, int, int, int]]] = None   # scene mode (scene.ScenePipeline): the planned (x0, y0, w, h) windows
     window_of: Optional[List[int]] = None   # scene mode: window_of[j] = index into `windows` of the window box j was decoded in
+
+    @property
+    def ap_tables(self) -> Optional[dict]:
+        """This tile's COCO matching as ``coco_ap.accumulate`` takes it (scores = `quality`, order, match, dt_ignore, n_valid,
+        n_kept); None unless the pipeline ran with ap=True."""
+        if self.ap_order is None:
+            return None
+        return {"scores": np.asarray(self.quality, dtype=np.float64), "order": self.ap_order, "match": self.ap_match,
+                "dt_ignore": self.ap_dt_ignore, "n_valid": self.ap_n_valid, "n_kept": int(self.ap_n_kept[0])}
 
     def png(self, kind: str) -> memoryview:
         """The bytes of ``gray/<stem>.png`` (kind "gray") or ``color/<stem>.png`` ("color") of this tile, encoded on the device
@@ -379,17 +394,19 @@ class TileResult:
 
 class OutputTable(NamedTuple):
     """One fixed-size per-box output, declared once (``output_tables``): per input set a device table [batch, max_boxes, *tail] that
-    the decode chain fills, per output buffer a pinned mirror, per tile the ``TileResult`` field of its [n_boxes, *tail] rows."""
+    the decode chain fills, per output buffer a pinned mirror, per tile the ``TileResult`` field of its [n_boxes, *tail] rows.
+    A `per_tile` output has one row per tile instead: tables [batch, *tail], the field is the tile's whole row."""
     field: str                      # the TileResult field
     dev: str                        # the pipeline attribute that holds the two device tables
     tail: Tuple[int, ...]           # shape of one box's row
     dtype: torch.dtype
     fill: Optional[str] = "zeros"   # the device tables start as "zeros" / "ones" / None: uninitialised
     as_bool: bool = False           # the host rows: a copy, or astype(bool)
+    per_tile: bool = False          # one row per tile, not per box: the tables are [batch, *tail] and a tile's result is its whole row
 
     def alloc(self, batch: int, max_boxes: int, device=None) -> torch.Tensor:
         """The device table (filled) on `device`; without one, its pinned host mirror."""
-        shape = (batch, max_boxes, *self.tail)
+        shape = (batch, *self.tail) if self.per_tile else (batch, max_boxes, *self.tail)
         if device is None:
             return torch.empty(shape, dtype=self.dtype).pin_memory()
         return {"zeros": torch.zeros, "ones": torch.ones, None: torch.empty}[self.fill](shape, dtype=self.dtype, device=device)
@@ -400,10 +417,11 @@ class OutputTable(NamedTuple):
 
 
 def output_tables(min_region_area: int = 0, mask_boxes: bool = False, quality: bool = False, gt: bool = False, rle: bool = False,
-                  instance: bool = False, overlap: str = "order") -> List[OutputTable]:
+                  instance: bool = False, overlap: str = "order", ap: bool = False) -> List[OutputTable]:
     """The per-box tables a pipeline with these (resolved) options allocates, copies to the host and hands out, in that order.
     Pure.  An option that is off contributes nothing: no allocation, no copy, and its TileResult fields stay None.  `instance`: an
-    InstancePipeline, which always reports the predicted IoU of the mask it kept."""
+    InstancePipeline, which always reports the predicted IoU of the mask it kept.  `ap`: the per-tile tables of the COCO matching
+    (``AP_SHAPE`` = area ranges, IoU thresholds, max detections)."""
     T, i64, i32 = OutputTable, torch.int64, torch.int32
     tabs = [T("areas", "area_dev", (), i64)]
     if min_region_area:
@@ -421,7 +439,16 @@ def output_tables(min_region_area: int = 0, mask_boxes: bool = False, quality: b
         tabs += [T("inter", "inter_dev", (), i64), T("gt_area", "gta_dev", (), i64)]
         if rle and mask_boxes:      # the ground-truth masks are only materialised for their RLE
             tabs.append(T("gt_hbox", "gt_hbox_dev", (4,), i32))
+    if ap:
+        A, Tn, D = AP_SHAPE
+        tile = dict(fill=None, per_tile=True)       # every tile's row is written whole by samrs_coco_match
+        tabs += [T("ap_order", "ap_order_dev", (D,), i32, **tile), T("ap_match", "ap_match_dev", (A, Tn, D), i32, **tile),
+                 T("ap_dt_ignore", "ap_ign_dev", (A, Tn, D), torch.uint8, **tile), T("ap_n_valid", "ap_nvalid_dev", (A,), i32, **tile),
+                 T("ap_n_kept", "ap_nkept_dev", (1,), i32, **tile)]
     return tabs
+
+
+AP_SHAPE = (4, 10, 100)     # coco_ap.AREA_RANGES, IOU_THRESHOLDS, MAX_DETS[-1]
 
 
 def check_packed(tab: np.ndarray, total: int, holder: str, now: int, what: str = "RLE buffer too small: a mask",
@@ -710,7 +737,8 @@ class TilePipeline:
         self.dev_lab = [torch.empty(batch * max_boxes, dtype=torch.int32, device=dev) for _ in range(2)]
         self.seg_dev = [torch.empty(batch, side, side, dtype=torch.uint8, device=dev) for _ in range(2)]
         # the fixed per-box outputs: one declaration each (output_tables), two device tables per entry under the entry's name
-        self.tables = output_tables(self.min_region_area, self.mask_boxes, self.quality, self.gt, rle, self.INSTANCE, self.overlap)
+        self.tables = output_tables(self.min_region_area, self.mask_boxes, self.quality, self.gt, rle, self.INSTANCE, self.overlap,
+                                    self.ap)
         for t in self.tables:
             setattr(self, t.dev, [t.alloc(batch, max_boxes, dev) for _ in range(2)])
         # the packed outputs, per input set: the payload (16-byte aligned entries) here, cursor and table in the stream
@@ -859,8 +887,9 @@ class TilePipeline:
             self.ev_enc[b].record(self.s_enc)
             self.ev_in_free[b].record(self.s_enc)
 
-    multimask = False      # InstancePipeline sets these three
+    multimask = False      # InstancePipeline sets these four
     gt = False
+    ap = False
     INSTANCE = False
 
     def _tile_prompts(self, b: int, tile, hw, off: int, nb: int):
@@ -1000,7 +1029,8 @@ class TilePipeline:
             seg = (odd[i].numpy() if odd[i] is not None else None) if i in odd else out.seg[i].numpy()
             m = out.masks[i].numpy() if out.masks[i] is not None else None
             r = TileResult(it.key, seg, boxes=np.asarray(it.boxes), labels=np.asarray(it.labels), masks=m,
-                           **{t.field: t.rows(out.tables[t.field][i, :nb]) for t in self.tables})
+                           **{t.field: t.rows(out.tables[t.field][i] if t.per_tile else out.tables[t.field][i, :nb])
+                              for t in self.tables})
             if seg is not None:
                 r.size = (int(seg.shape[0]), int(seg.shape[1]))
             else:
@@ -1093,13 +1123,23 @@ class InstancePipeline(TilePipeline):
     INSTANCE = True
 
     def __init__(self, sam, n_classes: int, prompt: str = "box", multimask: bool = True, fill_rule: str = "auto", gt: bool = False,
-                 **kw):
+                 ap: bool = False, **kw):
         """prompt: "box" / "rbox_mask" (annotations = rotated boxes [n, 4, 2]) or "point"
         (main_sam_hbox_mask_instance.py:160-165: annotations = one foreground point [n, 2] per object, handed to the prompt
         encoder AS IS -- the reference does not run them through apply_coords -- labels all 1, no box, no mask;
-        that driver uses multimask_output=False: pass multimask=False)."""
+        that driver uses multimask_output=False: pass multimask=False).
+        ap (needs gt=True): COCO mask AP's per-image matching on the device, every prediction of a tile against every ground truth
+        of it.  Each decode chunk packs its kept masks, as they go out, and its ground truth (straight from the staged label image)
+        into bit planes -- an eighth of the mask bytes, kept for the whole tile while the masks come and go `box_batch` at a time;
+        after the tile's last chunk ``Engine.mask_pair_counts`` and ``Engine.coco_match`` (score = the kept mask's predicted IoU)
+        run on the decode stream and ``TileResult.ap_tables`` holds the fixed-size tables ``coco_ap.accumulate`` takes.  The plane
+        buffers hold one tile and grow on demand (max_boxes x ceil(H W / 64) words each); tiles follow each other on one stream.
+        False (default) launches and allocates nothing, and every other output is byte for byte the same either way."""
         if prompt not in ("box", "rbox_mask", "point"):
             raise ValueError("prompt must be 'box', 'rbox_mask' or 'point'")
+        if ap and not gt:
+            raise ValueError("InstancePipeline(ap=True) matches predictions against the ground truth: it needs gt=True")
+        self.ap = bool(ap)             # read by TilePipeline.__init__ (output_tables)
         refuse_quality_options("InstancePipeline", "scoring the best-of-3 path is not built", **kw)
         refuse_overlap_option("InstancePipeline", "resolving the best-of-3 masks is not built", **kw)
         if prompt == "point":
@@ -1120,6 +1160,32 @@ class InstancePipeline(TilePipeline):
             self.dev_col = [torch.empty(B * M, 3, dtype=torch.uint8, device=dev) for _ in range(2)]
             self.gt_lab: List[List[torch.Tensor]] = [[], []]          # per input set: the label images on the device
             self.ev_gt = [torch.cuda.Event() for _ in range(2)]
+        if self.ap:                    # one tile's planes and pair counts, all used on s_dec alone
+            M = self.max_boxes
+            self.ap_words = 0
+            self.ap_pred = self.ap_gt = None
+            self.ap_inter = torch.empty(M * M, dtype=torch.int64, device=self.dev)
+            self.ap_area = torch.empty(2, M, dtype=torch.int64, device=self.dev)
+
+    def _ap_planes(self, hw):
+        """The tile's plane buffers [max_boxes, words] (prediction, ground truth), grown to the tile's size on the decode stream."""
+        words = (int(hw[0]) * int(hw[1]) + 63) // 64
+        if words > self.ap_words:
+            self.ap_pred = self.ap_gt = None              # stream-ordered: the allocator hands the blocks out on s_dec again
+            self.ap_pred = torch.empty(self.max_boxes * words, dtype=torch.int64, device=self.dev)
+            self.ap_gt = torch.empty(self.max_boxes * words, dtype=torch.int64, device=self.dev)
+            self.ap_words = words
+        n = self.max_boxes * words
+        return self.ap_pred[:n].view(self.max_boxes, words), self.ap_gt[:n].view(self.max_boxes, words)
+
+    def _ap_match(self, b: int, i: int, nb: int, planes) -> None:
+        """After a tile's last chunk: its nb predictions against its nb ground truths, matched into the batch's tables."""
+        eng = self.eng
+        pp, gp = (planes[0][:nb], planes[1][:nb]) if planes is not None else (torch.zeros(0, 1, dtype=torch.int64, device=self.dev),) * 2
+        inter, ad, ag = eng.mask_pair_counts(pp, gp, self.ap_inter[:nb * nb].view(nb, nb), self.ap_area[0, :nb], self.ap_area[1, :nb])
+        eng.coco_match(inter, ad, ag, self.qual_dev[b][i, :nb], max_det=AP_SHAPE[2], order_out=self.ap_order_dev[b][i],
+                       match_out=self.ap_match_dev[b][i], dt_ignore_out=self.ap_ign_dev[b][i], n_valid_out=self.ap_nvalid_dev[b][i],
+                       n_kept_out=self.ap_nkept_dev[b][i])
 
     def _stage(self, b: int, items: List[WorkItem]):
         if not self.gt:
@@ -1176,6 +1242,7 @@ class InstancePipeline(TilePipeline):
         kept = []
         if self.gt:
             self.s_dec.wait_event(self.ev_gt[b])
+        planes = self._ap_planes(hw) if (self.ap and nb) else None
         for s, e in box_chunks(nb, self.box_batch):
             m, q, _ = self._chunk_masks(b, i, tile, hw, off, s, e, pre)
             # best of the C masks by predicted IoU, its quality and area: one pass on the device, straight into the tables
@@ -1195,7 +1262,12 @@ class InstancePipeline(TilePipeline):
                     eng.rle_encode(gm, self.gt_rle_dev[b], self.gt_rle_out.cur[b], self.gt_rle_out.tab[b][off + s:off + e])
                     if self.mask_boxes:                   # the ground-truth masks are on the device here: their hbox too
                         eng.mask_boxes(gm, (0, 0), self.gt_hbox_dev[b][i, s:e], False, False)
+            if planes is not None:                        # the chunk's planes stay while its masks go
+                eng.pack_mask_bits(mk, planes[0][s:e])
+                eng.pack_label_bits(self.gt_lab[b][i], self.dev_col[b][off + s:off + e], planes[1][s:e])
             kept.append(mk)
+        if self.ap:
+            self._ap_match(b, i, nb, planes)
         self.last_masks = kept[-1].view(torch.bool) if kept else None
         out.masks[i] = torch.cat(kept).cpu() if (self.keep_masks and kept) else None
         out.odd[i] = None                      # instance pipelines paint no class map

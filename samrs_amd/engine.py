@@ -132,7 +132,13 @@ def load_library() -> C.CDLL:
     lib.samrs_score_masks.argtypes = [vp, vp, ip, ip, ip, ip, ip, fp, vp, vp, vp]
     lib.samrs_filter_masks.argtypes = [vp, vp, ip, ip, ip, vp, vp, fp, fp, fp, vp, vp]
     lib.samrs_resolve_overlaps.argtypes = [vp, vp, ip, ip, ip, ip, vp, ip, ip, vp, vp, vp, vp, vp]
-    for name in ("samrs_score_masks", "samrs_filter_masks", "samrs_resolve_overlaps"):
+    lib.samrs_mask_pack_bits.argtypes = [vp, vp, ip, ip, ip, vp, vp]
+    lib.samrs_label_pack_bits.argtypes = [vp, vp, vp, ip, ip, ip, vp, vp]
+    lib.samrs_mask_pair_counts.argtypes = [vp, vp, ip, vp, ip, C.c_int64, vp, vp, vp, vp]
+    lib.samrs_coco_match.argtypes = [vp, vp, vp, vp, vp, ip, ip, ip, C.POINTER(C.c_double), ip, C.POINTER(C.c_double), ip, ip,
+                                     vp, vp, vp, vp, vp, vp]
+    for name in ("samrs_score_masks", "samrs_filter_masks", "samrs_resolve_overlaps", "samrs_mask_pack_bits", "samrs_label_pack_bits",
+                 "samrs_mask_pair_counts", "samrs_coco_match"):
         getattr(lib, name).restype = ip
     lib.samrs_png_encode_labels.argtypes = [vp, vp, ip, ip, ip, vp, vp, C.c_int64, vp, vp, vp]
     lib.samrs_k_upscaler_fused.argtypes = [ip, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, vp]
@@ -950,6 +956,100 @@ class Engine:
             self._check(self.lib.samrs_gt_match(self.handle, m.data_ptr(), n, h, w, label_rgb.data_ptr(), colors.data_ptr(),
                                                 inter.data_ptr(), gta.data_ptr(), _ptr(gt_masks_out), _stream()))
         return inter, gta, gt_masks_out
+
+    # -- COCO mask AP (samrs_amd/coco_ap.py): bit planes, pairwise counts, the greedy matching ---------------------------------
+    def _out(self, name: str, t, shape, dtype) -> torch.Tensor:
+        """A caller-owned contiguous output of that shape and type, or with None a new one."""
+        if t is None:
+            return torch.empty(shape, dtype=dtype, device=self.device)
+        if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_cuda and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+            raise ValueError(f"{name} must be a contiguous {dtype} {list(shape)} tensor on the engine's device, or None")
+        return t
+
+    def pack_mask_bits(self, masks: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Bit planes of masks [n, H, W] bool / uint8 (non-zero = set; contiguous, any alignment) on the device
+        (samrs_mask_pack_bits) -> int64 [n, words], words = ceil(H W / 64): pixel p in row-major order is bit p % 64 of word p / 64
+        (the int64 holds the uint64 bit pattern; ``numpy().view(np.uint64)``), the unused high bits of the last word are zero.
+        `out`: a caller-owned contiguous int64 [n, words] slice.  Asynchronous on the current stream."""
+        m = self._masks_u8(masks)
+        n, h, w = m.shape
+        out = self._out("out", out, (n, (h * w + 63) // 64), torch.int64)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.samrs_mask_pack_bits(self.handle, m.data_ptr(), n, h, w, out.data_ptr(), _stream()))
+        return out
+
+    def pack_label_bits(self, label_rgb: torch.Tensor, colors: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Bit planes of the instances of a label image (samrs_label_pack_bits): label_rgb uint8 [H, W, 3], colors uint8 [n, 3] ->
+        int64 [n, words] in ``pack_mask_bits``' layout; instance j = the pixels whose RGB equals colors[j].  The image is read once
+        per call and no mask bytes are written."""
+        if label_rgb.dim() != 3 or label_rgb.shape[2] != 3 or label_rgb.dtype != torch.uint8:
+            raise ValueError(f"label_rgb must be uint8 [H, W, 3], got {label_rgb.dtype} {tuple(label_rgb.shape)}")
+        if colors.dim() != 2 or colors.shape[1] != 3 or colors.dtype != torch.uint8:
+            raise ValueError(f"colors must be uint8 [n, 3], got {colors.dtype} {tuple(colors.shape)}")
+        for t in (label_rgb, colors):
+            if not (t.is_cuda and t.is_contiguous()):
+                raise ValueError("label_rgb and colors must be contiguous tensors on the engine's device")
+        h, w, n = int(label_rgb.shape[0]), int(label_rgb.shape[1]), int(colors.shape[0])
+        out = self._out("out", out, (n, (h * w + 63) // 64), torch.int64)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.samrs_label_pack_bits(self.handle, label_rgb.data_ptr(), colors.data_ptr(), n, h, w, out.data_ptr(),
+                                                       _stream()))
+        return out
+
+    def mask_pair_counts(self, a: torch.Tensor, b: torch.Tensor, inter_out=None, area_a_out=None, area_b_out=None):
+        """Every plane of `a` against every plane of `b` (samrs_mask_pair_counts): a int64 [na, words], b int64 [nb, words] (bit
+        planes of masks of one size) -> (inter int64 [na, nb] = |a_i AND b_j|, area_a int64 [na], area_b int64 [nb]).  Exact integer
+        counts.  Each output: None = a new tensor, or a caller-owned contiguous tensor of that shape."""
+        for name, t in (("a", a), ("b", b)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.int64 and t.dim() == 2 and t.is_cuda and t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous int64 [n, words] tensor on the engine's device (pack_mask_bits)")
+        if a.shape[1] != b.shape[1]:
+            raise ValueError(f"a and b hold planes of different sizes: {a.shape[1]} and {b.shape[1]} words")
+        na, nb, words = int(a.shape[0]), int(b.shape[0]), int(a.shape[1])
+        inter = self._out("inter_out", inter_out, (na, nb), torch.int64)
+        area_a = self._out("area_a_out", area_a_out, (na,), torch.int64)
+        area_b = self._out("area_b_out", area_b_out, (nb,), torch.int64)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.samrs_mask_pair_counts(self.handle, a.data_ptr(), na, b.data_ptr(), nb, words, inter.data_ptr(),
+                                                        area_a.data_ptr(), area_b.data_ptr(), _stream()))
+        return inter, area_a, area_b
+
+    def coco_match(self, inter: torch.Tensor, area_d: torch.Tensor, area_g: torch.Tensor, scores, thresholds=None, area_ranges=None,
+                   max_det: int = 100, order_out=None, match_out=None, dt_ignore_out=None, n_valid_out=None, n_kept_out=None):
+        """COCOeval.evaluateImg's greedy matching of one image on the device (samrs_coco_match; the rule is stated there and in
+        samrs_amd/coco_ap.py): inter int64 [nd, ng], area_d int64 [nd], area_g int64 [ng] (``mask_pair_counts``), scores fp32 [nd]
+        on the device, or on the host (a CPU tensor / array: checked for NaN, then uploaded by the library) ->
+        (order int32 [max_det], match int32 [A, T, max_det] = ground-truth INDEX or -1, dt_ignore uint8 [A, T, max_det],
+        n_valid int32 [A], n_kept int32 [1]) for the T `thresholds` (default: COCO's ten) and A `area_ranges` (default: COCO's
+        four).  Ranks past n_kept hold -1 / -1 / 0.  A NaN among device scores yields n_kept = -1.  Asynchronous on the current
+        stream; the outputs may be caller-owned contiguous tensors."""
+        from . import coco_ap
+        thr = np.ascontiguousarray(coco_ap.IOU_THRESHOLDS if thresholds is None else thresholds, dtype=np.float64).reshape(-1)
+        rng = np.ascontiguousarray(coco_ap.AREA_RANGES if area_ranges is None else area_ranges, dtype=np.float64).reshape(-1, 2)
+        T, A, max_det = len(thr), len(rng), int(max_det)
+        nd, ng = int(area_d.numel()), int(area_g.numel())
+        for name, t, shape in (("inter", inter, (nd, ng)), ("area_d", area_d, (nd,)), ("area_g", area_g, (ng,))):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.int64 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shape):
+                raise ValueError(f"{name} must be a contiguous int64 {list(shape)} tensor on the engine's device")
+        on_host = not (isinstance(scores, torch.Tensor) and scores.is_cuda)
+        if on_host:
+            scores = torch.as_tensor(np.ascontiguousarray(np.asarray(scores, dtype=np.float32).reshape(-1)))
+        if not (scores.dtype == torch.float32 and scores.is_contiguous() and scores.numel() == nd):
+            raise ValueError(f"scores must be a contiguous fp32 [{nd}] tensor or array")
+        order = self._out("order_out", order_out, (max_det,), torch.int32)
+        match = self._out("match_out", match_out, (A, T, max_det), torch.int32)
+        ign = self._out("dt_ignore_out", dt_ignore_out, (A, T, max_det), torch.uint8)
+        n_valid = self._out("n_valid_out", n_valid_out, (A,), torch.int32)
+        n_kept = self._out("n_kept_out", n_kept_out, (1,), torch.int32)
+        dp = C.POINTER(C.c_double)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.samrs_coco_match(self.handle, _ptr(inter) if nd and ng else None, _ptr(area_d) if nd else None,
+                                                  _ptr(area_g) if ng else None, scores.data_ptr() if nd else None, int(on_host), nd, ng,
+                                                  thr.ctypes.data_as(dp), T, rng.ctypes.data_as(dp), A, max_det, order.data_ptr(),
+                                                  match.data_ptr(), ign.data_ptr(), n_valid.data_ptr(), n_kept.data_ptr(), _stream()))
+            if on_host and nd:
+                torch.cuda.current_stream().synchronize()      # the library reads the host scores on the stream
+        return order, match, ign, n_valid, n_kept
 
     def paint(self, masks: torch.Tensor, labels: torch.Tensor, seg: torch.Tensor,
               class_pixels: Optional[torch.Tensor] = None, class_instances: Optional[torch.Tensor] = None,

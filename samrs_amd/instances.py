@@ -16,6 +16,11 @@ quality, its area, |mask AND ground truth|, |ground truth| and the two COCO RLE 
 (``samrs_select_best``, ``samrs_gt_match``, ``samrs_rle_encode``).  Each rank writes one fragment per image
 (``OUT/parts/<stem>.json``); after a barrier rank 0 merges them in sorted-stem order.
 
+``--ap`` (needs ``--gt-labels``) adds the number the two JSON files exist for (main_sam_rhbox_mask_instance.py:246-255): on the
+device every prediction of an image is matched against every ground truth of it (``InstancePipeline(ap=True)``), each fragment
+gains an ``"ap"`` record, rank 0 writes ``ap.json`` and prints COCO's twelve lines after the mIoU line (``samrs_amd.coco_ap``; a
+match is a match by index, so ground truth 0 counts).
+
 One deliberate difference from the reference: image ids follow the SORTED image stems.  The reference numbers images in
 ``os.listdir`` order (main_sam_rhbox_mask_instance.py:83), which is unspecified.  Images without an annotation file are ignored.
 """
@@ -139,9 +144,10 @@ def write_fragment(out_dir: str, stem: str, frag: dict) -> None:
 
 
 def make_fragment(height: int, width: int, scores, rles: Sequence[str], pred_area=None, inter=None, gt_area=None,
-                  gt_rles: Optional[Sequence[str]] = None, bboxes=None, gt_bboxes=None) -> dict:
+                  gt_rles: Optional[Sequence[str]] = None, bboxes=None, gt_bboxes=None, ap: Optional[dict] = None) -> dict:
     """scores: fp32 qualities (stored as float(fp32), instance_to_json.py:103); rles / gt_rles: the COCO counts strings; bboxes /
-    gt_bboxes (--mask-boxes): COCO [x, y, w, h] per prediction / ground-truth mask."""
+    gt_bboxes (--mask-boxes): COCO [x, y, w, h] per prediction / ground-truth mask; ap (--ap): the image's matching tables
+    (``TileResult.ap_tables``), stored as the ranks in use: order, match, dt_ignore, n_valid."""
     frag = {"height": int(height), "width": int(width), "scores": [float(np.float32(s)) for s in scores], "rles": list(rles)}
     if gt_rles is not None:
         frag.update(pred_area=[int(v) for v in pred_area], inter=[int(v) for v in inter], gt_area=[int(v) for v in gt_area],
@@ -150,6 +156,12 @@ def make_fragment(height: int, width: int, scores, rles: Sequence[str], pred_are
         frag["bboxes"] = [[int(v) for v in b] for b in bboxes]
     if gt_bboxes is not None:
         frag["gt_bboxes"] = [[int(v) for v in b] for b in gt_bboxes]
+    if ap is not None:
+        k = int(ap["n_kept"])
+        if k < 0:
+            raise ValueError("a predicted IoU is NaN: the matching cannot order the detections")
+        frag["ap"] = {"order": np.asarray(ap["order"])[:k].tolist(), "match": np.asarray(ap["match"])[:, :, :k].tolist(),
+                      "dt_ignore": np.asarray(ap["dt_ignore"])[:, :, :k].tolist(), "n_valid": np.asarray(ap["n_valid"]).tolist()}
     return frag
 
 
@@ -159,9 +171,18 @@ def coco_bboxes(hbox: np.ndarray, areas) -> List[List[int]]:
             for b, a in zip(hbox, areas)]
 
 
-def pending_stems(out_dir: str, stems: Sequence[str]) -> List[str]:
-    """--resume: the stems whose fragment is not on disk yet."""
-    return [s for s in stems if not os.path.exists(fragment_path(out_dir, s))]
+def pending_stems(out_dir: str, stems: Sequence[str], need_ap: bool = False) -> List[str]:
+    """--resume: the stems whose fragment is not on disk yet; with `need_ap` (--ap) a fragment without an "ap" record (written by
+    a run without the flag) counts as not done."""
+    def done(s):
+        path = fragment_path(out_dir, s)
+        if not os.path.exists(path):
+            return False
+        if not need_ap:
+            return True
+        with open(path) as f:
+            return "ap" in json.load(f)
+    return [s for s in stems if not done(s)]
 
 
 def miou_from_tallies(inter: Sequence[int], pred_area: Sequence[int], gt_area: Sequence[int]) -> Tuple[float, float, int]:
@@ -179,10 +200,11 @@ def miou_from_tallies(inter: Sequence[int], pred_area: Sequence[int], gt_area: S
     return float(np.mean(ious)), float(np.sum(inter_all) / np.sum(union_all)), len(ious)
 
 
-def merge_fragments(out_dir: str, stems: Sequence[str], tag: str, with_gt: bool) -> Optional[dict]:
+def merge_fragments(out_dir: str, stems: Sequence[str], tag: str, with_gt: bool, with_ap: bool = False) -> Optional[dict]:
     """Rank 0, after every rank has written its fragments: ``sam_ins_<tag>.json`` (binary_to_coco_pre_hrsc) and, with the
     ground truth, ``gt_ins_<tag>.json`` (binary_to_coco_gt_hrsc) and ``miou.json``; image id = position in `stems` (sorted),
-    annotation ids restart at 0 per image.  Returns the mIoU record (None without ground truth)."""
+    annotation ids restart at 0 per image.  `with_ap`: also ``ap.json`` from the fragments' matching tables
+    (``coco_ap.accumulate``) and COCO's twelve lines after the mIoU line.  Returns the mIoU record (None without ground truth)."""
     frags = []
     for stem in stems:
         path = fragment_path(out_dir, stem)
@@ -222,6 +244,21 @@ def merge_fragments(out_dir: str, stems: Sequence[str], tag: str, with_gt: bool)
     with open(os.path.join(out_dir, "miou.json"), "w") as f:
         json.dump(rec, f)
     print("Average mIOU: ", avg, "Area mIOU: ", area, flush=True)              # main_sam_rhbox_mask_instance.py:244
+    if with_ap:
+        from . import coco_ap
+        tables = []
+        for stem, fr in zip(stems, frags):
+            if "ap" not in fr:
+                raise RuntimeError(f"fragment {fragment_path(out_dir, stem)} holds no \"ap\" record: written without --ap (rerun with --resume)")
+            t = fr["ap"]
+            k, A, T = len(t["order"]), len(t["n_valid"]), len(coco_ap.IOU_THRESHOLDS)
+            tables.append(coco_ap.image_table(fr["scores"], t["order"], np.asarray(t["match"], dtype=np.int64).reshape(A, T, k),
+                                              np.asarray(t["dt_ignore"], dtype=np.uint8).reshape(A, T, k), t["n_valid"], k))
+        numbers = coco_ap.accumulate(tables)
+        with open(os.path.join(out_dir, "ap.json"), "w") as f:
+            json.dump(coco_ap.ap_record(numbers, tables), f)
+        for line in coco_ap.summary_lines(numbers):
+            print(line, flush=True)
     return rec
 
 
@@ -251,11 +288,14 @@ def run(args) -> Optional[dict]:
         else:
             dist.init_process_group("nccl", device_id=torch.device("cuda", local))
     with_gt = bool(getattr(args, "gt_labels", None))
+    with_ap = bool(getattr(args, "ap", False))
+    if with_ap and not with_gt:
+        raise ValueError("--ap matches the predictions against the ground truth: it needs --gt-labels")
     stems, files, anns = list_images(args.images, args.annotations)
     todo = stems
     if getattr(args, "resume", False):
         # listed once, on rank 0, and broadcast (generate.run: ranks must index the same list)
-        todo = driver.agree_on_list(pending_stems(args.out, stems) if rank == 0 else [])
+        todo = driver.agree_on_list(pending_stems(args.out, stems, need_ap=with_ap) if rank == 0 else [])
         if rank == 0:
             print(f"[rank 0] --resume: {len(stems) - len(todo)} of {len(stems)} images already complete", flush=True)
     batch = getattr(args, "batch", 8)
@@ -274,7 +314,7 @@ def run(args) -> Optional[dict]:
                                    batch_decode=True if getattr(args, "batch_decode", False) else "auto",
                                    min_region_area=int(getattr(args, "min_region_area", 0) or 0),
                                    region_mode=getattr(args, "region_mode", "both"),
-                                   mask_boxes=bool(getattr(args, "mask_boxes", False)))
+                                   mask_boxes=bool(getattr(args, "mask_boxes", False)), ap=with_ap)
     os.makedirs(os.path.join(args.out, "parts"), exist_ok=True)
     import zlib
     wq_name = "samrs_ins/%08x" % zlib.crc32(("\n".join(todo) + "|" + args.out).encode())
@@ -310,7 +350,7 @@ def run(args) -> Optional[dict]:
                 if with_gt:
                     gbs = coco_bboxes(r.gt_hbox, r.gt_area) if r.gt_hbox is not None else None
                     frag = make_fragment(r.size[0], r.size[1], r.quality, rles, r.areas, r.inter, r.gt_area,
-                                         [r.gt_rle(j)["counts"] for j in range(n)], bbs, gbs)
+                                         [r.gt_rle(j)["counts"] for j in range(n)], bbs, gbs, ap=r.ap_tables)
                 else:
                     frag = make_fragment(r.size[0], r.size[1], r.quality, rles, bboxes=bbs)
                 write_fragment(args.out, r.key, frag)
@@ -326,7 +366,7 @@ def run(args) -> Optional[dict]:
         dist.barrier()
     rec = None
     if rank == 0:
-        rec = merge_fragments(args.out, stems, tag, with_gt)
+        rec = merge_fragments(args.out, stems, tag, with_gt, with_ap)
         if getattr(args, "audit_passes", 0) > 0 and sam.finish_audit() is not None:
             from . import audit
             audit.write_json(sam.audit_report, os.path.join(args.out, "statistic", "audit.json"))
@@ -359,6 +399,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--rle-buffer-mb", type=int, default=256)
     ap.add_argument("--schedule", default="static", choices=["static", "dynamic"])
     ap.add_argument("--resume", action="store_true", help="skip images whose fragment OUT/parts/<stem>.json already exists")
+    ap.add_argument("--ap", action="store_true",
+                    help="COCO mask AP on the GPU (needs --gt-labels): every prediction of an image is matched against every ground "
+                         "truth of it on the device; OUT/ap.json holds the twelve COCO numbers, printed after the mIoU line "
+                         "(samrs_amd.coco_ap; a match is a match by index)")
     ap.add_argument("--batch-decode", action="store_true",
                     help="decode the prompts of all images of a batch in one decoder chain (Engine.predict_multi); same outputs")
     from . import generate
