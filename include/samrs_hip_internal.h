@@ -87,6 +87,11 @@ int samrs_k_layernorm(int prec, const float* X, const float* gamma, const float*
 int samrs_k_window_attention(int prec, const void* qkv_et, const float* qkv_bias, const float* rel_h,
                              const float* rel_w, void* out_et, int n_images, int grid, int window,
                              int heads, int head_dim, void* stream);
+/* TEST hook: the same kernel (window 14) with out_lo_et, the split remainder of out_et, written for the heads whose bit is set in
+ * lo_heads only (what the engine passes from the outlier columns of proj); rows of the other heads in out_lo_et are left alone. */
+int samrs_k_window_attention_lo(int prec, const void* qkv_et, const float* qkv_bias, const float* rel_h, const float* rel_w,
+                                void* out_et, void* out_lo_et, int n_images, int grid, int heads, int head_dim, uint32_t lo_heads,
+                                void* stream);
 /* TEST / BENCH hook (as is samrs_k_attention_mx with global = 1): the V^T workspace the engine owns is, here, one grow-only
  * buffer per device kept by the library; growing it synchronizes the device first.  Not for product code: an engine's own
  * encoder pass (samrs_set_images) uses the engine's workspace and never this one. */

@@ -102,6 +102,12 @@ int samrs_k_window_attention(int prec, const void* qkv, const float* qkv_bias, c
                              int n_images, int grid, int window, int heads, int head_dim, void* stream) {
     KRET(launch_window_attention(prec, qkv, qkv_bias, rel_h, rel_w, out, n_images, grid, window, heads, head_dim, (hipStream_t)stream));
 }
+// test hook: the windowed kernel with its split remainder and the per-head mask of out_lo that the engine sets from EncBlock::oc_heads
+int samrs_k_window_attention_lo(int prec, const void* qkv, const float* qkv_bias, const float* rel_h, const float* rel_w, void* out,
+                                void* out_lo, int n_images, int grid, int heads, int head_dim, uint32_t lo_heads, void* stream) {
+    KRET(launch_window_attention(prec, qkv, qkv_bias, rel_h, rel_w, out, n_images, grid, 14, heads, head_dim, (hipStream_t)stream, out_lo,
+                                 nullptr, nullptr, nullptr, nullptr, lo_heads));
+}
 // V^T workspace of the two global-attention TEST / BENCH hooks below (the engine owns its own: e->VTG).  One grow-only buffer per
 // DEVICE, looked up under a lock.  A buffer that is outgrown is RETIRED, never freed: another thread of the same device may hold the
 // old pointer between this function's return and its own kernel launch (the pointer leaves the lock), and a device synchronisation

@@ -145,6 +145,7 @@ def load_library() -> C.CDLL:
     lib.samrs_k_convert.argtypes = [ip, vp, vp, C.c_int64, vp]
     lib.samrs_k_layernorm.argtypes = [ip, vp, vp, vp, fp, vp, vp, ip, ip, ip, ip, ip, ip, vp]
     lib.samrs_k_window_attention.argtypes = [ip, vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, vp]
+    lib.samrs_k_window_attention_lo.argtypes = [ip, vp, vp, vp, vp, vp, vp, ip, ip, ip, ip, C.c_uint32, vp]
     lib.samrs_k_global_attention.argtypes = [ip, vp, vp, vp, vp, ip, ip, ip, ip, vp]
     lib.samrs_k_postprocess.argtypes = [vp, ip, ip, ip, ip, ip, ip, ip, vp, vp]
     lib.samrs_k_neck_im2col.argtypes = [vp, vp, ip, ip, ip, vp]
@@ -200,7 +201,7 @@ def load_library() -> C.CDLL:
     for name in ("samrs_load_weight", "samrs_finalize_weights", "samrs_set_images", "samrs_set_images_ragged", "samrs_get_embedding",
                  "samrs_set_embedding", "samrs_reset_image", "samrs_predict", "samrs_predict_multi", "samrs_paint", "samrs_k_gemm",
                  "samrs_k_gemm_f32", "samrs_k_convert", "samrs_k_layernorm", "samrs_k_window_attention",
-                 "samrs_k_global_attention", "samrs_k_postprocess", "samrs_k_gemm_gln", "samrs_k_upscale2_masks",
+                 "samrs_k_window_attention_lo", "samrs_k_global_attention", "samrs_k_postprocess", "samrs_k_gemm_gln", "samrs_k_upscale2_masks",
                  "samrs_k_gemm_stats", "samrs_k_gemm_fold", "samrs_k_ln_fold_weight", "samrs_k_rowstats_convert", "samrs_k_ln_rowstat",
                  "samrs_set_option", "samrs_get_option", "samrs_rle_encode", "samrs_k_convert_split", "samrs_select_best", "samrs_gt_match",
                  "samrs_png_encode_labels", "samrs_k_upscaler_fused", "samrs_k_gemm_split3", "samrs_get_slot_info"):
