@@ -1,5 +1,5 @@
 // decoder_kernels.hip -- prompt encoder, two-way transformer glue, upscaler tail, postprocess,
-// painting (gfx950).  The GEMM-shaped parts run through gemm.hip; everything here is the
+// painting (gfx950).  The GEMM-shaped parts run through gemm.hip (launch_gemm_et) and gemm_decoder.hip; everything here is the
 // HBM-/latency-bound remainder, fp32 except where it feeds an MFMA GEMM.
 //
 // Reference semantics (paths under Generate Dataset/segment_anything/):

@@ -1675,7 +1675,7 @@ hipError_t launch_ln_fold_weight(int prec, const float* W, const float* gamma, c
 }
 
 // Entry of the folded path (the residual stream as the patch-embed GEMM left it): Xh = ET(X) and, per row, the (mean, M2) pairs
-// of eight 160-element groups -- the same partials the residual GEMMs emit (gemm.hip, epilogue_m32<STATS>; the merge does not
+// of eight 160-element groups -- the same partials the residual GEMMs emit (gemm_experiments.hip, epilogue_m32<STATS>; the merge does not
 // care WHICH 160 elements form a group).  One wave per row of 1280: lane l holds float4 l, l + 64, ... (20 values), a group =
 // 8 consecutive lanes, two-pass inside the group.
 template <int PREC>

@@ -17,387 +17,36 @@
 // reads are bank-conflict free.  MFMA operands are swapped (first = weight fragment, second =
 // activation fragment) so that each lane ends up with 4 CONSECUTIVE output columns of one row:
 // the epilogue then uses 8-byte (ET) / 16-byte (fp32) vector accesses and float4 bias loads.
-#include <cstdlib>
+//
+// One translation unit per kernel family.  This one keeps the dispatch (launch_gemm_et: validate -> gemm_select -> one switch), the
+// process state the selection rule reads, the dominant kernel (four-wave 256x256 gemm_et_w4x_kernel) and the eight-wave kernels on
+// 256-row tiles -- gemm_et_big_kernel, gemm_et_x64_kernel, gemm_et_x64p_kernel, gemm_et_mx_kernel -- which share instantiations of
+// epilogue_pair_et and must be compiled together (the optimizer shapes a caller by the other callers of an internal function it sees:
+// apart, two of them get other registers and spills; tools/device_code_diff.py, profiles/r12_gemm_split.txt).  Elsewhere:
+//   gemm_ring.hip        gemm_et_kernel (the v1 kernel above, 128 x 128) and gemm_et_stag_kernel (256 x 128, 3-stage ring)
+//   gemm_dual.hip        gemm_et_dual_kernel: 2 blocks / CU; the GELU(LayerNorm2d) launcher
+//   gemm_decoder.hip     gemm_et_k256_kernel (K = 256 streaming) and gemm_f32_kernel (exact fp32)
+//   gemm_experiments.hip make EXPERIMENTS=1 only: gemm_et_m32_kernel, gemm_et_w4_kernel, the LayerNorm fold's two public launchers
+//   gemm_device.h        device helpers that more than one file uses;  gemm_families.h: the launchers of the other files
+#include "gemm_device.h"
+#include "gemm_families.h"
 
-#include <type_traits>
 
-#include "common.h"
-#include "gemm_select.h"
-#include "kernels.h"
-
-using namespace gemm_sel;
-
-namespace {
-
-// f(std::integral_constant<int, PREC_*>) for the operand type named at run time
-template <class F>
-hipError_t with_prec(int prec, F&& f) {
-    if (prec == PREC_BF16) return f(std::integral_constant<int, PREC_BF16>{});
-    if (prec == PREC_F16) return f(std::integral_constant<int, PREC_F16>{});
-    return hipErrorInvalidValue;
-}
 // CUs of the current device: the grid of a persistent kernel.  cu_count() asks once per process (the first launch's device; the
 // devices of one box are the same part); the launchers that always asked per call go on doing so (cu_count_now()), since engines of
 // one process may sit on different devices (DeviceGuard).
-int cu_count_now() {
+int gemm_fam::cu_count_now() {
     int dev = 0, n = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
     return n > 0 ? n : 256;
 }
-int cu_count() {
+int gemm_fam::cu_count() {
     static const int n = cu_count_now();
     return n;
 }
 
-constexpr int GEMM_THREADS = 256;      // BM / BN / BK and the other tile shapes the selection rule reads: gemm_select.h
+namespace {
 
-// physical 16-byte chunk of logical chunk c in row r of a [rows][64] ET tile
-__device__ __forceinline__ int swz(int r, int c) { return c ^ ((r >> 1) & 7); }
-
-// LDS-DMA helper: 16 bytes per lane, global (per-lane address) -> LDS (wave-uniform base + lane*16).
-__device__ __forceinline__ void glds16(const uint16_t* gsrc, uint16_t* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                     (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-template <int PREC, bool OUT_F32, bool GELU, bool GLDS, int GROUP_M>
-__global__ __launch_bounds__(GEMM_THREADS) void gemm_et_kernel(
-    const uint16_t* __restrict__ A, const uint16_t* __restrict__ B, void* __restrict__ Cv,
-    const float* __restrict__ bias, const float* __restrict__ add2d, int add2d_period,
-    int M, int N, int K, int accumulate) {
-    __shared__ __attribute__((aligned(16))) uint16_t lds[2][2][BM * BK];  // [buf][A|B] 64 KiB
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-
-    // Tile order.  (1) xcd_remap gives every XCD a contiguous range of logical ids (blocks that
-    // run together share one 4 MB L2).  (2) Inside that range ids walk GROUP_M tile rows fastest,
-    // then tile columns: the ~64 blocks resident on an XCD form a ~8x8 super-tile, so each A and B
-    // panel fetched into L2 is reused 8 times instead of streaming the whole weight matrix through
-    // L2 once per tile row.
-    const int tiles_n = N / BN, tiles_m = M / BM;
-    const int nwg = gridDim.x;
-    const int bid = xcd_remap(blockIdx.x, nwg);
-    int tile_m, tile_n;
-    if (GROUP_M > 1) {
-        const int per_group = GROUP_M * tiles_n;
-        const int group = bid / per_group, first_m = group * GROUP_M;
-        const int gsz = (tiles_m - first_m) < GROUP_M ? (tiles_m - first_m) : GROUP_M;
-        const int in_g = bid - group * per_group;
-        tile_m = first_m + in_g % gsz;
-        tile_n = in_g / gsz;
-    } else {
-        tile_m = bid / tiles_n;
-        tile_n = bid % tiles_n;
-    }
-    const int m0 = tile_m * BM, n0 = tile_n * BN;
-
-    // --- staging map: thread t moves chunks (row = (t>>3) + 32*i, chunk = t&7), i = 0..3 ---
-    const int ld_row = tid >> 3;
-    const int ld_chunk = tid & 7;
-    const uint16_t* gA = A + (size_t)(m0 + ld_row) * K + ld_chunk * 8;
-    const uint16_t* gB = B + (size_t)(n0 + ld_row) * K + ld_chunk * 8;
-
-    // Staging registers.  Plain macros (not lambdas / conditionals): anything that makes the
-    // compiler see these arrays through a pointer puts them in scratch.
-    uint4 ra0, ra1, ra2, ra3, rb0, rb1, rb2, rb3;
-#define GEMM_LOAD_TILE(kt_)                                                                   \
-    do {                                                                                       \
-        const size_t koff_ = (size_t)(kt_) * BK;                                               \
-        ra0 = *reinterpret_cast<const uint4*>(gA + koff_);                                     \
-        ra1 = *reinterpret_cast<const uint4*>(gA + (size_t)32 * K + koff_);                    \
-        ra2 = *reinterpret_cast<const uint4*>(gA + (size_t)64 * K + koff_);                    \
-        ra3 = *reinterpret_cast<const uint4*>(gA + (size_t)96 * K + koff_);                    \
-        rb0 = *reinterpret_cast<const uint4*>(gB + koff_);                                     \
-        rb1 = *reinterpret_cast<const uint4*>(gB + (size_t)32 * K + koff_);                    \
-        rb2 = *reinterpret_cast<const uint4*>(gB + (size_t)64 * K + koff_);                    \
-        rb3 = *reinterpret_cast<const uint4*>(gB + (size_t)96 * K + koff_);                    \
-    } while (0)
-    // swz(r + 32*i, c) == swz(r, c) ^ ... is NOT row-invariant, so compute the 4 offsets once.
-    int st_off[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int r = ld_row + 32 * i;
-        st_off[i] = r * BK + swz(r, ld_chunk) * 8;
-    }
-#define GEMM_STORE_TILE(buf_)                                                                 \
-    do {                                                                                       \
-        uint16_t* la_ = &lds[buf_][0][0];                                                      \
-        uint16_t* lb_ = &lds[buf_][1][0];                                                      \
-        *reinterpret_cast<uint4*>(la_ + st_off[0]) = ra0;                                      \
-        *reinterpret_cast<uint4*>(la_ + st_off[1]) = ra1;                                      \
-        *reinterpret_cast<uint4*>(la_ + st_off[2]) = ra2;                                      \
-        *reinterpret_cast<uint4*>(la_ + st_off[3]) = ra3;                                      \
-        *reinterpret_cast<uint4*>(lb_ + st_off[0]) = rb0;                                      \
-        *reinterpret_cast<uint4*>(lb_ + st_off[1]) = rb1;                                      \
-        *reinterpret_cast<uint4*>(lb_ + st_off[2]) = rb2;                                      \
-        *reinterpret_cast<uint4*>(lb_ + st_off[3]) = rb3;                                      \
-    } while (0)
-
-    f32x4_t acc[4][4];  // [n-tile i][m-tile j]; D[i_local = n][j_local = m]
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-    const int nk = K / BK;
-    // GLDS staging (cdna_hip_programming.md section 5, rule 21): the DMA writes LDS linearly
-    // (wave-uniform base + lane*16 B), so wave w's i-th instruction fills rows 32i + 8w .. +7
-    // (lane l -> row +(l>>3), physical chunk l&7) and the swizzle goes on the SOURCE address:
-    // the lane fetches logical chunk (l&7) ^ swz(row).  swz(row) does not depend on i.
-    const int g_row = 8 * wave + (lane >> 3);
-    const int g_chunk = (lane & 7) ^ ((g_row >> 1) & 7);
-    const uint16_t* gAg = A + (size_t)(m0 + g_row) * K + g_chunk * 8;
-    const uint16_t* gBg = B + (size_t)(n0 + g_row) * K + g_chunk * 8;
-#define GEMM_GLDS_TILE(kt_, buf_)                                                              \
-    do {                                                                                       \
-        const size_t koff_ = (size_t)(kt_) * BK;                                               \
-        _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                     \
-            glds16(gAg + (size_t)(32 * i_) * K + koff_, &lds[buf_][0][(32 * i_ + 8 * wave) * BK]); \
-            glds16(gBg + (size_t)(32 * i_) * K + koff_, &lds[buf_][1][(32 * i_ + 8 * wave) * BK]); \
-        }                                                                                      \
-    } while (0)
-
-    if (GLDS) {
-        GEMM_GLDS_TILE(0, 0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
-        GEMM_LOAD_TILE(0);
-        GEMM_STORE_TILE(0);
-    }
-    __syncthreads();
-
-    const int fr = lane & 15;   // fragment row within a 16-row tile
-    const int fq = lane >> 4;   // k-quarter (8 elements) within a 32-wide k-substep
-
-    for (int kt = 0; kt < nk; ++kt) {
-        const int buf = kt & 1;
-        if (GLDS) {
-            if (kt + 1 < nk) GEMM_GLDS_TILE(kt + 1, buf ^ 1);
-        } else {
-            // unconditional prefetch (the last iteration re-reads the last tile; nobody consumes it)
-            GEMM_LOAD_TILE(kt + 1 < nk ? kt + 1 : kt);
-        }
-
-        const uint16_t* la = &lds[buf][0][0];
-        const uint16_t* lb = &lds[buf][1][0];
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            uint4 fa[4], fb[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int r = wm * 64 + j * 16 + fr;
-                fa[j] = *reinterpret_cast<const uint4*>(la + r * BK + swz(r, ks * 4 + fq) * 8);
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int r = wn * 64 + i * 16 + fr;
-                fb[i] = *reinterpret_cast<const uint4*>(lb + r * BK + swz(r, ks * 4 + fq) * 8);
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] = ET<PREC>::mfma16(fb[i], fa[j], acc[i][j]);
-        }
-
-        if (GLDS) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // next tile has landed in LDS
-        } else {
-            GEMM_STORE_TILE(buf ^ 1);
-        }
-        __syncthreads();
-    }
-
-    // --- epilogue: lane holds C[m][n..n+3], m = m0 + wm*64 + j*16 + (lane&15),
-    //                                      n = n0 + wn*64 + i*16 + 4*(lane>>4)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int n = n0 + wn * 64 + i * 16 + 4 * fq;
-        float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (bias) bv = *reinterpret_cast<const float4*>(bias + n);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int m = m0 + wm * 64 + j * 16 + fr;
-            float v0 = acc[i][j][0] + bv.x, v1 = acc[i][j][1] + bv.y;
-            float v2 = acc[i][j][2] + bv.z, v3 = acc[i][j][3] + bv.w;
-            if (add2d) {
-                const float4 e = *reinterpret_cast<const float4*>(
-                    add2d + (size_t)(m % add2d_period) * N + n);
-                v0 += e.x; v1 += e.y; v2 += e.z; v3 += e.w;
-            }
-            if (GELU) { const float2_t g01 = gelu_erf2(float2_t{v0, v1}), g23 = gelu_erf2(float2_t{v2, v3}); v0 = g01.x; v1 = g01.y; v2 = g23.x; v3 = g23.y; }
-            if (OUT_F32) {
-                float* C = reinterpret_cast<float*>(Cv) + (size_t)m * N + n;
-                if (accumulate) {
-                    const float4 o = *reinterpret_cast<const float4*>(C);
-                    v0 += o.x; v1 += o.y; v2 += o.z; v3 += o.w;
-                }
-                *reinterpret_cast<float4*>(C) = make_float4(v0, v1, v2, v3);
-            } else {
-                uint16_t* C = reinterpret_cast<uint16_t*>(Cv) + (size_t)m * N + n;
-                uint2 o;
-                o.x = pack2<PREC>(v0, v1);
-                o.y = pack2<PREC>(v2, v3);
-                *reinterpret_cast<uint2*>(C) = o;
-            }
-        }
-    }
-}
-
-
-__device__ __forceinline__ void wave_lds_sync_g() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// ---------------------------------------------------------------------------------------------
-// Coalesced epilogue.  In the MFMA accumulator layout a lane owns 4 consecutive columns of ONE row,
-// so a direct store instruction scatters 16 rows x 32-byte pieces: measured (ablation)
-// that costs a third of the whole GEMM.  Instead each wave bounces its 64-column sub-tile through
-// its private slice of the (now idle) LDS ring and writes / read-modify-writes FULL 128- or 256-byte
-// row segments with 16 bytes per lane.  bias + GELU are applied before the bounce (per-lane column
-// known), the 2-D addend and the residual accumulate after it (coalesced loads).
-//   acc[i][j]: n-tile i (16 cols), m-tile j (16 rows); NJ m-tiles per wave, JC of them per pass.
-// ---------------------------------------------------------------------------------------------
-// DRAIN (persistent kernels): the caller has LDS-DMA pieces of its NEXT tile in flight; they are retired (vmcnt(0)) right
-// before this wave's first global store, i.e. after the bias loads, the VALU work and the first LDS bounce have covered
-// their latency, and before any store joins the queue -- so the stores themselves are never waited for.
-template <int PREC, bool OUT_F32, int GELU /* 0 none, 1 fp32-epsilon erf, 2 the cheaper erf (ET output) */, int NJ, int JC, int NI = 4, bool GLN = false,
-          bool DRAIN = false, bool STREAM = false /* ET output: non-temporal stores (common.h store16_stream) */>
-__device__ __forceinline__ void epilogue_coalesced(f32x4_t (&acc)[NI][NJ], unsigned char* scr /* wave-private */,
-                                                   void* __restrict__ Cv, const float* __restrict__ bias,
-                                                   const float* __restrict__ add2d, int add2d_period, int N,
-                                                   int m_base /* first row of the wave tile */,
-                                                   int n_base /* first column of the wave tile */, int accumulate,
-                                                   int lane, const float* __restrict__ pre2d = nullptr /* ET output: 2-D addend
-                                                   applied before the bounce, loaded element by element (keeps registers low) */) {
-    const int fr = lane & 15, fq = lane >> 4;
-    // padded row stride: the smallest >= the 16*NI-column row with (words % 32) == 4, which spreads the 16
-    // rows of an accumulator column block over all banks (NI = 4: 272 / 144 bytes)
-    constexpr int ROWW = 16 * NI * (OUT_F32 ? 4 : 2) / 4;
-    constexpr int RS = (((ROWW - 4 + 31) / 32) * 32 + 4) * 4;
-    constexpr int TS = 16 * RS;                                     // one m-tile
-    constexpr int CPR = 16 * NI * (OUT_F32 ? 4 : 2) / 16;           // 16-byte chunks per row segment
-    constexpr int NCH = 16 * CPR, NPASS = (NCH + 63) / 64;
-    float4 bv[NI];
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-        bv[i] = bias ? *reinterpret_cast<const float4*>(bias + n_base + i * 16 + 4 * fq) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int j0 = 0; j0 < NJ; j0 += JC) {
-        // fp32 output: the residual (old C) and the 2-D addend of this pass do not depend on the accumulators --
-        // issue their loads FIRST, so that they are in flight during the LDS bounce instead of after it
-        float4 res[OUT_F32 ? JC : 1][OUT_F32 ? NPASS : 1];
-        if (OUT_F32) {
-#pragma unroll
-            for (int jj = 0; jj < JC; ++jj)
-#pragma unroll
-                for (int h = 0; h < NPASS; ++h) {
-                    const int idx = lane + 64 * h;
-                    float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (NCH % 64 == 0 || idx < NCH) {
-                        const int m = m_base + (j0 + jj) * 16 + idx / CPR, n = n_base + (idx % CPR) * 4;
-                        if (accumulate) r = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(Cv) + (size_t)m * N + n);
-                        if (add2d && !GLN) {      // GLN: `add2d` carries gamma | beta, not a 2-D addend
-                            const float4 e = *reinterpret_cast<const float4*>(add2d + (size_t)(m % add2d_period) * N + n);
-                            r.x += e.x; r.y += e.y; r.z += e.z; r.w += e.w;
-                        }
-                    }
-                    res[jj][h] = r;
-                }
-        }
-        if (j0) wave_lds_sync_g();
-#pragma unroll
-        for (int jj = 0; jj < JC; ++jj) {
-            const int j = j0 + jj;
-            // GLN: LayerNorm2d over the wave's 64 columns (= one channel group of the transposed-conv output,
-            // mask_decoder.py:55-56, eps 1e-6) before the GELU.  A row's 64 values sit in the 4 lane quarters x
-            // 16 registers; two-pass statistics like the stand-alone kernel.  `add2d` carries gamma[64] | beta[64].
-            float gmean = 0.f, grstd = 1.f;
-            if (GLN) {
-                float s1 = 0.f;
-#pragma unroll
-                for (int i = 0; i < NI; ++i)
-                    s1 += ((acc[i][j][0] + bv[i].x) + (acc[i][j][1] + bv[i].y)) + ((acc[i][j][2] + bv[i].z) + (acc[i][j][3] + bv[i].w));
-                s1 += __shfl_xor(s1, 16, 64);
-                s1 += __shfl_xor(s1, 32, 64);
-                gmean = s1 * (1.0f / 64.0f);
-                float s2 = 0.f;
-#pragma unroll
-                for (int i = 0; i < NI; ++i) {
-                    const float a0 = acc[i][j][0] + bv[i].x - gmean, a1 = acc[i][j][1] + bv[i].y - gmean;
-                    const float a2 = acc[i][j][2] + bv[i].z - gmean, a3 = acc[i][j][3] + bv[i].w - gmean;
-                    s2 += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
-                }
-                s2 += __shfl_xor(s2, 16, 64);
-                s2 += __shfl_xor(s2, 32, 64);
-                grstd = 1.0f / sqrtf(s2 * (1.0f / 64.0f) + 1e-6f);
-            }
-#pragma unroll
-            for (int i = 0; i < NI; ++i) {
-                float v0 = acc[i][j][0] + bv[i].x, v1 = acc[i][j][1] + bv[i].y;
-                float v2 = acc[i][j][2] + bv[i].z, v3 = acc[i][j][3] + bv[i].w;
-                if (pre2d) {
-                    const float4 e = *reinterpret_cast<const float4*>(pre2d + (size_t)((m_base + j * 16 + fr) % add2d_period) * N +
-                                                                      n_base + i * 16 + 4 * fq);
-                    v0 += e.x; v1 += e.y; v2 += e.z; v3 += e.w;
-                }
-                if (GLN) {
-                    const float4 gm = *reinterpret_cast<const float4*>(add2d + i * 16 + 4 * fq);
-                    const float4 bt = *reinterpret_cast<const float4*>(add2d + 64 + i * 16 + 4 * fq);
-                    v0 = (v0 - gmean) * grstd * gm.x + bt.x; v1 = (v1 - gmean) * grstd * gm.y + bt.y;
-                    v2 = (v2 - gmean) * grstd * gm.z + bt.z; v3 = (v3 - gmean) * grstd * gm.w + bt.w;
-                }
-                if constexpr (GELU == 2 && !OUT_F32) { const float2_t g01 = gelu_erf2_et(float2_t{v0, v1}), g23 = gelu_erf2_et(float2_t{v2, v3}); v0 = g01.x; v1 = g01.y; v2 = g23.x; v3 = g23.y; }
-                else if constexpr (GELU != 0) { const float2_t g01 = gelu_erf2(float2_t{v0, v1}), g23 = gelu_erf2(float2_t{v2, v3}); v0 = g01.x; v1 = g01.y; v2 = g23.x; v3 = g23.y; }
-                unsigned char* p = scr + jj * TS + fr * RS;
-                if (OUT_F32) {
-                    *reinterpret_cast<float4*>(p + (i * 16 + 4 * fq) * 4) = make_float4(v0, v1, v2, v3);
-                } else {
-                    uint2 o;
-                    o.x = pack2<PREC>(v0, v1);
-                    o.y = pack2<PREC>(v2, v3);
-                    *reinterpret_cast<uint2*>(p + (i * 16 + 4 * fq) * 2) = o;
-                }
-            }
-        }
-        wave_lds_sync_g();
-        if (DRAIN && j0 == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int jj = 0; jj < JC; ++jj) {
-            const int j = j0 + jj;
-            if (OUT_F32) {
-                // 16 rows x (64 NI) B in 16-byte chunks, consecutive lanes on consecutive chunks of a row
-#pragma unroll
-                for (int h = 0; h < NPASS; ++h) {
-                    const int idx = lane + 64 * h;
-                    if (NCH % 64 != 0 && idx >= NCH) break;
-                    const int row = idx / CPR, ch = idx % CPR;
-                    float4 v = *reinterpret_cast<const float4*>(scr + jj * TS + row * RS + ch * 16);
-                    const int m = m_base + j * 16 + row, n = n_base + ch * 4;
-                    const float4 o = res[OUT_F32 ? jj : 0][OUT_F32 ? h : 0];
-                    v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
-                    float* C = reinterpret_cast<float*>(Cv) + (size_t)m * N + n;
-                    *reinterpret_cast<float4*>(C) = v;
-                }
-            } else {
-                // 16 rows x (32 NI) B
-#pragma unroll
-                for (int h = 0; h < NPASS; ++h) {
-                    const int idx = lane + 64 * h;
-                    if (NCH % 64 != 0 && idx >= NCH) break;
-                    const int row = idx / CPR, ch = idx % CPR;
-                    const uint4 v = *reinterpret_cast<const uint4*>(scr + jj * TS + row * RS + ch * 16);
-                    uint16_t* C = reinterpret_cast<uint16_t*>(Cv) + (size_t)(m_base + j * 16 + row) * N + n_base + ch * 8;
-                    store16_stream<STREAM>(C, v);
-                }
-            }
-        }
-    }
-}
 
 // ---------------------------------------------------------------------------------------------
 // ET-output epilogue of the 256x320 kernel (NI = 5).  A wave's sub-tile is 80 columns = 160 bytes per row:
@@ -525,202 +174,6 @@ __device__ __forceinline__ void epilogue_pair_et(f32x4_t (&acc)[5][8], unsigned 
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// Shared geometry of the 256x128x64 staggered kernel below (its lock-step round-1 flavour was removed): block tile, 512 threads = 8 waves (4 along M x 2 along N, each
-// a 64x64 sub-tile exactly as above), THREE-stage LDS ring filled by LDS-DMA with a COUNTED
-// s_waitcnt vmcnt: the loads of tile t+2 are issued before computing tile t and only tile t+1 is
-// waited for at the (raw) barrier, so DMA traffic stays in flight across barriers instead of
-// draining every K step (rocprofv3 on the 2-stage kernel: 47 % of wave cycles parked in
-// s_waitcnt/s_barrier, MFMA busy 30 %).  144 KiB LDS -> one block (8 waves) per CU.
-// ---------------------------------------------------------------------------------------------
-constexpr int PBN = 128, PTHREADS = 512, PSTAGES = 3;
-constexpr int PSTAGE_ELEMS = (PBM + PBN) * BK;          // A rows then B rows, 64 ET each
-constexpr int P_GLDS_PER_TILE = (PBM + PBN) * BK * 2 / (PTHREADS * 16);   // 6 per thread
-
-// LDS-DMA issued from inline asm so that hipcc's s_waitcnt insertion does not know about it (it
-// would otherwise put vmcnt(0) in front of every ds_read).  M0 = LDS byte address of the wave's
-// 1 KiB destination; M0 is compiler-reserved, so it is saved / restored inside the statement, and
-// the SALU-write -> LDS-DMA hazard gets its s_nop (cdna_hip_programming.md 5.7).  The caller
-// counts vmcnt by hand.
-template <int OFF>
-__device__ __forceinline__ void glds16_asm(const uint16_t* gsrc, uint32_t wave_lds_base) {
-    uint32_t keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_add_u32 m0, %2, %3\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(wave_lds_base), "n"(OFF)
-        : "memory", "scc");
-}
-
-// one K tile (A: 4 x 64 rows, B: 2 x 64 rows) into ring stage `stage_`: six DMA pieces per wave
-#define PIPE_ISSUE(kt_, stage_)                                                                 \
-    do {                                                                                         \
-        const size_t koff_ = (size_t)(kt_) * BK;                                                 \
-        constexpr int SB_ = (stage_) * PSTAGE_ELEMS * 2;                                         \
-        glds16_asm<SB_ + 0 * 64 * BK * 2>(gAg + koff_, wave_lds_base);                           \
-        glds16_asm<SB_ + 1 * 64 * BK * 2>(gAg + rs64 + koff_, wave_lds_base);                    \
-        glds16_asm<SB_ + 2 * 64 * BK * 2>(gAg + 2 * rs64 + koff_, wave_lds_base);                \
-        glds16_asm<SB_ + 3 * 64 * BK * 2>(gAg + 3 * rs64 + koff_, wave_lds_base);                \
-        glds16_asm<SB_ + PBM * BK * 2 + 0 * 64 * BK * 2>(gBg + koff_, wave_lds_base);            \
-        glds16_asm<SB_ + PBM * BK * 2 + 1 * 64 * BK * 2>(gBg + rs64 + koff_, wave_lds_base);     \
-    } while (0)
-
-// ---------------------------------------------------------------------------------------------
-// gemm_et_stag_kernel: the tile / ring / DMA described above, and the two waves that share
-// a SIMD (waves w and w+4) run STAGGERED by one barrier interval.  Every K step is cut into four
-// segments separated by raw barriers -- L0 (fragment reads, k 0..31 + DMA issue), C0 (16 MFMAs),
-// L1 (reads, k 32..63), C1 (16 MFMAs) -- and group 1 (waves 4..7) executes one extra barrier up
-// front, so while group 0 is in a C segment group 1 is in an L segment and vice versa: the matrix
-// pipe of every SIMD always has one wave feeding it while its partner waits on LDS (rocprofv3 on the
-// lock-step kernel: 48 % of wave cycles parked, MFMA busy 37 %).  s_setprio(1) around the MFMA
-// segments lets the computing wave win issue arbitration (cdna_hip_programming.md T5).
-//
-// Ring safety with the stagger (interval numbering 4*kt + {0,1,2,3} for group 0, +1 for group 1):
-//  WAR  the slot of tile kt-1 is last read by group 1 in interval 4kt-1; its refill (tile kt+2) is
-//       issued in an L0 segment, i.e. interval 4kt (group 0) / 4kt+1 (group 1): after that barrier.
-//  RAW  tile kt+1 is first read in interval 4kt+4; every wave waits vmcnt for its own share at the
-//       end of BOTH its L1 and C1 segments (interval 4kt+3 for either group) and then passes the
-//       barrier that opens interval 4kt+4.
-// Both groups execute exactly 2 + 4*nk barriers.
-// ---------------------------------------------------------------------------------------------
-template <int PREC, bool OUT_F32, bool GELU>
-__global__ __launch_bounds__(PTHREADS) void gemm_et_stag_kernel(
-    const uint16_t* __restrict__ A, const uint16_t* __restrict__ B, void* __restrict__ Cv,
-    const float* __restrict__ bias, const float* __restrict__ add2d, int add2d_period,
-    int M, int N, int K, int accumulate) {
-    __shared__ __attribute__((aligned(16))) uint16_t lds[PSTAGES * PSTAGE_ELEMS];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // provably wave-uniform
-    const int grp = wave >> 2;
-    const int wm = wave >> 1, wn = wave & 1;
-
-    constexpr int GROUP = 8;
-    const int tiles_n = N / PBN, tiles_m = M / PBM;
-    const int bid = xcd_remap(blockIdx.x, gridDim.x);
-    const int per_group = GROUP * tiles_n;
-    const int group = bid / per_group, first_m = group * GROUP;
-    const int gsz = (tiles_m - first_m) < GROUP ? (tiles_m - first_m) : GROUP;
-    const int in_g = bid - group * per_group;
-    const int tile_m = first_m + in_g % gsz, tile_n = in_g / gsz;
-    const int m0 = tile_m * PBM, n0 = tile_n * PBN;
-
-    const int g_row = 8 * wave + (lane >> 3);
-    const int g_chunk = (lane & 7) ^ ((g_row >> 1) & 7);
-    const uint16_t* gAg = A + (size_t)(m0 + g_row) * K + g_chunk * 8;
-    const uint16_t* gBg = B + (size_t)(n0 + g_row) * K + g_chunk * 8;
-    const uint32_t wave_lds_base = __builtin_amdgcn_readfirstlane(
-        (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)lds + (uint32_t)wave * (8 * BK * 2));
-    const size_t rs64 = (size_t)64 * K;
-
-    f32x4_t acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-    const int nk = K / BK;
-    PIPE_ISSUE(0, 0);
-    if (nk > 1) {
-        PIPE_ISSUE(1, 1);
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(P_GLDS_PER_TILE) : "memory");
-    } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __builtin_amdgcn_s_barrier();
-    if (grp == 1) __builtin_amdgcn_s_barrier();          // stagger: group 1 runs one interval behind
-
-    const int fr = lane & 15, fq = lane >> 4;
-#define STAG_LOAD(S_, KS_)                                                                        \
-    _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                               \
-        const int r = wm * 64 + j * 16 + fr;                                                      \
-        fa[j] = *reinterpret_cast<const uint4*>(lds + (S_) * PSTAGE_ELEMS + r * BK + swz(r, (KS_) * 4 + fq) * 8); \
-    }                                                                                             \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                               \
-        const int r = wn * 64 + i * 16 + fr;                                                      \
-        fb[i] = *reinterpret_cast<const uint4*>(lds + (S_) * PSTAGE_ELEMS + PBM * BK + r * BK + swz(r, (KS_) * 4 + fq) * 8); \
-    }
-#define STAG_MMA()                                                                                \
-    __builtin_amdgcn_s_setprio(1);                                                                \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                 \
-        _Pragma("unroll") for (int j = 0; j < 4; ++j) acc[i][j] = ET<PREC>::mfma16(fb[i], fa[j], acc[i][j]); \
-    __builtin_amdgcn_s_setprio(0);
-#define STAG_WAIT_NEXT(kt_)                                                                       \
-    if ((kt_) + 2 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(P_GLDS_PER_TILE) : "memory");    \
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#define STAG_STEP(kt_, S_)                                                                        \
-    if ((kt_) < nk) {                                                                             \
-        uint4 fa[4], fb[4];                                                                       \
-        /* L0 */                                                                                  \
-        if ((kt_) + 2 < nk) PIPE_ISSUE((kt_) + 2, ((S_) + 2) % PSTAGES);                          \
-        STAG_LOAD(S_, 0)                                                                          \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                        \
-        __builtin_amdgcn_sched_barrier(0);                                                        \
-        __builtin_amdgcn_s_barrier();                                                             \
-        /* C0 */                                                                                  \
-        STAG_MMA()                                                                                \
-        __builtin_amdgcn_sched_barrier(0);                                                        \
-        __builtin_amdgcn_s_barrier();                                                             \
-        /* L1 */                                                                                  \
-        STAG_LOAD(S_, 1)                                                                          \
-        STAG_WAIT_NEXT(kt_)                                                                       \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                        \
-        __builtin_amdgcn_sched_barrier(0);                                                        \
-        __builtin_amdgcn_s_barrier();                                                             \
-        /* C1 */                                                                                  \
-        STAG_MMA()                                                                                \
-        STAG_WAIT_NEXT(kt_)                                                                       \
-        __builtin_amdgcn_sched_barrier(0);                                                        \
-        __builtin_amdgcn_s_barrier();                                                             \
-    }
-    for (int kt = 0; kt < nk; kt += PSTAGES) {
-        STAG_STEP(kt, 0)
-        STAG_STEP(kt + 1, 1)
-        STAG_STEP(kt + 2, 2)
-    }
-    if (grp == 0) __builtin_amdgcn_s_barrier();          // group 0 finishes one interval early
-    // every wave is past its last ring read here -> the ring is free scratch (18 KiB per wave)
-    {
-        unsigned char* scr = reinterpret_cast<unsigned char*>(lds) + wave * (PSTAGES * PSTAGE_ELEMS * 2 / 8);
-        // add2d (if any) only comes with fp32 output in the engine; ET output ignores accumulate
-        if (!OUT_F32 && add2d) {
-            // rare combination (ET out + 2-D addend): fold the addend in before the bounce
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int m = m0 + wm * 64 + j * 16 + fr, n = n0 + wn * 64 + i * 16 + 4 * fq;
-                    const float4 e = *reinterpret_cast<const float4*>(add2d + (size_t)(m % add2d_period) * N + n);
-                    acc[i][j][0] += e.x; acc[i][j][1] += e.y; acc[i][j][2] += e.z; acc[i][j][3] += e.w;
-                }
-        }
-        epilogue_coalesced<PREC, OUT_F32, GELU, 4, 4>(acc, scr, Cv, bias, OUT_F32 ? add2d : nullptr, add2d_period, N,
-                                                      m0 + wm * 64, n0 + wn * 64, accumulate, lane);
-    }
-}
-
-template <int PREC>
-hipError_t launch_gemm_stag(const void* A, const void* B, void* C, const float* bias, const float* add2d, int period,
-                            int M, int N, int K, bool out_f32, bool gelu, bool accumulate, hipStream_t s) {
-    dim3 grid((M / PBM) * (N / PBN)), block(PTHREADS);
-    const uint16_t* a = reinterpret_cast<const uint16_t*>(A);
-    const uint16_t* b = reinterpret_cast<const uint16_t*>(B);
-    const int acc = accumulate ? 1 : 0;
-    if (out_f32) {
-        if (gelu) gemm_et_stag_kernel<PREC, true, true><<<grid, block, 0, s>>>(a, b, C, bias, add2d, period, M, N, K, acc);
-        else gemm_et_stag_kernel<PREC, true, false><<<grid, block, 0, s>>>(a, b, C, bias, add2d, period, M, N, K, acc);
-    } else {
-        if (gelu) gemm_et_stag_kernel<PREC, false, true><<<grid, block, 0, s>>>(a, b, C, bias, add2d, period, M, N, K, acc);
-        else gemm_et_stag_kernel<PREC, false, false><<<grid, block, 0, s>>>(a, b, C, bias, add2d, period, M, N, K, acc);
-    }
-    return hipGetLastError();
-}
-
 
 // ---------------------------------------------------------------------------------------------
 // gemm_et_big_kernel: 256x256x32 block tile, 8 waves as 2 (M) x 4 (N), wave tile 128x64
@@ -734,9 +187,6 @@ hipError_t launch_gemm_stag(const void* A, const void* B, void* C, const float* 
 // (MI355X_MICROARCH.md, LDS table) need the 16-byte chunk index XORed with g(row>>2),
 // g = [0,2,3,1]: checked conflict-free for all four lane groups.
 // ---------------------------------------------------------------------------------------------
-constexpr int QSTAGES = 4, QTHREADS = 512;     // WBN = 320: the NI = 5 flavour, 256x320 tile (wave tile 128x80), 4 x 36 KiB ring
-
-__device__ __forceinline__ int qswz(int r, int c) { return c ^ ((0x78 >> (2 * ((r >> 2) & 3))) & 3); }
 
 // ABL (ablation bits, timing experiments only; results are garbage when non-zero):
 //   1 = no DMA, 2 = no fragment reads, 4 = no MFMA, 8 = no barriers
@@ -930,22 +380,6 @@ static int g_x64_skew = [] {
     sscanf(v, "%d,%d", &a, &b);
     return (a & 0xffff) | (b << 16);
 }();
-
-// LDS-DMA, scalar-base form: source = sbase (SGPR pair, wave-uniform) + voff (per-lane byte offset, one VGPR),
-// destination = LDS byte address m0v (wave-uniform) + 16 * lane.  Issued from inline asm for the same reason as
-// glds16_asm (hipcc must not see it in its waitcnt bookkeeping); the caller counts vmcnt by hand.
-__device__ __forceinline__ void glds16_s(uint32_t voff, const void* sbase, uint32_t m0v) {
-    uint32_t keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %3\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, %2\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(sbase), "s"(m0v)
-        : "memory");
-}
 
 // SPLIT3 (reference-grade operand split, engine option bits 16 / 32): A = A_hi + A_lo, B = B_hi + B_lo, and the product
 // A_lo B_hi^T + A_hi B_lo^T + A_hi B_hi^T is ONE pass over a K axis of three segments -- the accumulators stay in registers, no
@@ -1328,7 +762,6 @@ __global__ __launch_bounds__(QTHREADS) void gemm_et_x64_kernel(
 //     LN(x) W^T + b  =  rstd (x W'^T - mean cvec) + bias'
 // rowstat[m] = (rstd, -rstd mean) comes from ln_rowstat_kernel (encoder_kernels.hip), which merges the per-row (mean, M2)
 // partials of the LN_NS 160-column groups; only the ET epilogue reads it (8 bytes per row and lane, next to the bias loads).
-constexpr int LN_NS = 8;                       // 1280 / 160: ViT-H only
 
 // MXO (round 4; ET output, no FOLD / SPLIT3): the epilogue also writes the output as MXFP4 hi / lo rows (epilogue_pair_et<MXO>: lin1 of
 // split 207, whose lin2 takes MXFP4 lo terms while lin1 itself takes none).  The four output pointers travel in their own MxOut
@@ -1570,588 +1003,6 @@ hipError_t launch_gemm_x64p_mxo(const void* A, const void* B, void* C, const flo
 }
 
 // ---------------------------------------------------------------------------------------------
-// gemm_et_m32_kernel: the pair-stage 256x320 kernel (same LDS image, same whole-line LDS-DMA map) on
-// v_mfma_f32_32x32x16 with a SYMMETRIC, register-double-buffered schedule.
-//
-// Why another main loop.  Measured on the 16x16x32 kernels above: a 64-k stage takes ~3.5 k cycles
-// against 2.56 k of matrix-pipe time; one 16x16x32 MFMA occupies the pipe for ~17 cycles (MI355X_MICROARCH.md: 4.2
-// quad-cycles, i.e. 6 % above its nominal 16), leaves ~4 issue slots before the next one is due, and an LDS-DMA piece
-// (m0 write + s_nop + the load + address SALU) does not fit into such a gap -- every piece opens a bubble in the issuing
-// wave's MFMA stream that only the partner wave can fill, which is why that schedule needs the two wave groups half a
-// stage apart and L / C segments.  A 32x32x16 MFMA runs 32 cycles at the full rate, reads HALF the operand registers
-// per FLOP (2 x 512 elements for 32 K FLOP instead of 16 K) and leaves ~8 issue slots: one ds_read_b128 plus one DMA
-// piece fit behind every MFMA.  So here every wave runs ONE uninterrupted MFMA stream; the fragments of k-step s+1 are
-// read while the MFMAs of step s run (two register sets), the DMA pieces ride in the same gaps, and there is no load
-// segment and no group asymmetry.  The two waves of a SIMD share its matrix pipe by the hardware's age arbitration.
-//
-// Wave layout 4 (M) x 2 (N): wave tile 64 x 160 = 2 x 5 MFMA tiles, 160 accumulator registers; a wave owns whole
-// 320-byte (f16) / 640-byte (fp32) row segments of the output, so the epilogue bounces through a wave-private scratch
-// without block barriers.  Per 16-k step and wave: 10 MFMAs, 7 ds_read_b128 (14.3 KiB per 32 k against 13.3 KiB for
-// the 128 x 80 wave tile).
-//
-// Stage hand-over (one block barrier per 64-k stage, placed between steps 2 and 3 of the stage):
-//     steps 0, 1, 2 of stage t : MFMAs | reads of the next step's fragments (buffer t & 1)
-//     lgkmcnt(0) (every fragment of stage t is in registers), vmcnt(0) (this wave's pieces of stage t+1 have landed), barrier B_t
-//     step 3 of stage t        : MFMAs | reads of step 0 of stage t+1 (other buffer) | DMA pieces of stage t+2 -> buffer t & 1
-// so a stage is in flight for three steps (~2 k cycles).  Persistent: the stream of stages simply continues into the next
-// tile -- at t = nst-2 the pieces issued are the next tile's stage 0 (they land under the last stage and the epilogue);
-// the epilogue bounces through buffer 1 (free after B_nst-1; nst must be even), and the next tile's stage 1 goes out
-// right after it.  K % 128 == 0, M % 256 == 0, N % 320 == 0, no 2-D addend.
-// k is accumulated in 16-wide MFMA steps, so results are NOT bit-identical with the 16x16x32 kernels (same fp32
-// accumulation error class; tests/test_kernels_gpu.py::test_gemm_m32_*).
-// ---------------------------------------------------------------------------------------------
-#ifdef SAMRS_EXPERIMENTS   // the round-2 32x32x16 kernels (m32, w4) and the LayerNorm fold built on them: measured slower, tools / A-B builds only (make EXPERIMENTS=1)
-constexpr int M32_RS = 144;                   // scratch row stride (bytes): 128 data bytes + 16; 36 words = 4 (mod 32)
-
-// Epilogue of one wave tile: acc[i][j] = 32 (n) x 32 (m) block, lane (m = l & 31, h = l >> 5) holds n = 8 g + 4 h + 0..3
-// for g = 0..3 in registers 4 g .. 4 g + 3.  Bounce through `scr` (wave-private, 32 rows x M32_RS bytes) so that the global
-// accesses are whole 128-byte row segments, 8 rows per instruction.
-// STATS (fp32 output = the residual stream; the LayerNorm that follows is folded into the next GEMM, gemm_et_x64p_kernel<FOLD>):
-// besides C the final values are written rounded to ET into Xh (same [M][N] shape), and stats[m][n_base / 160] receives
-// (mean, M2 = sum of squared deviations) of the wave's 160 columns of row m.  In the read-out a row's 32 columns of a pass sit
-// in 8 consecutive lanes: group mean / M2 by three xor-shuffles each (two-pass inside the group), merged into the running
-// pair over the five passes by Chan's update -- no E[x^2] - mean^2 cancellation, fixed order, bit-reproducible.
-template <int PREC, bool OUT_F32, bool GELU, bool STATS = false, int NJ = 2>
-__device__ __forceinline__ void epilogue_m32(f32x16_t (&acc)[5][NJ], unsigned char* scr, void* __restrict__ Cv,
-                                             const float* __restrict__ bias, int N, int m_base, int n_base, int wn,
-                                             int accumulate, int lane, uint16_t* __restrict__ Xh = nullptr,
-                                             float2* __restrict__ stats = nullptr) {
-    const int l31 = lane & 31, h = lane >> 5;
-    if constexpr (OUT_F32) {
-        float* C = reinterpret_cast<float*>(Cv);
-        bool first = true;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            float rmean[4], rm2[4];
-#pragma unroll
-            for (int i = 0; i < 5; ++i) {
-                // the residual (old C) does not depend on the accumulators: its loads go out first
-                float4 res[4];
-#pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    const int idx = lane + 64 * p, row = idx >> 3, ch = idx & 7;
-                    res[p] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (accumulate) res[p] = *reinterpret_cast<const float4*>(C + (size_t)(m_base + j * 32 + row) * N + n_base + i * 32 + ch * 4);
-                }
-                if (!first) wave_lds_sync_g();
-                first = false;
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const float4 bv = bias ? *reinterpret_cast<const float4*>(bias + n_base + i * 32 + 8 * g + 4 * h) : make_float4(0.f, 0.f, 0.f, 0.f);
-                    float v0 = acc[i][j][4 * g] + bv.x, v1 = acc[i][j][4 * g + 1] + bv.y;
-                    float v2 = acc[i][j][4 * g + 2] + bv.z, v3 = acc[i][j][4 * g + 3] + bv.w;
-                    if (GELU) { const float2_t g01 = gelu_erf2(float2_t{v0, v1}), g23 = gelu_erf2(float2_t{v2, v3}); v0 = g01.x; v1 = g01.y; v2 = g23.x; v3 = g23.y; }
-                    *reinterpret_cast<float4*>(scr + l31 * M32_RS + (8 * g + 4 * h) * 4) = make_float4(v0, v1, v2, v3);
-                }
-                wave_lds_sync_g();
-#pragma unroll
-                for (int p = 0; p < 4; ++p) {
-                    const int idx = lane + 64 * p, row = idx >> 3, ch = idx & 7;
-                    float4 v = *reinterpret_cast<const float4*>(scr + row * M32_RS + ch * 16);
-                    v.x += res[p].x; v.y += res[p].y; v.z += res[p].z; v.w += res[p].w;
-                    const size_t o = (size_t)(m_base + j * 32 + row) * N + n_base + i * 32 + ch * 4;
-                    *reinterpret_cast<float4*>(C + o) = v;
-                    if constexpr (STATS) {
-                        uint2 e;
-                        e.x = pack2<PREC>(v.x, v.y);
-                        e.y = pack2<PREC>(v.z, v.w);
-                        *reinterpret_cast<uint2*>(Xh + o) = e;
-                        float sm = (v.x + v.y) + (v.z + v.w);
-                        sm += __shfl_xor(sm, 1, 64); sm += __shfl_xor(sm, 2, 64); sm += __shfl_xor(sm, 4, 64);
-                        const float gm = sm * (1.0f / 32.0f);
-                        const float d0 = v.x - gm, d1 = v.y - gm, d2 = v.z - gm, d3 = v.w - gm;
-                        float gq = (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-                        gq += __shfl_xor(gq, 1, 64); gq += __shfl_xor(gq, 2, 64); gq += __shfl_xor(gq, 4, 64);
-                        if (i == 0) { rmean[p] = gm; rm2[p] = gq; }
-                        else {
-                            const float d = gm - rmean[p];
-                            rmean[p] += d * (1.0f / (i + 1));
-                            rm2[p] += gq + d * d * (32.0f * i / (i + 1));
-                        }
-                    }
-                }
-            }
-            if constexpr (STATS) {
-                if ((lane & 7) == 0) {
-#pragma unroll
-                    for (int p = 0; p < 4; ++p)
-                        stats[(size_t)(m_base + j * 32 + (lane >> 3) + 8 * p) * (N / 160) + n_base / 160] = make_float2(rmean[p], rm2[p]);
-                }
-            }
-        }
-    } else {
-        uint16_t* C = reinterpret_cast<uint16_t*>(Cv);
-        // one pass = n-tiles [I0, I0 + CNT): CNT * 64 bytes per row.  The wave's 320-byte row segment starts on a 128-byte
-        // line for wn = 0 and in the middle of one for wn = 1, so the passes are grouped {0,1}{2,3}{4} / {0}{1,2}{3,4}: every
-        // two-tile pass writes whole lines.
-#define M32_ET_PASS(j_, I0, CNT)                                                                                     \
-        do {                                                                                                         \
-            wave_lds_sync_g();                                                                                       \
-            _Pragma("unroll") for (int ii = 0; ii < (CNT); ++ii)                                                     \
-            _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                          \
-                const int i = (I0) + ii;                                                                             \
-                const float4 bv = bias ? *reinterpret_cast<const float4*>(bias + n_base + i * 32 + 8 * g + 4 * h) : make_float4(0.f, 0.f, 0.f, 0.f); \
-                float v0 = acc[i][j_][4 * g] + bv.x, v1 = acc[i][j_][4 * g + 1] + bv.y;                              \
-                float v2 = acc[i][j_][4 * g + 2] + bv.z, v3 = acc[i][j_][4 * g + 3] + bv.w;                          \
-                if (GELU) { const float2_t g01 = gelu_erf2(float2_t{v0, v1}), g23 = gelu_erf2(float2_t{v2, v3}); v0 = g01.x; v1 = g01.y; v2 = g23.x; v3 = g23.y; } \
-                uint2 o;                                                                                             \
-                o.x = pack2<PREC>(v0, v1);                                                                           \
-                o.y = pack2<PREC>(v2, v3);                                                                           \
-                *reinterpret_cast<uint2*>(scr + l31 * M32_RS + (ii * 32 + 8 * g + 4 * h) * 2) = o;                   \
-            }                                                                                                        \
-            wave_lds_sync_g();                                                                                       \
-            _Pragma("unroll") for (int p = 0; p < 2 * (CNT); ++p) {                                                  \
-                const int idx = lane + 64 * p, row = idx / (4 * (CNT)), ch = idx % (4 * (CNT));                      \
-                const uint4 v = *reinterpret_cast<const uint4*>(scr + row * M32_RS + ch * 16);                       \
-                *reinterpret_cast<uint4*>(C + (size_t)(m_base + (j_) * 32 + row) * N + n_base + (I0) * 32 + ch * 8) = v; \
-            }                                                                                                        \
-        } while (0)
-        if (wn == 0) {
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) { M32_ET_PASS(j, 0, 2); M32_ET_PASS(j, 2, 2); M32_ET_PASS(j, 4, 1); }
-        } else {
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) { M32_ET_PASS(j, 0, 1); M32_ET_PASS(j, 1, 2); M32_ET_PASS(j, 3, 2); }
-        }
-#undef M32_ET_PASS
-    }
-}
-
-#endif  // SAMRS_EXPERIMENTS (epilogue_m32)
-// LDS-DMA piece with M0 declared as clobbered instead of saved / restored (two SALU instructions less per piece)
-__device__ __forceinline__ void glds16_m(uint32_t voff, const void* sbase, uint32_t m0v) {
-    asm volatile(
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %0, %1"
-        :
-        : "v"(voff), "s"(sbase), "s"(m0v)
-        : "memory", "m0");
-}
-
-#ifdef SAMRS_EXPERIMENTS
-// SPREAD: 0 = the 9 DMA pieces of a stage all go out in step 3 (one behind each of the first 9 MFMAs); 1 = pieces 0-4 in
-// step 3 and pieces 5-8 in step 0 of the following stage (fewer fillers per gap, one step less in flight)
-template <int PREC, bool OUT_F32, bool GELU, int SPREAD, bool STATS = false>
-__global__ __launch_bounds__(QTHREADS) void gemm_et_m32_kernel(
-    const uint16_t* __restrict__ A, const uint16_t* __restrict__ B, void* __restrict__ Cv,
-    const float* __restrict__ bias, int M, int N, int K, int accumulate,
-    uint16_t* __restrict__ Xh = nullptr, float2* __restrict__ stats = nullptr) {
-    static_assert(!STATS || (OUT_F32 && !GELU), "row statistics accompany the fp32 residual output only");
-    constexpr int NI = 5, NJ = 2;
-    constexpr int XBN = 32 * NI * 2;                       // 320
-    constexpr int XROWS = QBM + XBN;
-    constexpr int XSTAGE_ELEMS = XROWS * XBK;
-    constexpr uint32_t XSB = XSTAGE_ELEMS * 2;             // 72 KiB per stage
-    constexpr int NP3 = SPREAD ? 5 : 9;                    // pieces [0, NP3) ride in step 3, [NP3, 9) in the next step 0
-    __shared__ __attribute__((aligned(16))) uint16_t lds[2 * XSTAGE_ELEMS];   // 144 KiB, ONE object
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;   // wave tile rows wm*64.., cols wn*160..
-
-    constexpr int GROUP = 8;
-    const int tiles_n = N / XBN, tiles_m = M / QBM, ntiles = tiles_n * tiles_m;
-    const int per_group = GROUP * tiles_n;
-#define M32_TILE(L_, m_, n_)                                                                     \
-    do {                                                                                         \
-        const int bid_ = xcd_remap((L_), ntiles);                                                \
-        const int group_ = bid_ / per_group, first_m_ = group_ * GROUP;                           \
-        const int gsz_ = (tiles_m - first_m_) < GROUP ? (tiles_m - first_m_) : GROUP;            \
-        const int in_g_ = bid_ - group_ * per_group;                                             \
-        (m_) = (first_m_ + in_g_ % gsz_) * QBM;                                                  \
-        (n_) = (in_g_ / gsz_) * XBN;                                                             \
-    } while (0)
-
-    // DMA map: identical to the 16x16x32 pair-stage kernels (piece q of a wave = stage rows 64 q + 8 wave .. + 7)
-    const int prow = 8 * wave + ((lane >> 2) & 7);
-    const uint32_t voff = ((uint32_t)prow * (uint32_t)K + (uint32_t)(lane >> 5) * 32u + (uint32_t)qswz(prow, lane & 3) * 8u) * 2u;
-    const size_t rs64 = (size_t)64 * K;
-    const uint32_t lds0 = __builtin_amdgcn_readfirstlane(
-        (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)lds + (uint32_t)wave * 1024u);
-    // piece q_ (literal) of the stage whose A / B rows start at pa_ / pb_ (wave-uniform) into the buffer at byte offset wr_
-#define M32_PIECE(pa_, pb_, wr_, q_)                                                                       \
-    glds16_m(voff, ((q_) < 4 ? (pa_) + (size_t)(q_) * rs64 : (pb_) + (size_t)((q_) - 4) * rs64),          \
-             lds0 + (wr_) + ((q_) < 4 ? (q_) * 8192u : (uint32_t)(QBM * XBK * 2) + ((q_) - 4) * 8192u))
-
-    // fragment BYTE offsets inside a stage for k-step 0 of k-half 0 (16-byte chunk h of the row); step parity 1 = chunk
-    // h + 2 = the physical chunk XOR 2 (byte offset XOR 32), k-half 1 = +512
-    const int nst = K / XBK;
-    const int l31 = lane & 31, hh = lane >> 5;
-    uint32_t offA[NJ], offB[NI];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) { const int r = wm * 64 + j * 32 + l31; offA[j] = ((r >> 3) * 512 + (r & 7) * 32 + qswz(r, hh) * 8) * 2; }
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-        const int r = QBM + wn * 160 + i * 32 + l31;
-        offB[i] = ((r >> 3) * 512 + (r & 7) * 32 + qswz(r, hh) * 8) * 2;
-    }
-    const unsigned char* ldsb = reinterpret_cast<const unsigned char*>(lds);
-
-    // fragments of k-step s_ (0..3) of the stage in the buffer at byte offset rd_ -> register set fa / fb
-#define M32_RDB(fb_, rd_, s_, i_) fb_[i_] = *reinterpret_cast<const uint4*>(ldsb + (rd_) + ((s_) >> 1) * 512 + (offB[i_] ^ (((s_) & 1) * 32u)))
-#define M32_RDA(fa_, rd_, s_, j_) fa_[j_] = *reinterpret_cast<const uint4*>(ldsb + (rd_) + ((s_) >> 1) * 512 + (offA[j_] ^ (((s_) & 1) * 32u)))
-    // one k-step: 10 MFMAs on the set (ca_, cb_); behind MFMA k one read of the NEXT step's set (na_, nb_) from (nrd_, ns_)
-    // and DMA piece Q0_ + k (while < Q1_) of the stage (pa_, pb_) -> buffer wr_: D_ = 0 none, 1 always, 2 when dma_ (wave-
-    // uniform) is set.  The accumulators never sit inside a conditional region.
-#define M32_SLOT(k_, i_, j_, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)             \
-        acc[i_][j_] = ET<PREC>::mfma32(cb_[i_], ca_[j_], acc[i_][j_]);                                     \
-        if constexpr ((k_) < 5) { M32_RDB(nb_, nrd_, ns_, ((k_) < 5 ? (k_) : 0)); }                        \
-        else if constexpr ((k_) < 7) { M32_RDA(na_, nrd_, ns_, ((k_) >= 5 && (k_) < 7 ? (k_) - 5 : 0)); }  \
-        if constexpr ((D_) != 0 && (Q0_) + (k_) < (Q1_)) {                                                 \
-            if ((D_) == 1 || (dma_)) M32_PIECE(pa_, pb_, wr_, ((Q0_) + (k_) < 9 ? (Q0_) + (k_) : 0));      \
-        }                                                                                                  \
-        __builtin_amdgcn_sched_barrier(0);
-#define M32_STEP(ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                         \
-        M32_SLOT(0, 0, 0, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                \
-        M32_SLOT(1, 1, 0, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                \
-        M32_SLOT(2, 2, 0, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                \
-        M32_SLOT(3, 3, 0, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                \
-        M32_SLOT(4, 4, 0, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                \
-        M32_SLOT(5, 0, 1, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                \
-        M32_SLOT(6, 1, 1, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                \
-        M32_SLOT(7, 2, 1, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                \
-        M32_SLOT(8, 3, 1, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                \
-        M32_SLOT(9, 4, 1, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)
-    // one 64-k stage held in buffer rd.  Step 0 carries the late pieces [NP3, 9) of the stage that goes into the OTHER buffer
-    // (D0_, d0_, a0_, b0_); step 3, after the hand-over barrier, the early pieces [0, NP3) of the stage that goes into THIS
-    // buffer (D3_, d3_, a3_, b3_).
-#define M32_STAGE(D0_, d0_, a0_, b0_, D3_, d3_, a3_, b3_)                                                  \
-        {                                                                                                  \
-            const uint32_t ot = XSB - rd;                                                                  \
-            M32_STEP(fa0, fb0, fa1, fb1, rd, 1, D0_, d0_, NP3, 9, a0_, b0_, ot)                            \
-            M32_STEP(fa1, fb1, fa0, fb0, rd, 2, 0, false, 0, 0, a0_, b0_, ot)                              \
-            M32_STEP(fa0, fb0, fa1, fb1, rd, 3, 0, false, 0, 0, a0_, b0_, ot)                              \
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                    \
-            __builtin_amdgcn_s_barrier();                                                                  \
-            __builtin_amdgcn_sched_barrier(0);                                                             \
-            M32_STEP(fa1, fb1, fa0, fb0, ot, 0, D3_, d3_, 0, NP3, a3_, b3_, rd)                            \
-            rd = ot;                                                                                       \
-        }
-
-    int L = blockIdx.x, m0, n0;
-    M32_TILE(L, m0, n0);
-    const uint16_t* sA = A + (size_t)m0 * K;       // rows of the tile being computed (wave-uniform: SGPR pairs)
-    const uint16_t* sB = B + (size_t)n0 * K;
-    M32_PIECE(sA, sB, 0u, 0); M32_PIECE(sA, sB, 0u, 1); M32_PIECE(sA, sB, 0u, 2); M32_PIECE(sA, sB, 0u, 3); M32_PIECE(sA, sB, 0u, 4);
-    M32_PIECE(sA, sB, 0u, 5); M32_PIECE(sA, sB, 0u, 6); M32_PIECE(sA, sB, 0u, 7); M32_PIECE(sA, sB, 0u, 8);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    f32x16_t acc[NI][NJ];
-    for (;;) {
-        // the tile after this one (its stage 0 is fed from inside this tile's main loop)
-        const int Ln = L + (int)gridDim.x;
-        const bool more = Ln < ntiles;
-        int m1 = m0, n1 = n0;
-        if (more) M32_TILE(Ln, m1, n1);
-        const uint16_t* nA = A + (size_t)m1 * K;
-        const uint16_t* nB = B + (size_t)n1 * K;
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-        {   // early pieces of stage 1 -> buffer 1 (the late ones ride in step 0 of stage 0)
-            const uint16_t* a1 = sA + XBK;
-            const uint16_t* b1 = sB + XBK;
-            M32_PIECE(a1, b1, XSB, 0); M32_PIECE(a1, b1, XSB, 1); M32_PIECE(a1, b1, XSB, 2); M32_PIECE(a1, b1, XSB, 3); M32_PIECE(a1, b1, XSB, 4);
-            if constexpr (!SPREAD) { M32_PIECE(a1, b1, XSB, 5); M32_PIECE(a1, b1, XSB, 6); M32_PIECE(a1, b1, XSB, 7); M32_PIECE(a1, b1, XSB, 8); }
-        }
-        uint4 fa0[NJ], fb0[NI], fa1[NJ], fb1[NI];
-#pragma unroll
-        for (int i = 0; i < NI; ++i) M32_RDB(fb0, 0u, 0, i);
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) M32_RDA(fa0, 0u, 0, j);
-        __builtin_amdgcn_sched_barrier(0);
-        uint32_t rd = 0;
-        // stage t: step 0 completes stage t+1, step 3 starts stage t+2
-        const uint16_t* pa = sA + XBK;
-        const uint16_t* pb = sB + XBK;
-        for (int t = 0; t + 2 < nst; ++t) {
-            M32_STAGE(1, true, pa, pb, 1, true, pa + XBK, pb + XBK)
-            pa += XBK;
-            pb += XBK;
-        }
-        // t = nst-2 (buffer 0): completes the last stage; starts the NEXT tile's stage 0 in buffer 0 when there is one
-        M32_STAGE(1, true, pa, pb, 2, more, nA, nB)
-        // t = nst-1 (buffer 1): completes the next tile's stage 0
-        M32_STAGE(2, more, nA, nB, 0, false, nA, nB)
-        // all fragment reads of this tile are complete (B_nst-1); buffer 1 held its last stage -> scratch
-        {
-            unsigned char* scr = reinterpret_cast<unsigned char*>(lds) + XSB + wave * (XSB / 8);
-            epilogue_m32<PREC, OUT_F32, GELU, STATS>(acc, scr, Cv, bias, N, m0 + wm * 64, n0 + wn * 160, wn, accumulate, lane, Xh, stats);
-        }
-        if (!more) break;
-        __builtin_amdgcn_s_barrier();              // every wave is done with its scratch before stage 1 of the next tile lands there
-        L = Ln; m0 = m1; n0 = n1; sA = nA; sB = nB;
-    }
-#undef M32_TILE
-#undef M32_PIECE
-#undef M32_RDA
-#undef M32_RDB
-#undef M32_SLOT
-#undef M32_STEP
-#undef M32_STAGE
-}
-
-// persistent = one block per CU walks the tiles; otherwise one tile per block (same kernel: `more` is never true)
-template <int PREC, int SPREAD>
-hipError_t launch_gemm_m32(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, bool out_f32, bool gelu,
-                           bool accumulate, bool persistent, hipStream_t s) {
-    const int ntiles = (M / QBM) * (N / WBN);
-    const int n_cu = cu_count();
-    dim3 grid(persistent && ntiles > n_cu ? n_cu : ntiles), block(QTHREADS);
-    const uint16_t* a = reinterpret_cast<const uint16_t*>(A);
-    const uint16_t* b = reinterpret_cast<const uint16_t*>(B);
-    const int acc = accumulate ? 1 : 0;
-    if (out_f32) {
-        if (gelu) gemm_et_m32_kernel<PREC, true, true, SPREAD><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, acc);
-        else gemm_et_m32_kernel<PREC, true, false, SPREAD><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, acc);
-    } else {
-        if (gelu) gemm_et_m32_kernel<PREC, false, true, SPREAD><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, acc);
-        else gemm_et_m32_kernel<PREC, false, false, SPREAD><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, acc);
-    }
-    return hipGetLastError();
-}
-#endif  // SAMRS_EXPERIMENTS (gemm_et_m32_kernel)
-// ---------------------------------------------------------------------------------------------
-// gemm_et_w4_kernel: the symmetric 32x32x16 schedule above on FOUR waves with 512 registers each (one wave per SIMD).
-//
-// Why: the DVFS probe says the encoder GEMMs are limited by energy per FLOP, and the one structural knob on it
-// is the number of bytes that cross LDS -> registers per FLOP, i.e. the perimeter of the WAVE tile: 8 waves x (128 + 80) rows
-// of fragments per k-step for the 2 x 4 layout, 8 x (64 + 160) for the 4 x 2 layout of gemm_et_m32_kernel, 4 x (128 + 160) here
-// (-31 % / -36 %).  A 128 x 160 wave tile needs 320 accumulator registers; hipcc keeps all MFMA results of a kernel either in
-// VGPRs or in AGPRs (256 each), so the MFMAs are issued from inline asm: the 16 accumulator tiles of n-tiles 0-3 are constrained
-// to AGPRs ("+a"), the 4 tiles of n-tile 4 to VGPRs ("+v"); everything else (fragments 2 x 36, addressing) fits the VGPR half.
-// The compiler does not know these statements are MFMAs, so the two hazards it would pad are padded by hand (s_nop after the
-// accumulators are zeroed and before the epilogue reads them).
-//
-// Stage image, DMA pieces (now 18 per wave and stage: rows 32 q + 8 wave .. + 7), hand-over barrier, persistent stage stream and
-// epilogue are those of gemm_et_m32_kernel; pieces 0-9 ride in step 3 (slots 10-19, the reads use slots 0-8), pieces 10-17 in
-// the next step 0.  With one wave per SIMD nothing covers a stall, so the single barrier per stage costs what it costs.
-// ---------------------------------------------------------------------------------------------
-constexpr int W4THREADS = 256;
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-
-#ifdef SAMRS_EXPERIMENTS
-template <int PREC, bool AG>
-__device__ __forceinline__ void mfma32_asm(f32x16_t& c, const uint4& a, const uint4& b) {
-    const u32x4_t av = __builtin_bit_cast(u32x4_t, a), bv = __builtin_bit_cast(u32x4_t, b);
-    if constexpr (PREC == PREC_F16) {
-        if constexpr (AG) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(c) : "v"(av), "v"(bv));
-        else asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(c) : "v"(av), "v"(bv));
-    } else {
-        if constexpr (AG) asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(av), "v"(bv));
-        else asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(av), "v"(bv));
-    }
-}
-
-template <int PREC, bool OUT_F32, bool GELU>
-__global__ __attribute__((amdgpu_flat_work_group_size(W4THREADS, W4THREADS), amdgpu_waves_per_eu(1, 1))) void gemm_et_w4_kernel(
-    const uint16_t* __restrict__ A, const uint16_t* __restrict__ B, void* __restrict__ Cv,
-    const float* __restrict__ bias, int M, int N, int K, int accumulate) {
-    constexpr int NI = 5, NJ = 4;
-    constexpr int XBN = 320;
-    constexpr int XROWS = QBM + XBN;
-    constexpr int XSTAGE_ELEMS = XROWS * XBK;
-    constexpr uint32_t XSB = XSTAGE_ELEMS * 2;             // 72 KiB per stage
-    constexpr int NP = 18, NP3 = 10;                       // pieces per wave and stage; [0, NP3) in step 3, the rest in step 0
-    __shared__ __attribute__((aligned(16))) uint16_t lds[2 * XSTAGE_ELEMS];   // 144 KiB, ONE object
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;   // wave tile rows wm*128.., cols wn*160..
-
-    constexpr int GROUP = 8;
-    const int tiles_n = N / XBN, tiles_m = M / QBM, ntiles = tiles_n * tiles_m;
-    const int per_group = GROUP * tiles_n;
-#define W4_TILE(L_, m_, n_)                                                                      \
-    do {                                                                                         \
-        const int bid_ = xcd_remap((L_), ntiles);                                                \
-        const int group_ = bid_ / per_group, first_m_ = group_ * GROUP;                           \
-        const int gsz_ = (tiles_m - first_m_) < GROUP ? (tiles_m - first_m_) : GROUP;            \
-        const int in_g_ = bid_ - group_ * per_group;                                             \
-        (m_) = (first_m_ + in_g_ % gsz_) * QBM;                                                  \
-        (n_) = (in_g_ / gsz_) * XBN;                                                             \
-    } while (0)
-
-    // DMA map: piece q of this wave covers stage rows 32 q + 8 wave .. + 7 (q < 8: A rows, else B rows 32 (q - 8) + ..); lane
-    // l -> k-half l>>5, row (l>>2)&7, physical chunk l&3 (same image and swizzle as the eight-wave kernels: 32 q = 0 mod 16)
-    const int prow = 8 * wave + ((lane >> 2) & 7);
-    const uint32_t voff = ((uint32_t)prow * (uint32_t)K + (uint32_t)(lane >> 5) * 32u + (uint32_t)qswz(prow, lane & 3) * 8u) * 2u;
-    const size_t rs32 = (size_t)32 * K;
-    const uint32_t lds0 = __builtin_amdgcn_readfirstlane(
-        (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)lds + (uint32_t)wave * 1024u);
-#define W4_PIECE(pa_, pb_, wr_, q_)                                                                        \
-    glds16_m(voff, ((q_) < 8 ? (pa_) + (size_t)(q_) * rs32 : (pb_) + (size_t)((q_) - 8) * rs32), lds0 + (wr_) + (q_) * 4096u)
-
-    const int nst = K / XBK;
-    const int l31 = lane & 31, hh = lane >> 5;
-    uint32_t offA[NJ], offB[NI];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) { const int r = wm * 128 + j * 32 + l31; offA[j] = ((r >> 3) * 512 + (r & 7) * 32 + qswz(r, hh) * 8) * 2; }
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-        const int r = QBM + wn * 160 + i * 32 + l31;
-        offB[i] = ((r >> 3) * 512 + (r & 7) * 32 + qswz(r, hh) * 8) * 2;
-    }
-    const unsigned char* ldsb = reinterpret_cast<const unsigned char*>(lds);
-
-#define W4_RDB(fb_, rd_, s_, i_) fb_[i_] = *reinterpret_cast<const uint4*>(ldsb + (rd_) + ((s_) >> 1) * 512 + (offB[i_] ^ (((s_) & 1) * 32u)))
-#define W4_RDA(fa_, rd_, s_, j_) fa_[j_] = *reinterpret_cast<const uint4*>(ldsb + (rd_) + ((s_) >> 1) * 512 + (offA[j_] ^ (((s_) & 1) * 32u)))
-    // slot k (0..19) of a k-step: MFMA on accumulator tile (i = k % 5, j = k / 5) of the set (ca_, cb_); slots 0-8: one read of
-    // the NEXT step's set; slots 10-19: DMA piece Q0_ + (k - 10) while < Q1_ (D_: 0 none, 1 always, 2 when dma_ is set)
-#define W4_SLOT(k_, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                      \
-        mfma32_asm<PREC, ((k_) % 5) < 4>(acc[(k_) % 5][(k_) / 5], cb_[(k_) % 5], ca_[(k_) / 5]);           \
-        if constexpr ((k_) < 5) { W4_RDB(nb_, nrd_, ns_, ((k_) < 5 ? (k_) : 0)); }                         \
-        else if constexpr ((k_) < 9) { W4_RDA(na_, nrd_, ns_, ((k_) >= 5 && (k_) < 9 ? (k_) - 5 : 0)); }   \
-        if constexpr ((D_) != 0 && (k_) >= 10 && (Q0_) + (k_) - 10 < (Q1_)) {                              \
-            if ((D_) == 1 || (dma_)) W4_PIECE(pa_, pb_, wr_, ((k_) >= 10 && (Q0_) + (k_) - 10 < NP ? (Q0_) + (k_) - 10 : 0)); \
-        }                                                                                                  \
-        __builtin_amdgcn_sched_barrier(0);
-#define W4_STEP(ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                          \
-        W4_SLOT(0, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                       \
-        W4_SLOT(1, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                       \
-        W4_SLOT(2, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                       \
-        W4_SLOT(3, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                       \
-        W4_SLOT(4, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                       \
-        W4_SLOT(5, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                       \
-        W4_SLOT(6, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                       \
-        W4_SLOT(7, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                       \
-        W4_SLOT(8, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                       \
-        W4_SLOT(9, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                       \
-        W4_SLOT(10, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                      \
-        W4_SLOT(11, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                      \
-        W4_SLOT(12, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                      \
-        W4_SLOT(13, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                      \
-        W4_SLOT(14, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                      \
-        W4_SLOT(15, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                      \
-        W4_SLOT(16, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                      \
-        W4_SLOT(17, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                      \
-        W4_SLOT(18, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)                      \
-        W4_SLOT(19, ca_, cb_, na_, nb_, nrd_, ns_, D_, dma_, Q0_, Q1_, pa_, pb_, wr_)
-#define W4_STAGE(D0_, d0_, a0_, b0_, D3_, d3_, a3_, b3_)                                                   \
-        {                                                                                                  \
-            const uint32_t ot = XSB - rd;                                                                  \
-            W4_STEP(fa0, fb0, fa1, fb1, rd, 1, D0_, d0_, NP3, NP, a0_, b0_, ot)                            \
-            W4_STEP(fa1, fb1, fa0, fb0, rd, 2, 0, false, 0, 0, a0_, b0_, ot)                               \
-            W4_STEP(fa0, fb0, fa1, fb1, rd, 3, 0, false, 0, 0, a0_, b0_, ot)                               \
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                    \
-            __builtin_amdgcn_s_barrier();                                                                  \
-            __builtin_amdgcn_sched_barrier(0);                                                             \
-            W4_STEP(fa1, fb1, fa0, fb0, ot, 0, D3_, d3_, 0, NP3, a3_, b3_, rd)                             \
-            rd = ot;                                                                                       \
-        }
-#define W4_ISSUE_RANGE(pa_, pb_, wr_, LO, HI)                                                              \
-    do {                                                                                                   \
-        _Pragma("unroll") for (int q_ = 0; q_ < NP; ++q_)                                                  \
-            if (q_ >= (LO) && q_ < (HI)) {                                                                 \
-                glds16_m(voff, (q_ < 8 ? (pa_) + (size_t)q_ * rs32 : (pb_) + (size_t)(q_ - 8) * rs32), lds0 + (wr_) + q_ * 4096u); \
-            }                                                                                              \
-    } while (0)
-
-    int L = blockIdx.x, m0, n0;
-    W4_TILE(L, m0, n0);
-    const uint16_t* sA = A + (size_t)m0 * K;
-    const uint16_t* sB = B + (size_t)n0 * K;
-    W4_ISSUE_RANGE(sA, sB, 0u, 0, NP);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    f32x16_t acc[NI][NJ];
-    for (;;) {
-        const int Ln = L + (int)gridDim.x;
-        const bool more = Ln < ntiles;
-        int m1 = m0, n1 = n0;
-        if (more) W4_TILE(Ln, m1, n1);
-        const uint16_t* nA = A + (size_t)m1 * K;
-        const uint16_t* nB = B + (size_t)n1 * K;
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-        {
-            const uint16_t* a1 = sA + XBK;
-            const uint16_t* b1 = sB + XBK;
-            W4_ISSUE_RANGE(a1, b1, XSB, 0, NP3);           // early pieces of stage 1 -> buffer 1
-        }
-        uint4 fa0[NJ], fb0[NI], fa1[NJ], fb1[NI];
-#pragma unroll
-        for (int i = 0; i < NI; ++i) W4_RDB(fb0, 0u, 0, i);
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) W4_RDA(fa0, 0u, 0, j);
-        // accumulator writes (VALU / v_accvgpr_write) before the first MFMA: same tie
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            if (j == NJ - 1)
-                asm volatile("s_nop 7" : "+a"(acc[0][j]), "+a"(acc[1][j]), "+a"(acc[2][j]), "+a"(acc[3][j]), "+v"(acc[4][j]));
-            else
-                asm volatile("" : "+a"(acc[0][j]), "+a"(acc[1][j]), "+a"(acc[2][j]), "+a"(acc[3][j]), "+v"(acc[4][j]));
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        uint32_t rd = 0;
-        const uint16_t* pa = sA + XBK;
-        const uint16_t* pb = sB + XBK;
-        for (int t = 0; t + 2 < nst; ++t) {
-            W4_STAGE(1, true, pa, pb, 1, true, pa + XBK, pb + XBK)
-            pa += XBK;
-            pb += XBK;
-        }
-        W4_STAGE(1, true, pa, pb, 2, more, nA, nB)         // t = nst-2
-        W4_STAGE(2, more, nA, nB, 0, false, nA, nB)        // t = nst-1
-        // The last MFMA results must not be read for 18 wait states, and hipcc neither knows that the asm statements above are
-        // MFMAs nor keeps register-only code behind a bare asm: the padding is tied to every accumulator tile by data dependence.
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            if (j == 0)
-                asm volatile("s_nop 15\n\ts_nop 15" : "+a"(acc[0][j]), "+a"(acc[1][j]), "+a"(acc[2][j]), "+a"(acc[3][j]), "+v"(acc[4][j]));
-            else
-                asm volatile("" : "+a"(acc[0][j]), "+a"(acc[1][j]), "+a"(acc[2][j]), "+a"(acc[3][j]), "+v"(acc[4][j]));
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        {
-            unsigned char* scr = reinterpret_cast<unsigned char*>(lds) + XSB + wave * (XSB / 4);
-            epilogue_m32<PREC, OUT_F32, GELU, false, NJ>(acc, scr, Cv, bias, N, m0 + wm * 128, n0 + wn * 160, wn, accumulate, lane);
-        }
-        if (!more) break;
-        __builtin_amdgcn_s_barrier();
-        L = Ln; m0 = m1; n0 = n1; sA = nA; sB = nB;
-    }
-#undef W4_TILE
-#undef W4_PIECE
-#undef W4_RDA
-#undef W4_RDB
-#undef W4_SLOT
-#undef W4_STEP
-#undef W4_STAGE
-#undef W4_ISSUE_RANGE
-}
-
-template <int PREC>
-hipError_t launch_gemm_w4(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, bool out_f32, bool gelu,
-                          bool accumulate, bool persistent, hipStream_t s) {
-    const int ntiles = (M / QBM) * (N / WBN);
-    const int n_cu = cu_count();
-    dim3 grid(persistent && ntiles > n_cu ? n_cu : ntiles), block(W4THREADS);
-    const uint16_t* a = reinterpret_cast<const uint16_t*>(A);
-    const uint16_t* b = reinterpret_cast<const uint16_t*>(B);
-    const int acc = accumulate ? 1 : 0;
-    if (out_f32) {
-        if (gelu) gemm_et_w4_kernel<PREC, true, true><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, acc);
-        else gemm_et_w4_kernel<PREC, true, false><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, acc);
-    } else {
-        if (gelu) gemm_et_w4_kernel<PREC, false, true><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, acc);
-        else gemm_et_w4_kernel<PREC, false, false><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, acc);
-    }
-    return hipGetLastError();
-}
-
-#endif  // SAMRS_EXPERIMENTS (gemm_et_w4_kernel)
-// ---------------------------------------------------------------------------------------------
 // gemm_et_w4x_kernel (round 5): the vendor's tile geometry on this file's LDS-DMA pair stages -- 256 x 256 x 64 macro tile, FOUR waves
 // with 512 registers each, wave tile 128 x 128 on v_mfma_f32_16x16x32 (the form tools/mfma_rate.hip measures 24 % faster than
 // 32x32x16 in the bare pipe; the round-2 four-wave kernel above was built on 32x32x16).  VERDICT r04 item 1a.
@@ -2381,19 +1232,6 @@ hipError_t launch_gemm_w4x(const void* A, const void* B, void* C, const float* b
 }
 
 #ifdef SAMRS_EXPERIMENTS
-// producer of the folded LayerNorm: C = A B^T + bias + C (fp32), Xh = ET(C), stats[m][N / 160] = (mean, M2) per 160 columns
-template <int PREC>
-hipError_t launch_gemm_m32_stats(const void* A, const void* B, float* C, const float* bias, void* Xh, float* stats,
-                                 int M, int N, int K, int spread, hipStream_t s) {
-    const int ntiles = (M / QBM) * (N / WBN);
-    const int n_cu = cu_count_now();
-    dim3 grid(ntiles > n_cu ? n_cu : ntiles), block(QTHREADS);
-    const uint16_t* a = reinterpret_cast<const uint16_t*>(A);
-    const uint16_t* b = reinterpret_cast<const uint16_t*>(B);
-    if (spread) gemm_et_m32_kernel<PREC, true, false, 1, true><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, 1, reinterpret_cast<uint16_t*>(Xh), reinterpret_cast<float2*>(stats));
-    else gemm_et_m32_kernel<PREC, true, false, 0, true><<<grid, block, 0, s>>>(a, b, C, bias, M, N, K, 1, reinterpret_cast<uint16_t*>(Xh), reinterpret_cast<float2*>(stats));
-    return hipGetLastError();
-}
 // consumer: C (ET) = [GELU](rstd (Xh Wf^T - mean cvec) + bias_f) on the persistent pair-stage kernel
 template <int PREC>
 hipError_t launch_gemm_x64p_fold(const void* A, const void* B, void* C, const float* bias, const float* cvec, const float* rowstat,
@@ -2455,475 +1293,8 @@ hipError_t launch_gemm_big(const void* A, const void* B, void* C, const float* b
 }
 
 
-// ---------------------------------------------------------------------------------------------
-// gemm_et_dual_kernel: the staggered 256x128 kernel with a 32-wide K step: three 24 KiB ring stages
-// = 72 KiB of LDS and <= 128 VGPRs, so TWO blocks (16 waves) are resident per CU and one block's
-// epilogue (HBM-write bound: up to a third of the single-block kernel, ablation in DESIGN.md)
-// overlaps the other block's main loop.  Per K step and wave: 3 DMA pieces, 8 ds_read_b128,
-// 16 MFMAs, two raw barriers (L | C segments, wave groups staggered by one interval).
-// ---------------------------------------------------------------------------------------------
-constexpr int DSTAGES = 3, DTHREADS = 512;
-constexpr int DSTAGE_ELEMS = (DBM + DBN) * DBK;               // 12288 ET = 24 KiB
-constexpr int D_DMA_PER_TILE = (DBM + DBN) * DBK * 2 / (DTHREADS * 16);   // 3 per thread
-
-// SPLIT: both operands come as hi + lo (two-term split, common.h) and the k loop runs three times over K:
-// A_lo B_hi, A_hi B_lo, A_hi B_hi (small terms first), all into the same fp32 accumulators -- the product of the
-// un-rounded operands to ~2^-22 at three times the MFMA work.  Used for the decoder's first transposed conv, whose
-// operand rounding cost 376 of the 899 class-map pixels of the round-2 engine at ViT-H (oracle/error_budget.py).
-template <int PREC, bool OUT_F32, bool GELU, bool STAG = true, bool GLN = false, bool SPLIT = false>
-__global__ __launch_bounds__(DTHREADS, 4) void gemm_et_dual_kernel(
-    const uint16_t* __restrict__ A, const uint16_t* __restrict__ B, void* __restrict__ Cv,
-    const float* __restrict__ bias, const float* __restrict__ add2d, int add2d_period,
-    int M, int N, int K, int accumulate, const uint16_t* __restrict__ A_lo = nullptr, const uint16_t* __restrict__ B_lo = nullptr) {
-    __shared__ __attribute__((aligned(16))) uint16_t lds[DSTAGES * DSTAGE_ELEMS];   // 72 KiB, ONE object
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int grp = wave >> 2;
-    const int wm = wave >> 1, wn = wave & 1;
-
-    constexpr int GROUP = 8;
-    const int tiles_n = N / DBN, tiles_m = M / DBM;
-    const int bid = xcd_remap(blockIdx.x, gridDim.x);
-    const int per_group = GROUP * tiles_n;
-    const int group = bid / per_group, first_m = group * GROUP;
-    const int gsz = (tiles_m - first_m) < GROUP ? (tiles_m - first_m) : GROUP;
-    const int in_g = bid - group * per_group;
-    const int tile_m = first_m + in_g % gsz, tile_n = in_g / gsz;
-    const int m0 = tile_m * DBM, n0 = tile_n * DBN;
-
-    // DMA: piece = 16 rows x 64 B; lane l -> row l>>2, physical chunk l&3 (source chunk swizzled).
-    // wave w: A rows 16w.. and 128+16w.., B rows 16w..
-    const int g_row = 16 * wave + (lane >> 2);
-    const int g_chunk = qswz(g_row, lane & 3);
-    const uint16_t* gAg = A + (size_t)(m0 + g_row) * K + g_chunk * 8;
-    const uint16_t* gBg = B + (size_t)(n0 + g_row) * K + g_chunk * 8;
-    const uint16_t* gAl = SPLIT ? A_lo + (size_t)(m0 + g_row) * K + g_chunk * 8 : gAg;
-    const uint16_t* gBl = SPLIT ? B_lo + (size_t)(n0 + g_row) * K + g_chunk * 8 : gBg;
-    const uint32_t wave_lds_base = __builtin_amdgcn_readfirstlane(
-        (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)lds + (uint32_t)wave * (16 * DBK * 2));
-    const size_t rs128 = (size_t)128 * K;
-    const int nk1 = K / DBK;                   // k tiles of one pass over K
-#define DUAL_ISSUE(kt_, stage_)                                                                 \
-    do {                                                                                         \
-        const int ph_ = SPLIT ? (kt_) / nk1 : 2;       /* 0: A_lo B_hi, 1: A_hi B_lo, 2: A_hi B_hi */ \
-        const size_t koff_ = (size_t)((kt_) - (SPLIT ? ph_ * nk1 : 0)) * DBK;                    \
-        const uint16_t* pa_ = ph_ == 0 ? gAl : gAg;                                              \
-        const uint16_t* pb_ = ph_ == 1 ? gBl : gBg;                                              \
-        constexpr int SB_ = (stage_) * DSTAGE_ELEMS * 2;                                         \
-        glds16_asm<SB_ + 0>(pa_ + koff_, wave_lds_base);                                         \
-        glds16_asm<SB_ + 128 * DBK * 2>(pa_ + rs128 + koff_, wave_lds_base);                     \
-        glds16_asm<SB_ + DBM * DBK * 2>(pb_ + koff_, wave_lds_base);                             \
-    } while (0)
-
-    f32x4_t acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-    const int nk = nk1 * (SPLIT ? 3 : 1);
-    DUAL_ISSUE(0, 0);
-    if (nk > 1) {
-        DUAL_ISSUE(1, 1);
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(D_DMA_PER_TILE) : "memory");
-    } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __builtin_amdgcn_s_barrier();
-    if (STAG && grp == 1) __builtin_amdgcn_s_barrier();          // stagger
-
-    const int fr = lane & 15, fq = lane >> 4;
-    int offA[4], offB[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { const int r = wm * 64 + j * 16 + fr; offA[j] = r * DBK + qswz(r, fq) * 8; }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { const int r = wn * 64 + i * 16 + fr; offB[i] = DBM * DBK + r * DBK + qswz(r, fq) * 8; }
-
-#define DUAL_WAIT(kt_)                                                                           \
-    if ((kt_) + 2 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(D_DMA_PER_TILE) : "memory");     \
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#define DUAL_STEP(kt_, S_)                                                                       \
-    if ((kt_) < nk) {                                                                            \
-        uint4 fa[4], fb[4];                                                                      \
-        if ((kt_) + 2 < nk) DUAL_ISSUE((kt_) + 2, ((S_) + 2) % DSTAGES);                         \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i)                                            \
-            fb[i] = *reinterpret_cast<const uint4*>(lds + (S_) * DSTAGE_ELEMS + offB[i]);        \
-        _Pragma("unroll") for (int j = 0; j < 4; ++j)                                            \
-            fa[j] = *reinterpret_cast<const uint4*>(lds + (S_) * DSTAGE_ELEMS + offA[j]);        \
-        if (STAG) {                                                                              \
-        DUAL_WAIT(kt_)                                                                           \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                       \
-        __builtin_amdgcn_sched_barrier(0);                                                       \
-        __builtin_amdgcn_s_barrier();                                                            \
-        }                                                                                        \
-        __builtin_amdgcn_s_setprio(1);                                                           \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i)                                            \
-            _Pragma("unroll") for (int j = 0; j < 4; ++j)                                        \
-                acc[i][j] = ET<PREC>::mfma16(fb[i], fa[j], acc[i][j]);                           \
-        __builtin_amdgcn_s_setprio(0);                                                           \
-        DUAL_WAIT(kt_)                                                                           \
-        if (!STAG) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                            \
-        __builtin_amdgcn_sched_barrier(0);                                                       \
-        __builtin_amdgcn_s_barrier();                                                            \
-    }
-    for (int kt = 0; kt < nk; kt += DSTAGES) {
-        DUAL_STEP(kt, 0)
-        DUAL_STEP(kt + 1, 1)
-        DUAL_STEP(kt + 2, 2)
-    }
-    if (STAG && grp == 0) __builtin_amdgcn_s_barrier();          // both groups: 2 + 2*nk barriers
-    {
-        unsigned char* scr = reinterpret_cast<unsigned char*>(lds) + wave * (DSTAGES * DSTAGE_ELEMS * 2 / 8);   // 9 KiB
-        if (!OUT_F32 && !GLN && add2d) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int m = m0 + wm * 64 + j * 16 + fr, n = n0 + wn * 64 + i * 16 + 4 * fq;
-                    const float4 e = *reinterpret_cast<const float4*>(add2d + (size_t)(m % add2d_period) * N + n);
-                    acc[i][j][0] += e.x; acc[i][j][1] += e.y; acc[i][j][2] += e.z; acc[i][j][3] += e.w;
-                }
-        }
-        epilogue_coalesced<PREC, OUT_F32, GELU, 4, OUT_F32 ? 2 : 4, 4, GLN>(acc, scr, Cv, bias, (OUT_F32 || GLN) ? add2d : nullptr,
-                                                                             add2d_period, N, m0 + wm * 64, n0 + wn * 64, accumulate, lane);
-    }
-}
-
-// C (ET) = GELU(LayerNorm2d_64(A B^T + bias)): the 64-column groups of N are normalised independently.
-// A_lo / B_lo given: split-precision product (see the kernel), C is then FP32 (its consumer splits it again).
-template <int PREC>
-hipError_t launch_gemm_dual_gln(const void* A, const void* B, void* C, const float* bias, const float* gamma_beta,
-                                int M, int N, int K, hipStream_t s, const void* A_lo = nullptr, const void* B_lo = nullptr) {
-    dim3 grid((M / DBM) * (N / DBN)), block(DTHREADS);
-    if (A_lo && B_lo)
-        gemm_et_dual_kernel<PREC, true, true, true, true, true><<<grid, block, 0, s>>>(
-            reinterpret_cast<const uint16_t*>(A), reinterpret_cast<const uint16_t*>(B), C, bias, gamma_beta, 1, M, N, K, 0,
-            reinterpret_cast<const uint16_t*>(A_lo), reinterpret_cast<const uint16_t*>(B_lo));
-    else
-        gemm_et_dual_kernel<PREC, false, true, true, true><<<grid, block, 0, s>>>(
-            reinterpret_cast<const uint16_t*>(A), reinterpret_cast<const uint16_t*>(B), C, bias, gamma_beta, 1, M, N, K, 0);
-    return hipGetLastError();
-}
-
-template <int PREC, bool STAG = true>
-hipError_t launch_gemm_dual(const void* A, const void* B, void* C, const float* bias, const float* add2d, int period,
-                            int M, int N, int K, bool out_f32, bool gelu, bool accumulate, hipStream_t s) {
-    dim3 grid((M / DBM) * (N / DBN)), block(DTHREADS);
-    const uint16_t* a = reinterpret_cast<const uint16_t*>(A);
-    const uint16_t* b = reinterpret_cast<const uint16_t*>(B);
-    const int acc = accumulate ? 1 : 0;
-    if (out_f32) {
-        if (gelu) gemm_et_dual_kernel<PREC, true, true, STAG><<<grid, block, 0, s>>>(a, b, C, bias, add2d, period, M, N, K, acc);
-        else gemm_et_dual_kernel<PREC, true, false, STAG><<<grid, block, 0, s>>>(a, b, C, bias, add2d, period, M, N, K, acc);
-    } else {
-        if (gelu) gemm_et_dual_kernel<PREC, false, true, STAG><<<grid, block, 0, s>>>(a, b, C, bias, add2d, period, M, N, K, acc);
-        else gemm_et_dual_kernel<PREC, false, false, STAG><<<grid, block, 0, s>>>(a, b, C, bias, add2d, period, M, N, K, acc);
-    }
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------
-// K = 256 streaming GEMM (the decoder's image-side projections: rows = prompts x 4096 keys, N = 256 / 384).
-// With K this short a tiled GEMM is all prologue and epilogue (82 / 52 us for 167 / 134 MB, hipBLASLt 66 / 32): the
-// operand that matters is A, read once, and C, written once.  So: a PERSISTENT block keeps its whole weight slice in
-// registers (wave w: columns 64 w .. +63 x 256 k = 32 uint4 fragments), walks 128-row tiles of A that arrive by LDS-DMA
-// into a double buffer (tile t+1 is in flight while tile t is multiplied and stored), and stores straight from the
-// accumulators (a wave's 4 column blocks complete whole 128-byte lines of a row).  No B traffic after the first tile, one
-// barrier per tile.  Same k order as every other kernel (ascending 32-wide steps from a zero accumulator), same
-// epilogue arithmetic as the tiled path ((acc + add2d) + bias) -> bit-identical results.
-// LDS image of a tile: row r = 32 16-byte chunks, chunk c of the row at position c ^ (r & 15): the fragment reads of a
-// 16-row group (lane (fr, fq) reads chunk 4 ks + fq of row fr) are conflict-free, and a DMA piece is two whole rows.
-// ---------------------------------------------------------------------------------------------
-constexpr int K2_TILE_BYTES = K2_ROWS * K2_K * 2;
-
-// RS = row split: RS waves share a column slice (each keeps its own copy of the weight fragments) and take every RS-th
-// 16-row group -- N = 256: 8 waves instead of 4, twice the loads in flight per CU for the L2-latency-bound 2-D addend.
-template <int PREC, int NW, int RS>
-__global__ __launch_bounds__(64 * NW * RS) void gemm_et_k256_kernel(
-    const uint16_t* __restrict__ A, const uint16_t* __restrict__ B, uint16_t* __restrict__ C,
-    const float* __restrict__ bias, const float* __restrict__ add2d, int add2d_period, int M) {
-    constexpr int N = 64 * NW, K = K2_K;
-    extern __shared__ __attribute__((aligned(16))) unsigned char k2_lds[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);     // 0 .. NW RS - 1: DMA piece owner
-    const int wave = wid % NW, part = wid / NW;                    // column slice, row-group phase
-    const int fr = lane & 15, fq = lane >> 4;
-    const int ntiles = M / K2_ROWS;
-    const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)k2_lds);
-    constexpr int NWT = NW * RS;
-
-    // DMA piece p (two rows 2p, 2p + 1): lane l fetches row 2p + (l >> 5), source chunk (l & 31) ^ (row & 15)
-#define K2_ISSUE(tile_, buf_)                                                                                      \
-    do {                                                                                                           \
-        const uint16_t* sb_ = A + (size_t)(tile_) * K2_ROWS * K;                                                   \
-        _Pragma("unroll") for (int i_ = 0; i_ < (64 + NWT - 1) / NWT; ++i_) {                                      \
-            const int p_ = wid + NWT * i_;                                                                         \
-            if (p_ < 64) {                                                                                         \
-                const int row_ = 2 * p_ + (lane >> 5);                                                             \
-                const uint32_t voff_ = (uint32_t)(row_ * K + (((lane & 31) ^ (row_ & 15)) << 3)) * 2u;             \
-                glds16_s(voff_, sb_, lds0 + (uint32_t)(buf_) * K2_TILE_BYTES + (uint32_t)p_ * 1024u);              \
-            }                                                                                                      \
-        }                                                                                                          \
-    } while (0)
-
-    int t = blockIdx.x, buf = 0;
-    if (t < ntiles) K2_ISSUE(t, 0);
-    // weight slice and bias of this wave: resident for the whole launch
-    uint4 wf[4][8];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks)
-            wf[i][ks] = *reinterpret_cast<const uint4*>(B + (size_t)(wave * 64 + i * 16 + fr) * K + ks * 32 + fq * 8);
-    // the bias lives in LDS behind the two tile buffers (16 registers the pipelined loop needs elsewhere)
-    constexpr int K2_PS = 144;                 // patch row stride (bytes): 128 + 16
-    unsigned char* patch = k2_lds + 2 * K2_TILE_BYTES + 2048 + wid * (16 * K2_PS);
-    float* bias_s = reinterpret_cast<float*>(k2_lds + 2 * K2_TILE_BYTES);
-    for (int i = tid; i < N; i += 64 * NWT) bias_s[i] = bias ? bias[i] : 0.f;
-#ifdef K2_TIMING
-    unsigned long long kph[4] = {0, 0, 0, 0}, kprev = __builtin_amdgcn_s_memtime();
-    const unsigned long long kstart = kprev;
-    int kn = 0;
-#define K2_STAMP(i_) { const unsigned long long tn_ = __builtin_amdgcn_s_memtime(); kph[i_] += tn_ - kprev; kprev = tn_; }
-#else
-#define K2_STAMP(i_)
-#endif
-    constexpr int NG = (K2_ROWS / 16) / RS;                   // row groups per wave and tile
-#define K2_AF(tile_, g_, ks_) (*reinterpret_cast<const uint4*>((tile_) + ((((g_) * 16 + fr) * 32 + (((ks_) * 4 + fq) ^ fr)) << 4)))
-#define K2_ADDEND(dst_, row_)                                                                                      \
-    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                                               \
-        dst_[i_] = add2d ? *reinterpret_cast<const float4*>(add2d + (size_t)((row_) % add2d_period) * N + wave * 64 + i_ * 16 + 4 * fq) \
-                         : make_float4(0.f, 0.f, 0.f, 0.f)
-    for (; t < ntiles; t += gridDim.x, buf ^= 1) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's pieces of tile t have landed
-        K2_STAMP(0)
-        __syncthreads();                                        // everybody's; and nobody reads the other buffer any more
-        K2_STAMP(1)
-        if (t + (int)gridDim.x < ntiles) K2_ISSUE(t + (int)gridDim.x, buf ^ 1);
-        K2_STAMP(2)
-        const unsigned char* tile = k2_lds + buf * K2_TILE_BYTES;
-        // Software pipeline over this wave's NG row groups: a group's addend is loaded before its MFMAs, the next group's A
-        // fragments replace the current ones k-step by k-step as the MFMAs consume them; the four column blocks advance
-        // together (4 independent accumulator chains).
-        uint4 af[8];
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) af[ks] = K2_AF(tile, part, ks);
-#pragma unroll
-        for (int gi = 0; gi < NG; ++gi) {
-            const int g = part + gi * RS;
-            const bool more = gi + 1 < NG;
-            float4 e[4];                          // in flight during this group's MFMAs (no room for a second set)
-            K2_ADDEND(e, t * K2_ROWS + g * 16 + fr);
-            f32x4_t acc[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) acc[i] = ET<PREC>::mfma16(wf[i][ks], af[ks], acc[i]);
-                if (more) af[ks] = K2_AF(tile, g + RS, ks);
-            }
-            // Bounce through a wave-private LDS patch: straight from the accumulators a store instruction would touch 16
-            // cache lines with 32 bytes each (measured: ~320 cycles of issue time per store, 5 k of 9 k cycles per tile);
-            // after the bounce a lane stores 16 bytes and an instruction covers 8 whole 128-byte lines.
-            if (gi) wave_lds_sync_g();            // the previous group's reads of the patch are done
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float4 bb = *reinterpret_cast<const float4*>(bias_s + wave * 64 + i * 16 + 4 * fq);
-                uint2 o;
-                o.x = pack2<PREC>((acc[i][0] + e[i].x) + bb.x, (acc[i][1] + e[i].y) + bb.y);
-                o.y = pack2<PREC>((acc[i][2] + e[i].z) + bb.z, (acc[i][3] + e[i].w) + bb.w);
-                *reinterpret_cast<uint2*>(patch + fr * K2_PS + (i * 16 + 4 * fq) * 2) = o;
-            }
-            wave_lds_sync_g();
-            uint16_t* cbase = C + (size_t)(t * K2_ROWS + g * 16) * N + wave * 64;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int r = h * 8 + (lane >> 3), ch = lane & 7;
-                const uint4 v = *reinterpret_cast<const uint4*>(patch + r * K2_PS + ch * 16);
-                *reinterpret_cast<uint4*>(cbase + (size_t)r * N + ch * 8) = v;
-            }
-        }
-        K2_STAMP(3)
-#ifdef K2_TIMING
-        ++kn;
-#endif
-    }
-#ifdef K2_TIMING
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane == 0 && wid == 0) {   // timing build: the first rows of C hold the stamps instead of results
-        unsigned long long* tp = reinterpret_cast<unsigned long long*>(C) + (size_t)blockIdx.x * 8;
-        for (int i = 0; i < 4; ++i) tp[i] = kph[i];
-        tp[4] = __builtin_amdgcn_s_memtime() - kstart;
-        tp[5] = kn;
-    }
-#endif
-#undef K2_ISSUE
-#undef K2_STAMP
-#undef K2_AF
-#undef K2_ADDEND
-}
-
-template <int PREC>
-hipError_t launch_gemm_k256(const void* A, const void* B, void* C, const float* bias, const float* add2d, int period,
-                            int M, int N, hipStream_t s) {
-    const int n_cu = cu_count();
-    const int ntiles = M / K2_ROWS;
-    dim3 grid(ntiles < n_cu ? ntiles : n_cu);
-    const uint16_t* a = reinterpret_cast<const uint16_t*>(A);
-    const uint16_t* b = reinterpret_cast<const uint16_t*>(B);
-    constexpr int LDS = 2 * K2_TILE_BYTES + 2048 + 8 * 16 * 144;   // two tile buffers + the bias + 8 store patches
-#define K2_LAUNCH(NW_, RS_)                                                                                          \
-    do {                                                                                                             \
-        auto k = gemm_et_k256_kernel<PREC, NW_, RS_>;                                                                \
-        HIP_CHECK_RET(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, LDS)); \
-        k<<<grid, 64 * NW_ * RS_, LDS, s>>>(a, b, (uint16_t*)C, bias, add2d, period, M);                             \
-    } while (0)
-    if (N == 256) K2_LAUNCH(4, 2);
-    else if (N == 384) K2_LAUNCH(6, 1);
-    else return hipErrorInvalidValue;
-#undef K2_LAUNCH
-    return hipGetLastError();
-}
-
 thread_local int tl_gemm_variant = -1;   // per-engine override, set around an engine's launches (engine_state.h GemmVariantScope)
 int g_gemm_variant = 8;   // 0 reg-staged 128^2, 1 +LDS-DMA, 2 +grouped order, 3 reg+grouped, 4 256x128 3-stage pipe, 5 +staggered groups, 6 256x256, 7 2 blocks/CU, 8 auto(5|6|7)
-
-template <int PREC, bool GLDS, int GROUP_M>
-hipError_t launch_gemm_prec(const void* A, const void* B, void* C, const float* bias,
-                            const float* add2d, int period, int M, int N, int K, bool out_f32,
-                            bool gelu, bool accumulate, hipStream_t s) {
-    dim3 grid((M / BM) * (N / BN)), block(GEMM_THREADS);
-    const uint16_t* a = reinterpret_cast<const uint16_t*>(A);
-    const uint16_t* b = reinterpret_cast<const uint16_t*>(B);
-    const int acc = accumulate ? 1 : 0;
-    if (out_f32) {
-        if (gelu)
-            gemm_et_kernel<PREC, true, true, GLDS, GROUP_M><<<grid, block, 0, s>>>(a, b, C, bias, add2d, period, M, N, K, acc);
-        else
-            gemm_et_kernel<PREC, true, false, GLDS, GROUP_M><<<grid, block, 0, s>>>(a, b, C, bias, add2d, period, M, N, K, acc);
-    } else {
-        if (gelu)
-            gemm_et_kernel<PREC, false, true, GLDS, GROUP_M><<<grid, block, 0, s>>>(a, b, C, bias, add2d, period, M, N, K, acc);
-        else
-            gemm_et_kernel<PREC, false, false, GLDS, GROUP_M><<<grid, block, 0, s>>>(a, b, C, bias, add2d, period, M, N, K, acc);
-    }
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------
-// exact fp32 GEMM: C[M,N] = (A [+ A2])[M,K] * W[N,K]^T + bias, optional ReLU / accumulate, for up
-// to F32_BATCH_MAX independent problems of one shape per launch (blockIdx.z picks the pointer set).
-// Token side of the decoder: M is a few hundred rows, so the launch is latency- and parallelism-
-// bound, not FLOP-bound.  A block of S waves owns one 32x32 output tile and splits K S ways;
-// partial tiles are combined through LDS in a FIXED order, so the result is bit-reproducible
-// (unlike a blockIdx-level split-K with fp32 atomics).
-//
-// No LDS staging of the operands: v_mfma_f32_16x16x4_f32 takes, per lane (i = lane&15, q = lane>>4),
-// ONE element P[i][k_q] of the 16x4 slab, and a sum over k does not care which physical k sits in
-// slot q as long as both operands agree.  So each lane loads a float4 = row i, columns 4q..4q+3 of
-// a 16-wide K slab straight from global memory (16 rows x 64 contiguous bytes per instruction),
-// and MFMA t of the slab consumes component t of both operands: slot q of MFMA t holds k = 4q + t.
-// Up to F32_PF slabs are kept in flight per wave (a register ring).
-// M, N arbitrary (bounds-checked), K % 16 == 0.  lda / ldc in elements; W is dense [N][K].
-// ---------------------------------------------------------------------------------------------
-constexpr int FM = 32, FN = 32, FKS = 16, F32_PF = 4;
-
-template <int S>
-__global__ __launch_bounds__(64 * S) void gemm_f32_kernel(F32Batch bt, int lda, int ldc, int M, int N, int K,
-                                                          int relu, int accumulate) {
-    __shared__ float red[S][FM][FN + 1];
-    const int z = blockIdx.z;
-    const float* __restrict__ A = bt.A[z];
-    const float* __restrict__ A2 = bt.A2[z];
-    const float* __restrict__ W = bt.W[z];
-    const float* __restrict__ bias = bt.bias[z];
-    float* __restrict__ C = bt.C[z];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int m0 = blockIdx.y * FM, n0 = blockIdx.x * FN;
-    const int KW = K / S, NS = KW / FKS;
-    const int r = lane & 15, q = lane >> 4;
-
-    f32x4_t acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-
-    bool va[2], vw[2];
-    const float *pa[2], *pa2[2], *pw[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        va[h] = m0 + 16 * h + r < M;
-        vw[h] = n0 + 16 * h + r < N;
-        const size_t ao = (size_t)(va[h] ? m0 + 16 * h + r : 0) * lda + wave * KW + 4 * q;
-        pa[h] = A + ao;
-        pa2[h] = A2 ? A2 + ao : nullptr;
-        pw[h] = W + (size_t)(vw[h] ? n0 + 16 * h + r : 0) * K + wave * KW + 4 * q;
-    }
-    float4 xa[F32_PF][2], xw[F32_PF][2];
-#define F32_LOAD(slot_, s_)                                                                        \
-    if ((s_) < NS) {                                                                               \
-        _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_) {                                         \
-            float4 a_ = make_float4(0.f, 0.f, 0.f, 0.f), w_ = a_;                                  \
-            if (va[h_]) {                                                                          \
-                a_ = *reinterpret_cast<const float4*>(pa[h_] + (s_) * FKS);                        \
-                if (pa2[h_]) {                                                                     \
-                    const float4 b_ = *reinterpret_cast<const float4*>(pa2[h_] + (s_) * FKS);      \
-                    a_.x += b_.x; a_.y += b_.y; a_.z += b_.z; a_.w += b_.w;                        \
-                }                                                                                  \
-            }                                                                                      \
-            if (vw[h_]) w_ = *reinterpret_cast<const float4*>(pw[h_] + (s_) * FKS);                \
-            xa[slot_][h_] = a_; xw[slot_][h_] = w_;                                                \
-        }                                                                                          \
-    }
-#pragma unroll
-    for (int p = 0; p < F32_PF; ++p) F32_LOAD(p, p)
-    for (int g = 0; g < NS; g += F32_PF) {
-#pragma unroll
-        for (int p = 0; p < F32_PF; ++p) {
-            if (g + p < NS) {
-                const float fa[2][4] = {{xa[p][0].x, xa[p][0].y, xa[p][0].z, xa[p][0].w},
-                                        {xa[p][1].x, xa[p][1].y, xa[p][1].z, xa[p][1].w}};
-                const float fw[2][4] = {{xw[p][0].x, xw[p][0].y, xw[p][0].z, xw[p][0].w},
-                                        {xw[p][1].x, xw[p][1].y, xw[p][1].z, xw[p][1].w}};
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int i = 0; i < 2; ++i)
-#pragma unroll
-                        for (int j = 0; j < 2; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fw[i][t], fa[j][t], acc[i][j], 0, 0, 0);
-                F32_LOAD(p, g + p + F32_PF)
-            }
-        }
-    }
-#undef F32_LOAD
-    // D[i_local = n][j_local = m]: lane holds n = base + 4*(lane>>4) + rr, m = base + (lane&15)
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) red[wave][j * 16 + r][i * 16 + 4 * q + rr] = acc[i][j][rr];
-    __syncthreads();
-    for (int o = threadIdx.x; o < FM * FN; o += 64 * S) {
-        const int ml = o >> 5, nl = o & 31;
-        float v = red[0][ml][nl];
-#pragma unroll
-        for (int w = 1; w < S; ++w) v += red[w][ml][nl];     // fixed order: reproducible
-        const int m = m0 + ml, n = n0 + nl;
-        if (m < M && n < N) {
-            float* c = C + (size_t)m * ldc + n;
-            v += bias ? bias[n] : 0.f;
-            if (relu) v = fmaxf(v, 0.f);
-            if (accumulate) v += *c;
-            *c = v;
-        }
-    }
-}
 
 
 // =============================================================================================================================
@@ -3317,11 +1688,6 @@ hipError_t launch_gemm_et_ext(int prec, const void* A, const void* B, const void
     return with_prec(prec, [&](auto P) { return launch_gemm_x64_ext<P.value>(A, B, Ax, Bx, C, bias, M, N, K, s); });
 }
 
-namespace {
-template <int V>
-using Int = std::integral_constant<int, V>;
-}
-
 #ifdef SAMRS_EXPERIMENTS
 // the timing ablations (f16, ET output, no GELU): one instantiation per ablation number
 static hipError_t launch_gemm_abl(const GemmChoice& ch, const void* A, const void* B, void* C, const float* bias, const float* add2d,
@@ -3354,19 +1720,14 @@ hipError_t launch_gemm_et(int prec, const void* A, const void* B, void* C, const
     if (ch.reject) return hipErrorInvalidValue;
     return with_prec(prec, [&](auto P) -> hipError_t {
         constexpr int PR = P.value;
-        auto base = [&](auto GLDS, auto GROUP_M) {
-            return launch_gemm_prec<PR, (GLDS.value != 0), GROUP_M.value>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
-        };
         auto x64 = [&](auto NI, auto MODE) {
             return launch_gemm_x64<PR, NI.value, MODE.value>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
         };
         switch (ch.kernel) {
-            case GemmKernel::BASE:
-                if (ch.glds) return ch.group_m == 1 ? base(Int<1>{}, Int<1>{}) : base(Int<1>{}, Int<8>{});
-                return ch.group_m == 1 ? base(Int<0>{}, Int<1>{}) : base(Int<0>{}, Int<8>{});
-            case GemmKernel::STAG: return launch_gemm_stag<PR>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
-            case GemmKernel::DUAL: return launch_gemm_dual<PR>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
-            case GemmKernel::DUAL_LOCKSTEP: return launch_gemm_dual<PR, false>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
+            case GemmKernel::BASE: return gemm_fam::base(prec, ch.glds, ch.group_m, A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
+            case GemmKernel::STAG: return gemm_fam::stag(prec, A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
+            case GemmKernel::DUAL: return gemm_fam::dual(prec, true, A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
+            case GemmKernel::DUAL_LOCKSTEP: return gemm_fam::dual(prec, false, A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
             case GemmKernel::STAG_256x256: return launch_gemm_big<PR>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
             case GemmKernel::STAG_256x320: return launch_gemm_big<PR, 5>(A, B, C, bias, add2d, add2d_period, M, N, K, out_f32, gelu, accumulate, s);
             case GemmKernel::X64:
@@ -3384,12 +1745,10 @@ hipError_t launch_gemm_et(int prec, const void* A, const void* B, void* C, const
                 return hipErrorInvalidValue;
             case GemmKernel::X64P: return launch_gemm_x64p<PR>(A, B, C, bias, M, N, K, out_f32, gelu, accumulate, opts.ld, opts.gelu_form, s);
             case GemmKernel::W4X: return launch_gemm_w4x<PR>(A, B, C, bias, M, N, K, out_f32, gelu, accumulate, opts.ld, opts.gelu_form, s);
-            case GemmKernel::K256: return launch_gemm_k256<PR>(A, B, C, bias, add2d, add2d_period, M, N, s);
+            case GemmKernel::K256: return gemm_fam::k256(prec, A, B, C, bias, add2d, add2d_period, M, N, s);
 #ifdef SAMRS_EXPERIMENTS
-            case GemmKernel::M32:
-                if (ch.mode) return launch_gemm_m32<PR, 1>(A, B, C, bias, M, N, K, out_f32, gelu, accumulate, ch.persistent, s);
-                return launch_gemm_m32<PR, 0>(A, B, C, bias, M, N, K, out_f32, gelu, accumulate, ch.persistent, s);
-            case GemmKernel::W4: return launch_gemm_w4<PR>(A, B, C, bias, M, N, K, out_f32, gelu, accumulate, ch.persistent, s);
+            case GemmKernel::M32: return gemm_fam::m32(prec, ch.mode ? 1 : 0, A, B, C, bias, M, N, K, out_f32, gelu, accumulate, ch.persistent, s);
+            case GemmKernel::W4: return gemm_fam::w4(prec, A, B, C, bias, M, N, K, out_f32, gelu, accumulate, ch.persistent, s);
             case GemmKernel::ABL_BIG:
             case GemmKernel::ABL_X64: return launch_gemm_abl(ch, A, B, C, bias, add2d, add2d_period, M, N, K, s);
 #else
@@ -3400,7 +1759,6 @@ hipError_t launch_gemm_et(int prec, const void* A, const void* B, void* C, const
     });
 }
 
-// LayerNorm folded into the neighbouring GEMMs (ViT-H: the residual stream has N = 1280 = LN_NS x 160 columns).
 bool gemm_has_experiments() {
 #ifdef SAMRS_EXPERIMENTS
     return true;
@@ -3408,22 +1766,12 @@ bool gemm_has_experiments() {
     return false;
 #endif
 }
-#ifndef SAMRS_EXPERIMENTS
-hipError_t launch_gemm_et_stats(int, const void*, const void*, float*, const float*, void*, float*, int, int, int, hipStream_t) { return hipErrorInvalidValue; }
-hipError_t launch_gemm_et_fold(int, const void*, const void*, void*, const float*, const float*, const float*, int, int, int, bool, hipStream_t) { return hipErrorInvalidValue; }
-#else
-hipError_t launch_gemm_et_stats(int prec, const void* A, const void* B, float* C, const float* bias, void* Xh, float* stats,
-                                int M, int N, int K, hipStream_t s) {
-    if (!m32_ok(M, N, K, false) || N != 160 * LN_NS || !Xh || !stats) return hipErrorInvalidValue;
-    static const int spread = [] { const char* v = getenv("SAMRS_GEMM_M32"); return v ? ((atoi(v) & 8) ? 1 : 0) : 1; }();
-    return with_prec(prec, [&](auto P) { return launch_gemm_m32_stats<P.value>(A, B, C, bias, Xh, stats, M, N, K, spread, s); });
+#ifdef SAMRS_EXPERIMENTS
+hipError_t gemm_fam::x64p_fold(int prec, const void* A, const void* B, void* C, const float* bias, const float* cvec, const float* rowstat,
+                               int M, int N, int K, bool gelu, hipStream_t s) {
+    return with_prec(prec, [&](auto P) { return launch_gemm_x64p_fold<P.value>(A, B, C, bias, cvec, rowstat, M, N, K, gelu, s); });
 }
-hipError_t launch_gemm_et_fold(int prec, const void* Xh, const void* Wf, void* C, const float* bias_f, const float* cvec,
-                               const float* rowstat, int M, int N, int K, bool gelu, hipStream_t s) {
-    if (M % QBM || N % WBN || K != 160 * LN_NS || !bias_f || !cvec || !rowstat) return hipErrorInvalidValue;
-    return with_prec(prec, [&](auto P) { return launch_gemm_x64p_fold<P.value>(Xh, Wf, C, bias_f, cvec, rowstat, M, N, K, gelu, s); });
-}
-#endif  // SAMRS_EXPERIMENTS
+#endif
 
 // One-launch split product (see seg_src_a): C = (A + A_lo)(B + B_lo)^T minus the lo x lo term, + bias; ET output (rounded once
 // from the fp32 accumulators) or fp32 output, optionally accumulated into C.  Shapes of the pair-stage 256x320 tile only; the
@@ -3489,39 +1837,6 @@ hipError_t launch_gemm_et_lntail(int prec, const void* A, const void* B, float* 
 void set_gemm_variant(int v) { g_gemm_variant = v; }
 int swap_gemm_variant_override(int v) { const int old = tl_gemm_variant; tl_gemm_variant = v; return old; }
 void set_gemm_skew(int xcd_units, int cu_units) { g_x64_skew = (xcd_units & 0xffff) | (cu_units << 16); }
-
-hipError_t launch_gemm_f32_batch(const F32Batch& bt, int count, int lda, int ldc, int M, int N, int K, bool relu,
-                                 bool accumulate, hipStream_t s) {
-    if (K % FKS || M <= 0 || N <= 0 || (lda % 4) || count < 1 || count > F32_BATCH_MAX) return hipErrorInvalidValue;
-    // waves per tile = K split: a function of K ALONE, so that the summation order (hence every bit of the
-    // result) does not depend on how many rows -- prompts -- a call carries: predict(32 boxes) must equal
-    // predict(20) + predict(12).  M is a few hundred rows on this path, so the deepest split always pays.
-    int S = 1;
-    while (S < 16 && K % (2 * FKS * S) == 0) S *= 2;
-    dim3 grid((N + FN - 1) / FN, (M + FM - 1) / FM, count);
-    const int r = relu ? 1 : 0, a = accumulate ? 1 : 0;
-    switch (S) {
-        case 1: gemm_f32_kernel<1><<<grid, 64, 0, s>>>(bt, lda, ldc, M, N, K, r, a); break;
-        case 2: gemm_f32_kernel<2><<<grid, 128, 0, s>>>(bt, lda, ldc, M, N, K, r, a); break;
-        case 4: gemm_f32_kernel<4><<<grid, 256, 0, s>>>(bt, lda, ldc, M, N, K, r, a); break;
-        case 8: gemm_f32_kernel<8><<<grid, 512, 0, s>>>(bt, lda, ldc, M, N, K, r, a); break;
-        default: gemm_f32_kernel<16><<<grid, 1024, 0, s>>>(bt, lda, ldc, M, N, K, r, a); break;
-    }
-    return hipGetLastError();
-}
-
-hipError_t launch_gemm_f32(const float* A, int lda, const float* W, const float* bias, float* C,
-                           int ldc, int M, int N, int K, bool relu, bool accumulate, hipStream_t s) {
-    F32Batch bt{};
-    bt.A[0] = A; bt.W[0] = W; bt.bias[0] = bias; bt.C[0] = C;
-    return launch_gemm_f32_batch(bt, 1, lda, ldc, M, N, K, relu, accumulate, s);
-}
-
-hipError_t launch_gemm_et_gln(int prec, const void* A, const void* B, void* C, const float* bias, const float* gamma_beta,
-                              int M, int N, int K, hipStream_t s, const void* A_lo, const void* B_lo) {
-    if (M % DBM || N % DBN || K % DBK || M <= 0 || !gamma_beta || ((A_lo == nullptr) != (B_lo == nullptr))) return hipErrorInvalidValue;
-    return with_prec(prec, [&](auto P) { return launch_gemm_dual_gln<P.value>(A, B, C, bias, gamma_beta, M, N, K, s, A_lo, B_lo); });
-}
 
 
 // ---- MXFP4 lo-term GEMM (gemm_et_mx_kernel) ----------------------------------------------------------------------------------

@@ -3,7 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// ---- gemm.hip -------------------------------------------------------------------------------
+// ---- gemm.hip (the dispatch) and the kernel families beside it: gemm_ring / gemm_dual / gemm_decoder / gemm_experiments.hip ------
 // Which kernel runs a launch is decided by gemm_select (gemm_select.h) from the shape, the flags and the variant in force.
 struct GemmOpts {
     int ld = 0;           // row stride of A and B in elements, 0 = K: the persistent ET kernels alone read with it (gemm_ld_ok says whether

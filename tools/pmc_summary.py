@@ -77,7 +77,9 @@ def main() -> None:
             "mfma_busy_frac": v.get("mfma_busy_frac"),
             "l2_hit_rate": v.get("l2_hit_rate"),
             "launches": v["launches"],
-            # bench.py reports `traffic` only while this hash matches the gemm.hip it runs (a stale measurement is dropped)
+            # bench.py reports `traffic` only while this hash matches the gemm.hip it runs (a stale measurement is dropped).  gemm.hip is
+            # the file of the dominant kernel (gemm_et_w4x_kernel) and of the dispatch that sends lin1 + GELU there; the base, staggered,
+            # dual, decoder and experiment kernels live in gemm_ring / gemm_dual / gemm_decoder / gemm_experiments.hip, outside the pin
             "gemm_hip_sha16": hashlib.sha256(open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                                                                "samrs_amd", "csrc", "gemm.hip"), "rb").read()).hexdigest()[:16],
             "source": "profiles/dominant_kernel_pmc.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of bench.py, tools/gpu_round.sh pmc)",
