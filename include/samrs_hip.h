@@ -446,6 +446,36 @@ int samrs_coco_match(samrs_engine_t* e, const int64_t* inter, const int64_t* are
 int samrs_png_encode_labels(samrs_engine_t* e, const uint8_t* maps, int n, int h, int w, const uint8_t* lut, uint8_t* out,
                             int64_t out_capacity, int64_t* cursor, int64_t* table, void* stream);
 
+/* -- visualize.py's overlays (Image.blend(image, seg_color, 0.4) saved under vis/), on the device.
+ * samrs_blend_labels: out = blend(images, lut[maps], alpha) for n images uint8 [n][h][w][3] and their class maps uint8 [n][h][w]
+ * through lut uint8 [256][3] (class id -> RGB), all on the device; out uint8 [n][h][w][3] must not alias images.  Bit-exact with
+ * Pillow's Image.blend for 0 <= alpha <= 1: per byte (uint8)((int)a + alpha * ((int)b - (int)a)) in float arithmetic, the product
+ * and the sum each rounded to float, the result truncated.  Any h, w >= 1.  alpha outside [0, 1] (or NaN), n, h or w < 1, a null
+ * pointer: SAMRS_ERR_BAD_ARG, nothing launched.  No host synchronisation, no scratch.
+ *
+ * samrs_png_encode_rgb: n images uint8 [n][h][w][3] on the device -> n complete PNG files (8-bit colour type 2, not interlaced, one
+ * IDAT; zlib header 78 9c; the filtered bytes as literals of dynamic-Huffman blocks of SAMRS_PNG_RGB_BLOCK_BYTES filtered bytes, no
+ * LZ77 matches).  filter 0 .. 4 forces that PNG row filter on every row; -1 chooses per row the filter with the least sum of the
+ * filtered bytes' magnitudes as int8 (v < 128 ? v : 256 - v; the filter byte itself not counted), the lowest number on a tie.  The
+ * bytes of a file are a function of its pixels and `filter` alone.  Same buffer protocol as samrs_png_encode_labels: the files are
+ * packed into `out` (device bytes, 16-byte aligned, capacity out_capacity) at 16-byte aligned offsets behind *cursor (device int64,
+ * in / out), and table [n][2] (device int64) receives (offset, length) per image; length < 0 means the file did not fit (-length - 1
+ * bytes were needed), nothing of it was written and the cursor did not move for it.  h, w <= 65536 and (3 w + 1) h < 2^31.
+ * Worst-case file size, to size `out`: with N = (3 w + 1) h filtered bytes in B = ceil(N / SAMRS_PNG_RGB_BLOCK_BYTES) blocks,
+ *     63 + ceil((9 N + B (4498 + 9)) / 8) bytes,
+ * rounded up to a multiple of 16 per file in the buffer: an optimal prefix code over a block's <= 257 symbols costs no more than the
+ * 9-bit fixed code, and a block adds a header of <= 4498 bits; 63 bytes are framing.  The bound holds whenever no code would be
+ * longer than deflate's 15 bits (every image whose rarest byte value is not rarer than about 1 in 2^15 of a block); where the
+ * length limit steps in, the code is no longer optimal and only 15 bits per byte are guaranteed -- such data is far below the bound
+ * in practice, and a file that does not fit is reported, never truncated.
+ * No host synchronisation; the filtered bytes and code tables live in ONE scratch buffer per handle (8 images per pass, about
+ * (3 w + 1) h bytes each), so all samrs_png_encode_rgb calls on a handle must be stream-ordered with each other. */
+#define SAMRS_PNG_RGB_BLOCK_BYTES 1048576
+int samrs_blend_labels(samrs_engine_t* e, const uint8_t* images, const uint8_t* maps, const uint8_t* lut, float alpha, uint8_t* out, int n,
+                       int h, int w, void* stream);
+int samrs_png_encode_rgb(samrs_engine_t* e, const uint8_t* rgb, int n, int h, int w, int filter, uint8_t* out, int64_t out_capacity,
+                         int64_t* cursor, int64_t* table, void* stream);
+
 /* -- "next row" N3: one separable pass of Pillow's 8-bit resample (ResizeLongestSide.apply_image,
  * utils/transforms.py:26-31 -> PIL Image.resize BILINEAR).  `bounds` int32 [out_len,2] = (first input
  * index, tap count), `coef` int32 [out_len,ksize] 22-bit fixed point, both computed on the host exactly

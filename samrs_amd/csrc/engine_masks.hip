@@ -1,6 +1,6 @@
 // engine_masks.hip -- the entry points that work on finished masks, class maps and prompts' pixels and read no model weights: paint,
 // selection, ground-truth match, RLE, scene stitching, clean-up, boxes, polygons, quality gate, overlap, COCO AP (bit planes, pair counts,
-// matching), PNG, resampling, rbox mask prompts.
+// matching), PNG, overlays, resampling, rbox mask prompts.
 #include <cmath>
 
 #include "engine_state.h"
@@ -322,6 +322,33 @@ int samrs_png_encode_labels(samrs_engine_t* e, const uint8_t* maps, int n, int h
     const size_t need = png_scratch_bytes(n, h, w);
     CK(e, scratch_reserve(e->png_scratch, need, s));
     CK(e, launch_png_encode(maps, n, h, w, lut, e->png_scratch.p, out, (long long)out_capacity, (long long*)cursor, (long long*)table, s));
+    return SAMRS_OK;
+}
+
+// visualize.py's overlay of n images with their class maps (see samrs_hip.h)
+int samrs_blend_labels(samrs_engine_t* e, const uint8_t* images, const uint8_t* maps, const uint8_t* lut, float alpha, uint8_t* out, int n,
+                       int h, int w, void* stream) {
+    if (!e || !images || !maps || !lut || !out || out == images || n < 1 || h < 1 || w < 1)
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_blend_labels: bad argument");
+    if (!(alpha >= 0.f && alpha <= 1.f)) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_blend_labels: alpha = %g must lie in [0, 1]", (double)alpha);
+    ON_DEVICE(e);
+    CK(e, launch_blend_labels(images, maps, lut, alpha, out, n, h, w, (hipStream_t)stream));
+    return SAMRS_OK;
+}
+
+// truecolour PNG files of n images, packed behind *cursor into `out` (see samrs_hip.h)
+int samrs_png_encode_rgb(samrs_engine_t* e, const uint8_t* rgb, int n, int h, int w, int filter, uint8_t* out, int64_t out_capacity,
+                         int64_t* cursor, int64_t* table, void* stream) {
+    if (!e || !rgb || !out || !cursor || !table || n < 1 || h < 1 || w < 1 || out_capacity < 16 || filter < -1 || filter > 4)
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_png_encode_rgb: bad argument");
+    if (((uintptr_t)out & 15) != 0) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_png_encode_rgb: out must be 16-byte aligned");
+    if (h > 65536 || w > 65536 || ((size_t)3 * w + 1) * h > 0x7fffffffull)
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_png_encode_rgb: %d x %d image too large (h, w <= 65536, (3 w + 1) h < 2^31)", h, w);
+    ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    CK(e, scratch_reserve(e->png_rgb_scratch, png_rgb_scratch_bytes(n, h, w), s));
+    CK(e, launch_png_encode_rgb(rgb, n, h, w, filter, e->png_rgb_scratch.p, out, (long long)out_capacity, (long long*)cursor,
+                                (long long*)table, s));
     return SAMRS_OK;
 }
 

@@ -241,6 +241,7 @@ struct samrs_engine {
     DeviceScratch box_scratch;     // row extents of samrs_mask_boxes
     DeviceScratch poly_scratch;    // edge lists and ranking state of samrs_mask_polygons
     DeviceScratch png_scratch;     // class-map PNG scratch (samrs_png_encode_labels)
+    DeviceScratch png_rgb_scratch; // filtered bytes + code tables of samrs_png_encode_rgb
     DeviceScratch overlap_scratch; // entry areas of samrs_resolve_overlaps (rule SMALLEST without before_out)
     DeviceScratch ap_scratch;      // matched flags (+ host scores staged) of samrs_coco_match
 

@@ -274,6 +274,38 @@ hipError_t launch_scene_resolve(const int32_t* order, const int32_t* labels_by_r
 size_t png_scratch_bytes(int n, int h, int w);
 hipError_t launch_png_encode(const uint8_t* maps, int n, int h, int w, const uint8_t* lut, void* scratch, unsigned char* out,
                              long long out_cap, long long* cursor, long long* table, hipStream_t s);
+// The stages of that encoder that do not look at tokens, for `streams` (2: gray + colour; 1: stream 0 alone) streams of each of nm
+// files' slots (nm <= 8, the encoder's own pass); overlay_kernels.hip's truecolour encoder runs them on buffers of the same layout
+// (png_device.h: the meta block; B deflate blocks of 2^20 symbols and C chunks of 1024 symbols per file at most):
+//   hist, tables [nm][B][2][316] (tables: code | length << 16), hdr [nm][B][2][160] + hdrbits [nm][B][2] (the block headers' bits),
+//   chunkbits [nm][2][C], chunkoff [nm][2][C], gapoff [nm][2][B + 1], meta [nm][16].
+//   tables : hist + meta NBLK -> tables, hdr, hdrbits        offsets: chunkbits + tables + hdrbits + meta NCHUNK / NBLK -> chunkoff,
+//   gapoff, meta BITS        zero: the placed files' bytes (meta OFF / LEN)        headers: block headers + end-of-block codes OR-ed in
+//   crc    : the IDAT CRC of the framed files (meta CRC zeroed beforehand); looks at BOTH streams' OFF: a caller with one stream sets
+//            meta OFF1 = ~0.  worst_file_bytes sizes the grid.
+struct PngStageBuffers {
+    unsigned long long* meta;
+    uint32_t *hist, *tables, *hdr, *hdrbits, *chunkbits;
+    unsigned long long *chunkoff, *gapoff;
+    size_t B, C;
+};
+void png_stage_tables(const PngStageBuffers& L, int nm, int streams, hipStream_t s);
+void png_stage_offsets(const PngStageBuffers& L, int nm, int streams, hipStream_t s);
+void png_stage_zero(const PngStageBuffers& L, unsigned char* out, int nm, int streams, hipStream_t s);
+void png_stage_headers(const PngStageBuffers& L, unsigned char* out, int nm, int streams, hipStream_t s);
+void png_stage_crc(const PngStageBuffers& L, unsigned char* out, int nm, int streams, size_t worst_file_bytes, hipStream_t s);
+
+// ---- overlay_kernels.hip --------------------------------------------------------------------
+// out = Pillow's Image.blend(images, lut[maps], alpha): per byte (uint8)((int)a + alpha * ((int)b - (int)a)), float multiply and
+// add each rounded, truncated.  images / out uint8 [n][h][w][3], maps uint8 [n][h][w], lut uint8 [256][3], all on the device.
+hipError_t launch_blend_labels(const uint8_t* images, const uint8_t* maps, const uint8_t* lut, float alpha, uint8_t* out, int n, int h,
+                               int w, hipStream_t s);
+// Truecolour PNG files of n images uint8 [n][h][w][3] (samrs_png_encode_rgb in samrs_hip.h: filter -1 .. 4, the buffer protocol of
+// launch_png_encode with table [n][2]).  scratch: png_rgb_scratch_bytes(n, h, w).  png_rgb_worst_file_bytes: the documented bound.
+size_t png_rgb_scratch_bytes(int n, int h, int w);
+size_t png_rgb_worst_file_bytes(int h, int w);
+hipError_t launch_png_encode_rgb(const uint8_t* rgb, int n, int h, int w, int filter, void* scratch, unsigned char* out,
+                                 long long out_cap, long long* cursor, long long* table, hipStream_t s);
 
 // ---- region_kernels.hip ---------------------------------------------------------------------
 // Small-region removal (utils/amg.py:267-291 remove_small_regions, 8-connectivity) on n <= REGION_CHUNK masks uint8 [n][h][w], in

@@ -27,24 +27,17 @@
 //  15. png_crc_finish_kernel the IDAT CRC.
 // Integer work only; every cross-block dependence is a kernel boundary and every atomic is an order-free integer sum / OR / XOR:
 // the bytes do not depend on scheduling.
+// Stages 5, 7, 9, 11, 14 and 15 look at no token: png_stage_* (kernels.h, at the end of this file) launch them for overlay_kernels.hip's
+// truecolour encoder too, whose symbols are filtered bytes, for stream 0 of each slot.  The helpers both sources use: png_device.h.
 #include "common.h"
 #include "kernels.h"
+#include "png_device.h"
 
 namespace {
 
-constexpr int PNG_MAPS = 8;                      // maps per pass: bounds the scratch (8 bytes per token slot per map)
-constexpr int PNG_CHUNK = 1024;                  // tokens per chunk (= threads of the chunk kernels)
-constexpr int PNG_BLOCK_SHIFT = 20;              // parse tokens per deflate block: 2^20, as the host encoder
-constexpr int PNG_CHUNKS_PER_BLOCK = 1 << (PNG_BLOCK_SHIFT - 10);
-constexpr int PNG_NSYM = 316;                    // 286 literal / length + 30 distance symbols
-constexpr int PNG_HDR_WORDS = 160;               // <= 3 + 14 + 19 * 3 + 316 * 14 = 4498 bits of block header
 constexpr int PNG_TOKEN_BITS = 144;              // most bits of one token: 3 colour matches of (15 + 5) + (15 + 13) bits
 constexpr int PNG_PACK_WORDS = (PNG_CHUNK * PNG_TOKEN_BITS + 31) / 32 + 2;
-constexpr int PNG_CRC_PIECE = 256;               // IDAT bytes per thread of the CRC kernel
-constexpr uint32_t PNG_ADLER_MOD = 65521u;
-
-// per-map values in the meta block (uint64 each)
-enum { MT_NTOK, MT_NBLK, MT_NCHUNK, MT_BITS0, MT_BITS1, MT_OFF0, MT_OFF1, MT_LEN0, MT_LEN1, MT_CRC0, MT_CRC1, MT_N = 16 };
+// the constants of the scratch layout, the meta block and the helpers both device encoders use: png_device.h
 
 // token (uint32): 0 = the row's filter byte; 0x40000000 | label = a literal pixel;
 // 0x80000000 | up << 29 | v1 << 17 | v0 << 9 | npx = a run of npx (1 .. 258) pixels equal to the row above (up) or to the left
@@ -74,8 +67,6 @@ struct Layout {                                   // scratch of one pass, carved
     size_t T, C, B;                               // worst-case tokens, chunks, deflate blocks per map
 };
 
-__host__ __device__ inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // base == nullptr: only *bytes is computed.  Every piece starts 256-byte aligned.
 Layout carve(void* base, int nm, int h, int w, size_t* bytes) {
     Layout L;
@@ -100,27 +91,6 @@ Layout carve(void* base, int nm, int h, int w, size_t* bytes) {
     L.adler = reinterpret_cast<uint32_t*>(take((size_t)nm * 2 * h * 8));
     if (bytes) *bytes = used;
     return L;
-}
-
-__device__ __forceinline__ uint32_t block_scan_excl(uint32_t v, uint32_t* sm /*[17]*/, uint32_t* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
-    __syncthreads();
-    if (lane == 63) sm[wave] = inc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t run = 0;
-        for (int i = 0; i < nw; ++i) { const uint32_t t = sm[i]; sm[i] = run; run += t; }
-        sm[16] = run;
-    }
-    __syncthreads();
-    *total = sm[16];
-    return sm[wave] + inc - v;
 }
 
 // ---- 1. parse ----------------------------------------------------------------------------------------------------------------
@@ -539,9 +509,6 @@ __global__ __launch_bounds__(1024) void png_scan_chunks_kernel(const uint32_t* _
 }
 
 // ---- 8. placement ------------------------------------------------------------------------------------------------------------
-// file = signature 8 + IHDR 25 + IDAT (12 + 2 + deflate bytes + 4) + IEND 12
-__device__ __forceinline__ long long png_file_len(unsigned long long bits) { return 63 + (long long)((bits + 7) >> 3); }
-
 __global__ void png_place_kernel(unsigned long long* __restrict__ meta, int nm, long long out_cap, long long* __restrict__ cursor,
                                  long long* __restrict__ table) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -686,42 +653,6 @@ __global__ __launch_bounds__(64) void png_adler_rows_kernel(const uint8_t* __res
     }
 }
 
-// ---- CRC-32 helpers (reflected polynomial 0xedb88320; multmodp / x2nmodp as zlib's crc32.c) ------------------------------------
-__device__ __forceinline__ uint32_t crc_mult(uint32_t a, uint32_t b) {     // a * b mod P; a != 0
-    uint32_t m = 1u << 31, p = 0;
-    for (;;) {
-        if (a & m) {
-            p ^= b;
-            if ((a & (m - 1)) == 0) break;
-        }
-        m >>= 1;
-        b = b & 1 ? (b >> 1) ^ 0xedb88320u : b >> 1;
-    }
-    return p;
-}
-__device__ uint32_t crc_x8n(unsigned long long n) {               // x^(8 n) mod P
-    uint32_t p = 1u << 31, x2k = 1u << 30;                        // x^0; x^(2^k) for k = 0
-    for (int k = 0; k < 3; ++k) x2k = crc_mult(x2k, x2k);         // x^8
-    while (n) {
-        if (n & 1) p = crc_mult(x2k, p);
-        n >>= 1;
-        x2k = crc_mult(x2k, x2k);
-    }
-    return p;
-}
-__device__ uint32_t crc_bytes_slow(uint32_t c, const unsigned char* p, int n) {   // standard CRC-32 update, bitwise
-    c = ~c;
-    for (int i = 0; i < n; ++i) {
-        c ^= p[i];
-        for (int k = 0; k < 8; ++k) c = c & 1 ? (c >> 1) ^ 0xedb88320u : c >> 1;
-    }
-    return ~c;
-}
-
-__device__ __forceinline__ void put_be32(unsigned char* p, uint32_t v) {
-    p[0] = (unsigned char)(v >> 24); p[1] = (unsigned char)(v >> 16); p[2] = (unsigned char)(v >> 8); p[3] = (unsigned char)v;
-}
-
 // ---- 13. Adler-32 + framing --------------------------------------------------------------------------------------------------
 // grid (2, nm), 64 threads
 __global__ __launch_bounds__(64) void png_frame_kernel(const unsigned long long* __restrict__ meta, const uint32_t* __restrict__ adler,
@@ -837,12 +768,30 @@ size_t png_worst_file_bytes(int h, int w) {
     return 63 + (bits + 7) / 8;
 }
 
+// ---- the stages that do not look at tokens, for `streams` streams of each of nm files' slots (kernels.h) -----------------------
+void png_stage_tables(const PngStageBuffers& L, int nm, int streams, hipStream_t st) {
+    png_tables_kernel<<<dim3((unsigned)L.B, streams, nm), 64, 0, st>>>(L.hist, L.meta, L.tables, L.hdr, L.hdrbits, L.B);
+}
+void png_stage_offsets(const PngStageBuffers& L, int nm, int streams, hipStream_t st) {
+    png_scan_chunks_kernel<<<dim3(streams, nm), 1024, 0, st>>>(L.chunkbits, L.tables, L.hdrbits, L.meta, L.chunkoff, L.gapoff, L.B, L.C);
+}
+void png_stage_zero(const PngStageBuffers& L, unsigned char* out, int nm, int streams, hipStream_t st) {
+    png_zero_kernel<<<dim3(256, streams, nm), 256, 0, st>>>(L.meta, out);
+}
+void png_stage_headers(const PngStageBuffers& L, unsigned char* out, int nm, int streams, hipStream_t st) {
+    png_headers_kernel<<<dim3((unsigned)L.B + 1, streams, nm), 64, 0, st>>>(L.meta, L.tables, L.hdr, L.hdrbits, L.gapoff, out, L.B);
+}
+void png_stage_crc(const PngStageBuffers& L, unsigned char* out, int nm, int streams, size_t worst_file_bytes, hipStream_t st) {
+    const unsigned crc_blocks = (unsigned)((worst_file_bytes + 256ull * PNG_CRC_PIECE - 1) / (256ull * PNG_CRC_PIECE));
+    png_crc_kernel<<<dim3(crc_blocks, streams, nm), 256, 0, st>>>(L.meta, out);
+    png_crc_finish_kernel<<<1, 64, 0, st>>>(L.meta, out, nm);
+}
+
 hipError_t launch_png_encode(const uint8_t* maps, int n, int h, int w, const uint8_t* lut, void* scratch, unsigned char* out,
                              long long out_cap, long long* cursor, long long* table, hipStream_t st) {
     if (n < 1 || h < 1 || w < 1 || h > 65536 || w > 65536 || ((size_t)3 * w + 1) * h > 0x7fffffffull) return hipErrorInvalidValue;
     const int up_ok = (size_t)w * 3 + 1 <= 32768 ? 1 : 0;
     const size_t worst = png_worst_file_bytes(h, w);
-    const unsigned crc_blocks = (unsigned)((worst + 256ull * PNG_CRC_PIECE - 1) / (256ull * PNG_CRC_PIECE));
     for (int p0 = 0; p0 < n; p0 += PNG_MAPS) {
         const int nm = n - p0 < PNG_MAPS ? n - p0 : PNG_MAPS;
         const Layout L = carve(scratch, nm, h, w, nullptr);
@@ -851,23 +800,23 @@ hipError_t launch_png_encode(const uint8_t* maps, int n, int h, int w, const uin
         hipError_t err;
         if ((err = hipMemsetAsync(L.meta, 0, (size_t)nm * MT_N * 8, st)) != hipSuccess) return err;
         if ((err = hipMemsetAsync(L.hist, 0, (size_t)nm * L.B * 2 * PNG_NSYM * 4, st)) != hipSuccess) return err;
-        const unsigned C = (unsigned)L.C, B = (unsigned)L.B;
+        const unsigned C = (unsigned)L.C;
+        const PngStageBuffers S{L.meta, L.hist, L.tables, L.hdr, L.hdrbits, L.chunkbits, L.chunkoff, L.gapoff, L.B, L.C};
         png_parse_kernel<<<dim3((h + 63) / 64, nm), 64, 0, st>>>(mp, L.slot, L.rowcnt, h, w, up_ok, L.T);
         png_scan_rows_kernel<<<nm, 1024, 0, st>>>(L.rowcnt, L.rowoff, L.meta, h);
         png_compact_kernel<<<dim3(h, nm), 256, 0, st>>>(L.slot, L.rowcnt, L.rowoff, L.tok, h, w, L.T);
         png_hist_kernel<<<dim3(C, nm), PNG_CHUNK, 0, st>>>(L.tok, L.meta, lut, L.hist, w, up_ok, L.T, L.B);
-        png_tables_kernel<<<dim3(B, 2, nm), 64, 0, st>>>(L.hist, L.meta, L.tables, L.hdr, L.hdrbits, L.B);
+        png_stage_tables(S, nm, 2, st);
         png_tokbits_kernel<<<dim3(C, nm), PNG_CHUNK, 0, st>>>(L.tok, L.meta, lut, L.tables, L.chunkbits, w, up_ok, L.T, L.B, L.C);
-        png_scan_chunks_kernel<<<dim3(2, nm), 1024, 0, st>>>(L.chunkbits, L.tables, L.hdrbits, L.meta, L.chunkoff, L.gapoff, L.B, L.C);
+        png_stage_offsets(S, nm, 2, st);
         png_place_kernel<<<1, 64, 0, st>>>(L.meta, nm, out_cap, cursor, tb);
-        png_zero_kernel<<<dim3(256, 2, nm), 256, 0, st>>>(L.meta, out);
+        png_stage_zero(S, out, nm, 2, st);
         png_pack_kernel<<<dim3(C, 2, nm), PNG_CHUNK, 0, st>>>(L.tok, L.meta, lut, L.tables, L.chunkoff, L.chunkbits, out, w, up_ok,
                                                               L.T, L.B, L.C);
-        png_headers_kernel<<<dim3(B + 1, 2, nm), 64, 0, st>>>(L.meta, L.tables, L.hdr, L.hdrbits, L.gapoff, out, L.B);
+        png_stage_headers(S, out, nm, 2, st);
         png_adler_rows_kernel<<<dim3(h, 2, nm), 64, 0, st>>>(mp, lut, L.meta, L.adler, h, w);
         png_frame_kernel<<<dim3(2, nm), 64, 0, st>>>(L.meta, L.adler, out, h, w);
-        png_crc_kernel<<<dim3(crc_blocks, 2, nm), 256, 0, st>>>(L.meta, out);
-        png_crc_finish_kernel<<<1, 64, 0, st>>>(L.meta, out, nm);
+        png_stage_crc(S, out, nm, 2, worst, st);
         if ((err = hipGetLastError()) != hipSuccess) return err;
     }
     return hipSuccess;

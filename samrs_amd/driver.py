@@ -323,6 +323,8 @@ class TileResult:
     gt_rle_data: Optional[np.ndarray] = None
     png_table: Optional[np.ndarray] = None  # int64 [2, 2] (offset, length) of the gray and the colour PNG in png_data (png_lut)
     png_data: Optional[np.ndarray] = None   # uint8 view of the batch's pinned PNG byte buffer
+    vis_table: Optional[np.ndarray] = None  # int64 [2] (offset, length) of the overlay PNG in vis_data (vis_lut)
+    vis_data: Optional[np.ndarray] = None   # uint8 view of the batch's pinned overlay byte buffer
     changed: Optional[np.ndarray] = None    # int64 [n_boxes] pixels the small-region clean-up changed (min_region_area > 0)
     removed: Optional[np.ndarray] = None    # int64 [n_boxes] pixels the overlap stage took from the instance (overlap != "order")
     # mask_boxes=True (samrs_mask_boxes, in the image's own frame; an empty mask has mask_record[j, 6] == 0 and zeros everywhere):
@@ -357,7 +359,14 @@ class TileResult:
 
     def png(self, kind: str) -> memoryview:
         """The bytes of ``gray/<stem>.png`` (kind "gray") or ``color/<stem>.png`` ("color") of this tile, encoded on the device
-        (samrs_png_encode_labels) and byte-identical with tile_io.write_label_pair; only when the pipeline ran with png_lut."""
+        (samrs_png_encode_labels) and byte-identical with tile_io.write_label_pair; only when the pipeline ran with png_lut.
+        Kind "vis": the bytes of ``vis/<stem>.png``, visualize.py's blend of the image with this class map through the pipeline's
+        vis_lut (samrs_blend_labels, samrs_png_encode_rgb); only when the pipeline ran with vis_lut."""
+        if kind == "vis":
+            if self.vis_table is None:
+                raise ValueError("no overlay PNG file: the pipeline ran without vis_lut")
+            off, n = (int(v) for v in self.vis_table)
+            return memoryview(self.vis_data[off:off + n])
         if self.png_table is None:
             raise ValueError("no device PNG files: the pipeline ran without png_lut")
         off, n = (int(v) for v in self.png_table[{"gray": 0, "color": 1}[kind]])
@@ -565,6 +574,28 @@ def refuse_quality_options(who: str, why: str, **opts) -> None:
                          f"{'is a' if len(given) == 1 else 'are'} TilePipeline option{'' if len(given) == 1 else 's'}")
 
 
+def refuse_vis_option(who: str, why: str, **opts) -> None:
+    """ValueError naming TilePipeline's `vis_lut` option when `who` (a pipeline that writes no overlays) was handed one."""
+    if opts.get("vis_lut") is not None:
+        raise ValueError(f"{who} writes no overlays ({why}): vis_lut is a TilePipeline option")
+
+
+def validate_vis_options(vis_lut, vis_alpha: float = 0.4, vis_buffer_mb: Optional[int] = None):
+    """TilePipeline's overlay options -> (vis_lut as contiguous uint8 [256, 3], alpha), or (None, alpha) without vis_lut.
+    Touches no device."""
+    if vis_lut is None:
+        return None, float(vis_alpha)
+    lut = np.ascontiguousarray(vis_lut, dtype=np.uint8)
+    if lut.shape != (256, 3):
+        raise ValueError("vis_lut must be uint8 [256, 3] (tile_io.class_lut)")
+    alpha = float(vis_alpha)
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"vis_alpha must lie in [0, 1], got {vis_alpha!r}")
+    if vis_buffer_mb is not None and int(vis_buffer_mb) < 1:
+        raise ValueError("vis_buffer_mb must be >= 1")
+    return lut, alpha
+
+
 def refuse_overlap_option(who: str, why: str, **opts) -> None:
     """ValueError naming TilePipeline's `overlap` option when `who` (a pipeline that does not resolve overlapping masks) was handed
     anything but "order"."""
@@ -619,7 +650,16 @@ class TilePipeline:
     With `png_lut` (uint8 [256, 3], ``tile_io.class_lut(palette)``) the class maps are also encoded on the device into the
     complete ``gray/<stem>.png`` and ``color/<stem>.png`` files (`samrs_png_encode_labels`, byte-identical with
     ``tile_io.write_label_pair``): ``TileResult.png(kind)``.  `png_buffer_mb` is the device buffer for one batch's files
-    (default: 6 MiB per tile, which holds a batch of all-literal 1024^2 tiles -- at most 9 bits per byte, 4.5 MiB per pair)."""
+    (default: 6 MiB per tile, which holds a batch of all-literal 1024^2 tiles -- at most 9 bits per byte, 4.5 MiB per pair).
+
+    With `vis_lut` (uint8 [256, 3]) every tile also yields visualize.py's overlay, ``Image.blend(image, vis_lut[seg_mask],
+    vis_alpha)`` bit for bit, as a complete truecolour PNG file: ``TileResult.png("vis")``.  The blend (`samrs_blend_labels`) runs
+    on the decode stream after painting, at the image's own size and from its original pixels (an odd-sized tile blends the
+    uploaded original, not the resized tile), and `samrs_png_encode_rgb` packs the files into a buffer of their own.
+    `vis_buffer_mb` is that buffer for one batch (default: the encoder's documented worst case for a batch of side x side tiles,
+    ``engine.png_rgb_bound``); a batch that overflows it raises, naming the option.  Input set b is then read after the encoder,
+    so it is handed back to staging only once the batch's blends are enqueued.  None (default) launches and allocates nothing,
+    and event order, allocations and results are what they were."""
 
     BOX_WIDTH = 4          # floats per annotation: xyxy
 
@@ -629,7 +669,8 @@ class TilePipeline:
                  png_buffer_mb: Optional[int] = None, batch_decode="auto", min_region_area: int = 0,
                  region_mode: str = "both", mask_boxes: bool = False, quality: bool = False, min_stability: float = 0.0,
                  min_pred_iou: float = 0.0, min_inside_box: float = 0.0, polygons: bool = False, polygon_buffer_mb: int = 64,
-                 polygon_max_edges: int = 65536, overlap: str = "order"):
+                 polygon_max_edges: int = 65536, overlap: str = "order", vis_lut: Optional[np.ndarray] = None, vis_alpha: float = 0.4,
+                 vis_buffer_mb: Optional[int] = None):
         """precision: the operand-split mode (engine option "split") THIS PIPELINE'S OWN CALLS run in.  The option is set around
         each of the pipeline's encode / decode calls and restored afterwards (``Engine.options``), so the mode never outlives
         them: a ``SamPredictor`` built on the same model keeps the engine's own default (round 3 changed the engine's option for
@@ -686,6 +727,8 @@ class TilePipeline:
         from .transforms import ResizeLongestSide
         lut, poly_vertices = validate_output_options(min_region_area, region_mode, polygons, polygon_buffer_mb, polygon_max_edges, png_lut,
                                                      overlap)
+        vlut, self.vis_alpha = validate_vis_options(vis_lut, vis_alpha, vis_buffer_mb)
+        self.vis = vlut is not None
         self.overlap = overlap
         self.min_region_area, self.region_mode = int(min_region_area), region_mode
         self.thresholds = (float(min_stability), float(min_pred_iou), float(min_inside_box))
@@ -743,7 +786,7 @@ class TilePipeline:
             setattr(self, t.dev, [t.alloc(batch, max_boxes, dev) for _ in range(2)])
         # the packed outputs, per input set: the payload (16-byte aligned entries) here, cursor and table in the stream
         self.streams: List[PackedStream] = []
-        if rle or self.png or polygons:
+        if rle or self.png or polygons or self.vis:
             self.s_d2h = torch.cuda.Stream(dev)
         nbm = batch * max_boxes
         if rle:      # the batch's RLE strings; (offset, length, n_counts) per box
@@ -764,6 +807,17 @@ class TilePipeline:
                                         lambda tab, used: check_packed(tab, used[0], "batch", self.png_dev[0].numel() >> 20,
                                                                        what="PNG buffer too small: a file", knob="png_buffer_mb"))
             self.streams.append(self.png_out)
+        if self.vis:   # the LUT once; one batch's blended pixels (used on s_dec alone); the batch's overlay files; (offset, length) per tile
+            from .engine import png_rgb_bound
+            self.vis_lut = torch.from_numpy(vlut).to(dev)
+            self.vis_buffer_mb = int(vis_buffer_mb) if vis_buffer_mb else (batch * png_rgb_bound(side, side) >> 20) + 1
+            self.vis_rgb = torch.empty(batch, side, side, 3, dtype=torch.uint8, device=dev)
+            self.vis_dev = [torch.empty(self.vis_buffer_mb << 20, dtype=torch.uint8, device=dev) for _ in range(2)]
+            self.vis_src: List[list] = [[], []]         # per input set: each tile's original pixels on the device
+            self.vis_out = PackedStream(self, "vis", batch, (2,), [("vis_dev", (), torch.uint8, 1 << 20)],
+                                        lambda tab, used: check_packed(tab, used[0], "batch", self.vis_dev[0].numel() >> 20,
+                                                                       what="overlay buffer too small: a file", knob="vis_buffer_mb"))
+            self.streams.append(self.vis_out)
         if self.polygons:   # the batch's vertices and ring records; the cursor counts both; five table columns per box
             self.polygon_buffer_mb, self.polygon_max_edges = int(polygon_buffer_mb), int(polygon_max_edges)
             self.poly_vert_dev = [torch.empty(poly_vertices, 2, dtype=torch.int32, device=dev) for _ in range(2)]
@@ -825,6 +879,8 @@ class TilePipeline:
     # -- stage A: stage tiles + boxes of one batch, H2D on s_h2d ------------------------------------------------
     def _stage(self, b: int, items: List[WorkItem]):
         tiles = []         # per image: (device tensor uint8 [h, w, 3] with long side == img_size, original (H, W))
+        if self.vis:
+            self.vis_src[b] = []
         same = True
         n_off = 0
         offs = []
@@ -866,6 +922,11 @@ class TilePipeline:
                 else:
                     src = img if isinstance(img, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(img))
                     t = src.to(self.dev)                                          # odd sizes: plain upload, then
+                if self.vis:                                                      # the blend reads the image's own pixels on s_dec
+                    orig = t.contiguous()
+                    if not native:
+                        orig.record_stream(self.s_dec)
+                    self.vis_src[b].append(orig)
                 if not native:
                     t = self.transform.apply_image_device(t.contiguous())         # PIL-exact resize on the GPU
                     t.record_stream(self.s_enc)                                   # allocated on s_h2d, read by the encoder
@@ -885,7 +946,8 @@ class TilePipeline:
                 else:
                     self.eng.set_images_ragged([t for t, _ in tiles], b * self.batch)
             self.ev_enc[b].record(self.s_enc)
-            self.ev_in_free[b].record(self.s_enc)
+            if not self.vis:                                       # with vis_lut the blend reads input set b after the encoder: _decode
+                self.ev_in_free[b].record(self.s_enc)
 
     multimask = False      # InstancePipeline sets these four
     gt = False
@@ -949,6 +1011,9 @@ class TilePipeline:
                 kept.append(masks[:, 0].view(torch.uint8))
         if self.png and not native:                                              # an odd-sized tile: its own call
             eng.png_encode(seg, self.png_lut, self.png_dev[b], self.png_out.cur[b], self.png_out.tab[b][i:i + 1])
+        if self.vis and not native:                                              # the same for its overlay, from the uploaded original
+            over = eng.blend_labels(self.vis_src[b][i], seg, self.vis_lut, self.vis_alpha)
+            eng.png_encode_rgb(over, self.vis_dev[b], self.vis_out.cur[b], self.vis_out.tab[b][i:i + 1])
         if native:
             out.seg[i].copy_(seg, non_blocking=True)
         else:
@@ -988,6 +1053,8 @@ class TilePipeline:
                     self._decode_tile(b, i, t, hw, off, nb, out, None if pre is None else pre[i])
             if self.png:
                 self._encode_png(b, tiles)
+            if self.vis:
+                self._encode_vis(b, tiles)
             for t in self.tables:
                 out.tables[t.field].copy_(getattr(self, t.dev)[b], non_blocking=True)
             for st in self.streams:
@@ -995,9 +1062,8 @@ class TilePipeline:
             self.ev_dec[b].record(self.s_dec)
             out.done.record(self.s_dec)
 
-    def _encode_png(self, b: int, tiles) -> None:
-        """gray + colour PNG of the batch's native tiles: one samrs_png_encode_labels call per run of consecutive native tiles
-        (one call for a batch of native tiles), on s_dec after painting.  Odd-sized tiles were encoded in _decode_tile."""
+    def _native_runs(self, tiles) -> List[Tuple[int, int]]:
+        """[i0, i1) of every run of consecutive native (side x side) tiles of a batch."""
         native = [i for i, (_, hw) in enumerate(tiles) if tuple(hw) == (self.side, self.side)]
         runs: List[List[int]] = []
         for i in native:
@@ -1005,8 +1071,23 @@ class TilePipeline:
                 runs[-1].append(i)
             else:
                 runs.append([i])
-        for r in runs:
-            i0, i1 = r[0], r[-1] + 1
+        return [(r[0], r[-1] + 1) for r in runs]
+
+    def _encode_vis(self, b: int, tiles) -> None:
+        """The overlays of the batch's native tiles, on s_dec after painting: per run of consecutive native tiles one blend of input
+        set b's pixels with the painted class maps and one samrs_png_encode_rgb call.  Odd-sized tiles were done in _decode_tile.
+        Every blend of the batch is enqueued once this returns: input set b goes back to staging."""
+        runs = self._native_runs(tiles)
+        for i0, i1 in runs:
+            self.eng.blend_labels(self.dev_in[b][i0:i1], self.seg_dev[b][i0:i1], self.vis_lut, self.vis_alpha, out=self.vis_rgb[i0:i1])
+        self.ev_in_free[b].record(self.s_dec)
+        for i0, i1 in runs:
+            self.eng.png_encode_rgb(self.vis_rgb[i0:i1], self.vis_dev[b], self.vis_out.cur[b], self.vis_out.tab[b][i0:i1])
+
+    def _encode_png(self, b: int, tiles) -> None:
+        """gray + colour PNG of the batch's native tiles: one samrs_png_encode_labels call per run of consecutive native tiles
+        (one call for a batch of native tiles), on s_dec after painting.  Odd-sized tiles were encoded in _decode_tile."""
+        for i0, i1 in self._native_runs(tiles):
             self.eng.png_encode(self.seg_dev[b][i0:i1], self.png_lut, self.png_dev[b], self.png_out.cur[b], self.png_out.tab[b][i0:i1])
 
     def _finish(self, pending, sink):
@@ -1022,6 +1103,8 @@ class TilePipeline:
         if self.png:                                        # two table rows per tile: its gray and its colour file
             ptab, (pdat,), _ = self.png_out.fetch(b, out, 2 * len(items))
             ptab = ptab.reshape(-1, 2, 2)
+        if self.vis:
+            vtab, (vdat,), _ = self.vis_out.fetch(b, out, len(items))
         if self.polygons:
             gtab, (gvert, gring), (nv, nr) = self.poly_out.fetch(b, out, n_boxes)
             gtab, gvert, gring = gtab.copy(), gvert[:nv].numpy(), gring[:nr].numpy()
@@ -1041,6 +1124,8 @@ class TilePipeline:
                     r.gt_rle_table, r.gt_rle_data = ttab[off:off + nb], tdat.numpy()
             if self.png:
                 r.png_table, r.png_data = ptab[i], pdat.numpy()
+            if self.vis:
+                r.vis_table, r.vis_data = vtab[i], vdat.numpy()
             if self.polygons:
                 r.polygon_table, r.polygon_rings, r.polygon_vertices = gtab[off:off + nb], gring, gvert
             res.append(r)
@@ -1142,6 +1227,7 @@ class InstancePipeline(TilePipeline):
         self.ap = bool(ap)             # read by TilePipeline.__init__ (output_tables)
         refuse_quality_options("InstancePipeline", "scoring the best-of-3 path is not built", **kw)
         refuse_overlap_option("InstancePipeline", "resolving the best-of-3 masks is not built", **kw)
+        refuse_vis_option("InstancePipeline", "it paints no class map to blend", **kw)
         if prompt == "point":
             self.BOX_WIDTH = 2
         from . import transforms

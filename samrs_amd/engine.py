@@ -141,6 +141,10 @@ def load_library() -> C.CDLL:
                  "samrs_mask_pair_counts", "samrs_coco_match"):
         getattr(lib, name).restype = ip
     lib.samrs_png_encode_labels.argtypes = [vp, vp, ip, ip, ip, vp, vp, C.c_int64, vp, vp, vp]
+    lib.samrs_blend_labels.argtypes = [vp, vp, vp, vp, fp, vp, ip, ip, ip, vp]
+    lib.samrs_png_encode_rgb.argtypes = [vp, vp, ip, ip, ip, ip, vp, C.c_int64, vp, vp, vp]
+    for name in ("samrs_blend_labels", "samrs_png_encode_rgb"):
+        getattr(lib, name).restype = ip
     lib.samrs_k_upscaler_fused.argtypes = [ip, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, vp]
     lib.samrs_k_convert.argtypes = [ip, vp, vp, C.c_int64, vp]
     lib.samrs_k_layernorm.argtypes = [ip, vp, vp, vp, fp, vp, vp, ip, ip, ip, ip, ip, ip, vp]
@@ -210,6 +214,17 @@ def load_library() -> C.CDLL:
         raise ImportError("libsamrs_hip.so ABI version mismatch; rebuild it")
     _lib = lib
     return lib
+
+
+PNG_RGB_BLOCK_BYTES = 1 << 20      # filtered bytes per deflate block of samrs_png_encode_rgb (SAMRS_PNG_RGB_BLOCK_BYTES in samrs_hip.h)
+
+
+def png_rgb_bound(h: int, w: int) -> int:
+    """The worst-case size samrs_hip.h documents for one file of samrs_png_encode_rgb, rounded up to the 16 bytes files are
+    aligned to: 9 bits per filtered byte, 4498 + 9 bits per deflate block, 63 bytes of framing."""
+    n = (3 * int(w) + 1) * int(h)
+    blocks = -(-n // PNG_RGB_BLOCK_BYTES)
+    return (63 + -(-(9 * n + blocks * (4498 + 9)) // 8) + 15) & ~15
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
@@ -623,6 +638,41 @@ class Engine:
         with torch.cuda.device(self.device):
             self._check(self.lib.samrs_png_encode_labels(self.handle, m.data_ptr(), n, h, w, lut.data_ptr(), out.data_ptr(),
                                                          out.numel(), cursor.data_ptr(), table.data_ptr(), _stream()))
+
+    def blend_labels(self, images: torch.Tensor, maps: torch.Tensor, lut: torch.Tensor, alpha: float = 0.4,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """visualize.py's overlay: ``Image.blend(image, lut[map], alpha)`` bit for bit, for `images` ([n, H, W, 3] or [H, W, 3] uint8 on
+        this device) and their class maps `maps` ([n, H, W] or [H, W] uint8) through `lut` (uint8 [256, 3], device) -> uint8 of the
+        images' shape (`out`, contiguous and not the images themselves, or a new tensor).  0 <= alpha <= 1.  Asynchronous on the
+        current stream; see samrs_blend_labels in samrs_hip.h."""
+        img = images.reshape(-1, *images.shape[-3:]).contiguous()
+        m = maps.reshape(-1, *maps.shape[-2:]).contiguous()
+        n, h, w, _ = img.shape
+        assert img.dtype == torch.uint8 and img.is_cuda and img.shape[-1] == 3
+        assert m.dtype == torch.uint8 and m.is_cuda and tuple(m.shape) == (n, h, w)
+        assert lut.dtype == torch.uint8 and lut.is_cuda and lut.is_contiguous() and lut.numel() == 768
+        res = out if out is not None else torch.empty_like(img)
+        assert res.dtype == torch.uint8 and res.is_cuda and res.is_contiguous() and res.numel() == img.numel()
+        with torch.cuda.device(self.device):
+            self._check(self.lib.samrs_blend_labels(self.handle, img.data_ptr(), m.data_ptr(), lut.data_ptr(), float(alpha),
+                                                    res.data_ptr(), n, h, w, _stream()))
+        return res if out is not None else res.view(images.shape)
+
+    def png_encode_rgb(self, rgb: torch.Tensor, out: torch.Tensor, cursor: torch.Tensor, table: torch.Tensor, filter: int = -1) -> None:
+        """Truecolour PNG files of `rgb` ([n, H, W, 3] or [H, W, 3] uint8 on this device), appended to the byte buffer `out` (uint8,
+        device, 16-byte aligned) behind `cursor` (int64 [1], device, in / out); `table` (int64 [n, 2], device) receives (offset,
+        length) per image, length < 0: did not fit (-length - 1 bytes needed).  `filter`: 0 .. 4 = that PNG row filter on every row,
+        -1 = per row the least sum of absolute filtered values.  ``png_rgb_bound(H, W)`` bytes per image always suffice for data
+        whose codes stay under deflate's length limit.  Asynchronous on the current stream; see samrs_png_encode_rgb in samrs_hip.h."""
+        x = rgb.reshape(-1, *rgb.shape[-3:]).contiguous()
+        n, h, w, _ = x.shape
+        assert x.dtype == torch.uint8 and x.is_cuda and x.shape[-1] == 3
+        assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and out.data_ptr() % 16 == 0
+        assert cursor.dtype == torch.int64 and cursor.is_cuda and table.dtype == torch.int64 and table.is_cuda
+        assert table.is_contiguous() and table.numel() >= 2 * n
+        with torch.cuda.device(self.device):
+            self._check(self.lib.samrs_png_encode_rgb(self.handle, x.data_ptr(), n, h, w, int(filter), out.data_ptr(), out.numel(),
+                                                      cursor.data_ptr(), table.data_ptr(), _stream()))
 
     def select_best(self, masks: torch.Tensor, iou: torch.Tensor, best_out: Optional[torch.Tensor] = None,
                     quality_out: Optional[torch.Tensor] = None, areas_out: Optional[torch.Tensor] = None):

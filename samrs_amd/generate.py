@@ -61,7 +61,7 @@ def write_outputs(out_dir: str, stem: str, seg: np.ndarray, masks: Optional[np.n
                   rles: Optional[Sequence[dict]] = None, clock: Optional[StageClock] = None, png_level: int = tile_io.LEVEL_LABELS,
                   png_files: Optional[Tuple[bytes, bytes]] = None, mask_bboxes: Optional[Sequence] = None,
                   mask_rboxes: Optional[Sequence] = None, dota_txt: bool = False, scores: Optional[dict] = None,
-                  polygons: Optional[Sequence] = None, removed: Optional[Sequence[int]] = None) -> None:
+                  polygons: Optional[Sequence] = None, removed: Optional[Sequence[int]] = None, vis_file: Optional[bytes] = None) -> None:
     """`rles`: the per-instance COCO RLE dicts when they were encoded on the device (driver.TileResult.rle); otherwise they are
     encoded here from `masks` (host restatement), or left out when both are None (--no-rle).  `png_files`: the complete
     (gray, color) PNG files when they were encoded on the device (--png-device: driver.TileResult.png, byte-identical with the
@@ -75,7 +75,8 @@ def write_outputs(out_dir: str, stem: str, seg: np.ndarray, masks: Optional[np.n
     (int32 [k, 2] lattice vertices, is_hole) pairs (driver.TileResult.polygons), or None for a mask over the edge cap; they become
     the pickle entries' ``"polygons"`` (the list of vertex arrays, or None) and ``"polygon_holes"`` (the list of bool, or None).
     `removed` (--overlap logit / smallest): per instance the pixels the overlap stage gave to another instance; the entries' ``"removed"``
-    (`areas` and `rles` are then those of the disjoint masks already)."""
+    (`areas` and `rles` are then those of the disjoint masks already).  `vis_file` (--vis): the complete ``vis/<stem>.png``, the
+    overlay blended and encoded on the device (driver.TileResult.png("vis")); written as it is, before the pickle."""
     import time
     t0 = time.perf_counter()
     for sub in ("gray", "color", "ins"):
@@ -100,6 +101,10 @@ def write_outputs(out_dir: str, stem: str, seg: np.ndarray, masks: Optional[np.n
         if clock: t0 = clock.add("write.gray_png", t0)
         tile_io.write_lut_rgb(os.path.join(out_dir, "color", stem + ".png"), seg, tile_io.class_lut(palette), png_level)   # :213,215
         if clock: t0 = clock.add("write.color_png", t0)
+    if vis_file is not None:                                                                # visualize.py:56-57, as PNG
+        os.makedirs(os.path.join(out_dir, "vis"), exist_ok=True)
+        _write_atomic(os.path.join(out_dir, "vis", stem + ".png"), vis_file)
+        if clock: t0 = clock.add("write.vis_png", t0)
     info = []
     for j in range(len(labels)):                                                            # :200-206
         if scores is not None and not scores["kept"][j]:
@@ -217,9 +222,25 @@ def host_bound_warning(readers: int, writers: int, gpu_images_per_s: float = 140
     return "; ".join(msgs) if msgs else None
 
 
-def outputs_exist(out_dir: str, stem: str) -> bool:
-    """All three files of an image are on disk (main_sam_hbox_semantic.py:214-216 writes gray, color, then ins)."""
-    return all(os.path.exists(os.path.join(out_dir, sub, stem + ext)) for sub, ext in (("gray", ".png"), ("color", ".png"), ("ins", ".pkl")))
+def outputs_exist(out_dir: str, stem: str, vis: bool = False) -> bool:
+    """All three files of an image are on disk (main_sam_hbox_semantic.py:214-216 writes gray, color, then ins); with `vis`
+    (--vis) its vis/<stem>.png too."""
+    subs = (("gray", ".png"), ("color", ".png"), ("ins", ".pkl")) + ((("vis", ".png"),) if vis else ())
+    return all(os.path.exists(os.path.join(out_dir, sub, stem + ext)) for sub, ext in subs)
+
+
+def vis_options(args, palette: np.ndarray):
+    """(overlay LUT uint8 [256, 3] or None, alpha) of --vis / --vis-alpha / --vis-palette; the colours default to the run's palette
+    and class 255 is white (visualize.py's MAPPING_VISUALIZE[255]).  ValueError for what does not fit together."""
+    alpha = float(getattr(args, "vis_alpha", 0.4))
+    if not getattr(args, "vis", False):
+        return None, alpha
+    if int(getattr(args, "scene_window", 0) or 0) > 0:
+        raise ValueError("--vis does not apply with --scene-window: the scene's composite lives in another buffer; scene overlays are not built")
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"--vis-alpha must lie in [0, 1], got {alpha}")
+    vp = getattr(args, "vis_palette", None)
+    return tile_io.class_lut(np.load(vp) if vp else palette), alpha
 
 
 _RUN_SEQ = [0]          # run() calls of this process (part of the work queue's store key)
@@ -306,7 +327,7 @@ def run(args) -> Dict[str, List[int]]:
         # restart = re-run what is missing.  The output directory is listed ONCE, on rank 0, and the result is
         # broadcast: a rank that finished loading its weights earlier may already be writing files while a slower one would
         # still be listing, and ranks indexing different todo lists skip or repeat images (round-3 advisor finding).
-        todo = [s for s in stems if not outputs_exist(args.out, s)] if rank == 0 else None
+        todo = [s for s in stems if not outputs_exist(args.out, s, bool(getattr(args, "vis", False)))] if rank == 0 else None
         todo = driver.agree_on_list(todo if todo is not None else [])
         keep = set(todo)
         done_before = [s for s in stems if s not in keep]
@@ -341,6 +362,9 @@ def run(args) -> Dict[str, List[int]]:
     # --overlap: a pixel several masks of an image are set at goes to one of them on the device (samrs_resolve_overlaps) before the masks
     # are painted, counted and RLE-encoded; "order" = the reference's painting order, nothing launched
     overlap = getattr(args, "overlap", "order") or "order"
+    # --vis: visualize.py's overlay of every image with its class map as written, blended and encoded on the device
+    # (samrs_blend_labels, samrs_png_encode_rgb); the host writes vis/<stem>.png's bytes
+    vis_lut, vis_alpha = vis_options(args, palette)
     if scene_window > 0:
         from . import scene
         if overlap != "order":
@@ -358,7 +382,8 @@ def run(args) -> Dict[str, List[int]]:
                                    png_buffer_mb=getattr(args, "png_buffer_mb", None),
                                    batch_decode=True if getattr(args, "batch_decode", False) else "auto",
                                    min_region_area=min_region_area, region_mode=getattr(args, "region_mode", "both"),
-                                   mask_boxes=mask_boxes, quality=want_quality, overlap=overlap, **thresholds, **poly_kw)
+                                   mask_boxes=mask_boxes, quality=want_quality, overlap=overlap, vis_lut=vis_lut, vis_alpha=vis_alpha,
+                                   vis_buffer_mb=getattr(args, "vis_buffer_mb", None), **thresholds, **poly_kw)
     # rank r takes chunks of `batch` consecutive stems: statically (r, r + world, ...) or from the shared counter (whose
     # store key must be unique per work list: a second run() in the same process group must not find a spent counter)
     import zlib
@@ -463,7 +488,7 @@ def run(args) -> Dict[str, List[int]]:
                               "inside_box": quality.inside_fraction(r.score_counts), "kept": r.kept}
                 polys = [r.polygons(j) for j in range(len(r.labels))] if r.polygon_table is not None else None
                 write_outputs(args.out, r.key, r.seg_mask, None, r.boxes, r.labels, r.areas, palette, names, rles, clock, png_level, files,
-                              bbs, rbs, dota_txt, scores, polys, r.removed)
+                              bbs, rbs, dota_txt, scores, polys, r.removed, r.png("vis") if r.vis_table is not None else None)
             finally:
                 with lock:
                     left[0] -= 1
@@ -585,6 +610,10 @@ class _Parser(argparse.ArgumentParser):
                          ("--min-inside-box", ns.min_inside_box > 0)):
             if on and ns.scene_window > 0:
                 self.error(f"{flag} does not apply with --scene-window: masks are not scored across scene windows")
+        if ns.vis and ns.scene_window > 0:
+            self.error("--vis does not apply with --scene-window: the scene's composite lives in another buffer; scene overlays are not built")
+        if not 0.0 <= ns.vis_alpha <= 1.0:
+            self.error("--vis-alpha must lie in [0, 1]")
         if ns.overlap != "order" and ns.scene_window > 0:
             self.error(f"--overlap {ns.overlap} does not apply with --scene-window: overlaps are not resolved across scene windows")
         for flag, v in (("--min-stability", ns.min_stability), ("--min-pred-iou", ns.min_pred_iou), ("--min-inside-box", ns.min_inside_box)):
@@ -610,7 +639,7 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--box-batch", type=int, default=64)
     ap.add_argument("--no-rle", action="store_true", help="skip per-instance RLE (only class maps + areas)")
     ap.add_argument("--rle-buffer-mb", type=int, default=256, help="device buffer for one batch's RLE strings (real masks need KBs each)")
-    ap.add_argument("--resume", action="store_true", help="skip images whose gray / color / ins outputs already exist")
+    ap.add_argument("--resume", action="store_true", help="skip images whose gray / color / ins outputs (with --vis: and vis) already exist")
     ap.add_argument("--batch", type=int, default=8, help="tiles per encoder pass")
     ap.add_argument("--schedule", default="static", choices=["static", "dynamic"],
                     help="static: rank r takes chunks r, r+world, ...; dynamic: shared-counter work queue (long-tailed box counts)")
@@ -636,6 +665,16 @@ def build_parser() -> argparse.ArgumentParser:
                          "the host only writes the files' bytes")
     ap.add_argument("--png-buffer-mb", type=int, default=None,
                     help="device buffer for one batch's PNG files with --png-device (default: 6 MiB per tile of --batch)")
+    ap.add_argument("--vis", action="store_true",
+                    help="also write vis/<stem>.png, visualize.py's overlay: Image.blend(image, colour per class, --vis-alpha) of every "
+                         "image with its class map as written (after --overlap, --min-region-area and the --quality thresholds), blended "
+                         "and PNG-encoded on the GPU, with or without --png-device.  Always a PNG named after the stem (visualize.py keeps "
+                         "the source file's name and extension).  Not with --scene-window")
+    ap.add_argument("--vis-alpha", type=float, default=0.4, metavar="A", help="with --vis: the class colours' weight, 0 .. 1 (default 0.4, as visualize.py)")
+    ap.add_argument("--vis-palette", default=None, metavar="P.npy",
+                    help="with --vis: .npy uint8 [n_classes, 3] overlay colours (default: --palette); class 255 (unlabeled) is white")
+    ap.add_argument("--vis-buffer-mb", type=int, default=None,
+                    help="with --vis: device buffer for one batch's overlay files (default: the encoder's worst case for --batch tiles)")
     ap.add_argument("--batch-decode", action="store_true",
                     help="decode the boxes of all tiles of a batch in one decoder chain (Engine.predict_multi); same outputs")
     ap.add_argument("--scene-window", type=int, default=0, metavar="N",

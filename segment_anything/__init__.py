@@ -8,6 +8,7 @@ shapes, same error behaviour -- the compute is in ``libsamrs_hip.so``.
 
 Not provided (never called by a SAMRS driver): ``SamAutomaticMaskGenerator``,
 the ONNX exporter.  Asking for them raises with a message instead of an ImportError deep inside a job.
+The overlays of ``Generate Dataset/visualize.py`` are provided, by the generation CLI: ``python -m samrs_amd.generate --vis``.
 """
 from samrs_amd import (ResizeLongestSide, SamPredictor, build_sam, build_sam_vit_b, build_sam_vit_h,  # noqa: F401
                        build_sam_vit_l, sam_model_registry)
