@@ -220,6 +220,42 @@ int samrs_k_convert_split(int prec, const float* in, void* out_hi_et, void* out_
 int samrs_k_range_profile(int prec, const void* x_et, long n, int cols, int ld, int64_t* row48, void* stream);
 int samrs_k_column_stats(int prec, const void* x_et, int M, int K, int ld, float* partials, double* sumsq, uint32_t* maxbits, void* stream);
 int samrs_k_audit_rows_per_partial(void);
+/* -- the outlier-column route (option "outlier_cols") and the padded operand rows of the ViT-H block GEMMs, one kernel or launch each;
+ * tests/test_outlier_kernels_gpu.py.  Every index array is a DEVICE array of at most 32 distinct, ascending int32 below the column
+ * count it indexes; the hooks read it back and refuse anything else (and any shape the launcher does not cover) with nothing launched.
+ *   samrs_k_gemm_ld             C_et [M][N] = [GELU](A_et B_et^T + bias) with A, B rows at a stride of ld elements (0 = K): the plain ET
+ *                               launch of the engine's qkv / lin1 (kernels.h GemmOpts); gelu_form 1 or 2.  Refused where the selection
+ *                               rule does not pick a kernel that takes a stride (samrs_debug_gemm_choice says which).
+ *   samrs_k_gemm_ext            C (fp32 [M][N]) += A_et B_et^T + Ax_et Bx_et^T + bias, Ax [M][64], Bx [N][64] dense: proj / lin2 with
+ *                               the outlier-column stage; SAMRS_ERR_BAD_SHAPE where the 256 x 320 pair-stage kernel does not take the shape
+ *   samrs_k_layernorm_ext       samrs_k_layernorm (plain row order, ET output) into rows of ld_out elements (0 = D) with the extension:
+ *                               [D + j] = lo, [D + 32 + j] = hi of column oc_idx[j], j < n_oc; zeros in the unused slots and in
+ *                               [D + 64, ld_out).  n_oc > 0 needs ld_out >= D + 64 and window_mode == 0.
+ *   samrs_k_outlier_weight_ext  out_et[r][col0 + j] = hi, [col0 + 32 + j] = lo of W[r][idx[j]] (W fp32 [N][K]), rows of ld elements,
+ *                               zeros in the unused slots of the 64
+ *   samrs_k_outlier_side_weight out_et [32][Ks]: row j < n2 = ET(W1[idx2[j]][0 .. D)) | hi x 32 | lo x 32 of its columns idx1 | zeros;
+ *                               rows >= n2 zero; bias_out [32] = b1[idx2[j]] | zeros.  W1 fp32 [n_rows1][D]; Ks >= D (+ 64 when n1 > 0)
+ *   samrs_k_outlier_gather      out_et [rows][64]: [j] = lo_et[r][idx[j]], [32 + j] = hi_et[r][idx[j]] (hi, lo [rows][D]), zeros behind n_oc
+ *   samrs_k_outlier_side_gemm   out_et [M][64] = lo x 32 | hi x 32 of GELU(Y_et Ws_et^T + bias) before its rounding; Y rows of lda
+ *                               elements, Ws [32][K], bias [32]; M % 64 == 0, K % 32 == 0, lda >= K, lda % 8 == 0
+ *   samrs_k_weight_norms        col_sq [K] / row_sq [N] (either may be null) = squared L2 norms of the columns / rows of W fp32 [N][K]
+ *   samrs_k_range_scan          *counter (device uint64) += the elements of x_et at the operand type's saturation value or beyond; n
+ *                               elements as rows of `cols` live elements at a stride of ld (cols <= 0: one dense run); n, cols, ld % 8 == 0 */
+int samrs_k_gemm_ld(int prec, const void* A_et, const void* B_et, void* C_et, const float* bias, int M, int N, int K, int ld, int gelu,
+                    int gelu_form, void* stream);
+int samrs_k_gemm_ext(int prec, const void* A_et, const void* B_et, const void* Ax_et, const void* Bx_et, float* C, const float* bias, int M,
+                     int N, int K, void* stream);
+int samrs_k_layernorm_ext(int prec, const float* X, const float* gamma, const float* beta, float eps, void* out_et, int rows, int D,
+                          int ld_out, const int32_t* oc_idx, int n_oc, int window_mode, void* stream);
+int samrs_k_outlier_weight_ext(int prec, const float* W, int N, int K, const int32_t* idx, int n_oc, void* out_et, int ld, int col0,
+                               void* stream);
+int samrs_k_outlier_side_weight(int prec, const float* W1, const float* b1, int n_rows1, int D, const int32_t* idx2, int n2,
+                                const int32_t* idx1, int n1, void* out_et, int Ks, float* bias_out, void* stream);
+int samrs_k_outlier_gather(const void* hi_et, const void* lo_et, int D, const int32_t* idx, int n_oc, void* out_et, int rows, void* stream);
+int samrs_k_outlier_side_gemm(int prec, const void* Y_et, int lda, const void* Ws_et, const float* bias, int M, int K, void* out_et,
+                              void* stream);
+int samrs_k_weight_norms(const float* W, int N, int K, float* col_sq, float* row_sq, void* stream);
+int samrs_k_range_scan(int prec, const void* x_et, int64_t n, int cols, int ld, uint64_t* counter, void* stream);
 /* the connected-component labelling of samrs_clean_masks alone (region_kernels.hip): masks uint8 [n][h][w] (non-zero = set) ->
  * labels_out int32 [n][h][w] = the flattened root of every pixel, i.e. the smallest row-major pixel index of its 8-connected
  * component of the set pixels (complement != 0: of the unset pixels), -1 where the pixel is not in that working set */

@@ -169,6 +169,77 @@ int samrs_k_column_stats(int prec, const void* x, int M, int K, int ld, float* p
     KRET(launch_column_stats(prec, x, M, K, ld, partials, sumsq, maxbits, (hipStream_t)stream));
 }
 int samrs_k_audit_rows_per_partial(void) { return AUDIT_ROWS_PER_PARTIAL; }
+// ---- the outlier-column kernels and the padded-row / EXT-stage GEMM launches, one each (tests/test_outlier_kernels_gpu.py).  The engine
+// builds its column lists itself (engine.hip pick_outlier_columns: distinct, ascending, below the column count) and sizes every buffer from
+// its own shapes; a caller of these hooks does neither, so each repeats those guarantees on the host before anything is launched.
+// idx_ok: n <= 32 device indices, read back on `stream`, are distinct, ascending and below `bound` (n == 0: nothing to read).
+static bool idx_ok(const int32_t* idx, int n, int bound, void* stream) {
+    if (n == 0) return true;
+    int32_t h[32];
+    if (!idx || n < 0 || n > 32 || bound < 1) return false;
+    if (hipMemcpyAsync(h, idx, sizeof(int32_t) * n, hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess) return false;
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return false;
+    for (int j = 0; j < n; ++j)
+        if (h[j] < 0 || h[j] >= bound || (j && h[j] <= h[j - 1])) return false;
+    return true;
+}
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+int samrs_k_gemm_ld(int prec, const void* A, const void* B, void* C, const float* bias, int M, int N, int K, int ld, int gelu, int gelu_form,
+                    void* stream) {
+    if (!A || !B || !C || !aligned16(A) || !aligned16(B) || !aligned16(C)) return SAMRS_ERR_BAD_ARG;
+    if (ld < 0 || (gelu_form != 1 && gelu_form != 2)) return SAMRS_ERR_BAD_ARG;
+    GemmOpts opts;
+    opts.ld = ld;
+    opts.gelu_form = gelu_form;
+    KRET(launch_gemm_et(prec, A, B, C, bias, nullptr, 0, M, N, K, false, gelu != 0, false, (hipStream_t)stream, opts));
+}
+int samrs_k_gemm_ext(int prec, const void* A, const void* B, const void* Ax, const void* Bx, float* C, const float* bias, int M, int N, int K,
+                     void* stream) {
+    if (!A || !B || !Ax || !Bx || !C || !aligned16(A) || !aligned16(B) || !aligned16(Ax) || !aligned16(Bx) || !aligned16(C)) return SAMRS_ERR_BAD_ARG;
+    if (M < 1 || N < 1 || K < 1 || !gemm_ext_ok(M, N, K)) return SAMRS_ERR_BAD_SHAPE;
+    KRET(launch_gemm_et_ext(prec, A, B, Ax, Bx, C, bias, M, N, K, (hipStream_t)stream));
+}
+int samrs_k_layernorm_ext(int prec, const float* X, const float* gamma, const float* beta, float eps, void* out_et, int rows, int D, int ld_out,
+                          const int32_t* oc_idx, int n_oc, int window_mode, void* stream) {
+    if (!X || !gamma || !beta || !out_et || !aligned16(X) || !aligned16(gamma) || !aligned16(beta) || !aligned16(out_et)) return SAMRS_ERR_BAD_ARG;
+    if (rows < 1 || D < 4 || ld_out < 0 || n_oc < 0 || n_oc > 32 || (n_oc && ld_out < D + 64)) return SAMRS_ERR_BAD_SHAPE;
+    if (window_mode) return SAMRS_ERR_BAD_SHAPE;       // the extension goes with plain row order only, and the hook has no grid to give
+    if (!idx_ok(oc_idx, n_oc, D, stream)) return SAMRS_ERR_BAD_ARG;
+    KRET(launch_layernorm(prec, X, gamma, beta, eps, out_et, nullptr, rows, D, 0, 0, 0, (hipStream_t)stream, nullptr, nullptr, nullptr, nullptr,
+                          nullptr, ld_out, n_oc ? oc_idx : nullptr, n_oc));
+}
+int samrs_k_outlier_weight_ext(int prec, const float* W, int N, int K, const int32_t* idx, int n_oc, void* out, int ld, int col0, void* stream) {
+    if (!W || !out || N < 1 || K < 1 || n_oc < 0 || n_oc > 32 || col0 < 0 || ld < col0 + 64) return SAMRS_ERR_BAD_SHAPE;
+    if (!idx_ok(idx, n_oc, K, stream)) return SAMRS_ERR_BAD_ARG;
+    KRET(launch_outlier_weight_ext(prec, W, N, K, idx, n_oc, out, ld, col0, (hipStream_t)stream));
+}
+// n_rows1: the rows of W1 (lin1's output width), which the launcher does not need and the check of idx2 does
+int samrs_k_outlier_side_weight(int prec, const float* W1, const float* b1, int n_rows1, int D, const int32_t* idx2, int n2, const int32_t* idx1,
+                                int n1, void* out, int Ks, float* bias_out, void* stream) {
+    if (!W1 || !b1 || !out || n_rows1 < 1 || D < 1 || n2 < 1 || n2 > 32 || n1 < 0 || n1 > 32 || Ks < D + (n1 ? 64 : 0)) return SAMRS_ERR_BAD_SHAPE;
+    if (!idx_ok(idx2, n2, n_rows1, stream) || !idx_ok(idx1, n1, D, stream)) return SAMRS_ERR_BAD_ARG;
+    KRET(launch_outlier_side_weight(prec, W1, b1, D, idx2, n2, idx1, n1, out, Ks, bias_out, (hipStream_t)stream));
+}
+int samrs_k_outlier_gather(const void* hi, const void* lo, int D, const int32_t* idx, int n_oc, void* out, int rows, void* stream) {
+    if (!hi || !lo || !out || D < 1 || n_oc < 1 || n_oc > 32 || rows < 1) return SAMRS_ERR_BAD_SHAPE;
+    if (!idx_ok(idx, n_oc, D, stream)) return SAMRS_ERR_BAD_ARG;
+    KRET(launch_outlier_gather(hi, lo, D, idx, n_oc, out, rows, (hipStream_t)stream));
+}
+int samrs_k_outlier_side_gemm(int prec, const void* Y, int lda, const void* Ws, const float* bias, int M, int K, void* out, void* stream) {
+    if (!Y || !Ws || !bias || !out || !aligned16(Y) || !aligned16(Ws)) return SAMRS_ERR_BAD_ARG;
+    if (M < 64 || M % 64 || K < 32 || K % 32 || lda < K || lda % 8) return SAMRS_ERR_BAD_SHAPE;
+    KRET(launch_outlier_side_gemm(prec, Y, lda, Ws, bias, M, K, out, (hipStream_t)stream));
+}
+int samrs_k_weight_norms(const float* W, int N, int K, float* col_sq, float* row_sq, void* stream) {
+    if (!W || (!col_sq && !row_sq)) return SAMRS_ERR_BAD_ARG;
+    if (N < 1 || K < 1) return SAMRS_ERR_BAD_SHAPE;
+    KRET(launch_weight_norms(W, N, K, col_sq, row_sq, (hipStream_t)stream));
+}
+int samrs_k_range_scan(int prec, const void* x, int64_t n, int cols, int ld, uint64_t* counter, void* stream) {
+    if (!x || !counter || !aligned16(x)) return SAMRS_ERR_BAD_ARG;
+    if (n < 0 || n % 8 || (cols > 0 && (cols % 8 || ld % 8 || ld < cols || n % cols))) return SAMRS_ERR_BAD_SHAPE;
+    KRET(launch_range_scan(prec, x, (long)n, reinterpret_cast<unsigned long long*>(counter), (hipStream_t)stream, cols, ld));
+}
 int samrs_k_neck_im2col(const void* in, void* A, int n_images, int grid, int C, void* stream) {
     if (!in || !A || n_images < 1 || grid < 1 || C < 8 || C % 8) return SAMRS_ERR_BAD_ARG;
     KRET(launch_neck_im2col(in, A, n_images, grid, C, (hipStream_t)stream));

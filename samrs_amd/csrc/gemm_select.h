@@ -198,8 +198,10 @@ inline GemmChoice gemm_select(const GemmCall& c, const GemmEnv& e) {
     if (c.has_add2d && c.gelu) return no;   // not needed by the path; the coalesced epilogue orders them differently
     const GemmChoice ch = gemm_rule(c, e);
     // a padded operand stride is understood by the persistent ET kernels only, and planned for (gemm_ld_ok) under the automatic rule
-    // only: refuse anything else instead of reading garbage
-    if (c.ld != 0 && (c.ld < c.K || e.variant != 8 || c.out_f32 || c.has_add2d || !gemm_takes_ld(ch.kernel))) return no;
+    // only: refuse anything else instead of reading garbage.  Both kernels fetch a row's k-slice as 16-byte LDS-DMA pieces at byte offset
+    // 2 (row ld + 8 chunk) from a 16-byte-aligned base (gemm.hip voff / voffq): a stride that is no multiple of 8 elements would put
+    // every odd row's pieces off their 16-byte alignment, so it is refused too
+    if (c.ld != 0 && (c.ld < c.K || c.ld % 8 || e.variant != 8 || c.out_f32 || c.has_add2d || !gemm_takes_ld(ch.kernel))) return no;
     return ch;
 }
 

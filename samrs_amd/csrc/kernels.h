@@ -6,7 +6,7 @@
 // ---- gemm.hip (the dispatch) and the kernel families beside it: gemm_ring / gemm_dual / gemm_decoder / gemm_experiments.hip ------
 // Which kernel runs a launch is decided by gemm_select (gemm_select.h) from the shape, the flags and the variant in force.
 struct GemmOpts {
-    int ld = 0;           // row stride of A and B in elements, 0 = K: the persistent ET kernels alone read with it (gemm_ld_ok says whether
+    int ld = 0;           // row stride of A and B in elements (>= K, a multiple of 8), 0 = K: the persistent ET kernels alone read with it (gemm_ld_ok says whether
                           // a launch of the shape runs on one of them; anything else refuses a stride)
     int gelu_form = 1;    // erf form of their GELU epilogue (lin1): 1 = fp32-epsilon class, 2 = cheaper
 };

@@ -202,6 +202,20 @@ def load_library() -> C.CDLL:
     for name in ("samrs_audit_site_count", "samrs_audit_site_name", "samrs_audit_read_profile", "samrs_audit_read_columns",
                  "samrs_k_range_profile", "samrs_k_column_stats", "samrs_k_audit_rows_per_partial"):
         getattr(lib, name).restype = ip
+    # the outlier-column kernels and the padded-row / EXT-stage GEMM launches, one each (tests/test_outlier_kernels_gpu.py)
+    if hasattr(lib, "samrs_k_gemm_ext"):              # an older build of the same ABI (SAMRS_LIB_PATH: A/B runs) has none of them
+        lib.samrs_k_gemm_ld.argtypes = [ip, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, vp]
+        lib.samrs_k_gemm_ext.argtypes = [ip, vp, vp, vp, vp, vp, vp, ip, ip, ip, vp]
+        lib.samrs_k_layernorm_ext.argtypes = [ip, vp, vp, vp, fp, vp, ip, ip, ip, vp, ip, ip, vp]
+        lib.samrs_k_outlier_weight_ext.argtypes = [ip, vp, ip, ip, vp, ip, vp, ip, ip, vp]
+        lib.samrs_k_outlier_side_weight.argtypes = [ip, vp, vp, ip, ip, vp, ip, vp, ip, vp, ip, vp, vp]
+        lib.samrs_k_outlier_gather.argtypes = [vp, vp, ip, vp, ip, vp, ip, vp]
+        lib.samrs_k_outlier_side_gemm.argtypes = [ip, vp, ip, vp, vp, ip, ip, vp, vp]
+        lib.samrs_k_weight_norms.argtypes = [vp, ip, ip, vp, vp, vp]
+        lib.samrs_k_range_scan.argtypes = [ip, vp, i64, ip, ip, vp, vp]
+        for name in ("samrs_k_gemm_ld", "samrs_k_gemm_ext", "samrs_k_layernorm_ext", "samrs_k_outlier_weight_ext", "samrs_k_outlier_side_weight",
+                     "samrs_k_outlier_gather", "samrs_k_outlier_side_gemm", "samrs_k_weight_norms", "samrs_k_range_scan"):
+            getattr(lib, name).restype = ip
     for name in ("samrs_load_weight", "samrs_finalize_weights", "samrs_set_images", "samrs_set_images_ragged", "samrs_get_embedding",
                  "samrs_set_embedding", "samrs_reset_image", "samrs_predict", "samrs_predict_multi", "samrs_paint", "samrs_k_gemm",
                  "samrs_k_gemm_f32", "samrs_k_convert", "samrs_k_layernorm", "samrs_k_window_attention",

@@ -5,8 +5,10 @@ rounded reference).  All under the automatic variant but one: the 256x320 stagge
 automatic rule prefers the pair-stage kernel whenever K % 64 == 0, which every launch satisfies), here as variant 10.
 
 The two launch options the engine passes explicitly (kernels.h GemmOpts):
-  * ld (padded operand rows of qkv / lin1, on both kernels that take a stride, with either erf form): tests/test_parity_gpu.py
-    test_operand_row_padding_is_bit_identical -- nothing is added here;
+  * ld (padded operand rows of qkv / lin1, on both kernels that take a stride, with either erf form): the launches alone, with NaN
+    in the pad columns, against the dense launch and the fp64 product in tests/test_outlier_kernels_gpu.py test_padded_row_gemm (the
+    strides the rule refuses: tests/test_gemm_select_host.py); inside a whole engine in tests/test_parity_gpu.py
+    test_operand_row_padding_is_bit_identical;
   * gelu_form = 2: test_gelu_form_reaches_the_kernel below."""
 import ctypes
 import math

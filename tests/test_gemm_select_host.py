@@ -64,6 +64,20 @@ def test_recorded_table(choice):
     assert reached == set(KERNELS[:10]), reached
 
 
+def test_stride_keeps_the_dma_pieces_aligned(choice):
+    """Both kernels that take an operand stride fetch 16-byte LDS-DMA pieces at byte offset 2 (row ld + ...) from an aligned base: a
+    stride is taken exactly when it is >= K and a multiple of 8 elements, on either kernel and in either operand type."""
+    for prec in (0, 1):
+        for M, N, K, gelu, kernel in ((4096, 5120, 128, 0, "X64P"), (16384, 5120, 256, 1, "W4X"), (32768, 3840, 1280, 0, "X64P")):
+            for ld in range(K - 8, K + 137):
+                got = choice(prec, M, N, K, gelu=gelu, ld=ld)
+                if ld >= K and ld % 8 == 0:
+                    assert not got["reject"] and got["kernel"] == kernel, (prec, M, N, K, ld, got)
+                else:
+                    assert got["reject"], (prec, M, N, K, ld, got)
+            assert choice(prec, M, N, K, gelu=gelu, ld=-8)["reject"]
+
+
 GRID_M = [128, 256, 384, 4096, 8192, 12288, 16384, 32768, 65536]
 GRID_N = [128, 256, 320, 384, 640, 1280, 1536, 2048, 2560, 3840, 5120]
 GRID_K = [32, 64, 96, 128, 256, 1280, 1536, 1600, 5120]
