@@ -256,6 +256,28 @@ int samrs_k_outlier_side_gemm(int prec, const void* Y_et, int lda, const void* W
                               void* stream);
 int samrs_k_weight_norms(const float* W, int N, int K, float* col_sq, float* row_sq, void* stream);
 int samrs_k_range_scan(int prec, const void* x_et, int64_t n, int cols, int ld, uint64_t* counter, void* stream);
+/* -- the token side of the mask decoder, image ingest, the embedding hand-over and the reference-grade GELU, one kernel each;
+ * tests/test_token_side_kernels_gpu.py.  Each hook repeats on the host what the engine's call sites guarantee by construction and
+ * returns SAMRS_ERR_BAD_ARG otherwise, with nothing launched.
+ *   samrs_k_gemm_f32_batch  `count` (1 .. 5) fp32 problems of one shape in one launch, as the decoder batches its q / k / v, k / v and head
+ *                           GEMMs: C[z] [M][N] (rows of ldc elements) = (A[z] + A2[z]) [M][K] (rows of lda elements) W[z]^T (dense [N][K])
+ *                           + bias[z], then ReLU, then + what C[z] held when `accumulate`.  A, A2, W, bias, C are HOST arrays of `count`
+ *                           device pointers; A2 may be a null array or hold null entries (no addend for that problem; the sum is rounded
+ *                           to fp32 once), bias may hold null entries.  K % 16 == 0, lda % 4 == 0, lda >= K, ldc >= N, M, N >= 1; A[z], A2[z]
+ *                           and W[z] 16-byte aligned; A[z], W[z], C[z] non-null.  The bits of a row do not depend on M or on count.
+ *   samrs_k_patch_im2col    preprocess + im2col of the patch convolution (sam.py:164-174, image_encoder.py:364-395): img_u8 [n_images][in_h]
+ *                           [in_w][3] -> A_et [n_images * grid * grid][3 patch^2], k = c patch^2 + ky patch + kx, value
+ *                           (pixel - mean[c]) / std[c] inside in_h x in_w and zero outside; A_lo_et (may be null): the split remainder
+ *                           ET(v - hi), same layout.  patch % 8 == 0, in_h, in_w, n_images, grid >= 1, outputs 16-byte aligned.
+ *   samrs_k_transpose_f32   out [cols][rows] = in [rows][cols]^T, fp32 bits moved as they are (samrs_get_embedding / samrs_set_embedding)
+ *   samrs_k_gelu_split      hi_et | lo_et [n] = the two-term split of the exact-erf GELU of in fp32 [n] (lin1 -> lin2 of the reference-grade
+ *                           mode); n % 4 == 0, 16-byte aligned */
+int samrs_k_gemm_f32_batch(const float* const* A, const float* const* A2, const float* const* W, const float* const* bias, float* const* C,
+                           int count, int lda, int ldc, int M, int N, int K, int relu, int accumulate, void* stream);
+int samrs_k_patch_im2col(int prec, const uint8_t* img_u8, void* A_et, void* A_lo_et, int n_images, int in_h, int in_w, int grid, int patch,
+                         void* stream);
+int samrs_k_transpose_f32(const float* in, float* out, int rows, int cols, void* stream);
+int samrs_k_gelu_split(int prec, const float* in, void* hi_et, void* lo_et, int64_t n, void* stream);
 /* the connected-component labelling of samrs_clean_masks alone (region_kernels.hip): masks uint8 [n][h][w] (non-zero = set) ->
  * labels_out int32 [n][h][w] = the flattened root of every pixel, i.e. the smallest row-major pixel index of its 8-connected
  * component of the set pixels (complement != 0: of the unset pixels), -1 where the pixel is not in that working set */

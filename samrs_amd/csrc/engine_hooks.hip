@@ -244,6 +244,36 @@ int samrs_k_neck_im2col(const void* in, void* A, int n_images, int grid, int C, 
     if (!in || !A || n_images < 1 || grid < 1 || C < 8 || C % 8) return SAMRS_ERR_BAD_ARG;
     KRET(launch_neck_im2col(in, A, n_images, grid, C, (hipStream_t)stream));
 }
+// ---- the token-side fp32 GEMM batch, image ingest, embedding hand-over and reference-grade GELU, one kernel each
+// (tests/test_token_side_kernels_gpu.py).  The engine fills an F32Batch from its own buffers (hipMalloc: 256-byte aligned; row strides
+// C, Ci, T C, 2048: multiples of 4 floats no shorter than K; weights dense [N][K] with K % 16 == 0, a row offset into them whole rows) and
+// sizes every output from its own shapes; a caller of these hooks does neither, so each repeats that on the host before anything is launched.
+int samrs_k_gemm_f32_batch(const float* const* A, const float* const* A2, const float* const* W, const float* const* bias, float* const* C,
+                           int count, int lda, int ldc, int M, int N, int K, int relu, int accumulate, void* stream) {
+    if (!A || !W || !bias || !C || count < 1 || count > F32_BATCH_MAX) return SAMRS_ERR_BAD_ARG;
+    if (M < 1 || N < 1 || K < 16 || K % 16 || lda % 4 || lda < K || ldc < N) return SAMRS_ERR_BAD_ARG;
+    F32Batch bt{};
+    for (int z = 0; z < count; ++z) {
+        const float* a2 = A2 ? A2[z] : nullptr;
+        if (!A[z] || !W[z] || !C[z] || !aligned16(A[z]) || !aligned16(a2) || !aligned16(W[z])) return SAMRS_ERR_BAD_ARG;      // the kernel reads float4
+        bt.A[z] = A[z]; bt.A2[z] = a2; bt.W[z] = W[z]; bt.bias[z] = bias[z]; bt.C[z] = C[z];
+    }
+    KRET(launch_gemm_f32_batch(bt, count, lda, ldc, M, N, K, relu != 0, accumulate != 0, (hipStream_t)stream));
+}
+int samrs_k_patch_im2col(int prec, const uint8_t* img_u8, void* A_et, void* A_lo_et /* may be null */, int n_images, int in_h, int in_w,
+                         int grid, int patch, void* stream) {
+    if (!img_u8 || !A_et || !aligned16(A_et) || !aligned16(A_lo_et)) return SAMRS_ERR_BAD_ARG;
+    if (patch < 8 || patch % 8 || in_h < 1 || in_w < 1 || n_images < 1 || grid < 1) return SAMRS_ERR_BAD_ARG;
+    KRET(launch_patch_im2col(prec, img_u8, A_et, n_images, in_h, in_w, grid, patch, (hipStream_t)stream, A_lo_et));
+}
+int samrs_k_transpose_f32(const float* in, float* out, int rows, int cols, void* stream) {
+    if (!in || !out || rows < 1 || cols < 1) return SAMRS_ERR_BAD_ARG;
+    KRET(launch_transpose_f32(in, out, rows, cols, (hipStream_t)stream));
+}
+int samrs_k_gelu_split(int prec, const float* in, void* hi_et, void* lo_et, int64_t n, void* stream) {
+    if (!in || !hi_et || !lo_et || !aligned16(in) || !aligned16(hi_et) || !aligned16(lo_et) || n < 4 || n % 4) return SAMRS_ERR_BAD_ARG;
+    KRET(launch_gelu_split(prec, in, hi_et, lo_et, (long)n, (hipStream_t)stream));
+}
 int samrs_k_postprocess(const float* low, int n_masks, int in_h, int in_w, int orig_h, int orig_w, int img_size,
                         int return_logits, void* out, void* stream) {
     KRET(launch_postprocess(low, n_masks, in_h, in_w, orig_h, orig_w, img_size, return_logits, out, (hipStream_t)stream));

@@ -216,6 +216,14 @@ def load_library() -> C.CDLL:
         for name in ("samrs_k_gemm_ld", "samrs_k_gemm_ext", "samrs_k_layernorm_ext", "samrs_k_outlier_weight_ext", "samrs_k_outlier_side_weight",
                      "samrs_k_outlier_gather", "samrs_k_outlier_side_gemm", "samrs_k_weight_norms", "samrs_k_range_scan"):
             getattr(lib, name).restype = ip
+    # the fp32 GEMM batch, image ingest, embedding hand-over and reference-grade GELU, one each (tests/test_token_side_kernels_gpu.py)
+    if hasattr(lib, "samrs_k_gemm_f32_batch"):        # an older build of the same ABI (SAMRS_LIB_PATH: A/B runs) has none of them
+        lib.samrs_k_gemm_f32_batch.argtypes = [vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, ip, ip, vp]
+        lib.samrs_k_patch_im2col.argtypes = [ip, vp, vp, vp, ip, ip, ip, ip, ip, vp]
+        lib.samrs_k_transpose_f32.argtypes = [vp, vp, ip, ip, vp]
+        lib.samrs_k_gelu_split.argtypes = [ip, vp, vp, vp, i64, vp]
+        for name in ("samrs_k_gemm_f32_batch", "samrs_k_patch_im2col", "samrs_k_transpose_f32", "samrs_k_gelu_split"):
+            getattr(lib, name).restype = ip
     for name in ("samrs_load_weight", "samrs_finalize_weights", "samrs_set_images", "samrs_set_images_ragged", "samrs_get_embedding",
                  "samrs_set_embedding", "samrs_reset_image", "samrs_predict", "samrs_predict_multi", "samrs_paint", "samrs_k_gemm",
                  "samrs_k_gemm_f32", "samrs_k_convert", "samrs_k_layernorm", "samrs_k_window_attention",
