@@ -232,6 +232,35 @@ int samrs_scene_resolve(samrs_engine_t* e, const int32_t* order, const int32_t* 
 int samrs_rle_encode_placed(samrs_engine_t* e, const uint8_t* masks, int n, int h, int w, int x0, int y0, int H, int W,
                             uint8_t* out, int64_t out_capacity, int64_t* cursor, int64_t* table, void* stream);
 
+/* -- the inverse of samrs_rle_encode: COCO RLE strings -> masks, on the device.  strings: device bytes [strings_bytes]; table [n][3]
+ * (device int64) has exactly the layout samrs_rle_encode writes, (offset, length, n_counts), n_counts ignored on input: an encode
+ * call's `out` + `table` can be fed straight back.  Offsets need no alignment.  masks_out uint8 [n][h][w], row-major 0 / 1, every
+ * byte of it written; areas_out [n] (device int64, or NULL) = set pixels of mask j; status_out [n] (device int32) = the
+ * lowest-numbered samrs_rle_status that applies.  A mask with a non-zero status is all zero and has area 0.  The format is cocoapi's
+ * rleFrString: char - 48, 5-bit groups, bit 5 = continuation, bit 4 of the last group sign-extends, from the 4th count on a delta
+ * against the count two back; counts are column-major runs starting with zeros, and zero-length counts are legal anywhere.
+ * The strings are untrusted: a mask is filled only after its whole string validated, sums are taken in 64 bits, no index derived
+ * from string bytes reaches memory unchecked, and the call is memory-safe for arbitrary bytes and table rows.  A delta that does not
+ * fit int32 is taken as saturated (its count is negative or above 2^30 either way).  The table rows of a call name distinct strings:
+ * a row that brings the summed lengths of its chunk of the call (up to 32 masks) above strings_bytes is reported RANGE.
+ * h * w < 2^30, h, w >= 1, strings_bytes < 2^31.  n == 0 is a no-op; a null handle or pointer, n < 0 or a size over the limit:
+ * SAMRS_ERR_BAD_ARG and nothing is launched.  Integer arithmetic only: bit-exact with samrs_amd/rle.py:decode.
+ * The token / count / boundary arrays (4 bytes per byte of `strings`) and the bit matrix live in ONE scratch buffer per handle, its
+ * own: all samrs_rle_decode calls on a handle must be stream-ordered with each other (same stream, or an event between them); two
+ * handles never share it.  A call with many or large masks runs as consecutive chunks on the stream (32 masks or 64 MiB of bit matrix
+ * at most, one mask at least). */
+enum samrs_rle_status {
+    SAMRS_RLE_OK = 0,          /* the mask was decoded                                             */
+    SAMRS_RLE_ABSENT = 1,      /* length < 0: the encoder's "did not fit" marker                   */
+    SAMRS_RLE_RANGE = 2,       /* offset < 0 or offset + length > strings_bytes                    */
+    SAMRS_RLE_BAD_CHAR = 3,    /* a byte outside 48..111                                           */
+    SAMRS_RLE_TRUNCATED = 4,   /* the last char has the continuation bit                           */
+    SAMRS_RLE_BAD_COUNT = 5,   /* a token of more than 7 chars, or a count negative after the delta */
+    SAMRS_RLE_BAD_SUM = 6      /* the counts do not sum to exactly h * w (the empty string too)    */
+};
+int samrs_rle_decode(samrs_engine_t* e, const uint8_t* strings, int64_t strings_bytes, const int64_t* table, int n, int h, int w,
+                     uint8_t* masks_out, int64_t* areas_out, int32_t* status_out, void* stream);
+
 /* -- mask clean-up before the masks become labels: `remove_small_regions` of utils/amg.py:267-291 on the device, for a batch of
  * masks that never leave HBM (the reference's runs on the host through cv2, one mask per call).  masks uint8 [n][h][w] device, in /
  * out (non-zero = set in, 0 / 1 out): the C = 1 output of samrs_predict, or the kept masks of samrs_select_best.  A region is an

@@ -171,14 +171,17 @@ def load_coco_files(dt_path: str, gt_path: str):
 
 
 def evaluate_files(engine, dt_path: str, gt_path: str):
-    """Any pair of such files on the GPU: RLE decoded on the host (``samrs_amd.rle.decode``) and uploaded image by image."""
+    """Any pair of such files on the GPU: per image the RLE strings are uploaded as they are and decoded on the device
+    (``samrs_amd.rle.decode_device``, samrs_rle_decode); the masks never exist on the host."""
+    import torch
     from . import rle
     ids, dts, gts = load_coco_files(dt_path, gt_path)
 
     def images():
         for i in ids:
             size = (dts[i][0][1] if dts[i] else gts[i][0])["size"] if (dts[i] or gts[i]) else [1, 1]
-            stack = lambda segs: (np.stack([rle.decode(s) for s in segs]) if segs else np.zeros((0, size[0], size[1]), bool))
+            stack = lambda segs: (rle.decode_device(engine, segs) if segs
+                                  else torch.zeros(0, size[0], size[1], dtype=torch.uint8, device=engine.device))
             yield stack([s for _, s in dts[i]]), np.array([sc for sc, _ in dts[i]], dtype=np.float32), stack(gts[i])
     return evaluate_masks(engine, images())
 

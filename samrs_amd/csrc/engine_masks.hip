@@ -55,6 +55,31 @@ int samrs_rle_encode(samrs_engine_t* e, const uint8_t* masks, int n, int h, int 
     return SAMRS_OK;
 }
 
+// the inverse: n COCO RLE strings decoded to row-major 0 / 1 bytes, with a status per mask (see samrs_hip.h)
+int samrs_rle_decode(samrs_engine_t* e, const uint8_t* strings, int64_t strings_bytes, const int64_t* table, int n, int h, int w,
+                     uint8_t* masks_out, int64_t* areas_out, int32_t* status_out, void* stream) {
+    if (!e || n < 0 || h < 1 || w < 1 || strings_bytes < 0 || (n > 0 && (!strings || !table || !masks_out || !status_out)))
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_rle_decode: bad argument");
+    if ((size_t)h * w >= (1ull << 30) || strings_bytes >= (1ll << 31))
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_rle_decode: too large (h * w must be < 2^30, strings_bytes < 2^31)");
+    if (n == 0) return SAMRS_OK;
+    ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    // masks per pass: as many as keep the bit matrix below 64 MiB (rle_decode_max_batch() at most), one at least
+    const size_t per = ((size_t)(h + 31) / 32) * w * 4;
+    int chunk = (int)(((size_t)64 << 20) / per);
+    chunk = chunk < 1 ? 1 : (chunk > rle_decode_max_batch() ? rle_decode_max_batch() : chunk);
+    const size_t need = rle_decode_scratch_bytes(n < chunk ? n : chunk, h, w, (long long)strings_bytes);
+    CK(e, scratch_reserve(e->rle_decode_scratch, need, s));
+    for (int off = 0; off < n; off += chunk) {
+        const int m = n - off < chunk ? n - off : chunk;
+        CK(e, launch_rle_decode(strings, (long long)strings_bytes, (const long long*)table + (size_t)off * 3, m, h, w,
+                                e->rle_decode_scratch.p, masks_out + (size_t)off * h * w, areas_out ? (long long*)areas_out + off : nullptr,
+                                status_out + off, s));
+    }
+    return SAMRS_OK;
+}
+
 // scene mode (see samrs_hip.h): one window's masks into the scene's rank map, the map into the class map, and the window's masks
 // as COCO RLE strings in the scene's frame
 int samrs_scene_claim(samrs_engine_t* e, const uint8_t* masks, const int32_t* ranks, const int32_t* labels, int n, int h, int w,

@@ -237,6 +237,7 @@ struct samrs_engine {
 
     // grown on demand (scratch_reserve) and kept for the next call
     DeviceScratch rle_scratch;     // COCO RLE (samrs_rle_encode, samrs_rle_encode_placed)
+    DeviceScratch rle_decode_scratch;  // tokens -> counts -> boundaries, bit matrix and counters of samrs_rle_decode
     DeviceScratch region_scratch;  // labels + areas + counters of samrs_clean_masks
     DeviceScratch box_scratch;     // row extents of samrs_mask_boxes
     DeviceScratch poly_scratch;    // edge lists and ranking state of samrs_mask_polygons

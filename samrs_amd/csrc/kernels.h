@@ -256,6 +256,16 @@ size_t rle_placed_scratch_bytes(int n, int h, int w, int x0, int H, int W);
 hipError_t launch_rle_encode_placed(const uint8_t* masks, int n, int h, int w, int x0, int y0, int H, int W, void* scratch,
                                     unsigned char* out, long long out_cap, long long* cursor, long long* table, hipStream_t s);
 
+// ---- rle_decode_kernels.hip -----------------------------------------------------------------
+// The inverse: n <= rle_decode_max_batch() strings (table [n][3] device int64 = (offset, length, ignored) into `strings`, device bytes)
+// -> row-major 0 / 1 bytes masks_out [n][h][w] (every byte written), areas_out [n] (or null), status_out [n] (samrs_rle_status; a mask
+// with a non-zero status is all zero).  Memory-safe for arbitrary bytes and table rows.  h * w < 2^30, strings_bytes < 2^31.
+// scratch: rle_decode_scratch_bytes(n, h, w, strings_bytes).
+int rle_decode_max_batch();
+size_t rle_decode_scratch_bytes(int n, int h, int w, long long strings_bytes);
+hipError_t launch_rle_decode(const uint8_t* strings, long long strings_bytes, const long long* table, int n, int h, int w, void* scratch,
+                             uint8_t* masks_out, long long* areas_out, int32_t* status_out, hipStream_t s);
+
 // ---- scene_kernels.hip ----------------------------------------------------------------------
 // order int32 [H][W] (-1 = unclaimed): order[p] = max(order[p], max{ranks[j] : mask j set at p}) over the masks uint8 [n][h][w] of
 // the window (x0, y0, w, h); areas (zeroed, then counted) and the class statistics as launch_paint.  n == 0 is a no-op.

@@ -103,6 +103,8 @@ def load_library() -> C.CDLL:
     lib.samrs_set_option.argtypes = [vp, C.c_char_p, ip]
     lib.samrs_get_option.argtypes = [vp, C.c_char_p, C.POINTER(ip)]
     lib.samrs_rle_encode.argtypes = [vp, vp, ip, ip, ip, vp, C.c_int64, vp, vp, vp]
+    lib.samrs_rle_decode.argtypes = [vp, vp, C.c_int64, vp, ip, ip, ip, vp, vp, vp, vp]
+    lib.samrs_rle_decode.restype = ip
     lib.samrs_scene_claim.argtypes = [vp, vp, vp, vp, ip, ip, ip, ip, ip, ip, ip, vp, vp, vp, vp, ip, vp]
     lib.samrs_scene_resolve.argtypes = [vp, vp, vp, ip, ip, ip, vp, vp]
     lib.samrs_rle_encode_placed.argtypes = [vp, vp, ip, ip, ip, ip, ip, ip, ip, vp, C.c_int64, vp, vp, vp]
@@ -236,6 +238,10 @@ def load_library() -> C.CDLL:
         raise ImportError("libsamrs_hip.so ABI version mismatch; rebuild it")
     _lib = lib
     return lib
+
+
+# samrs_rle_status (samrs_hip.h): the per-mask status codes of samrs_rle_decode
+RLE_STATUS = ("OK", "ABSENT", "RANGE", "BAD_CHAR", "TRUNCATED", "BAD_COUNT", "BAD_SUM")
 
 
 PNG_RGB_BLOCK_BYTES = 1 << 20      # filtered bytes per deflate block of samrs_png_encode_rgb (SAMRS_PNG_RGB_BLOCK_BYTES in samrs_hip.h)
@@ -642,6 +648,34 @@ class Engine:
         with torch.cuda.device(self.device):
             self._check(self.lib.samrs_rle_encode(self.handle, m.data_ptr(), n, h, w, out.data_ptr(), out.numel(),
                                                   cursor.data_ptr(), table.data_ptr(), _stream()))
+
+    def rle_decode(self, strings: torch.Tensor, table: torch.Tensor, size: Sequence[int], out: Optional[torch.Tensor] = None,
+                   areas_out: Optional[torch.Tensor] = None, status_out: Optional[torch.Tensor] = None):
+        """The inverse of :meth:`rle_encode`: `strings` (uint8, device, contiguous; any alignment) and `table` (int64 [n, 3], device:
+        (offset, length, ignored) per mask -- what ``rle_encode`` wrote) -> (masks uint8 [n, H, W] of 0 / 1 for `size` = (H, W), areas
+        int64 [n], status int32 [n]; ``RLE_STATUS`` names the codes), all on the device.  A mask whose status is not 0 is all zero.
+        `out` / `areas_out` / `status_out`: caller-owned contiguous tensors of those shapes and types (slices are fine) instead of
+        new ones.  Asynchronous on the current stream; see samrs_rle_decode in samrs_hip.h."""
+        h, w = int(size[0]), int(size[1])
+        if not (isinstance(strings, torch.Tensor) and strings.dtype == torch.uint8 and strings.is_cuda and strings.is_contiguous() and strings.dim() == 1):
+            raise ValueError("strings must be a contiguous uint8 [bytes] tensor on the engine's device")
+        if not (isinstance(table, torch.Tensor) and table.dtype == torch.int64 and table.is_cuda and table.is_contiguous()
+                and table.dim() == 2 and table.shape[1] == 3):
+            raise ValueError("table must be a contiguous int64 [n, 3] tensor on the engine's device")
+        n = int(table.shape[0])
+        outs = []
+        for name, t, shape, dt in (("out", out, (n, h, w), torch.uint8), ("areas_out", areas_out, (n,), torch.int64),
+                                   ("status_out", status_out, (n,), torch.int32)):
+            if t is None:
+                t = torch.empty(shape, dtype=dt, device=self.device)
+            elif not (isinstance(t, torch.Tensor) and t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shape):
+                raise ValueError(f"{name} must be a contiguous {dt} {list(shape)} tensor on the engine's device, or None")
+            outs.append(t)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.samrs_rle_decode(self.handle, _ptr(strings) if n else None, strings.numel(), _ptr(table) if n else None,
+                                                  n, h, w, _ptr(outs[0]) if n else None, _ptr(outs[1]) if n else None,
+                                                  _ptr(outs[2]) if n else None, _stream()))
+        return outs[0], outs[1], outs[2]
 
     def png_encode(self, maps: torch.Tensor, lut: torch.Tensor, out: torch.Tensor, cursor: torch.Tensor, table: torch.Tensor) -> None:
         """``gray/<stem>.png`` and ``color/<stem>.png`` of the class maps `maps` ([n, H, W] or [H, W] uint8 on this device, 255 =

@@ -61,7 +61,8 @@ def write_outputs(out_dir: str, stem: str, seg: np.ndarray, masks: Optional[np.n
                   rles: Optional[Sequence[dict]] = None, clock: Optional[StageClock] = None, png_level: int = tile_io.LEVEL_LABELS,
                   png_files: Optional[Tuple[bytes, bytes]] = None, mask_bboxes: Optional[Sequence] = None,
                   mask_rboxes: Optional[Sequence] = None, dota_txt: bool = False, scores: Optional[dict] = None,
-                  polygons: Optional[Sequence] = None, removed: Optional[Sequence[int]] = None, vis_file: Optional[bytes] = None) -> None:
+                  polygons: Optional[Sequence] = None, removed: Optional[Sequence[int]] = None, vis_file: Optional[bytes] = None,
+                  base_entries: Optional[Sequence[dict]] = None) -> None:
     """`rles`: the per-instance COCO RLE dicts when they were encoded on the device (driver.TileResult.rle); otherwise they are
     encoded here from `masks` (host restatement), or left out when both are None (--no-rle).  `png_files`: the complete
     (gray, color) PNG files when they were encoded on the device (--png-device: driver.TileResult.png, byte-identical with the
@@ -76,7 +77,10 @@ def write_outputs(out_dir: str, stem: str, seg: np.ndarray, masks: Optional[np.n
     the pickle entries' ``"polygons"`` (the list of vertex arrays, or None) and ``"polygon_holes"`` (the list of bool, or None).
     `removed` (--overlap logit / smallest): per instance the pixels the overlap stage gave to another instance; the entries' ``"removed"``
     (`areas` and `rles` are then those of the disjoint masks already).  `vis_file` (--vis): the complete ``vis/<stem>.png``, the
-    overlay blended and encoded on the device (driver.TileResult.png("vis")); written as it is, before the pickle."""
+    overlay blended and encoded on the device (driver.TileResult.png("vis")); written as it is, before the pickle.
+    `base_entries` (samrs_amd.relabel): entry j starts as a copy of ``base_entries[j]`` instead of the four standard keys, so every
+    key of an existing pickle survives (``rbox``, ``rhbox``, foreign ones); ``"size"`` and ``"mask"`` are replaced by those of the
+    masks as they go out, and the option keys are added as above."""
     import time
     t0 = time.perf_counter()
     for sub in ("gray", "color", "ins"):
@@ -109,7 +113,11 @@ def write_outputs(out_dir: str, stem: str, seg: np.ndarray, masks: Optional[np.n
     for j in range(len(labels)):                                                            # :200-206
         if scores is not None and not scores["kept"][j]:
             continue
-        entry = {"bbox": boxes[j], "category": class_names[int(labels[j])], "label": int(labels[j]), "size": int(areas[j])}
+        if base_entries is not None:
+            entry = dict(base_entries[j])
+            entry["size"] = int(areas[j])
+        else:
+            entry = {"bbox": boxes[j], "category": class_names[int(labels[j])], "label": int(labels[j]), "size": int(areas[j])}
         if scores is not None:
             for key in ("pred_iou", "stability", "inside_box"):
                 entry[key] = float(scores[key][j])

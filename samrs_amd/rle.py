@@ -11,7 +11,7 @@ pycocotools is not a dependency here, so the two pieces are restated:
 """
 from __future__ import annotations
 
-from typing import Dict, List
+from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
 
@@ -108,3 +108,52 @@ def decode(rle: Dict) -> np.ndarray:
         pos += c
         val = not val
     return flat.reshape((h, w), order="F")
+
+
+def pack_strings(rles: Sequence[Dict]) -> Tuple[np.ndarray, np.ndarray]:
+    """The strings of `rles` packed the way ``samrs_rle_encode`` packs them (host only): (uint8 buffer, int64 table [n, 3] =
+    (offset, length, 0)), every offset a multiple of 16.  ``counts`` may be a str, bytes (what pycocotools returns) or an
+    uncompressed list of counts, which is compressed with :func:`counts_to_string_np`."""
+    raw = []
+    for r in rles:
+        c = r["counts"]
+        if isinstance(c, str):
+            c = c.encode("ascii")
+        elif not isinstance(c, (bytes, bytearray)):
+            c = counts_to_string_np(np.asarray(c, dtype=np.int64)).encode("ascii")
+        raw.append(bytes(c))
+    table = np.zeros((len(raw), 3), dtype=np.int64)
+    off = 0
+    for j, c in enumerate(raw):
+        table[j, 0], table[j, 1] = off, len(c)
+        off += (len(c) + 15) & ~15
+    buf = np.zeros(off, dtype=np.uint8)
+    for j, c in enumerate(raw):
+        buf[table[j, 0]:table[j, 0] + len(c)] = np.frombuffer(c, dtype=np.uint8)
+    return buf, table
+
+
+def decode_device(engine, rles: Sequence[Dict]):
+    """`rles` (dicts of one ``size``) decoded on the device (``Engine.rle_decode``) -> torch.uint8 [n, h, w] of 0 / 1 there: one
+    upload of the packed strings, no host loop over counts.  ValueError for mixed sizes and for a string that does not decode,
+    naming its index and the status."""
+    import torch
+    from .engine import RLE_STATUS
+    if len(rles) == 0:
+        return torch.zeros(0, 1, 1, dtype=torch.uint8, device=engine.device)
+    sizes = {(int(r["size"][0]), int(r["size"][1])) for r in rles}
+    if len(sizes) != 1:
+        raise ValueError(f"decode_device: the RLEs have mixed sizes {sorted(sizes)}")
+    size = next(iter(sizes))
+    buf, table = pack_strings(rles)
+    both = np.concatenate([table.reshape(-1).view(np.uint8), buf])          # one H2D copy: the table, then the strings
+    dev = torch.from_numpy(both).to(engine.device)
+    nt = table.size * 8
+    masks, _, status = engine.rle_decode(dev[nt:], dev[:nt].view(torch.int64).view(-1, 3), size)
+    status = status.cpu().numpy()
+    bad = np.flatnonzero(status)
+    if bad.size:
+        j = int(bad[0])
+        raise ValueError(f"decode_device: RLE {j} does not decode: {RLE_STATUS[int(status[j])]}" +
+                         (f" ({bad.size - 1} more)" if bad.size > 1 else ""))
+    return masks
