@@ -453,7 +453,39 @@ int samrs_resolve_overlaps(samrs_engine_t* e, uint8_t* masks, int n, int h, int 
  * synchronisation: a NaN among them makes the kernel write n_kept = -1 and match nothing.  nd == 0 or ng == 0 is a valid image.
  * One block per area range, one wave per threshold; no host synchronisation.  Scratch: n_ranges * n_thresholds * ng bytes (+ 4 nd
  * for host scores) in ONE buffer per handle that grows on demand: calls on a handle must be stream-ordered with each other (same
- * stream, or an event between them); two handles never share it. */
+ * stream, or an event between them); two handles never share it.
+ *
+ * Boundary IoU and Boundary AP (Cheng et al., CVPR 2021): mask IoU is dominated by the interior of a large object, so a mask whose
+ * outline is a few pixels off still matches at every threshold; these count the band along the outline instead.  The rules below are
+ * the definition (the tests pin them to an independent host statement and to scipy.ndimage, not to cv2):
+ *   dilation      d = max(1, int(round(ratio * hypot(H, W)))), computed by the caller (samrs_amd.coco_ap.boundary_dilation); the
+ *                 usual ratio is 0.02: a 1024 x 1024 tile gives 29, 800 x 1200 gives 29, 45 x 70 gives 2.
+ *   band of M     band(M)[y][x] = M[y][x] AND NOT E[y][x], where E[y][x] = 1 iff every pixel of the (2 d + 1) x (2 d + 1) square
+ *                 centred on (y, x) lies inside the image and is set in M; everything outside the image counts as background.
+ *                 That is d iterations of a 3 x 3 all-ones erosion with a zero border; equivalently the band holds the set pixels
+ *                 within Chebyshev distance d of a background pixel or of the image edge.  Where w < 2 d + 1 or h < 2 d + 1 the band
+ *                 is the whole mask.
+ *   Boundary IoU  of prediction P and ground truth G: |band(P) AND band(G)| / |band(P) OR band(G)|, 0 for an empty union.
+ *   Boundary AP   samrs_coco_match's matching and COCO's accumulation with the pair score min(mask IoU, boundary IoU), each IoU a
+ *                 correctly rounded double.  Area ranges, the ground truths' ignore flags and the unmatched detection's ignore flag
+ *                 still use the MASK areas; order, ties, bar = min(t, 1 - 1e-10) and the match by index are samrs_coco_match's.
+ * samrs_mask_boundary_bits: planes uint64 [n][words] in the layout above (from samrs_mask_pack_bits or samrs_label_pack_bits alike)
+ *   -> band_out uint64 [n][words], tail bits zero; band_out must not overlap planes.  The square erosion runs as a horizontal and a
+ *   vertical pass on the packed bits, 64 pixels per lane operation; rows need not be word-aligned and a word may hold several rows.
+ *   One writer per output word, no atomics: deterministic.  A null handle or pointer, n < 0, h or w < 1, h * w >= 2^30, d outside
+ *   1..128 or an output that overlaps the input: SAMRS_ERR_BAD_ARG with nothing launched or written.  n == 0 is a no-op.  The
+ *   row-eroded planes live in ONE scratch per handle that grows on demand (8 bytes per word, at most 64 MiB: more masks are
+ *   banded in several passes): calls on a handle must be stream-ordered with each other.
+ * samrs_coco_match_min: samrs_coco_match with a second triple inter_b int64 [nd][ng], area_db int64 [nd], area_gb int64 [ng] -- the
+ *   samrs_mask_pair_counts of the two stacks' bands -- and the pair IoU replaced by min(IoU(inter, area_d, area_g), IoU(inter_b,
+ *   area_db, area_gb)).  The second triple is needed wherever the first is (else SAMRS_ERR_BAD_ARG); everything else, the scratch
+ *   and its stream-ordering rule included, is samrs_coco_match's, which itself is unchanged. */
+int samrs_mask_boundary_bits(samrs_engine_t* e, const uint64_t* planes, int n, int h, int w, int d, uint64_t* band_out, void* stream);
+int samrs_coco_match_min(samrs_engine_t* e, const int64_t* inter, const int64_t* area_d, const int64_t* area_g, const int64_t* inter_b,
+                         const int64_t* area_db, const int64_t* area_gb, const float* scores, int scores_on_host, int nd, int ng,
+                         const double* thresholds, int n_thresholds, const double* area_ranges, int n_ranges, int max_det,
+                         int32_t* order_out, int32_t* match_out, uint8_t* dt_ignore_out, int32_t* n_valid_out, int32_t* n_kept_out,
+                         void* stream);
 int samrs_mask_pack_bits(samrs_engine_t* e, const uint8_t* masks, int n, int h, int w, uint64_t* planes_out, void* stream);
 int samrs_label_pack_bits(samrs_engine_t* e, const uint8_t* label_rgb, const uint8_t* colors, int n, int h, int w, uint64_t* planes_out,
                           void* stream);

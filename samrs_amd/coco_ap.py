@@ -13,11 +13,28 @@ One deliberate difference from pycocotools: a match is a match BY INDEX.  pycoco
 ``gt_ins_<tag>.json`` restarts its ids at 0 per image (instance_to_json.py), so pycocotools would drop the first ship of every image.
 Here ground truth 0 is matched like any other, and ``ap.json`` says so (``"matching": "by index"``).  One category, no crowd
 annotations (the instance drivers write neither).
+
+Boundary AP (``--boundary``; Cheng et al., CVPR 2021).  Mask IoU is dominated by the interior of a large object: a mask whose outline
+is a few pixels off still scores above 0.95 and matches at every threshold.  Boundary AP runs the same matching and accumulation
+with the pair score min(mask IoU, boundary IoU), and the rules are (samrs_mask_boundary_bits in include/samrs_hip.h states them):
+
+    python -m samrs_amd.coco_ap --dt OUT/sam_ins_rhbox.json --gt OUT/gt_ins_rhbox.json --boundary --out OUT/boundary_ap.json
+
+* dilation: d = max(1, int(round(ratio * hypot(H, W)))) (``boundary_dilation``), ratio 0.02 by default: 29 for a 1024 x 1024 tile.
+* band(M)[y][x] = M[y][x] AND NOT E[y][x], E[y][x] = 1 iff every pixel of the (2 d + 1) x (2 d + 1) square centred on (y, x) lies
+  inside the image and is set in M (everything outside the image is background): d iterations of a 3 x 3 all-ones erosion with a
+  zero border.
+* Boundary IoU(P, G) = |band(P) AND band(G)| / |band(P) OR band(G)|, 0 for an empty union.
+* Area ranges, the ground truths' ignore flags and the unmatched detection's ignore flag still use the MASK areas; order, ties,
+  min(t, 1 - 1e-10) and the match by index are the mask matching's.
+The masks are packed once, banded on the device (``Engine.mask_boundary_bits``), counted twice and matched by the smaller IoU
+(``Engine.coco_match(boundary=...)``).  The definition is pinned by the tests to a host statement and to scipy.ndimage, not to cv2.
 """
 from __future__ import annotations
 
 import argparse
 import json
+import math
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -116,17 +133,49 @@ def summary_lines(numbers: Dict[str, float], max_dets: Sequence[int] = MAX_DETS)
             for t, ty, iou, area, m, key in rows]
 
 
-def ap_record(numbers: Dict[str, float], tables: Sequence[dict]) -> dict:
-    """What ``ap.json`` holds: the twelve numbers, the counts and how matches are told."""
+BOUNDARY_IOU = "min(mask, boundary)"
+DILATION_RATIO = 0.02
+
+
+def boundary_dilation(h: int, w: int, ratio: float = DILATION_RATIO) -> int:
+    """The band's width d for H x W masks: max(1, int(round(ratio * hypot(H, W)))) -- 29 for 1024 x 1024 and for 800 x 1200."""
+    return max(1, int(round(float(ratio) * math.hypot(int(h), int(w)))))
+
+
+def boundary_miou(band_inter, band_area_d, band_area_g) -> Dict[str, float]:
+    """Boundary mIoU over objects from their diagonal band counts: "average" = the mean of inter / union per object (0 for an empty
+    union), "area" = sum of inter / sum of union."""
+    i = np.asarray(band_inter, dtype=np.int64).reshape(-1)
+    u = np.asarray(band_area_d, dtype=np.int64).reshape(-1) + np.asarray(band_area_g, dtype=np.int64).reshape(-1) - i
+    per = np.divide(i.astype(np.float64), u.astype(np.float64), out=np.zeros(len(i)), where=u > 0)
+    return {"average": float(per.mean()) if len(per) else 0.0, "area": float(i.sum() / u.sum()) if u.sum() > 0 else 0.0}
+
+
+def boundary_heading(dilation_ratio: float = DILATION_RATIO) -> str:
+    """The line printed above the twelve lines of a Boundary AP."""
+    return f"Boundary AP (IoU = {BOUNDARY_IOU}, dilation ratio {float(dilation_ratio):g}):"
+
+
+def ap_record(numbers: Dict[str, float], tables: Sequence[dict], boundary: bool = False, dilation_ratio: float = DILATION_RATIO,
+              miou: Optional[Dict[str, float]] = None) -> dict:
+    """What ``ap.json`` holds: the twelve numbers, the counts and how matches are told.  `boundary`: a Boundary AP record
+    (``boundary_ap.json``) also says which IoU was matched on, the dilation ratio and, where known (`miou`, ``boundary_miou``'s
+    result), the Boundary mIoU.  A mask record is what it always was."""
     rec = {k: float(numbers[k]) for k in numbers}
     rec.update(n_images=len(tables), n_gt=int(sum(int(np.asarray(t["n_valid"]).reshape(-1)[0]) for t in tables)),
                n_dt=int(sum(len(np.asarray(t["scores"]).reshape(-1)) for t in tables)), matching="by index")
+    if boundary:
+        rec.update(iou=BOUNDARY_IOU, dilation_ratio=float(dilation_ratio))
+        if miou is not None:
+            rec["boundary_miou"] = {k: float(miou[k]) for k in ("average", "area")}
     return rec
 
 
-def match_image(engine, pred_masks, scores, gt_masks, max_det: int = MAX_DETS[-1]) -> dict:
+def match_image(engine, pred_masks, scores, gt_masks, max_det: int = MAX_DETS[-1], boundary: bool = False,
+                dilation_ratio: float = DILATION_RATIO) -> dict:
     """One image on the device -> its table (``image_table``).  pred_masks [nd, H, W] and gt_masks [ng, H, W]: bool / uint8 arrays
-    or tensors (uploaded when they are on the host); scores [nd]."""
+    or tensors (uploaded when they are on the host); scores [nd].  `boundary`: the Boundary AP table instead -- the planes are
+    banded with d = ``boundary_dilation(H, W, dilation_ratio)``, counted a second time and matched by min(mask IoU, boundary IoU)."""
     import torch
 
     def dev(m):
@@ -143,13 +192,19 @@ def match_image(engine, pred_masks, scores, gt_masks, max_det: int = MAX_DETS[-1
     ga = engine.pack_mask_bits(g) if g.shape[0] else empty()
     inter, ad, ag = engine.mask_pair_counts(pa, ga)
     sc = np.asarray(scores.cpu() if isinstance(scores, torch.Tensor) else scores, dtype=np.float32).reshape(-1)
-    order, match, ign, n_valid, n_kept = engine.coco_match(inter, ad, ag, sc, max_det=max_det)
+    band = None
+    if boundary:
+        if len(hw) == 2 and hw[0] * hw[1]:
+            d = boundary_dilation(hw[0], hw[1], dilation_ratio)
+            pa, ga = engine.mask_boundary_bits(pa, hw[0], hw[1], d), engine.mask_boundary_bits(ga, hw[0], hw[1], d)
+        band = engine.mask_pair_counts(pa, ga)
+    order, match, ign, n_valid, n_kept = engine.coco_match(inter, ad, ag, sc, max_det=max_det, boundary=band)
     return image_table(sc, order.cpu().numpy(), match.cpu().numpy(), ign.cpu().numpy(), n_valid.cpu().numpy(), int(n_kept.cpu()[0]))
 
 
-def evaluate_masks(engine, images, max_dets: Sequence[int] = MAX_DETS):
-    """`images`: (pred_masks, scores, gt_masks) per image -> (the twelve numbers, the per-image tables)."""
-    tables = [match_image(engine, p, s, g, max_det=max(max_dets)) for p, s, g in images]
+def evaluate_masks(engine, images, max_dets: Sequence[int] = MAX_DETS, boundary: bool = False, dilation_ratio: float = DILATION_RATIO):
+    """`images`: (pred_masks, scores, gt_masks) per image -> (the twelve numbers, the per-image tables); `boundary`: Boundary AP."""
+    tables = [match_image(engine, p, s, g, max_det=max(max_dets), boundary=boundary, dilation_ratio=dilation_ratio) for p, s, g in images]
     return accumulate(tables, max_dets), tables
 
 
@@ -170,9 +225,9 @@ def load_coco_files(dt_path: str, gt_path: str):
     return [i for i in dts if i in gts], dts, gts
 
 
-def evaluate_files(engine, dt_path: str, gt_path: str):
+def evaluate_files(engine, dt_path: str, gt_path: str, boundary: bool = False, dilation_ratio: float = DILATION_RATIO):
     """Any pair of such files on the GPU: per image the RLE strings are uploaded as they are and decoded on the device
-    (``samrs_amd.rle.decode_device``, samrs_rle_decode); the masks never exist on the host."""
+    (``samrs_amd.rle.decode_device``, samrs_rle_decode); the masks never exist on the host.  `boundary`: Boundary AP."""
     import torch
     from . import rle
     ids, dts, gts = load_coco_files(dt_path, gt_path)
@@ -183,22 +238,30 @@ def evaluate_files(engine, dt_path: str, gt_path: str):
             stack = lambda segs: (rle.decode_device(engine, segs) if segs
                                   else torch.zeros(0, size[0], size[1], dtype=torch.uint8, device=engine.device))
             yield stack([s for _, s in dts[i]]), np.array([sc for sc, _ in dts[i]], dtype=np.float32), stack(gts[i])
-    return evaluate_masks(engine, images())
+    return evaluate_masks(engine, images(), boundary=boundary, dilation_ratio=dilation_ratio)
 
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description="COCO mask AP of sam_ins_<tag>.json against gt_ins_<tag>.json, evaluated on the GPU")
     ap.add_argument("--dt", required=True, help="COCO results file (sam_ins_<tag>.json)")
     ap.add_argument("--gt", required=True, help="COCO dataset file (gt_ins_<tag>.json)")
-    ap.add_argument("--out", default=None, help="write the record here (ap.json)")
+    ap.add_argument("--out", default=None, help="write the record here (ap.json; with --boundary: boundary_ap.json)")
     ap.add_argument("--model", default="vit_tiny", help="the engine that hosts the kernels (no weights are used)")
+    ap.add_argument("--boundary", action="store_true",
+                    help="Boundary AP: match on min(mask IoU, boundary IoU), the bands computed on the GPU (samrs_mask_boundary_bits)")
+    ap.add_argument("--dilation-ratio", type=float, default=DILATION_RATIO, metavar="R",
+                    help="with --boundary: the band's width as a fraction of the image diagonal (default 0.02)")
     args = ap.parse_args(argv)
+    if not (args.dilation_ratio > 0):
+        ap.error("--dilation-ratio must be > 0")
     import samrs_amd
     sam = samrs_amd.sam_model_registry[args.model](max_prompts=1).to("cuda:0")
-    numbers, tables = evaluate_files(sam.engine, args.dt, args.gt)
+    numbers, tables = evaluate_files(sam.engine, args.dt, args.gt, boundary=args.boundary, dilation_ratio=args.dilation_ratio)
+    if args.boundary:
+        print(boundary_heading(args.dilation_ratio), flush=True)
     for line in summary_lines(numbers):
         print(line, flush=True)
-    rec = ap_record(numbers, tables)
+    rec = ap_record(numbers, tables, boundary=args.boundary, dilation_ratio=args.dilation_ratio)
     if args.out:
         with open(args.out, "w") as f:
             json.dump(rec, f)

@@ -210,8 +210,13 @@ __device__ __forceinline__ void cand_reduce(Cand& c) {         // greatest IoU, 
 }
 
 // grid = area ranges, block = 64 T threads, dynamic LDS = max_det ints.  gmatched: zeroed bytes [A][T][ng].
+// MIN (samrs_coco_match_min): a second triple of counts, those of the masks' boundary bands, and the pair's score is the smaller of
+// the two IoUs; areas, ignore flags and everything else stay the first triple's.  Without MIN the second triple is not looked at.
+template <bool MIN>
 __global__ void coco_match_kernel(const long long* __restrict__ inter, const long long* __restrict__ area_d,
-                                  const long long* __restrict__ area_g, const float* __restrict__ scores, int nd, int ng, CocoMatchParams P,
+                                  const long long* __restrict__ area_g, const long long* __restrict__ inter_b,
+                                  const long long* __restrict__ area_db, const long long* __restrict__ area_gb,
+                                  const float* __restrict__ scores, int nd, int ng, CocoMatchParams P,
                                   int T, int max_det, uint8_t* __restrict__ gmatched, int32_t* __restrict__ order_out,
                                   int32_t* __restrict__ match_out, uint8_t* __restrict__ ign_out, int32_t* __restrict__ n_valid_out,
                                   int32_t* __restrict__ n_kept_out) {
@@ -274,7 +279,12 @@ __global__ void coco_match_kernel(const long long* __restrict__ inter, const lon
         for (int g = lane; g < ng; g += 64) {
             if (gm[g]) continue;
             const long long ag = area_g[g], in = row[g], un = ad + ag - in;
-            const double iou = (un > 0 && in > 0) ? iou_rn(in, un) : 0.0;
+            double iou = (un > 0 && in > 0) ? iou_rn(in, un) : 0.0;
+            if constexpr (MIN) {
+                const long long inb = inter_b[(size_t)d * ng + g], unb = area_db[d] + area_gb[g] - inb;
+                const double iou_b = (unb > 0 && inb > 0) ? iou_rn(inb, unb) : 0.0;
+                iou = iou_b < iou ? iou_b : iou;
+            }
             const bool ig = (double)ag < lo || (double)ag > hi;
             Cand& c = ig ? ci : cv;
             if (iou >= c.iou) {                                  // ascending g: the later one on a tie
@@ -352,16 +362,24 @@ size_t coco_match_scratch_bytes(int ng, int n_thresholds, int n_ranges) {
     return (((size_t)(ng > 0 ? ng : 1) * n_thresholds * n_ranges) + 15) / 16 * 16;
 }
 
-hipError_t launch_coco_match(const long long* inter, const long long* area_d, const long long* area_g, const float* scores, int nd, int ng,
-                             const CocoMatchParams& P, int n_thresholds, int n_ranges, int max_det, void* scratch, int32_t* order_out,
+hipError_t launch_coco_match(const long long* inter, const long long* area_d, const long long* area_g, const long long* inter_b,
+                             const long long* area_db, const long long* area_gb, const float* scores, int nd, int ng, const CocoMatchParams& P, int n_thresholds, int n_ranges, int max_det, void* scratch, int32_t* order_out,
                              int32_t* match_out, uint8_t* ign_out, int32_t* n_valid_out, int32_t* n_kept_out, hipStream_t s) {
     if (nd < 0 || ng < 0 || n_thresholds < 1 || n_thresholds > COCO_MAX_THRESHOLDS || n_ranges < 1 || n_ranges > COCO_MAX_RANGES ||
         max_det < 1 || max_det > COCO_MAX_DET || !scratch || !order_out || !match_out || !ign_out || !n_valid_out || !n_kept_out)
         return hipErrorInvalidValue;
     if ((nd > 0 && (!scores || !area_d)) || (ng > 0 && !area_g) || (nd > 0 && ng > 0 && !inter)) return hipErrorInvalidValue;
+    const bool with_min = inter_b || area_db || area_gb;       // the band triple: all of it where the first triple is needed, or none
+    if (with_min && ((nd > 0 && !area_db) || (ng > 0 && !area_gb) || (nd > 0 && ng > 0 && !inter_b))) return hipErrorInvalidValue;
     HIP_CHECK_RET(hipMemsetAsync(scratch, 0, coco_match_scratch_bytes(ng, n_thresholds, n_ranges), s));
-    coco_match_kernel<<<n_ranges, 64 * n_thresholds, sizeof(int) * (size_t)max_det, s>>>(inter, area_d, area_g, scores, nd, ng, P, n_thresholds,
-                                                                                        max_det, (uint8_t*)scratch, order_out, match_out,
-                                                                                        ign_out, n_valid_out, n_kept_out);
+    const size_t lds = sizeof(int) * (size_t)max_det;
+    if (with_min)
+        coco_match_kernel<true><<<n_ranges, 64 * n_thresholds, lds, s>>>(inter, area_d, area_g, inter_b, area_db, area_gb, scores, nd, ng, P,
+                                                                         n_thresholds, max_det, (uint8_t*)scratch, order_out, match_out,
+                                                                         ign_out, n_valid_out, n_kept_out);
+    else
+        coco_match_kernel<false><<<n_ranges, 64 * n_thresholds, lds, s>>>(inter, area_d, area_g, nullptr, nullptr, nullptr, scores, nd, ng, P,
+                                                                          n_thresholds, max_det, (uint8_t*)scratch, order_out, match_out,
+                                                                          ign_out, n_valid_out, n_kept_out);
     return hipGetLastError();
 }

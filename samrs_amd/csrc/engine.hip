@@ -318,7 +318,7 @@ void samrs_destroy(samrs_engine_t* e) {
     if (!e) return;
     DeviceGuard dg(e->device);
     for (void* p : e->owned) (void)hipFree(p);
-    for (DeviceScratch* sc : {&e->rle_scratch, &e->rle_decode_scratch, &e->region_scratch, &e->box_scratch, &e->poly_scratch, &e->png_scratch, &e->png_rgb_scratch, &e->overlap_scratch, &e->ap_scratch}) scratch_release(*sc);
+    for (DeviceScratch* sc : {&e->rle_scratch, &e->rle_decode_scratch, &e->region_scratch, &e->box_scratch, &e->poly_scratch, &e->png_scratch, &e->png_rgb_scratch, &e->overlap_scratch, &e->ap_scratch, &e->boundary_scratch}) scratch_release(*sc);
     delete e;
 }
 

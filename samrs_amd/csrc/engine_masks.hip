@@ -295,30 +295,34 @@ int samrs_mask_pair_counts(samrs_engine_t* e, const uint64_t* a, int na, const u
                                  (unsigned long long*)inter_out, s));
     return SAMRS_OK;
 }
-int samrs_coco_match(samrs_engine_t* e, const int64_t* inter, const int64_t* area_d, const int64_t* area_g, const float* scores,
-                     int scores_on_host, int nd, int ng, const double* thresholds, int n_thresholds, const double* area_ranges,
-                     int n_ranges, int max_det, int32_t* order_out, int32_t* match_out, uint8_t* dt_ignore_out, int32_t* n_valid_out,
-                     int32_t* n_kept_out, void* stream) {
+// samrs_coco_match (band triple null) and samrs_coco_match_min (`with_min`: the triple is required like the first one)
+static int coco_match_entry(const char* who, bool with_min, samrs_engine_t* e, const int64_t* inter, const int64_t* area_d,
+                            const int64_t* area_g, const int64_t* inter_b, const int64_t* area_db, const int64_t* area_gb, const float* scores,
+                            int scores_on_host, int nd, int ng, const double* thresholds, int n_thresholds, const double* area_ranges,
+                            int n_ranges, int max_det, int32_t* order_out, int32_t* match_out, uint8_t* dt_ignore_out, int32_t* n_valid_out,
+                            int32_t* n_kept_out, void* stream) {
+    if (with_min && ((nd > 0 && !area_db) || (ng > 0 && !area_gb) || (nd > 0 && ng > 0 && !inter_b)))
+        return fail(e, SAMRS_ERR_BAD_ARG, "%s: bad argument", who);
     if (!e || nd < 0 || ng < 0 || !thresholds || !area_ranges || !order_out || !match_out || !dt_ignore_out || !n_valid_out || !n_kept_out ||
         (nd > 0 && (!scores || !area_d)) || (ng > 0 && !area_g) || (nd > 0 && ng > 0 && !inter))
-        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_coco_match: bad argument");
+        return fail(e, SAMRS_ERR_BAD_ARG, "%s: bad argument", who);
     if (n_thresholds < 1 || n_thresholds > COCO_MAX_THRESHOLDS || n_ranges < 1 || n_ranges > COCO_MAX_RANGES || max_det < 1 ||
         max_det > COCO_MAX_DET)
-        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_coco_match: %d thresholds (1..%d), %d area ranges (1..%d), max_det %d (1..%d)", n_thresholds,
+        return fail(e, SAMRS_ERR_BAD_ARG, "%s: %d thresholds (1..%d), %d area ranges (1..%d), max_det %d (1..%d)", who, n_thresholds,
                     COCO_MAX_THRESHOLDS, n_ranges, COCO_MAX_RANGES, max_det, COCO_MAX_DET);
     CocoMatchParams P{};
     for (int t = 0; t < n_thresholds; ++t) {
-        if (std::isnan(thresholds[t])) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_coco_match: threshold %d is NaN", t);
+        if (std::isnan(thresholds[t])) return fail(e, SAMRS_ERR_BAD_ARG, "%s: threshold %d is NaN", who, t);
         P.bar[t] = std::fmin(thresholds[t], 1.0 - 1e-10);
     }
     for (int a = 0; a < n_ranges; ++a) {
         P.lo[a] = area_ranges[2 * a];
         P.hi[a] = area_ranges[2 * a + 1];
-        if (std::isnan(P.lo[a]) || std::isnan(P.hi[a])) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_coco_match: area range %d is NaN", a);
+        if (std::isnan(P.lo[a]) || std::isnan(P.hi[a])) return fail(e, SAMRS_ERR_BAD_ARG, "%s: area range %d is NaN", who, a);
     }
     if (scores_on_host)
         for (int d = 0; d < nd; ++d)
-            if (std::isnan(scores[d])) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_coco_match: score %d is NaN", d);
+            if (std::isnan(scores[d])) return fail(e, SAMRS_ERR_BAD_ARG, "%s: score %d is NaN", who, d);
     ON_DEVICE(e);
     hipStream_t s = (hipStream_t)stream;
     const size_t flags = coco_match_scratch_bytes(ng, n_thresholds, n_ranges);
@@ -329,8 +333,52 @@ int samrs_coco_match(samrs_engine_t* e, const int64_t* inter, const int64_t* are
         CK(e, hipMemcpyAsync(staged, scores, sizeof(float) * (size_t)nd, hipMemcpyHostToDevice, s));
         dev_scores = staged;
     }
-    CK(e, launch_coco_match((const long long*)inter, (const long long*)area_d, (const long long*)area_g, dev_scores, nd, ng, P, n_thresholds,
-                            n_ranges, max_det, e->ap_scratch.p, order_out, match_out, dt_ignore_out, n_valid_out, n_kept_out, s));
+    CK(e, launch_coco_match((const long long*)inter, (const long long*)area_d, (const long long*)area_g,
+                            with_min ? (const long long*)inter_b : nullptr, with_min ? (const long long*)area_db : nullptr,
+                            with_min ? (const long long*)area_gb : nullptr, dev_scores, nd, ng, P, n_thresholds, n_ranges, max_det,
+                            e->ap_scratch.p, order_out, match_out, dt_ignore_out, n_valid_out, n_kept_out, s));
+    return SAMRS_OK;
+}
+
+int samrs_coco_match(samrs_engine_t* e, const int64_t* inter, const int64_t* area_d, const int64_t* area_g, const float* scores,
+                     int scores_on_host, int nd, int ng, const double* thresholds, int n_thresholds, const double* area_ranges,
+                     int n_ranges, int max_det, int32_t* order_out, int32_t* match_out, uint8_t* dt_ignore_out, int32_t* n_valid_out,
+                     int32_t* n_kept_out, void* stream) {
+    return coco_match_entry("samrs_coco_match", false, e, inter, area_d, area_g, nullptr, nullptr, nullptr, scores, scores_on_host, nd, ng,
+                            thresholds, n_thresholds, area_ranges, n_ranges, max_det, order_out, match_out, dt_ignore_out, n_valid_out,
+                            n_kept_out, stream);
+}
+int samrs_coco_match_min(samrs_engine_t* e, const int64_t* inter, const int64_t* area_d, const int64_t* area_g, const int64_t* inter_b,
+                         const int64_t* area_db, const int64_t* area_gb, const float* scores, int scores_on_host, int nd, int ng,
+                         const double* thresholds, int n_thresholds, const double* area_ranges, int n_ranges, int max_det,
+                         int32_t* order_out, int32_t* match_out, uint8_t* dt_ignore_out, int32_t* n_valid_out, int32_t* n_kept_out,
+                         void* stream) {
+    return coco_match_entry("samrs_coco_match_min", true, e, inter, area_d, area_g, inter_b, area_db, area_gb, scores, scores_on_host, nd, ng,
+                            thresholds, n_thresholds, area_ranges, n_ranges, max_det, order_out, match_out, dt_ignore_out, n_valid_out,
+                            n_kept_out, stream);
+}
+
+// the boundary bands of n bit planes (see samrs_hip.h)
+int samrs_mask_boundary_bits(samrs_engine_t* e, const uint64_t* planes, int n, int h, int w, int d, uint64_t* band_out, void* stream) {
+    if (!e || !planes || !band_out || n < 0) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_mask_boundary_bits: bad argument");
+    if (h < 1 || w < 1 || (long long)h * w >= (1ll << 30))
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_mask_boundary_bits: masks %d x %d (h, w >= 1, h * w < 2^30)", h, w);
+    if (d < 1 || d > 128) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_mask_boundary_bits: d = %d must lie in 1..128", d);
+    const size_t words = ((size_t)h * w + 63) / 64, total = words * (size_t)n;
+    if (n > 0 && planes < band_out + total && band_out < planes + total)
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_mask_boundary_bits: band_out overlaps planes");
+    if (n == 0) return SAMRS_OK;
+    ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t cap = ((size_t)64 << 20) / (words * sizeof(uint64_t));      // masks per pass: the intermediate planes stay below 64 MiB
+    const int chunk = cap < 1 ? 1 : ((size_t)n < cap ? n : (int)cap);
+    const bool trivial = w < 2 * d + 1 || h < 2 * d + 1;                     // no square fits: the band is the mask, no intermediate
+    if (!trivial) CK(e, scratch_reserve(e->boundary_scratch, mask_boundary_scratch_bytes(chunk, h, w), s));
+    for (int off = 0; off < n; off += chunk) {
+        const int m = n - off < chunk ? n - off : chunk;
+        CK(e, launch_mask_boundary((const unsigned long long*)planes + (size_t)off * words, m, h, w, d,
+                                   trivial ? nullptr : e->boundary_scratch.p, (unsigned long long*)band_out + (size_t)off * words, s));
+    }
     return SAMRS_OK;
 }
 

@@ -244,7 +244,8 @@ struct samrs_engine {
     DeviceScratch png_scratch;     // class-map PNG scratch (samrs_png_encode_labels)
     DeviceScratch png_rgb_scratch; // filtered bytes + code tables of samrs_png_encode_rgb
     DeviceScratch overlap_scratch; // entry areas of samrs_resolve_overlaps (rule SMALLEST without before_out)
-    DeviceScratch ap_scratch;      // matched flags (+ host scores staged) of samrs_coco_match
+    DeviceScratch ap_scratch;      // matched flags (+ host scores staged) of samrs_coco_match / samrs_coco_match_min
+    DeviceScratch boundary_scratch;    // the row-eroded planes of samrs_mask_boundary_bits
 
     // optional in-situ timing of the dominant kernel (MLP lin1 + GELU GEMM) with HIP events
     bool timing = false;

@@ -383,9 +383,20 @@ hipError_t launch_pair_counts(const unsigned long long* a, int na, const unsigne
 constexpr int COCO_MAX_THRESHOLDS = 16, COCO_MAX_RANGES = 16, COCO_MAX_DET = 4096;
 struct CocoMatchParams { double bar[COCO_MAX_THRESHOLDS], lo[COCO_MAX_RANGES], hi[COCO_MAX_RANGES]; };
 size_t coco_match_scratch_bytes(int ng, int n_thresholds, int n_ranges);
-hipError_t launch_coco_match(const long long* inter, const long long* area_d, const long long* area_g, const float* scores, int nd, int ng,
-                             const CocoMatchParams& P, int n_thresholds, int n_ranges, int max_det, void* scratch, int32_t* order_out,
+// inter_b / area_db / area_gb: the same counts of the masks' boundary bands (samrs_coco_match_min: the pair's IoU is the smaller of the
+// two), or all three null: the plain matching, whose kernel does not look at them.
+hipError_t launch_coco_match(const long long* inter, const long long* area_d, const long long* area_g, const long long* inter_b,
+                             const long long* area_db, const long long* area_gb, const float* scores, int nd, int ng, const CocoMatchParams& P, int n_thresholds, int n_ranges, int max_det, void* scratch, int32_t* order_out,
                              int32_t* match_out, uint8_t* ign_out, int32_t* n_valid_out, int32_t* n_kept_out, hipStream_t s);
+
+// ---- boundary_kernels.hip -------------------------------------------------------------------
+// The boundary bands of n >= 1 bit planes [n][words] (ap_kernels.hip's layout) of h x w masks: band = M & ~E, E = M eroded by the
+// (2 d + 1)^2 square with everything outside the image as background (the definition: samrs_hip.h samrs_mask_boundary_bits).
+// 1 <= d <= 128, h * w < 2^30; band_out [n][words] must not overlap planes; tail bits zero.  scratch: mask_boundary_scratch_bytes(n, h, w)
+// (one intermediate plane per mask; unused, and may be null, where w or h < 2 d + 1).
+size_t mask_boundary_scratch_bytes(int n, int h, int w);
+hipError_t launch_mask_boundary(const unsigned long long* planes, int n, int h, int w, int d, void* scratch, unsigned long long* band_out,
+                                hipStream_t s);
 
 // ---- polygon_kernels.hip --------------------------------------------------------------------
 // Mask outlines as polygons on the pixel lattice (definition: the header comment of polygon_kernels.hip; contract: samrs_hip.h

@@ -345,6 +345,16 @@ class TileResult:
     ap_dt_ignore: Optional[np.ndarray] = None   # uint8 [4, 10, 100] the detection does not count at that range / threshold
     ap_n_valid: Optional[np.ndarray] = None     # int32 [4] ground truths inside each area range
     ap_n_kept: Optional[np.ndarray] = None      # int32 [1] ranks in use = min(n_boxes, 100)
+    # InstancePipeline(gt=True, ap=True, boundary=True): the same matching on min(mask IoU, boundary IoU) (samrs_coco_match_min) ...
+    boundary_order: Optional[np.ndarray] = None     # int32 [100], as ap_order (the scores are the same, so it equals ap_order)
+    boundary_match: Optional[np.ndarray] = None     # int32 [4, 10, 100], as ap_match
+    boundary_dt_ignore: Optional[np.ndarray] = None # uint8 [4, 10, 100], as ap_dt_ignore
+    boundary_n_valid: Optional[np.ndarray] = None   # int32 [4], as ap_n_valid (the area ranges look at the MASK areas)
+    boundary_n_kept: Optional[np.ndarray] = None    # int32 [1], as ap_n_kept
+    # ... and per object the diagonal of the band counts, for the Boundary mIoU (union = band_area_d + band_area_g - band_inter):
+    band_inter: Optional[np.ndarray] = None     # int64 [n_boxes] |band(kept mask j) AND band(ground truth j)|
+    band_area_d: Optional[np.ndarray] = None    # int64 [n_boxes] |band(kept mask j)|
+    band_area_g: Optional[np.ndarray] = None    # int64 [n_boxes] |band(ground truth j)|
     windows: Optional[List[Tuple[int, int, int, int]]] = None   # scene mode (scene.ScenePipeline): the planned (x0, y0, w, h) windows
     window_of: Optional[List[int]] = None   # scene mode: window_of[j] = index into `windows` of the window box j was decoded in
 
@@ -356,6 +366,16 @@ class TileResult:
             return None
         return {"scores": np.asarray(self.quality, dtype=np.float64), "order": self.ap_order, "match": self.ap_match,
                 "dt_ignore": self.ap_dt_ignore, "n_valid": self.ap_n_valid, "n_kept": int(self.ap_n_kept[0])}
+
+    @property
+    def boundary_tables(self) -> Optional[dict]:
+        """This tile's Boundary AP matching, shaped like ``ap_tables``, plus the per-object band counts band_inter, band_area_d and
+        band_area_g (int64 [n_boxes]); None unless the pipeline ran with boundary=True."""
+        if self.boundary_order is None:
+            return None
+        return {"scores": np.asarray(self.quality, dtype=np.float64), "order": self.boundary_order, "match": self.boundary_match,
+                "dt_ignore": self.boundary_dt_ignore, "n_valid": self.boundary_n_valid, "n_kept": int(self.boundary_n_kept[0]),
+                "band_inter": self.band_inter, "band_area_d": self.band_area_d, "band_area_g": self.band_area_g}
 
     def png(self, kind: str) -> memoryview:
         """The bytes of ``gray/<stem>.png`` (kind "gray") or ``color/<stem>.png`` ("color") of this tile, encoded on the device
@@ -426,11 +446,12 @@ class OutputTable(NamedTuple):
 
 
 def output_tables(min_region_area: int = 0, mask_boxes: bool = False, quality: bool = False, gt: bool = False, rle: bool = False,
-                  instance: bool = False, overlap: str = "order", ap: bool = False) -> List[OutputTable]:
+                  instance: bool = False, overlap: str = "order", ap: bool = False, boundary: bool = False) -> List[OutputTable]:
     """The per-box tables a pipeline with these (resolved) options allocates, copies to the host and hands out, in that order.
     Pure.  An option that is off contributes nothing: no allocation, no copy, and its TileResult fields stay None.  `instance`: an
     InstancePipeline, which always reports the predicted IoU of the mask it kept.  `ap`: the per-tile tables of the COCO matching
-    (``AP_SHAPE`` = area ranges, IoU thresholds, max detections)."""
+    (``AP_SHAPE`` = area ranges, IoU thresholds, max detections); `boundary`: a second set of them for the matching on min(mask IoU,
+    boundary IoU), and per box the diagonal band counts."""
     T, i64, i32 = OutputTable, torch.int64, torch.int32
     tabs = [T("areas", "area_dev", (), i64)]
     if min_region_area:
@@ -454,6 +475,14 @@ def output_tables(min_region_area: int = 0, mask_boxes: bool = False, quality: b
         tabs += [T("ap_order", "ap_order_dev", (D,), i32, **tile), T("ap_match", "ap_match_dev", (A, Tn, D), i32, **tile),
                  T("ap_dt_ignore", "ap_ign_dev", (A, Tn, D), torch.uint8, **tile), T("ap_n_valid", "ap_nvalid_dev", (A,), i32, **tile),
                  T("ap_n_kept", "ap_nkept_dev", (1,), i32, **tile)]
+    if boundary:
+        A, Tn, D = AP_SHAPE
+        tile = dict(fill=None, per_tile=True)       # written whole by samrs_coco_match_min
+        tabs += [T("boundary_order", "bd_order_dev", (D,), i32, **tile), T("boundary_match", "bd_match_dev", (A, Tn, D), i32, **tile),
+                 T("boundary_dt_ignore", "bd_ign_dev", (A, Tn, D), torch.uint8, **tile),
+                 T("boundary_n_valid", "bd_nvalid_dev", (A,), i32, **tile), T("boundary_n_kept", "bd_nkept_dev", (1,), i32, **tile),
+                 T("band_inter", "band_inter_dev", (), i64), T("band_area_d", "band_ad_dev", (), i64),
+                 T("band_area_g", "band_ag_dev", (), i64)]
     return tabs
 
 
@@ -596,6 +625,13 @@ def validate_vis_options(vis_lut, vis_alpha: float = 0.4, vis_buffer_mb: Optiona
     return lut, alpha
 
 
+def refuse_boundary_option(who: str, why: str, **opts) -> None:
+    """ValueError naming InstancePipeline's `boundary` option when `who` (a pipeline without ground truth to match against) was handed it."""
+    if opts.get("boundary"):
+        raise ValueError(f"{who} evaluates nothing against ground truth ({why}): boundary is an InstancePipeline option "
+                         f"(gt=True, ap=True, boundary=True)")
+
+
 def refuse_overlap_option(who: str, why: str, **opts) -> None:
     """ValueError naming TilePipeline's `overlap` option when `who` (a pipeline that does not resolve overlapping masks) was handed
     anything but "order"."""
@@ -670,7 +706,7 @@ class TilePipeline:
                  region_mode: str = "both", mask_boxes: bool = False, quality: bool = False, min_stability: float = 0.0,
                  min_pred_iou: float = 0.0, min_inside_box: float = 0.0, polygons: bool = False, polygon_buffer_mb: int = 64,
                  polygon_max_edges: int = 65536, overlap: str = "order", vis_lut: Optional[np.ndarray] = None, vis_alpha: float = 0.4,
-                 vis_buffer_mb: Optional[int] = None):
+                 vis_buffer_mb: Optional[int] = None, boundary: bool = False):
         """precision: the operand-split mode (engine option "split") THIS PIPELINE'S OWN CALLS run in.  The option is set around
         each of the pipeline's encode / decode calls and restored afterwards (``Engine.options``), so the mode never outlives
         them: a ``SamPredictor`` built on the same model keeps the engine's own default (round 3 changed the engine's option for
@@ -725,6 +761,7 @@ class TilePipeline:
         engine cuts it into chains of its own), so n_boxes x H x W mask bytes live at once (512 MiB for 512 boxes of a 1024^2
         tile).  Under batch_decode the tile's rows of the batch's call are used as they are."""
         from .transforms import ResizeLongestSide
+        refuse_boundary_option("TilePipeline", "Boundary AP needs the instance pipeline's ground truth", boundary=boundary)
         lut, poly_vertices = validate_output_options(min_region_area, region_mode, polygons, polygon_buffer_mb, polygon_max_edges, png_lut,
                                                      overlap)
         vlut, self.vis_alpha = validate_vis_options(vis_lut, vis_alpha, vis_buffer_mb)
@@ -781,7 +818,7 @@ class TilePipeline:
         self.seg_dev = [torch.empty(batch, side, side, dtype=torch.uint8, device=dev) for _ in range(2)]
         # the fixed per-box outputs: one declaration each (output_tables), two device tables per entry under the entry's name
         self.tables = output_tables(self.min_region_area, self.mask_boxes, self.quality, self.gt, rle, self.INSTANCE, self.overlap,
-                                    self.ap)
+                                    self.ap, self.boundary)
         for t in self.tables:
             setattr(self, t.dev, [t.alloc(batch, max_boxes, dev) for _ in range(2)])
         # the packed outputs, per input set: the payload (16-byte aligned entries) here, cursor and table in the stream
@@ -949,9 +986,10 @@ class TilePipeline:
             if not self.vis:                                       # with vis_lut the blend reads input set b after the encoder: _decode
                 self.ev_in_free[b].record(self.s_enc)
 
-    multimask = False      # InstancePipeline sets these four
+    multimask = False      # InstancePipeline sets these five
     gt = False
     ap = False
+    boundary = False
     INSTANCE = False
 
     def _tile_prompts(self, b: int, tile, hw, off: int, nb: int):
@@ -1208,7 +1246,7 @@ class InstancePipeline(TilePipeline):
     INSTANCE = True
 
     def __init__(self, sam, n_classes: int, prompt: str = "box", multimask: bool = True, fill_rule: str = "auto", gt: bool = False,
-                 ap: bool = False, **kw):
+                 ap: bool = False, boundary: bool = False, dilation_ratio: float = 0.02, **kw):
         """prompt: "box" / "rbox_mask" (annotations = rotated boxes [n, 4, 2]) or "point"
         (main_sam_hbox_mask_instance.py:160-165: annotations = one foreground point [n, 2] per object, handed to the prompt
         encoder AS IS -- the reference does not run them through apply_coords -- labels all 1, no box, no mask;
@@ -1219,12 +1257,23 @@ class InstancePipeline(TilePipeline):
         after the tile's last chunk ``Engine.mask_pair_counts`` and ``Engine.coco_match`` (score = the kept mask's predicted IoU)
         run on the decode stream and ``TileResult.ap_tables`` holds the fixed-size tables ``coco_ap.accumulate`` takes.  The plane
         buffers hold one tile and grow on demand (max_boxes x ceil(H W / 64) words each); tiles follow each other on one stream.
-        False (default) launches and allocates nothing, and every other output is byte for byte the same either way."""
+        False (default) launches and allocates nothing, and every other output is byte for byte the same either way.
+        boundary (needs ap=True): Boundary AP's matching beside it (the rules: samrs_mask_boundary_bits in include/samrs_hip.h).  Two
+        more plane buffers of the same size; after the tile's last chunk, on the decode stream, both stacks of planes are banded
+        (``Engine.mask_boundary_bits``, d = ``coco_ap.boundary_dilation(H, W, dilation_ratio)``), counted a second time and matched by
+        min(mask IoU, boundary IoU) into a second set of fixed-size tables: ``TileResult.boundary_tables``, which also holds the
+        per-object band counts ``band_inter`` / ``band_area_d`` / ``band_area_g`` for the Boundary mIoU.  False (default) launches
+        and allocates nothing, and every other output, ``ap_tables`` included, is byte for byte the same either way."""
         if prompt not in ("box", "rbox_mask", "point"):
             raise ValueError("prompt must be 'box', 'rbox_mask' or 'point'")
         if ap and not gt:
             raise ValueError("InstancePipeline(ap=True) matches predictions against the ground truth: it needs gt=True")
+        if boundary and not ap:
+            raise ValueError("InstancePipeline(boundary=True) is a second matching beside the mask AP's: it needs ap=True")
+        if boundary and not (float(dilation_ratio) > 0):
+            raise ValueError(f"dilation_ratio must be > 0, got {dilation_ratio!r}")
         self.ap = bool(ap)             # read by TilePipeline.__init__ (output_tables)
+        self.boundary, self.dilation_ratio = bool(boundary), float(dilation_ratio)
         refuse_quality_options("InstancePipeline", "scoring the best-of-3 path is not built", **kw)
         refuse_overlap_option("InstancePipeline", "resolving the best-of-3 masks is not built", **kw)
         refuse_vis_option("InstancePipeline", "it paints no class map to blend", **kw)
@@ -1252,6 +1301,9 @@ class InstancePipeline(TilePipeline):
             self.ap_pred = self.ap_gt = None
             self.ap_inter = torch.empty(M * M, dtype=torch.int64, device=self.dev)
             self.ap_area = torch.empty(2, M, dtype=torch.int64, device=self.dev)
+        if self.boundary:              # the bands of those planes and their pair counts, on s_dec too
+            self.bd_pred = self.bd_gt = None
+            self.bd_inter = torch.empty(self.max_boxes * self.max_boxes, dtype=torch.int64, device=self.dev)
 
     def _ap_planes(self, hw):
         """The tile's plane buffers [max_boxes, words] (prediction, ground truth), grown to the tile's size on the decode stream."""
@@ -1260,18 +1312,36 @@ class InstancePipeline(TilePipeline):
             self.ap_pred = self.ap_gt = None              # stream-ordered: the allocator hands the blocks out on s_dec again
             self.ap_pred = torch.empty(self.max_boxes * words, dtype=torch.int64, device=self.dev)
             self.ap_gt = torch.empty(self.max_boxes * words, dtype=torch.int64, device=self.dev)
+            if self.boundary:
+                self.bd_pred = self.bd_gt = None
+                self.bd_pred = torch.empty(self.max_boxes * words, dtype=torch.int64, device=self.dev)
+                self.bd_gt = torch.empty(self.max_boxes * words, dtype=torch.int64, device=self.dev)
             self.ap_words = words
         n = self.max_boxes * words
         return self.ap_pred[:n].view(self.max_boxes, words), self.ap_gt[:n].view(self.max_boxes, words)
 
-    def _ap_match(self, b: int, i: int, nb: int, planes) -> None:
-        """After a tile's last chunk: its nb predictions against its nb ground truths, matched into the batch's tables."""
+    def _ap_match(self, b: int, i: int, nb: int, planes, hw=None) -> None:
+        """After a tile's last chunk: its nb predictions against its nb ground truths, matched into the batch's tables; with
+        `boundary` the bands of both stacks too, matched by the smaller IoU into the second set."""
         eng = self.eng
         pp, gp = (planes[0][:nb], planes[1][:nb]) if planes is not None else (torch.zeros(0, 1, dtype=torch.int64, device=self.dev),) * 2
         inter, ad, ag = eng.mask_pair_counts(pp, gp, self.ap_inter[:nb * nb].view(nb, nb), self.ap_area[0, :nb], self.ap_area[1, :nb])
         eng.coco_match(inter, ad, ag, self.qual_dev[b][i, :nb], max_det=AP_SHAPE[2], order_out=self.ap_order_dev[b][i],
                        match_out=self.ap_match_dev[b][i], dt_ignore_out=self.ap_ign_dev[b][i], n_valid_out=self.ap_nvalid_dev[b][i],
                        n_kept_out=self.ap_nkept_dev[b][i])
+        if not self.boundary:
+            return
+        bp, bg = pp, gp
+        if planes is not None:
+            from .coco_ap import boundary_dilation
+            d, words = boundary_dilation(hw[0], hw[1], self.dilation_ratio), pp.shape[1]
+            bp = eng.mask_boundary_bits(pp, hw[0], hw[1], d, self.bd_pred[:nb * words].view(nb, words))
+            bg = eng.mask_boundary_bits(gp, hw[0], hw[1], d, self.bd_gt[:nb * words].view(nb, words))
+        band = eng.mask_pair_counts(bp, bg, self.bd_inter[:nb * nb].view(nb, nb), self.band_ad_dev[b][i, :nb], self.band_ag_dev[b][i, :nb])
+        self.band_inter_dev[b][i, :nb].copy_(band[0].diagonal())
+        eng.coco_match(inter, ad, ag, self.qual_dev[b][i, :nb], max_det=AP_SHAPE[2], order_out=self.bd_order_dev[b][i],
+                       match_out=self.bd_match_dev[b][i], dt_ignore_out=self.bd_ign_dev[b][i], n_valid_out=self.bd_nvalid_dev[b][i],
+                       n_kept_out=self.bd_nkept_dev[b][i], boundary=band)
 
     def _stage(self, b: int, items: List[WorkItem]):
         if not self.gt:
@@ -1353,7 +1423,7 @@ class InstancePipeline(TilePipeline):
                 eng.pack_label_bits(self.gt_lab[b][i], self.dev_col[b][off + s:off + e], planes[1][s:e])
             kept.append(mk)
         if self.ap:
-            self._ap_match(b, i, nb, planes)
+            self._ap_match(b, i, nb, planes, hw)
         self.last_masks = kept[-1].view(torch.bool) if kept else None
         out.masks[i] = torch.cat(kept).cpu() if (self.keep_masks and kept) else None
         out.odd[i] = None                      # instance pipelines paint no class map

@@ -139,8 +139,11 @@ def load_library() -> C.CDLL:
     lib.samrs_mask_pair_counts.argtypes = [vp, vp, ip, vp, ip, C.c_int64, vp, vp, vp, vp]
     lib.samrs_coco_match.argtypes = [vp, vp, vp, vp, vp, ip, ip, ip, C.POINTER(C.c_double), ip, C.POINTER(C.c_double), ip, ip,
                                      vp, vp, vp, vp, vp, vp]
+    lib.samrs_coco_match_min.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ip, ip, ip, C.POINTER(C.c_double), ip, C.POINTER(C.c_double), ip, ip,
+                                         vp, vp, vp, vp, vp, vp]
+    lib.samrs_mask_boundary_bits.argtypes = [vp, vp, ip, ip, ip, ip, vp, vp]
     for name in ("samrs_score_masks", "samrs_filter_masks", "samrs_resolve_overlaps", "samrs_mask_pack_bits", "samrs_label_pack_bits",
-                 "samrs_mask_pair_counts", "samrs_coco_match"):
+                 "samrs_mask_pair_counts", "samrs_coco_match", "samrs_coco_match_min", "samrs_mask_boundary_bits"):
         getattr(lib, name).restype = ip
     lib.samrs_png_encode_labels.argtypes = [vp, vp, ip, ip, ip, vp, vp, C.c_int64, vp, vp, vp]
     lib.samrs_blend_labels.argtypes = [vp, vp, vp, vp, fp, vp, ip, ip, ip, vp]
@@ -1121,15 +1124,37 @@ class Engine:
                                                         area_a.data_ptr(), area_b.data_ptr(), _stream()))
         return inter, area_a, area_b
 
+    def mask_boundary_bits(self, planes: torch.Tensor, h: int, w: int, d: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The boundary bands of bit planes (samrs_mask_boundary_bits; the definition is stated there): planes int64 [n, words] of
+        h x w masks, from ``pack_mask_bits`` or ``pack_label_bits`` alike -> int64 [n, words], band = M AND NOT (M eroded by the
+        (2 d + 1)^2 square, everything outside the image background), tail bits zero.  d: ``coco_ap.boundary_dilation(h, w)``, 1..128.
+        `out`: a caller-owned contiguous int64 [n, words] slice that does not overlap `planes`.  Asynchronous on the current stream;
+        the call keeps one grown scratch per engine, so such calls must be stream-ordered with each other."""
+        h, w, d = int(h), int(w), int(d)
+        words = (h * w + 63) // 64 if h > 0 and w > 0 else -1
+        if not (isinstance(planes, torch.Tensor) and planes.dtype == torch.int64 and planes.dim() == 2 and planes.is_cuda
+                and planes.is_contiguous()) or (words > 0 and planes.shape[1] != words):
+            raise ValueError(f"planes must be a contiguous int64 [n, {words}] tensor on the engine's device (pack_mask_bits of {h} x {w} masks)")
+        n = int(planes.shape[0])
+        out = self._out("out", out, (n, int(planes.shape[1])), torch.int64)
+        if n:                                                  # an empty stack has no storage to point at
+            with torch.cuda.device(self.device):
+                self._check(self.lib.samrs_mask_boundary_bits(self.handle, planes.data_ptr(), n, h, w, d, out.data_ptr(), _stream()))
+        return out
+
     def coco_match(self, inter: torch.Tensor, area_d: torch.Tensor, area_g: torch.Tensor, scores, thresholds=None, area_ranges=None,
-                   max_det: int = 100, order_out=None, match_out=None, dt_ignore_out=None, n_valid_out=None, n_kept_out=None):
+                   max_det: int = 100, order_out=None, match_out=None, dt_ignore_out=None, n_valid_out=None, n_kept_out=None,
+                   boundary=None):
         """COCOeval.evaluateImg's greedy matching of one image on the device (samrs_coco_match; the rule is stated there and in
         samrs_amd/coco_ap.py): inter int64 [nd, ng], area_d int64 [nd], area_g int64 [ng] (``mask_pair_counts``), scores fp32 [nd]
         on the device, or on the host (a CPU tensor / array: checked for NaN, then uploaded by the library) ->
         (order int32 [max_det], match int32 [A, T, max_det] = ground-truth INDEX or -1, dt_ignore uint8 [A, T, max_det],
         n_valid int32 [A], n_kept int32 [1]) for the T `thresholds` (default: COCO's ten) and A `area_ranges` (default: COCO's
         four).  Ranks past n_kept hold -1 / -1 / 0.  A NaN among device scores yields n_kept = -1.  Asynchronous on the current
-        stream; the outputs may be caller-owned contiguous tensors."""
+        stream; the outputs may be caller-owned contiguous tensors.
+        `boundary` = (inter_b, area_db, area_gb), the same counts of the masks' boundary bands (``mask_boundary_bits`` +
+        ``mask_pair_counts``): Boundary AP's matching (samrs_coco_match_min), the pair IoU is min(mask IoU, boundary IoU) while
+        area ranges and ignore flags stay the masks'.  None (default) makes the plain call."""
         from . import coco_ap
         thr = np.ascontiguousarray(coco_ap.IOU_THRESHOLDS if thresholds is None else thresholds, dtype=np.float64).reshape(-1)
         rng = np.ascontiguousarray(coco_ap.AREA_RANGES if area_ranges is None else area_ranges, dtype=np.float64).reshape(-1, 2)
@@ -1138,6 +1163,12 @@ class Engine:
         for name, t, shape in (("inter", inter, (nd, ng)), ("area_d", area_d, (nd,)), ("area_g", area_g, (ng,))):
             if not (isinstance(t, torch.Tensor) and t.dtype == torch.int64 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shape):
                 raise ValueError(f"{name} must be a contiguous int64 {list(shape)} tensor on the engine's device")
+        if boundary is not None:
+            if len(boundary) != 3:
+                raise ValueError("boundary must be (inter_b, area_db, area_gb)")
+            for name, t, shape in zip(("inter_b", "area_db", "area_gb"), boundary, ((nd, ng), (nd,), (ng,))):
+                if not (isinstance(t, torch.Tensor) and t.dtype == torch.int64 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shape):
+                    raise ValueError(f"boundary: {name} must be a contiguous int64 {list(shape)} tensor on the engine's device")
         on_host = not (isinstance(scores, torch.Tensor) and scores.is_cuda)
         if on_host:
             scores = torch.as_tensor(np.ascontiguousarray(np.asarray(scores, dtype=np.float32).reshape(-1)))
@@ -1149,11 +1180,15 @@ class Engine:
         n_valid = self._out("n_valid_out", n_valid_out, (A,), torch.int32)
         n_kept = self._out("n_kept_out", n_kept_out, (1,), torch.int32)
         dp = C.POINTER(C.c_double)
+        counts = [_ptr(inter) if nd and ng else None, _ptr(area_d) if nd else None, _ptr(area_g) if ng else None]
+        fn = self.lib.samrs_coco_match
+        if boundary is not None:
+            counts += [_ptr(boundary[0]) if nd and ng else None, _ptr(boundary[1]) if nd else None, _ptr(boundary[2]) if ng else None]
+            fn = self.lib.samrs_coco_match_min
         with torch.cuda.device(self.device):
-            self._check(self.lib.samrs_coco_match(self.handle, _ptr(inter) if nd and ng else None, _ptr(area_d) if nd else None,
-                                                  _ptr(area_g) if ng else None, scores.data_ptr() if nd else None, int(on_host), nd, ng,
-                                                  thr.ctypes.data_as(dp), T, rng.ctypes.data_as(dp), A, max_det, order.data_ptr(),
-                                                  match.data_ptr(), ign.data_ptr(), n_valid.data_ptr(), n_kept.data_ptr(), _stream()))
+            self._check(fn(self.handle, *counts, scores.data_ptr() if nd else None, int(on_host), nd, ng,
+                           thr.ctypes.data_as(dp), T, rng.ctypes.data_as(dp), A, max_det, order.data_ptr(),
+                           match.data_ptr(), ign.data_ptr(), n_valid.data_ptr(), n_kept.data_ptr(), _stream()))
             if on_host and nd:
                 torch.cuda.current_stream().synchronize()      # the library reads the host scores on the stream
         return order, match, ign, n_valid, n_kept

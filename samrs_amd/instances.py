@@ -21,6 +21,12 @@ device every prediction of an image is matched against every ground truth of it 
 gains an ``"ap"`` record, rank 0 writes ``ap.json`` and prints COCO's twelve lines after the mIoU line (``samrs_amd.coco_ap``; a
 match is a match by index, so ground truth 0 counts).
 
+``--boundary`` (needs ``--ap``) adds Boundary AP and Boundary mIoU (Cheng et al., CVPR 2021; the rules: samrs_mask_boundary_bits in
+include/samrs_hip.h): mask IoU is dominated by an object's interior, these respond to its outline.  The bands are computed on the
+device (``InstancePipeline(boundary=True)``), each fragment gains ``"boundary_ap"`` and the per-object band counts, rank 0 writes
+``boundary_ap.json`` and prints the twelve lines and one ``Boundary mIOU`` line after the existing output.  ``miou.json``,
+``ap.json`` and the two COCO files are unchanged.
+
 One deliberate difference from the reference: image ids follow the SORTED image stems.  The reference numbers images in
 ``os.listdir`` order (main_sam_rhbox_mask_instance.py:83), which is unspecified.  Images without an annotation file are ignored.
 """
@@ -144,10 +150,12 @@ def write_fragment(out_dir: str, stem: str, frag: dict) -> None:
 
 
 def make_fragment(height: int, width: int, scores, rles: Sequence[str], pred_area=None, inter=None, gt_area=None,
-                  gt_rles: Optional[Sequence[str]] = None, bboxes=None, gt_bboxes=None, ap: Optional[dict] = None) -> dict:
+                  gt_rles: Optional[Sequence[str]] = None, bboxes=None, gt_bboxes=None, ap: Optional[dict] = None,
+                  boundary: Optional[dict] = None) -> dict:
     """scores: fp32 qualities (stored as float(fp32), instance_to_json.py:103); rles / gt_rles: the COCO counts strings; bboxes /
     gt_bboxes (--mask-boxes): COCO [x, y, w, h] per prediction / ground-truth mask; ap (--ap): the image's matching tables
-    (``TileResult.ap_tables``), stored as the ranks in use: order, match, dt_ignore, n_valid."""
+    (``TileResult.ap_tables``), stored as the ranks in use: order, match, dt_ignore, n_valid; boundary (--boundary): the same of the
+    Boundary AP matching (``TileResult.boundary_tables``) as "boundary_ap", and its three per-object band counts."""
     frag = {"height": int(height), "width": int(width), "scores": [float(np.float32(s)) for s in scores], "rles": list(rles)}
     if gt_rles is not None:
         frag.update(pred_area=[int(v) for v in pred_area], inter=[int(v) for v in inter], gt_area=[int(v) for v in gt_area],
@@ -162,6 +170,15 @@ def make_fragment(height: int, width: int, scores, rles: Sequence[str], pred_are
             raise ValueError("a predicted IoU is NaN: the matching cannot order the detections")
         frag["ap"] = {"order": np.asarray(ap["order"])[:k].tolist(), "match": np.asarray(ap["match"])[:, :, :k].tolist(),
                       "dt_ignore": np.asarray(ap["dt_ignore"])[:, :, :k].tolist(), "n_valid": np.asarray(ap["n_valid"]).tolist()}
+    if boundary is not None:
+        k = int(boundary["n_kept"])
+        if k < 0:
+            raise ValueError("a predicted IoU is NaN: the matching cannot order the detections")
+        frag["boundary_ap"] = {"order": np.asarray(boundary["order"])[:k].tolist(), "match": np.asarray(boundary["match"])[:, :, :k].tolist(),
+                               "dt_ignore": np.asarray(boundary["dt_ignore"])[:, :, :k].tolist(),
+                               "n_valid": np.asarray(boundary["n_valid"]).tolist()}
+        for key in ("band_inter", "band_area_d", "band_area_g"):
+            frag[key] = [int(v) for v in boundary[key]]
     return frag
 
 
@@ -171,17 +188,18 @@ def coco_bboxes(hbox: np.ndarray, areas) -> List[List[int]]:
             for b, a in zip(hbox, areas)]
 
 
-def pending_stems(out_dir: str, stems: Sequence[str], need_ap: bool = False) -> List[str]:
+def pending_stems(out_dir: str, stems: Sequence[str], need_ap: bool = False, need_boundary: bool = False) -> List[str]:
     """--resume: the stems whose fragment is not on disk yet; with `need_ap` (--ap) a fragment without an "ap" record (written by
-    a run without the flag) counts as not done."""
+    a run without the flag) counts as not done, and with `need_boundary` (--boundary) one without a "boundary_ap" record."""
     def done(s):
         path = fragment_path(out_dir, s)
         if not os.path.exists(path):
             return False
-        if not need_ap:
+        if not (need_ap or need_boundary):
             return True
         with open(path) as f:
-            return "ap" in json.load(f)
+            frag = json.load(f)
+        return (not need_ap or "ap" in frag) and (not need_boundary or "boundary_ap" in frag)
     return [s for s in stems if not done(s)]
 
 
@@ -200,11 +218,28 @@ def miou_from_tallies(inter: Sequence[int], pred_area: Sequence[int], gt_area: S
     return float(np.mean(ious)), float(np.sum(inter_all) / np.sum(union_all)), len(ious)
 
 
-def merge_fragments(out_dir: str, stems: Sequence[str], tag: str, with_gt: bool, with_ap: bool = False) -> Optional[dict]:
+def fragment_tables(out_dir: str, stems: Sequence[str], frags: Sequence[dict], key: str, flag: str) -> List[dict]:
+    """The fragments' matching tables under `key` ("ap" / "boundary_ap") as ``coco_ap.accumulate`` takes them."""
+    from . import coco_ap
+    tables = []
+    for stem, fr in zip(stems, frags):
+        if key not in fr:
+            raise RuntimeError(f"fragment {fragment_path(out_dir, stem)} holds no \"{key}\" record: written without {flag} (rerun with --resume)")
+        t = fr[key]
+        k, A, T = len(t["order"]), len(t["n_valid"]), len(coco_ap.IOU_THRESHOLDS)
+        tables.append(coco_ap.image_table(fr["scores"], t["order"], np.asarray(t["match"], dtype=np.int64).reshape(A, T, k),
+                                          np.asarray(t["dt_ignore"], dtype=np.uint8).reshape(A, T, k), t["n_valid"], k))
+    return tables
+
+
+def merge_fragments(out_dir: str, stems: Sequence[str], tag: str, with_gt: bool, with_ap: bool = False, with_boundary: bool = False,
+                    dilation_ratio: float = 0.02) -> Optional[dict]:
     """Rank 0, after every rank has written its fragments: ``sam_ins_<tag>.json`` (binary_to_coco_pre_hrsc) and, with the
     ground truth, ``gt_ins_<tag>.json`` (binary_to_coco_gt_hrsc) and ``miou.json``; image id = position in `stems` (sorted),
     annotation ids restart at 0 per image.  `with_ap`: also ``ap.json`` from the fragments' matching tables
-    (``coco_ap.accumulate``) and COCO's twelve lines after the mIoU line.  Returns the mIoU record (None without ground truth)."""
+    (``coco_ap.accumulate``) and COCO's twelve lines after the mIoU line.  `with_boundary`: also ``boundary_ap.json`` from the
+    "boundary_ap" tables and the band counts -- the twelve Boundary AP numbers and the Boundary mIoU over the objects ``miou.json``
+    covers (those with a non-empty mask union) -- printed after everything else.  Returns the mIoU record (None without ground truth)."""
     frags = []
     for stem in stems:
         path = fragment_path(out_dir, stem)
@@ -246,19 +281,25 @@ def merge_fragments(out_dir: str, stems: Sequence[str], tag: str, with_gt: bool,
     print("Average mIOU: ", avg, "Area mIOU: ", area, flush=True)              # main_sam_rhbox_mask_instance.py:244
     if with_ap:
         from . import coco_ap
-        tables = []
-        for stem, fr in zip(stems, frags):
-            if "ap" not in fr:
-                raise RuntimeError(f"fragment {fragment_path(out_dir, stem)} holds no \"ap\" record: written without --ap (rerun with --resume)")
-            t = fr["ap"]
-            k, A, T = len(t["order"]), len(t["n_valid"]), len(coco_ap.IOU_THRESHOLDS)
-            tables.append(coco_ap.image_table(fr["scores"], t["order"], np.asarray(t["match"], dtype=np.int64).reshape(A, T, k),
-                                              np.asarray(t["dt_ignore"], dtype=np.uint8).reshape(A, T, k), t["n_valid"], k))
+        tables = fragment_tables(out_dir, stems, frags, "ap", "--ap")
         numbers = coco_ap.accumulate(tables)
         with open(os.path.join(out_dir, "ap.json"), "w") as f:
             json.dump(coco_ap.ap_record(numbers, tables), f)
         for line in coco_ap.summary_lines(numbers):
             print(line, flush=True)
+    if with_boundary:
+        from . import coco_ap
+        tables = fragment_tables(out_dir, stems, frags, "boundary_ap", "--boundary")
+        numbers = coco_ap.accumulate(tables)
+        bi, bd, bg = ([v for fr in frags for v in fr[key]] for key in ("band_inter", "band_area_d", "band_area_g"))
+        covered = [j for j, (i, p, g) in enumerate(zip(inter, parea, garea)) if int(p) + int(g) - int(i) > 0]       # miou.json's objects
+        bm = coco_ap.boundary_miou([bi[j] for j in covered], [bd[j] for j in covered], [bg[j] for j in covered])
+        with open(os.path.join(out_dir, "boundary_ap.json"), "w") as f:
+            json.dump(coco_ap.ap_record(numbers, tables, boundary=True, dilation_ratio=dilation_ratio, miou=bm), f)
+        print(coco_ap.boundary_heading(dilation_ratio), flush=True)
+        for line in coco_ap.summary_lines(numbers):
+            print(line, flush=True)
+        print("Boundary mIOU: Average ", bm["average"], "Area ", bm["area"], flush=True)
     return rec
 
 
@@ -291,11 +332,15 @@ def run(args) -> Optional[dict]:
     with_ap = bool(getattr(args, "ap", False))
     if with_ap and not with_gt:
         raise ValueError("--ap matches the predictions against the ground truth: it needs --gt-labels")
+    with_boundary = bool(getattr(args, "boundary", False))
+    ratio = float(getattr(args, "dilation_ratio", 0.02))
+    if with_boundary and not with_ap:
+        raise ValueError("--boundary is a second matching beside the mask AP's: it needs --ap")
     stems, files, anns = list_images(args.images, args.annotations)
     todo = stems
     if getattr(args, "resume", False):
         # listed once, on rank 0, and broadcast (generate.run: ranks must index the same list)
-        todo = driver.agree_on_list(pending_stems(args.out, stems, need_ap=with_ap) if rank == 0 else [])
+        todo = driver.agree_on_list(pending_stems(args.out, stems, need_ap=with_ap, need_boundary=with_boundary) if rank == 0 else [])
         if rank == 0:
             print(f"[rank 0] --resume: {len(stems) - len(todo)} of {len(stems)} images already complete", flush=True)
     batch = getattr(args, "batch", 8)
@@ -314,7 +359,8 @@ def run(args) -> Optional[dict]:
                                    batch_decode=True if getattr(args, "batch_decode", False) else "auto",
                                    min_region_area=int(getattr(args, "min_region_area", 0) or 0),
                                    region_mode=getattr(args, "region_mode", "both"),
-                                   mask_boxes=bool(getattr(args, "mask_boxes", False)), ap=with_ap)
+                                   mask_boxes=bool(getattr(args, "mask_boxes", False)), ap=with_ap,
+                                   **(dict(boundary=True, dilation_ratio=ratio) if with_boundary else {}))
     os.makedirs(os.path.join(args.out, "parts"), exist_ok=True)
     import zlib
     wq_name = "samrs_ins/%08x" % zlib.crc32(("\n".join(todo) + "|" + args.out).encode())
@@ -350,7 +396,8 @@ def run(args) -> Optional[dict]:
                 if with_gt:
                     gbs = coco_bboxes(r.gt_hbox, r.gt_area) if r.gt_hbox is not None else None
                     frag = make_fragment(r.size[0], r.size[1], r.quality, rles, r.areas, r.inter, r.gt_area,
-                                         [r.gt_rle(j)["counts"] for j in range(n)], bbs, gbs, ap=r.ap_tables)
+                                         [r.gt_rle(j)["counts"] for j in range(n)], bbs, gbs, ap=r.ap_tables,
+                                         boundary=r.boundary_tables)
                 else:
                     frag = make_fragment(r.size[0], r.size[1], r.quality, rles, bboxes=bbs)
                 write_fragment(args.out, r.key, frag)
@@ -366,7 +413,7 @@ def run(args) -> Optional[dict]:
         dist.barrier()
     rec = None
     if rank == 0:
-        rec = merge_fragments(args.out, stems, tag, with_gt, with_ap)
+        rec = merge_fragments(args.out, stems, tag, with_gt, with_ap, with_boundary, ratio)
         if getattr(args, "audit_passes", 0) > 0 and sam.finish_audit() is not None:
             from . import audit
             audit.write_json(sam.audit_report, os.path.join(args.out, "statistic", "audit.json"))
@@ -403,6 +450,11 @@ def build_parser() -> argparse.ArgumentParser:
                     help="COCO mask AP on the GPU (needs --gt-labels): every prediction of an image is matched against every ground "
                          "truth of it on the device; OUT/ap.json holds the twelve COCO numbers, printed after the mIoU line "
                          "(samrs_amd.coco_ap; a match is a match by index)")
+    ap.add_argument("--boundary", action="store_true",
+                    help="Boundary AP and Boundary mIoU on the GPU (needs --ap): the matching on min(mask IoU, boundary IoU) beside the "
+                         "mask AP's; OUT/boundary_ap.json holds the twelve numbers and the Boundary mIoU, printed after the existing output")
+    ap.add_argument("--dilation-ratio", type=float, default=0.02, metavar="R",
+                    help="with --boundary: the band's width as a fraction of the image diagonal (default 0.02)")
     ap.add_argument("--batch-decode", action="store_true",
                     help="decode the prompts of all images of a batch in one decoder chain (Engine.predict_multi); same outputs")
     from . import generate
@@ -412,8 +464,19 @@ def build_parser() -> argparse.ArgumentParser:
     return ap
 
 
+def parse_args(argv=None):
+    """The arguments, with the usage errors that need no device: --boundary without --ap, a dilation ratio that is not positive."""
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.boundary and not args.ap:
+        parser.error("--boundary needs --ap (Boundary AP is a second matching beside the mask AP's)")
+    if not (args.dilation_ratio > 0):
+        parser.error("--dilation-ratio must be > 0")
+    return args
+
+
 def main(argv=None):
-    return run(build_parser().parse_args(argv))
+    return run(parse_args(argv))
 
 
 if __name__ == "__main__":

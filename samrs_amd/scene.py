@@ -118,10 +118,11 @@ class ScenePipeline:
                  box_batch: int = 64, rle: bool = False, png_lut: Optional[np.ndarray] = None, min_region_area: int = 0,
                  region_mode: str = "both", precision="auto", rle_buffer_mb: int = 256, mask_boxes: bool = False,
                  quality: bool = False, min_stability: float = 0.0, min_pred_iou: float = 0.0, min_inside_box: float = 0.0,
-                 polygons: bool = False, polygon_buffer_mb: int = 64, polygon_max_edges: int = 65536, vis_lut=None):
+                 polygons: bool = False, polygon_buffer_mb: int = 64, polygon_max_edges: int = 65536, vis_lut=None, boundary: bool = False):
         import torch
-        from .driver import (TilePipeline, output_tables, refuse_overlap_option, refuse_quality_options, refuse_vis_option,
-                             validate_output_options)
+        from .driver import (TilePipeline, output_tables, refuse_boundary_option, refuse_overlap_option, refuse_quality_options,
+                             refuse_vis_option, validate_output_options)
+        refuse_boundary_option("ScenePipeline", "scenes carry no ground truth; Boundary AP across windows is not built", boundary=boundary)
         refuse_vis_option("ScenePipeline", "the scene's composite lives in another buffer; scene overlays are not built", vis_lut=vis_lut)
         if isinstance(overlap, str):        # TilePipeline's overlap rule; the name means the windows' overlap in pixels here
             refuse_overlap_option("ScenePipeline", "resolving across scene windows is not built", overlap=overlap)
