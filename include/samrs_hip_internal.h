@@ -107,7 +107,10 @@ int samrs_k_postprocess(const float* lowres, int n_masks, int in_h, int in_w, in
  * (segment_anything/modeling/mask_decoder.py:53-56): C_et[M,N] = GELU(LN64(A_et[M,K] B_et[N,K]^T + bias)),
  * every 64-column group of N normalised on its own, eps 1e-6; gamma_beta = gamma[64] | beta[64].
  * M % 256 == 0, N % 128 == 0, K % 32 == 0.  A_lo_et / B_lo_et (both or neither; samrs_k_convert_split): the split
- * remainders of the operands -- the product then runs as A_lo B + A B_lo + A B and C is written in FP32 [M][N]. */
+ * remainders of the operands -- the product then runs as A_lo B + A B_lo + A B and C is written in FP32 [M][N].
+ * This hook and the two below (tests/test_upscaler_kernels_gpu.py) check on the host what the engine's call sites guarantee and
+ * launch nothing otherwise: SAMRS_ERR_BAD_ARG for a prec that is neither type, a null required pointer (bias and gamma_beta
+ * included), a pointer that is not 16-byte aligned, lo operands given in part; SAMRS_ERR_BAD_SHAPE for M, N, K outside the above. */
 int samrs_k_gemm_gln(int prec, const void* A_et, const void* B_et, void* C_et, const float* bias,
                      const float* gamma_beta, int M, int N, int K, const void* A_lo_et, const void* B_lo_et, void* stream);
 /* Split-precision GEMM in one launch (the block GEMMs of the reference-grade mode, option "split" bits 16 / 32):
@@ -121,14 +124,17 @@ int samrs_k_gemm_split3(int prec, const void* A_et, const void* A_lo_et, const v
  * u1_et [n*grid*grid*4, 64] (rows = prompt, token, sub-pixel 1), w_et [128, 64] (rows = sub-pixel 2 x 32
  * channels), bias [128], hyper [n, n_mask_tokens, 32] -> low [n, n_sel, 4*grid, 4*grid] fp32 for mask
  * tokens sel0 .. sel0+n_sel-1 (n_sel 1 or 3).  grid*grid*4 % 1024 == 0.  w_lo_et != NULL: split precision -- u1 is then
- * FP32 [rows][64] (split into hi + lo in registers) and w_lo_et the remainder of the weight split. */
+ * FP32 [rows][64] (split into hi + lo in registers) and w_lo_et the remainder of the weight split.
+ * SAMRS_ERR_BAD_SHAPE, nothing launched: n < 1, grid < 16 or not a multiple of 16 (or > 1024), n_mask_tokens < 1, sel0 < 0,
+ * n_sel not 1 or 3, sel0 + n_sel > n_mask_tokens (the last prompt's rows would be read past hyper). */
 int samrs_k_upscale2_masks(int prec, const void* u1, const void* w_et, const void* w_lo_et, const float* bias,
                            const float* hyper, float* low, int n, int grid, int n_mask_tokens,
                            int sel0, int n_sel, void* stream);
 /* The whole mask upscaler in one kernel (mask_decoder.py:53-59,154-167): keys_et [n*grid*grid, 256] -> ConvT #1 (w1_et [256][256]
  * rows = sub-pixel 1 x 64 channels, b1 [256]) -> LayerNorm2d(64) (ln = gamma[64] | beta[64], eps 1e-6) -> GELU -> ConvT #2
  * (w2_et [128][64] rows = sub-pixel 2 x 32 channels, b2 [128]) -> GELU -> dot with hyper [n, n_mask_tokens, 32] ->
- * low [n, n_sel, 4*grid, 4*grid] fp32.  keys_lo / w1_lo / w2_lo (all three or none): split precision.  grid % 16 == 0. */
+ * low [n, n_sel, 4*grid, 4*grid] fp32.  keys_lo / w1_lo / w2_lo (all three or none): split precision.  grid % 16 == 0.
+ * The same argument and shape checks as samrs_k_upscale2_masks; every pointer, low included, 16-byte aligned. */
 int samrs_k_upscaler_fused(int prec, const void* keys_et, const void* keys_lo_et, const void* w1_et, const void* w1_lo_et,
                            const float* b1, const float* ln, const void* w2_et, const void* w2_lo_et, const float* b2,
                            const float* hyper, float* low, int n, int grid, int n_mask_tokens, int sel0, int n_sel, void* stream);

@@ -307,8 +307,23 @@ int samrs_k_polygon_ranks(const uint8_t* masks, int n, int h, int w, int max_edg
                           int32_t* counts_out, void* stream) {
     KRET(launch_polygon_ranks(masks, n, h, w, max_edges, scratch, leader_out, rank_out, counts_out, (hipStream_t)stream));
 }
+// ---- the mask upscaler's three entry points (tests/test_upscaler_kernels_gpu.py).  The engine passes its own buffers (hipMalloc: 256-byte
+// aligned), prec from its own precision, n >= 1 prompts of a grid that is a multiple of 16, 4 mask tokens with (sel0, n_sel) = (0, 1) or (1, 3)
+// and the lo operands all or none (engine_decode.hip); a caller of these hooks guarantees none of that, so each repeats it on the host
+// before anything is launched: the kernels read 16-byte pieces, hyper row sel0 + n_sel - 1 of the last prompt must exist, and the
+// launchers take any prec other than bf16 as f16 or size their grids from n and grid as they come.
+static bool upscaler_prec_ok(int prec) { return prec == PREC_BF16 || prec == PREC_F16; }
+static bool upscaler_shape_ok(int n, int grid, int n_mask_tokens, int sel0, int n_sel) {
+    if (n < 1 || grid < 16 || grid % 16 || n_mask_tokens < 1 || sel0 < 0 || (n_sel != 1 && n_sel != 3)) return false;
+    if (n_sel > n_mask_tokens || sel0 > n_mask_tokens - n_sel) return false;
+    return grid <= 1024 && (int64_t)n * grid * grid * 16 <= INT32_MAX;                 // pixel and row counts stay in an int
+}
 int samrs_k_gemm_gln(int prec, const void* A, const void* B, void* C, const float* bias, const float* gamma_beta, int M, int N,
                      int K, const void* A_lo, const void* B_lo, void* stream) {
+    if (!upscaler_prec_ok(prec) || !A || !B || !C || !bias || !gamma_beta || (A_lo == nullptr) != (B_lo == nullptr)) return SAMRS_ERR_BAD_ARG;
+    if (!aligned16(A) || !aligned16(B) || !aligned16(C) || !aligned16(bias) || !aligned16(gamma_beta) || !aligned16(A_lo) || !aligned16(B_lo))
+        return SAMRS_ERR_BAD_ARG;
+    if (M < 256 || M % 256 || N < 128 || N % 128 || K < 32 || K % 32) return SAMRS_ERR_BAD_SHAPE;      // DBM, DBN, DBK of gemm_select.h
     KRET(launch_gemm_et_gln(prec, A, B, C, bias, gamma_beta, M, N, K, (hipStream_t)stream, A_lo, B_lo));
 }
 int samrs_k_gemm_split3(int prec, const void* A, const void* A_lo, const void* B, const void* B_lo, void* C, const float* bias,
@@ -318,11 +333,20 @@ int samrs_k_gemm_split3(int prec, const void* A, const void* A_lo, const void* B
 }
 int samrs_k_upscale2_masks(int prec, const void* u1, const void* w, const void* w_lo, const float* bias, const float* hyper,
                            float* low, int n, int grid, int n_mask_tokens, int sel0, int n_sel, void* stream) {
+    if (!upscaler_prec_ok(prec) || !u1 || !w || !bias || !hyper || !low) return SAMRS_ERR_BAD_ARG;
+    if (!aligned16(u1) || !aligned16(w) || !aligned16(w_lo) || !aligned16(bias) || !aligned16(hyper) || !aligned16(low)) return SAMRS_ERR_BAD_ARG;
+    if (!upscaler_shape_ok(n, grid, n_mask_tokens, sel0, n_sel)) return SAMRS_ERR_BAD_SHAPE;
     KRET(launch_upscale2_masks(prec, u1, w, w_lo, bias, hyper, low, n, grid, n_mask_tokens, sel0, n_sel, (hipStream_t)stream));
 }
 int samrs_k_upscaler_fused(int prec, const void* keys, const void* keys_lo, const void* w1, const void* w1_lo, const float* b1,
                            const float* ln, const void* w2, const void* w2_lo, const float* b2, const float* hyper, float* low, int n,
                            int grid, int n_mask_tokens, int sel0, int n_sel, void* stream) {
+    if (!upscaler_prec_ok(prec) || !keys || !w1 || !b1 || !ln || !w2 || !b2 || !hyper || !low) return SAMRS_ERR_BAD_ARG;
+    if ((keys_lo || w1_lo || w2_lo) && !(keys_lo && w1_lo && w2_lo)) return SAMRS_ERR_BAD_ARG;
+    if (!aligned16(keys) || !aligned16(keys_lo) || !aligned16(w1) || !aligned16(w1_lo) || !aligned16(b1) || !aligned16(ln) || !aligned16(w2) ||
+        !aligned16(w2_lo) || !aligned16(b2) || !aligned16(hyper) || !aligned16(low))
+        return SAMRS_ERR_BAD_ARG;
+    if (!upscaler_shape_ok(n, grid, n_mask_tokens, sel0, n_sel)) return SAMRS_ERR_BAD_SHAPE;
     KRET(launch_upscaler_fused(prec, keys, keys_lo, w1, w1_lo, b1, ln, w2, w2_lo, b2, hyper, low, n, grid, n_mask_tokens, sel0, n_sel,
                                (hipStream_t)stream));
 }

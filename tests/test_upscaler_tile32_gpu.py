@@ -3,7 +3,8 @@
 A tile is two 16-token groups; after the K halves of ConvT #1 have met in LDS each wave of a column group takes ONE group through
 LayerNorm2d, GELU, ConvT #2, GELU and the hypernetwork dot.  Checked here:
   * against the fp64 chain of tests/test_kernels_gpu.py::test_upscaler_fused_one_kernel, with its tolerances, on a NaN-filled
-    `low`, at n = 3, grid = 16 (8 tiles per prompt, a tile spans two grid rows) and n = 1, grid = 32 (a tile is one grid row);
+    `low`, at n = 3, grid = 16 (8 tiles per prompt, a tile spans two grid rows), n = 1, grid = 32 (a tile is one grid row) and
+    n = 3, grid = 64 (the persistent walk: more tiles than blocks);
   * byte for byte against the 16-token tile (SAMRS_UPSCALER_TILE=16): the switch is read once per process, so the same seeded
     calls run in two fresh child processes.
 
@@ -26,10 +27,12 @@ from test_kernels_gpu import PRECS, dev, rel_err, split_bits, stream  # noqa: E4
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(3, 16), (1, 32)]          # (prompts, grid)
+# (prompts, grid).  (3, 64): 384 tiles of 32 tokens / 768 of 16 -- more tiles than a 256-CU device has blocks, so both tile shapes walk
+# (1 - 2 and 3 tiles per block), prefetch the next tile's keys and cross prompt boundaries (tests/test_upscaler_kernels_gpu.py)
+SHAPES = [(3, 16), (1, 32), (3, 64)]
 SELS = [(1, 0), (3, 1)]              # (n_sel, sel0)
 TOL = {("f16", False): 4e-4, ("f16", True): 1e-5, ("bf16", False): 3e-3, ("bf16", True): 2e-4}
-CHILD_TIMEOUT_S = 240
+CHILD_TIMEOUT_S = 240             # a child takes 2 - 3 s on the MI355X: the import, 24 cases, the largest 12288 tokens
 
 
 @pytest.fixture(scope="module")
