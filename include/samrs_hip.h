@@ -346,6 +346,45 @@ int samrs_mask_polygons(samrs_engine_t* e, const uint8_t* masks, int n, int h, i
                         int64_t* cursor /* device [2], in / out: first free vertex, first free ring */,
                         int64_t* table /* device [n][5] */, void* stream);
 
+/* -- the traced rings simplified in place: Douglas-Peucker on every closed ring, distances to the chord SEGMENT, integers only (what
+ * polygon consumers otherwise do with cv2.approxPolyDP / shapely's simplify on the host, one ring at a time).  The rule, which is the
+ * definition (tests/polygon_simplify_ref.py restates it as a plain recursion over Python ints):
+ *   tolerance   eps_q, in sixteenths of a pixel, 1 <= eps_q <= 16384;
+ *   frame       a ring has the vertices v[0 .. k - 1] (k >= 4 for a lattice ring) in the order samrs_mask_polygons wrote.  Only
+ *               coordinate differences enter, so the offset (x0, y0) cannot matter.  Within samrs_mask_boxes's limits (h, w <= 8192)
+ *               a difference is at most 2^13 in magnitude, a squared length or a cross / dot product at most 2^27, and every product
+ *               below (N <= 2^54, 256 N <= 2^62, eps_q^2 D <= 2^55) fits in int64;
+ *   anchors     always kept: A = index 0; B = the index with the greatest |v[i] - v[A]|^2; C = the index with the greatest
+ *               |cross(v[B] - v[A], v[i] - v[A])|; ties go to the smallest index.  A traced ring has non-zero area, so C has a
+ *               non-zero cross product: every ring keeps at least 3 vertices that are not collinear.  The anchors in index order
+ *               cut the ring into three chains; the last one closes on index 0 again;
+ *   chain (i, j)  both ends are kept; a = v[i], b = v[j], L = |b - a|^2.  Every interior vertex p = v[m] has the numerator N(m) of its
+ *               squared distance to the segment over the common denominator D: L == 0 (one lattice point visited twice, at a saddle
+ *               vertex): N = |p - a|^2, D = 1; otherwise D = L and, with t = dot(p - a, b - a): t <= 0: N = |p - a|^2 L; t >= L:
+ *               N = |p - b|^2 L; else N = cross(b - a, p - a)^2.  m* = the interior vertex with the greatest N, ties to the smallest
+ *               m.  If N(m*) > floor(eps_q^2 D / 256) (that is 256 N > eps_q^2 D), m* is kept and (i, m*), (m*, j) are treated the
+ *               same way; otherwise every interior vertex is dropped.  The result depends on the ring and eps_q only, not on the
+ *               order in which chains are processed;
+ *   result      the kept vertices in index order, starting with v[0].
+ * Topology is NOT preserved (a simplified ring may touch or cross itself or a neighbour; so may approxPolyDP's), and the rule is not
+ * pinned against cv2.
+ * The call works IN PLACE on what consecutive samrs_mask_polygons calls of this handle wrote behind one cursor: table int64 [n][5] holds
+ * the n rows of those calls in placement order, whose placed masks cover the vertices [v0, cursor[0]) contiguously, v0 = the first
+ * vertex of the first placed row.  The vertices of that range are compacted towards v0 in order; each ring record's first vertex
+ * (relative to its mask's) and vertex count, and each placed row's first vertex and vertex count, are rewritten; cursor[0] becomes the
+ * new end (it stays as it is when no row is placed).  Unchanged: ring positions and counts, cursor[1], the table's edge count, a ring
+ * record's pixel index, and its third field, which stays the ORIGINAL ring's twice-signed area -- hole or outer is still its sign, a
+ * mask's rings still sum to twice its set pixels, and the simplified ring's own area is one shoelace sum away.  Rows with negative
+ * counts (not traced, not placed) pass through untouched; an empty mask keeps its zero counts.  n == 0 is a no-op.  A null handle /
+ * vertices / rings / table / cursor, n < 0, eps_q outside 1 .. 16384, or buffers into which this handle has not traced (the handle
+ * remembers the capacities samrs_mask_polygons was given for them; that is what bounds the scratch without reading the cursor back):
+ * SAMRS_ERR_BAD_ARG and nothing is written.  Integer arithmetic only, bitwise reproducible, no host synchronisation.  Keep flags,
+ * per-ring counts, their scan and the staging copy of the compaction (21 bytes per vertex and 36 per ring of the capacities, 8 per row) live in
+ * samrs_mask_polygons's scratch buffer: the call must be stream-ordered with every samrs_mask_polygons / samrs_simplify_polygons call
+ * on the handle. */
+int samrs_simplify_polygons(samrs_engine_t* e, int32_t* vertices, int32_t* rings, int64_t* table /* device [n][5] */, int n, int eps_q,
+                            int64_t* cursor /* device [2] */, void* stream);
+
 /* -- mask quality before the masks become labels: the three signals a box-prompted mask carries, counted on the device straight
  * from the 256^2 logits (`calculate_stability_score`, utils/amg.py:156-176, and the `pred_iou_thresh` / `stability_score_thresh`
  * gate of automatic_mask_generator.py:295-304; the box fit is this library's own).  lowres fp32 [n][256][256]: the lowres_out of

@@ -311,6 +311,16 @@ int samrs_k_polygon_edges(const uint8_t* masks, int n, int h, int w, int max_edg
                           uint8_t* corner_out, int32_t* counts_out, void* stream);
 int samrs_k_polygon_ranks(const uint8_t* masks, int n, int h, int w, int max_edges, void* scratch, int32_t* leader_out,
                           int32_t* rank_out, int32_t* counts_out, void* stream);
+/* the stages of samrs_simplify_polygons alone (polygon_simplify_kernels.hip).  scratch: a device buffer of
+ * samrs_k_polygon_simplify_scratch_bytes(n, vertex_capacity, ring_capacity) bytes (-1: bad arguments), the capacities those of the
+ * buffers that samrs_mask_polygons filled.
+ *   samrs_k_polygon_simplify_keep  the rows' rings listed, then the rounds: keep_out uint8 [vertex_capacity] = 1 at every kept vertex
+ *                                  (absolute index) and 0 elsewhere, kept_out int32 [ring_capacity] = kept vertices of every ring of
+ *                                  a placed row (absolute ring index), -1 elsewhere.  Reads vertices, rings and table, changes none. */
+int64_t samrs_k_polygon_simplify_scratch_bytes(int n, int64_t vertex_capacity, int64_t ring_capacity);
+int samrs_k_polygon_simplify_keep(const int32_t* vertices, const int32_t* rings, const int64_t* table, int n, int eps_q,
+                                  int64_t vertex_capacity, int64_t ring_capacity, void* scratch, uint8_t* keep_out, int32_t* kept_out,
+                                  void* stream);
 
 #ifdef __cplusplus
 }

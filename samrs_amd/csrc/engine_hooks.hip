@@ -307,6 +307,16 @@ int samrs_k_polygon_ranks(const uint8_t* masks, int n, int h, int w, int max_edg
                           int32_t* counts_out, void* stream) {
     KRET(launch_polygon_ranks(masks, n, h, w, max_edges, scratch, leader_out, rank_out, counts_out, (hipStream_t)stream));
 }
+int64_t samrs_k_polygon_simplify_scratch_bytes(int n, int64_t vertex_capacity, int64_t ring_capacity) {
+    if (n < 1 || vertex_capacity < 0 || ring_capacity < 0 || vertex_capacity >= (1ll << 40) || ring_capacity >= (1ll << 40)) return -1;
+    return (int64_t)polygon_simplify_scratch_bytes(n, (long long)vertex_capacity, (long long)ring_capacity);
+}
+int samrs_k_polygon_simplify_keep(const int32_t* vertices, const int32_t* rings, const int64_t* table, int n, int eps_q,
+                                  int64_t vertex_capacity, int64_t ring_capacity, void* scratch, uint8_t* keep_out, int32_t* kept_out,
+                                  void* stream) {
+    KRET(launch_polygon_simplify_keep(vertices, rings, (const long long*)table, n, eps_q, (long long)vertex_capacity,
+                                      (long long)ring_capacity, scratch, keep_out, kept_out, (hipStream_t)stream));
+}
 // ---- the mask upscaler's three entry points (tests/test_upscaler_kernels_gpu.py).  The engine passes its own buffers (hipMalloc: 256-byte
 // aligned), prec from its own precision, n >= 1 prompts of a grid that is a multiple of 16, 4 mask tokens with (sel0, n_sel) = (0, 1) or (1, 3)
 // and the lo operands all or none (engine_decode.hip); a caller of these hooks guarantees none of that, so each repeats it on the host

@@ -179,6 +179,13 @@ int samrs_mask_polygons(samrs_engine_t* e, const uint8_t* masks, int n, int h, i
     if (!mask_polygons_shape_ok(h, w, x0, y0))
         return fail(e, SAMRS_ERR_BAD_ARG, "samrs_mask_polygons: %d x %d masks at (%d, %d): h, w must be 1..8192, x0 + w, y0 + h <= 32768 "
                     "and h * w < 2^30", h, w, x0, y0);
+    {   // what samrs_simplify_polygons may later be handed: the same pair of buffers keeps one entry, with its latest capacities
+        auto& seen = e->poly_seen;
+        for (size_t i = 0; i < seen.size(); ++i)
+            if (seen[i].vertices == vertices && seen[i].rings == rings) { seen.erase(seen.begin() + i); break; }
+        if (seen.size() >= 16) seen.erase(seen.begin());
+        seen.push_back({vertices, rings, (long long)vertex_capacity, (long long)ring_capacity});
+    }
     if (n == 0) return SAMRS_OK;
     ON_DEVICE(e);
     hipStream_t s = (hipStream_t)stream;
@@ -194,6 +201,27 @@ int samrs_mask_polygons(samrs_engine_t* e, const uint8_t* masks, int n, int h, i
                                    (long long)vertex_capacity, rings, (long long)ring_capacity, (long long*)cursor,
                                    (long long*)table + (size_t)off * 5, s));
     }
+    return SAMRS_OK;
+}
+
+// the traced rings of n rows simplified in place (see samrs_hip.h)
+int samrs_simplify_polygons(samrs_engine_t* e, int32_t* vertices, int32_t* rings, int64_t* table, int n, int eps_q, int64_t* cursor,
+                            void* stream) {
+    if (!e || !vertices || !rings || !table || !cursor || n < 0) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_simplify_polygons: bad argument");
+    if (eps_q < 1 || eps_q > POLYGON_SIMPLIFY_EPS_MAX)
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_simplify_polygons: eps_q = %d must lie in 1..%d (sixteenths of a pixel)", eps_q,
+                    POLYGON_SIMPLIFY_EPS_MAX);
+    if (n == 0) return SAMRS_OK;
+    const samrs_engine::PolyBuffers* buf = nullptr;
+    for (const auto& b : e->poly_seen)
+        if (b.vertices == vertices && b.rings == rings) buf = &b;
+    if (!buf)
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_simplify_polygons: samrs_mask_polygons of this handle has not traced into these buffers "
+                    "(their capacities are not known)");
+    ON_DEVICE(e);
+    hipStream_t s = (hipStream_t)stream;
+    CK(e, scratch_reserve(e->poly_scratch, polygon_simplify_scratch_bytes(n, buf->vcap, buf->rcap), s));
+    CK(e, launch_polygon_simplify(vertices, rings, (long long*)table, n, eps_q, buf->vcap, buf->rcap, e->poly_scratch.p, (long long*)cursor, s));
     return SAMRS_OK;
 }
 

@@ -240,7 +240,10 @@ struct samrs_engine {
     DeviceScratch rle_decode_scratch;  // tokens -> counts -> boundaries, bit matrix and counters of samrs_rle_decode
     DeviceScratch region_scratch;  // labels + areas + counters of samrs_clean_masks
     DeviceScratch box_scratch;     // row extents of samrs_mask_boxes
-    DeviceScratch poly_scratch;    // edge lists and ranking state of samrs_mask_polygons
+    DeviceScratch poly_scratch;    // edge lists and ranking state of samrs_mask_polygons; the rounds' state and staging copy of samrs_simplify_polygons
+    // the buffers samrs_mask_polygons traced into, newest last (16 at most): their capacities bound samrs_simplify_polygons's scratch
+    struct PolyBuffers { const void* vertices; const void* rings; long long vcap, rcap; };
+    std::vector<PolyBuffers> poly_seen;
     DeviceScratch png_scratch;     // class-map PNG scratch (samrs_png_encode_labels)
     DeviceScratch png_rgb_scratch; // filtered bytes + code tables of samrs_png_encode_rgb
     DeviceScratch overlap_scratch; // entry areas of samrs_resolve_overlaps (rule SMALLEST without before_out)

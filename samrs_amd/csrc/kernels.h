@@ -415,3 +415,16 @@ hipError_t launch_polygon_edges(const uint8_t* masks, int n, int h, int w, int m
                                 int32_t* succ_out, uint8_t* corner_out, int32_t* counts_out, hipStream_t s);
 hipError_t launch_polygon_ranks(const uint8_t* masks, int n, int h, int w, int max_edges, void* scratch, int32_t* leader_out,
                                 int32_t* rank_out, int32_t* counts_out, hipStream_t s);
+
+// ---- polygon_simplify_kernels.hip -----------------------------------------------------------
+// The traced rings simplified in place (definition: samrs_hip.h samrs_simplify_polygons; the stages: the header comment of
+// polygon_simplify_kernels.hip).  table: the n rows of the samrs_mask_polygons calls in placement order; vertex_capacity and
+// ring_capacity: those of the two buffers, which bound the scratch (polygon_simplify_scratch_bytes).  launch_polygon_simplify_keep:
+// the listing and the rounds alone -- keep_out uint8 [vertex_capacity], kept_out int32 [ring_capacity] (-1: no ring of a placed row).
+constexpr int POLYGON_SIMPLIFY_EPS_MAX = 16384;
+size_t polygon_simplify_scratch_bytes(int n, long long vertex_capacity, long long ring_capacity);
+hipError_t launch_polygon_simplify(int32_t* vertices, int32_t* rings, long long* table, int n, int eps_q, long long vertex_capacity,
+                                   long long ring_capacity, void* scratch, long long* cursor, hipStream_t s);
+hipError_t launch_polygon_simplify_keep(const int32_t* vertices, const int32_t* rings, const long long* table, int n, int eps_q,
+                                        long long vertex_capacity, long long ring_capacity, void* scratch, uint8_t* keep_out,
+                                        int32_t* kept_out, hipStream_t s);

@@ -510,12 +510,34 @@ def check_polygons(tab: np.ndarray, nv: int, nr: int, holder: str, now: int) -> 
 OVERLAP_OPTIONS = ("order", "logit", "smallest")       # TilePipeline(overlap=...): "order" = painting order, nothing launched
 
 
+def polygon_eps_q(polygon_epsilon: float = 0.0, polygons: bool = True) -> int:
+    """The one declaration of the `polygon_epsilon` option: what the pipelines' argument becomes -- the tolerance of
+    ``Engine.simplify_polygons`` in sixteenths of a pixel, round(16 * polygon_epsilon), or 0 = off (no call is made).  It needs
+    polygons=True, must be >= 0 and at most 1024 pixels (eps_q <= 16384); a positive value below 1/32 pixel rounds to no tolerance at
+    all and is refused.  The effective tolerance is eps_q / 16.  Pure."""
+    from .engine import POLYGON_EPS_Q_MAX
+    eps = float(polygon_epsilon)
+    if eps != eps or eps < 0:
+        raise ValueError(f"polygon_epsilon must be >= 0 (0 = off), got {polygon_epsilon!r}")
+    if eps == 0:
+        return 0
+    if not polygons:
+        raise ValueError("polygon_epsilon simplifies the traced polygons: it needs polygons=True")
+    q = int(round(16.0 * min(eps, 1e6)))
+    if q > POLYGON_EPS_Q_MAX:
+        raise ValueError(f"polygon_epsilon = {polygon_epsilon!r} is above {POLYGON_EPS_Q_MAX // 16} pixels (eps_q = {q} > {POLYGON_EPS_Q_MAX})")
+    if q < 1:
+        raise ValueError(f"polygon_epsilon = {polygon_epsilon!r} rounds to 0 sixteenths of a pixel: pass 0 (off) or at least 1 / 32")
+    return q
+
+
 def validate_output_options(min_region_area: int = 0, region_mode: str = "both", polygons: bool = False, polygon_buffer_mb: int = 64,
-                            polygon_max_edges: int = 65536, png_lut=None, overlap: str = "order"):
+                            polygon_max_edges: int = 65536, png_lut=None, overlap: str = "order", polygon_epsilon: float = 0.0):
     """The output options TilePipeline and ScenePipeline share, checked in one place -> (png_lut as contiguous uint8 [256, 3] or
     None, the vertices one polygon buffer holds or None).  `overlap` is TilePipeline's alone (ScenePipeline refuses it before it gets
-    here: ``refuse_overlap_option``).  Touches no device."""
+    here: ``refuse_overlap_option``).  `polygon_epsilon` is checked here and resolved by ``polygon_eps_q``.  Touches no device."""
     from .engine import REGION_MODES
+    polygon_eps_q(polygon_epsilon, bool(polygons))
     if overlap not in OVERLAP_OPTIONS:
         raise ValueError(f"overlap must be one of {list(OVERLAP_OPTIONS)}, got {overlap!r}")
     if int(min_region_area) < 0:
@@ -706,7 +728,7 @@ class TilePipeline:
                  region_mode: str = "both", mask_boxes: bool = False, quality: bool = False, min_stability: float = 0.0,
                  min_pred_iou: float = 0.0, min_inside_box: float = 0.0, polygons: bool = False, polygon_buffer_mb: int = 64,
                  polygon_max_edges: int = 65536, overlap: str = "order", vis_lut: Optional[np.ndarray] = None, vis_alpha: float = 0.4,
-                 vis_buffer_mb: Optional[int] = None, boundary: bool = False):
+                 vis_buffer_mb: Optional[int] = None, boundary: bool = False, polygon_epsilon: float = 0.0):
         """precision: the operand-split mode (engine option "split") THIS PIPELINE'S OWN CALLS run in.  The option is set around
         each of the pipeline's encode / decode calls and restored afterwards (``Engine.options``), so the mode never outlives
         them: a ``SamPredictor`` built on the same model keeps the engine's own default (round 3 changed the engine's option for
@@ -749,6 +771,11 @@ class TilePipeline:
         with its share of ring records); a batch that overflows it raises, naming the option.  `polygon_max_edges`: a mask with
         more crack edges is not traced and yields None.  Every other output is byte for byte what polygons=False gives, and
         False (default) launches and allocates nothing.
+        polygon_epsilon: > 0 (pixels; needs polygons=True) simplifies the batch's polygon stream once, on the decode stream, after
+        the batch's last ``mask_polygons`` and before the download (``Engine.simplify_polygons``: Douglas-Peucker per ring at
+        round(16 * polygon_epsilon) / 16 pixels, in integers): ``polygons(j)``, ``polygon_table``, ``polygon_rings`` and
+        ``polygon_vertices`` then hold the simplified rings (a ring record's area stays the traced ring's), ``polygon_eps_q`` the
+        tolerance in sixteenths.  Every other output is unchanged; 0.0 (default) makes no call and changes no byte.
         overlap: what becomes of a pixel at which several masks of a tile are set.  "order" (default): today's behaviour -- the
         masks stay as they are and the class map follows the painting order, a later box wins; nothing is launched or allocated.
         "logit" / "smallest": the pixel is given to exactly one instance on the device, in place (``Engine.resolve_overlaps``):
@@ -763,7 +790,8 @@ class TilePipeline:
         from .transforms import ResizeLongestSide
         refuse_boundary_option("TilePipeline", "Boundary AP needs the instance pipeline's ground truth", boundary=boundary)
         lut, poly_vertices = validate_output_options(min_region_area, region_mode, polygons, polygon_buffer_mb, polygon_max_edges, png_lut,
-                                                     overlap)
+                                                     overlap, polygon_epsilon)
+        self.polygon_eps_q = polygon_eps_q(polygon_epsilon, bool(polygons))
         vlut, self.vis_alpha = validate_vis_options(vis_lut, vis_alpha, vis_buffer_mb)
         self.vis = vlut is not None
         self.overlap = overlap
@@ -1089,6 +1117,10 @@ class TilePipeline:
                 pre = self._decode_multi(b, tiles, offs) if self.batch_decode and sum(nb for _, nb in offs) else None
                 for i, ((t, hw), (off, nb)) in enumerate(zip(tiles, offs)):
                     self._decode_tile(b, i, t, hw, off, nb, out, None if pre is None else pre[i])
+            n_rows = sum(nb for _, nb in offs)
+            if self.polygons and self.polygon_eps_q and n_rows:                      # the batch's rings, once: its rows are 0 .. n_rows - 1
+                self.eng.simplify_polygons(self.poly_out.tab[b][:n_rows], self.poly_ring_dev[b], self.poly_vert_dev[b],
+                                           self.poly_out.cur[b], self.polygon_eps_q / 16.0)
             if self.png:
                 self._encode_png(b, tiles)
             if self.vis:
@@ -1285,6 +1317,8 @@ class InstancePipeline(TilePipeline):
             raise ValueError("InstancePipeline paints no class map: png_lut is a TilePipeline option")
         if kw.get("polygons"):
             raise ValueError("InstancePipeline does not trace polygons: polygons is a TilePipeline / ScenePipeline option")
+        if kw.get("polygon_epsilon"):
+            raise ValueError("InstancePipeline does not trace polygons: polygon_epsilon is a TilePipeline / ScenePipeline option")
         self.gt = bool(gt)             # read by TilePipeline.__init__: the ground-truth tables and stream are allocated with the rest
         super().__init__(sam, n_classes, precision=kw.pop("precision", "auto"), _multimask=bool(multimask), **kw)
         self.prompt, self.multimask = prompt, bool(multimask)

@@ -23,6 +23,7 @@ PREC_BF16, PREC_F16 = 0, 1
 PRECISIONS = {"bf16": PREC_BF16, "f16": PREC_F16, "fp16": PREC_F16}
 
 ABI_VERSION = 5
+POLYGON_EPS_Q_MAX = 16384          # samrs_simplify_polygons: eps_q in sixteenths of a pixel, 1 .. 16384
 REGION_MODES = {"holes": 1, "islands": 2, "both": 3}        # enum samrs_region_mode
 OVERLAP_RULES = {"logit": 1, "smallest": 2, "priority": 3}  # enum samrs_overlap_rule
 # "split" option bits (include/samrs_hip.h): rounding points that run as a two-term operand split
@@ -131,6 +132,12 @@ def load_library() -> C.CDLL:
         getattr(lib, name).restype = ip
     lib.samrs_k_polygon_scratch_bytes.restype = C.c_int64
     lib.samrs_k_polygon_edge_stride.restype = C.c_int64
+    lib.samrs_simplify_polygons.argtypes = [vp, vp, vp, vp, ip, ip, vp, vp]
+    lib.samrs_simplify_polygons.restype = ip
+    lib.samrs_k_polygon_simplify_scratch_bytes.argtypes = [ip, C.c_int64, C.c_int64]
+    lib.samrs_k_polygon_simplify_scratch_bytes.restype = C.c_int64
+    lib.samrs_k_polygon_simplify_keep.argtypes = [vp, vp, vp, ip, ip, C.c_int64, C.c_int64, vp, vp, vp, vp]
+    lib.samrs_k_polygon_simplify_keep.restype = ip
     lib.samrs_score_masks.argtypes = [vp, vp, ip, ip, ip, ip, ip, fp, vp, vp, vp]
     lib.samrs_filter_masks.argtypes = [vp, vp, ip, ip, ip, vp, vp, fp, fp, fp, vp, vp]
     lib.samrs_resolve_overlaps.argtypes = [vp, vp, ip, ip, ip, ip, vp, ip, ip, vp, vp, vp, vp, vp]
@@ -866,6 +873,58 @@ class Engine:
                                                          vertices.data_ptr(), vertices.shape[0], rings.data_ptr(), rings.shape[0],
                                                          cursor.data_ptr(), table.data_ptr(), _stream()))
         return vertices, rings, cursor, table
+
+    @staticmethod
+    def polygon_eps_q(epsilon: float) -> int:
+        """The tolerance of ``simplify_polygons`` in sixteenths of a pixel: round(16 * epsilon), which must lie in 1 .. 16384."""
+        eps = float(epsilon)
+        if not (eps == eps and 0.0 < eps < 1e9):
+            raise ValueError(f"polygon epsilon must be a positive number of pixels, got {epsilon}")
+        q = int(round(16.0 * eps))
+        if not 1 <= q <= POLYGON_EPS_Q_MAX:
+            raise ValueError(f"polygon epsilon {epsilon} is {q} sixteenths of a pixel: must lie in 1 .. {POLYGON_EPS_Q_MAX}")
+        return q
+
+    def _polygon_buffers(self, table, rings, vertices, cursor=None):
+        for name, t, dt, last in (("vertices", vertices, torch.int32, 2), ("rings", rings, torch.int32, 4), ("table", table, torch.int64, 5)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.is_cuda and t.is_contiguous() and t.dim() == 2 and t.shape[1] == last):
+                raise ValueError(f"{name} must be a contiguous {dt} [k, {last}] tensor on the engine's device")
+        if cursor is not None and not (isinstance(cursor, torch.Tensor) and cursor.dtype == torch.int64 and cursor.is_cuda
+                                       and cursor.is_contiguous() and cursor.numel() == 2):
+            raise ValueError("cursor must be a contiguous int64 [2] tensor on the engine's device")
+
+    def simplify_polygons(self, table: torch.Tensor, rings: torch.Tensor, vertices: torch.Tensor, cursor: torch.Tensor, epsilon: float):
+        """The rings that ``mask_polygons`` traced, simplified IN PLACE on the device (samrs_simplify_polygons): Douglas-Peucker on
+        every closed ring with distances to the chord segment, in integers, at the tolerance `epsilon` pixels (rounded to sixteenths
+        of a pixel, 1/16 .. 1024; ``polygon_eps_q``).  `table` int64 [n, 5]: the rows of the ``mask_polygons`` calls that appended
+        behind `cursor` into `vertices` / `rings`, in placement order (``torch.cat`` of their tables; rows that were not traced or
+        placed pass through).  The vertices are compacted towards the first placed row's first vertex, ring records and rows get
+        their new first vertex and vertex count, cursor[0] moves back to the new end; a ring record keeps the ORIGINAL ring's
+        twice-signed area and its pixel index.  Every ring keeps at least 3 vertices, beginning with its first; topology is not
+        preserved.  Returns (vertices, rings, cursor, table).  Asynchronous on the current stream."""
+        q = self.polygon_eps_q(epsilon)
+        self._polygon_buffers(table, rings, vertices, cursor)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.samrs_simplify_polygons(self.handle, vertices.data_ptr(), rings.data_ptr(), table.data_ptr(),
+                                                         int(table.shape[0]), q, cursor.data_ptr(), _stream()))
+        return vertices, rings, cursor, table
+
+    def polygon_simplify_stages(self, table: torch.Tensor, rings: torch.Tensor, vertices: torch.Tensor, eps_q: int):
+        """Test hook (samrs_k_polygon_simplify_keep): the listing and the rounds of ``simplify_polygons`` alone -> (keep uint8 [V] = 1
+        at every kept vertex (absolute index), kept int32 [R] = kept vertices per ring (absolute ring index; -1: no ring of a placed
+        row)).  Changes none of its inputs."""
+        self._polygon_buffers(table, rings, vertices)
+        n, V, R = int(table.shape[0]), int(vertices.shape[0]), int(rings.shape[0])
+        nbytes = int(self.lib.samrs_k_polygon_simplify_scratch_bytes(n, V, R))
+        if nbytes < 0:
+            raise ValueError("polygon_simplify_stages needs at least one row")
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        keep = torch.zeros(V, dtype=torch.uint8, device=self.device)
+        kept = torch.zeros(R, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            self._check(self.lib.samrs_k_polygon_simplify_keep(vertices.data_ptr(), rings.data_ptr(), table.data_ptr(), n, int(eps_q), V, R,
+                                                               scratch.data_ptr(), keep.data_ptr(), kept.data_ptr(), _stream()))
+        return keep, kept
 
     def score_masks(self, low: torch.Tensor, input_size: Sequence[int], original_size: Sequence[int], offset: float = 1.0,
                     boxes: Optional[torch.Tensor] = None, counts_out=None) -> torch.Tensor:

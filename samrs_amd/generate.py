@@ -62,7 +62,7 @@ def write_outputs(out_dir: str, stem: str, seg: np.ndarray, masks: Optional[np.n
                   png_files: Optional[Tuple[bytes, bytes]] = None, mask_bboxes: Optional[Sequence] = None,
                   mask_rboxes: Optional[Sequence] = None, dota_txt: bool = False, scores: Optional[dict] = None,
                   polygons: Optional[Sequence] = None, removed: Optional[Sequence[int]] = None, vis_file: Optional[bytes] = None,
-                  base_entries: Optional[Sequence[dict]] = None) -> None:
+                  base_entries: Optional[Sequence[dict]] = None, polygon_epsilon: Optional[float] = None) -> None:
     """`rles`: the per-instance COCO RLE dicts when they were encoded on the device (driver.TileResult.rle); otherwise they are
     encoded here from `masks` (host restatement), or left out when both are None (--no-rle).  `png_files`: the complete
     (gray, color) PNG files when they were encoded on the device (--png-device: driver.TileResult.png, byte-identical with the
@@ -75,6 +75,8 @@ def write_outputs(out_dir: str, stem: str, seg: np.ndarray, masks: Optional[np.n
     painted nothing and, being empty, has no DOTA line either).  `polygons` (--polygons): per instance the rings of its outline as
     (int32 [k, 2] lattice vertices, is_hole) pairs (driver.TileResult.polygons), or None for a mask over the edge cap; they become
     the pickle entries' ``"polygons"`` (the list of vertex arrays, or None) and ``"polygon_holes"`` (the list of bool, or None).
+    `polygon_epsilon` (--polygon-epsilon): the effective tolerance in pixels (eps_q / 16) the rings were simplified at on the device;
+    the entries' ``"polygon_epsilon"`` beside them.
     `removed` (--overlap logit / smallest): per instance the pixels the overlap stage gave to another instance; the entries' ``"removed"``
     (`areas` and `rles` are then those of the disjoint masks already).  `vis_file` (--vis): the complete ``vis/<stem>.png``, the
     overlay blended and encoded on the device (driver.TileResult.png("vis")); written as it is, before the pickle.
@@ -133,6 +135,8 @@ def write_outputs(out_dir: str, stem: str, seg: np.ndarray, masks: Optional[np.n
             pl = polygons[j]
             entry["polygons"] = None if pl is None else [np.array(p[0], dtype=np.int32) for p in pl]
             entry["polygon_holes"] = None if pl is None else [bool(p[1]) for p in pl]
+            if polygon_epsilon is not None:
+                entry["polygon_epsilon"] = float(polygon_epsilon)
         info.append(entry)
     if dota_txt:
         # before the pickle, whose presence says "this image is complete" (--resume)
@@ -364,9 +368,12 @@ def run(args) -> Dict[str, List[int]]:
     thresholds = {k: float(getattr(args, k, 0.0) or 0.0) for k in ("min_stability", "min_pred_iou", "min_inside_box")}
     want_quality = bool(getattr(args, "quality", False)) or any(t > 0 for t in thresholds.values())
     # --polygons: each mask's outline traced to polygons on the device (samrs_mask_polygons): outer rings and holes on the pixel lattice
-    want_polygons = bool(getattr(args, "polygons", False))
+    # --polygon-epsilon E: the traced rings simplified on the device (samrs_simplify_polygons) at round(16 E) / 16 pixels; implies --polygons
+    polygon_eps_q = driver.polygon_eps_q(float(getattr(args, "polygon_epsilon", 0.0) or 0.0))
+    want_polygons = bool(getattr(args, "polygons", False)) or polygon_eps_q > 0
     poly_kw = dict(polygons=True, polygon_buffer_mb=int(getattr(args, "polygon_buffer_mb", 64) or 64),
-                   polygon_max_edges=int(getattr(args, "polygon_max_edges", 65536) or 65536)) if want_polygons else {}
+                   polygon_max_edges=int(getattr(args, "polygon_max_edges", 65536) or 65536),
+                   polygon_epsilon=polygon_eps_q / 16.0) if want_polygons else {}
     # --overlap: a pixel several masks of an image are set at goes to one of them on the device (samrs_resolve_overlaps) before the masks
     # are painted, counted and RLE-encoded; "order" = the reference's painting order, nothing launched
     overlap = getattr(args, "overlap", "order") or "order"
@@ -496,7 +503,8 @@ def run(args) -> Dict[str, List[int]]:
                               "inside_box": quality.inside_fraction(r.score_counts), "kept": r.kept}
                 polys = [r.polygons(j) for j in range(len(r.labels))] if r.polygon_table is not None else None
                 write_outputs(args.out, r.key, r.seg_mask, None, r.boxes, r.labels, r.areas, palette, names, rles, clock, png_level, files,
-                              bbs, rbs, dota_txt, scores, polys, r.removed, r.png("vis") if r.vis_table is not None else None)
+                              bbs, rbs, dota_txt, scores, polys, r.removed, r.png("vis") if r.vis_table is not None else None,
+                              polygon_epsilon=polygon_eps_q / 16.0 if polygon_eps_q else None)
             finally:
                 with lock:
                     left[0] -= 1
@@ -724,6 +732,11 @@ def build_parser() -> argparse.ArgumentParser:
                     help="device buffer for one batch's (one scene's) polygon vertices and ring records (default 64)")
     ap.add_argument("--polygon-max-edges", type=int, default=65536, metavar="E",
                     help="masks with more boundary edges than this are not traced (default 65536; counted in the --log lines)")
+    ap.add_argument("--polygon-epsilon", type=float, default=0.0, metavar="E",
+                    help="simplify the traced rings on the GPU (Douglas-Peucker per ring, distances to the chord segment, in integers) at a "
+                         "tolerance of E pixels, rounded to sixteenths (1/16 .. 1024); implies --polygons.  'polygons' / 'polygon_holes' "
+                         "then hold the simplified rings and the entries gain 'polygon_epsilon', the effective tolerance.  Every ring "
+                         "keeps at least 3 vertices; topology is not preserved.  0 (default): off")
     return ap
 
 

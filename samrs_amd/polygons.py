@@ -95,3 +95,33 @@ def rasterize(rings_list: Sequence, h: int, w: int, origin: Sequence[int] = (0, 
             if xa == xb and ya != yb:
                 d[min(ya, yb):max(ya, yb), xa] += 1
     return (np.cumsum(d, axis=1)[:, :w] & 1).astype(np.uint8)
+
+
+def rasterize_any(rings_list: Sequence, h: int, w: int, origin: Sequence[int] = (0, 0)) -> np.ndarray:
+    """uint8 [h, w]: the even-odd fill of rings with ARBITRARY integer vertices (simplified rings: ``Engine.simplify_polygons``),
+    sampled at the pixel centres.  Exact, in doubled integer coordinates: the centre of pixel (row r, col c) is (2 c + 1, 2 r + 1), the
+    vertices are even, so a centre's row line never passes through a vertex.  An edge (a, b) crosses the row line Y = 2 r + 1 when
+    min(ya, yb) < Y < max(ya, yb), at X = xa + (Y - ya) (xb - xa) / (yb - ya); it toggles the pixels whose centre 2 c + 1 is to the
+    right of X or on it (a centre exactly on an edge counts as to its right; never the case for lattice rings).  Equals ``rasterize``
+    on rectilinear rings."""
+    d = np.zeros((h, w + 1), np.int32)
+    o = np.asarray(origin, np.int64)
+    for r in rings_list:
+        p = (np.asarray(r[0], np.int64) - o) * 2
+        q = np.roll(p, -1, axis=0)
+        for (xa, ya), (xb, yb) in zip(p.tolist(), q.tolist()):
+            if ya == yb:
+                continue
+            lo, hi = (ya, yb) if ya < yb else (yb, ya)
+            r0, r1 = max(lo // 2, 0), min(hi // 2, h)              # rows with lo < 2 r + 1 < hi
+            if r0 >= r1:
+                continue
+            Y = 2 * np.arange(r0, r1, dtype=np.int64) + 1
+            num, den = (Y - ya) * (xb - xa), yb - ya               # X = xa + num / den; first column c with 2 c + 1 >= X:
+            if den < 0:
+                num, den = -num, -den
+            # 2 c + 1 >= xa + num / den  <=>  c >= (den (xa - 1) + num) / (2 den): the ceiling, in integers
+            c = -((-(den * (xa - 1) + num)) // (2 * den))
+            c = np.clip(c, 0, w)
+            np.add.at(d, (np.arange(r0, r1), c), 1)
+    return (np.cumsum(d, axis=1)[:, :w] & 1).astype(np.uint8)

@@ -2,7 +2,7 @@
 
     python -m samrs_amd.relabel --ins DIR --out OUT [--classes / --n-classes / --palette]
         [--min-region-area N --region-mode M] [--overlap order|smallest] [--mask-boxes] [--dota-txt]
-        [--polygons [--polygon-max-edges E]] [--png-device] [--resume] [--box-batch B]
+        [--polygons [--polygon-max-edges E] [--polygon-epsilon E]] [--png-device] [--resume] [--box-batch B]
 
 ``DIR`` is a directory of ``*.pkl`` or a ``samrs_amd.generate`` output directory (its ``ins/`` is read): ours, a ``--resume``d run's,
 or the published SAMRS pickles, which have the same keys.  The pickle is the durable record -- COCO RLE per instance, label, box,
@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import generate, rle, tile_io
-from .driver import box_chunks, check_packed, check_polygons, validate_output_options
+from .driver import box_chunks, check_packed, check_polygons, polygon_eps_q, validate_output_options
 from .engine import RLE_STATUS
 from .polygons import rings_of
 
@@ -98,6 +98,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--polygons", action="store_true", help="trace each mask's outline to polygons on the GPU, as samrs_amd.generate does")
     ap.add_argument("--polygon-buffer-mb", type=int, default=64, metavar="N")
     ap.add_argument("--polygon-max-edges", type=int, default=65536, metavar="E")
+    ap.add_argument("--polygon-epsilon", type=float, default=0.0, metavar="E",
+                    help="simplify the traced rings on the GPU at a tolerance of E pixels, as samrs_amd.generate does; implies --polygons")
     # named so that they are refused with a reason instead of "unrecognized arguments"
     ap.add_argument("--quality", action="store_true", help="refused: " + NEEDS_LOGITS)
     ap.add_argument("--min-stability", type=float, default=0.0, help="refused: " + NEEDS_LOGITS)
@@ -136,12 +138,13 @@ class Relabeler:
         self.resolve = args.overlap != "order"
         self.overlap = args.overlap
         self.mask_boxes = bool(args.mask_boxes or args.dota_txt)
-        self.polygons = bool(args.polygons)
+        self.polygon_eps_q = polygon_eps_q(float(getattr(args, "polygon_epsilon", 0.0) or 0.0))
+        self.polygons = bool(args.polygons) or self.polygon_eps_q > 0
         self.polygon_max_edges, self.polygon_buffer_mb = int(args.polygon_max_edges), int(args.polygon_buffer_mb)
         self.rle_buffer_mb = int(args.rle_buffer_mb)
         lut, poly_vertices = validate_output_options(self.min_region_area, self.region_mode, self.polygons, self.polygon_buffer_mb,
                                                      self.polygon_max_edges, tile_io.class_lut(palette) if args.png_device else None,
-                                                     "smallest" if self.resolve else "order")
+                                                     "smallest" if self.resolve else "order", self.polygon_eps_q / 16.0)
         self.png_lut = None if lut is None else torch.from_numpy(np.ascontiguousarray(lut)).to(self.dev)
         self.class_pixels = torch.zeros(n_classes, dtype=torch.int64, device=self.dev)
         self.class_instances = torch.zeros(n_classes, dtype=torch.int64, device=self.dev)
@@ -187,6 +190,8 @@ class Relabeler:
                 eng.mask_polygons(masks, (0, 0), self.polygon_max_edges, self.poly_vert, self.poly_ring, pcur, ptab[s:e])
             eng.paint(masks, labels[s:e], seg, self.class_pixels, self.class_instances, areas_out=areas[s:e])
             eng.rle_encode(masks, self.rle_dev, rcur, rtab[s:e])
+        if self.polygons and self.polygon_eps_q and n:                             # the image's rings, once, after its last chunk
+            eng.simplify_polygons(ptab, self.poly_ring, self.poly_vert, pcur, self.polygon_eps_q / 16.0)
         png_tab = None
         if self.png_lut is not None:
             need = 6 << 20 if H * W <= (1 << 20) else 6 * H * W
@@ -265,7 +270,8 @@ def run(args) -> Dict:
         labels = np.array([int(e["label"]) for e in entries], dtype=np.int64)
         generate.write_outputs(args.out, stem, r["seg"], None, [e.get("bbox") for e in entries], labels, r["areas"], palette, names,
                                r["rles"], None, args.png_level, r["png_files"], r["mask_bboxes"], r["mask_rboxes"], dota_txt, None,
-                               r["polygons"], r["removed"], None, base_entries=entries)
+                               r["polygons"], r["removed"], None, base_entries=entries,
+                               polygon_epsilon=work.polygon_eps_q / 16.0 if work.polygon_eps_q else None)
         sizes.extend(int(a) for a in r["areas"] if a > 0)                                          # statistic.py:44-49
         if r["changed"] is not None:
             cleaned[0] += int(r["changed"].sum())

@@ -112,16 +112,19 @@ class ScenePipeline:
     ``TileResult.mask_hbox`` / ``mask_rbox`` / ``mask_record``; off (default) launches and allocates nothing.  `polygons`: each
     mask's outline as polygons on the pixel lattice (``Engine.mask_polygons``), again with the window's origin as the offset, so the
     vertices are in the scene's frame exactly: ``TileResult.polygons(j)``; `polygon_buffer_mb` holds one scene's vertices and ring
-    records (an overflow raises, naming it), a mask over `polygon_max_edges` edges yields None; off launches and allocates nothing."""
+    records (an overflow raises, naming it), a mask over `polygon_max_edges` edges yields None; off launches and allocates nothing.
+    `polygon_epsilon` > 0 (pixels; needs `polygons`): the scene's rings are simplified once, on the device, after the last window
+    (``Engine.simplify_polygons``; ``driver.polygon_eps_q``), in the scene's frame like the rings themselves; 0.0 makes no call."""
 
     def __init__(self, sam, n_classes: int, window: int = 1024, overlap: int = 256, context: float = 2.0, batch: int = 8,
                  box_batch: int = 64, rle: bool = False, png_lut: Optional[np.ndarray] = None, min_region_area: int = 0,
                  region_mode: str = "both", precision="auto", rle_buffer_mb: int = 256, mask_boxes: bool = False,
                  quality: bool = False, min_stability: float = 0.0, min_pred_iou: float = 0.0, min_inside_box: float = 0.0,
-                 polygons: bool = False, polygon_buffer_mb: int = 64, polygon_max_edges: int = 65536, vis_lut=None, boundary: bool = False):
+                 polygons: bool = False, polygon_buffer_mb: int = 64, polygon_max_edges: int = 65536, vis_lut=None, boundary: bool = False,
+                 polygon_epsilon: float = 0.0):
         import torch
-        from .driver import (TilePipeline, output_tables, refuse_boundary_option, refuse_overlap_option, refuse_quality_options,
-                             refuse_vis_option, validate_output_options)
+        from .driver import (TilePipeline, output_tables, polygon_eps_q, refuse_boundary_option, refuse_overlap_option,
+                             refuse_quality_options, refuse_vis_option, validate_output_options)
         refuse_boundary_option("ScenePipeline", "scenes carry no ground truth; Boundary AP across windows is not built", boundary=boundary)
         refuse_vis_option("ScenePipeline", "the scene's composite lives in another buffer; scene overlays are not built", vis_lut=vis_lut)
         if isinstance(overlap, str):        # TilePipeline's overlap rule; the name means the windows' overlap in pixels here
@@ -132,7 +135,9 @@ class ScenePipeline:
         from .transforms import ResizeLongestSide
         if not 0 <= int(overlap) < int(window):
             raise ValueError(f"overlap must satisfy 0 <= overlap < window, got overlap={overlap}, window={window}")
-        lut, nv = validate_output_options(min_region_area, region_mode, polygons, polygon_buffer_mb, polygon_max_edges, png_lut)
+        lut, nv = validate_output_options(min_region_area, region_mode, polygons, polygon_buffer_mb, polygon_max_edges, png_lut,
+                                          polygon_epsilon=polygon_epsilon)
+        self.polygon_eps_q = polygon_eps_q(polygon_epsilon, bool(polygons))
         eng = sam.engine
         if eng is None:
             raise RuntimeError("move the model to the GPU first: sam.to('cuda')")
@@ -290,6 +295,8 @@ class ScenePipeline:
             self.ev_dec[b].record(cur)
             if not two and g + 1 < len(groups):
                 encode(g + 1)
+        if self.polygons and self.polygon_eps_q and n:             # the scene's rings, once; the rows are in placement (window) order
+            eng.simplify_polygons(w_ptab, self.poly_ring_dev, self.poly_vert_dev, poly_cur, self.polygon_eps_q / 16.0)
         stage("windows")
         dev_lab = torch.from_numpy(labels).to(dev)
 
