@@ -385,6 +385,44 @@ int samrs_mask_polygons(samrs_engine_t* e, const uint8_t* masks, int n, int h, i
 int samrs_simplify_polygons(samrs_engine_t* e, int32_t* vertices, int32_t* rings, int64_t* table /* device [n][5] */, int n, int eps_q,
                             int64_t* cursor /* device [2] */, void* stream);
 
+/* -- rings back to masks: the even-odd fill of the rings of n table rows, sampled at the pixel centres, integers only -- the inverse of
+ * samrs_mask_polygons, and the raster that belongs to rings samrs_simplify_polygons or a caller has changed (what polygon consumers
+ * otherwise do on the host edge by edge: samrs_amd/polygons.py rasterize_any, cv2.fillPoly).  vertices / rings / table are exactly
+ * what samrs_mask_polygons writes and samrs_simplify_polygons rewrites: table int64 [n][5] with absolute first ring and first vertex,
+ * ring records whose first field is the ring's first vertex relative to its mask's and whose second is its vertex count; a ring
+ * record's area and pixel-index fields and the table's edge count are NOT read, so a caller may build the three arrays on the host
+ * from any integer polygons (samrs_amd/polygons.py pack_rings).  The rule, which is the definition (tests/polygon_fill_ref.py restates
+ * it as a per-pixel crossing count over Python ints):
+ *   frame     (x0, y0) is subtracted from every vertex; pixel (r, c), 0 <= r < h, 0 <= c < w, has its centre at (c + 1/2, r + 1/2).
+ *             A vertex farther than 2^20 from (x0, y0) in either coordinate makes its row "not rings" (below): within that bound a
+ *             coordinate difference is at most 2^21 in magnitude and every product below stays under 2^45, far inside int64;
+ *   edges     (xa, ya) -> (xb, yb), consecutive vertices of a ring; the ring's last vertex closes on its first.  Horizontal edges
+ *             (ya == yb) never count.  An edge acts on the rows r with min(ya, yb) <= r < max(ya, yb): those whose centre line it
+ *             crosses -- the vertices are integers, so a centre line never passes through a vertex;
+ *   toggle    in such a row the edge crosses the centre line at X = xa + (xb - xa) (2 r + 1 - 2 ya) / (2 (yb - ya)) and toggles every
+ *             pixel c whose centre is at or right of it, c + 1/2 >= X: a centre exactly on an edge counts as right of it.  With the
+ *             edge oriented so that dy = yb - ya > 0 and dx = xb - xa, the first toggled column is
+ *             ceil(((2 xa - 1) dy + dx (2 r + 1 - 2 ya)) / (2 dy)), clamped to [0, w] (w: the edge toggles nothing in that row);
+ *   pixel     (r, c) is 1 iff an odd number of the edges of ALL rings of the row toggle it, 0 otherwise (even-odd): holes, islands
+ *             inside holes, rings that cross themselves or each other all follow from that.
+ * masks_out [n][h][w] (or NULL): every byte written, 0 / 1.  counts_out int64 [n][3] (or NULL): (set pixels of the fill, set pixels of
+ * ref[j] -- non-zero bytes --, pixels set in both); without ref the last two are 0.  It is zeroed by the call itself, on the stream.
+ * With masks_out NULL only the counts are taken and nothing of size h * w is written; both NULL: SAMRS_ERR_BAD_ARG.
+ * Rows that are not rings: a negative ring or vertex count (not traced / not placed), a vertex beyond the 2^20 bound, counts of 2^30 or
+ * more, negative firsts, vertices without rings, or ring records that do not tile the row's vertex range in order (the first begins
+ * at 0, each begins where its predecessor ends, none is empty, the last ends at the vertex count) fill as the empty mask and report
+ * counts[j][0] = -1; ref[j] is still counted.  A row with zero rings (and zero vertices) is the empty mask: (0, ref area, 0).  The
+ * table and the ring records are treated as untrusted in that sense, but the capacities are not arguments: a row's firsts and counts
+ * are believed to lie inside the buffers.  No store leaves [n][h][w] / [n][3].
+ * h, w, x0, y0 within samrs_mask_boxes's limits (h, w in 1..8192, x0, y0 >= 0, x0 + w, y0 + h <= 32768).  n == 0 is a no-op; a null
+ * handle / vertices / rings / table, n < 0, a shape outside the limits: SAMRS_ERR_BAD_ARG and nothing is written.  One kernel, the
+ * band's bits in LDS: no scratch buffer, so no stream-ordering rule beyond the caller's own for its buffers.  Integer arithmetic only,
+ * bitwise reproducible, no host synchronisation. */
+int samrs_fill_polygons(samrs_engine_t* e, const int32_t* vertices, const int32_t* rings, const int64_t* table /* device [n][5] */,
+                        int n, int h, int w, int x0, int y0,
+                        uint8_t* masks_out /* device [n][h][w] or NULL */, const uint8_t* ref /* device [n][h][w] or NULL */,
+                        int64_t* counts_out /* device [n][3] or NULL */, void* stream);
+
 /* -- mask quality before the masks become labels: the three signals a box-prompted mask carries, counted on the device straight
  * from the 256^2 logits (`calculate_stability_score`, utils/amg.py:156-176, and the `pred_iou_thresh` / `stability_score_thresh`
  * gate of automatic_mask_generator.py:295-304; the box fit is this library's own).  lowres fp32 [n][256][256]: the lowres_out of

@@ -225,6 +225,21 @@ int samrs_simplify_polygons(samrs_engine_t* e, int32_t* vertices, int32_t* rings
     return SAMRS_OK;
 }
 
+// the rings of n table rows filled even-odd at the pixel centres, and counted against ref (see samrs_hip.h)
+int samrs_fill_polygons(samrs_engine_t* e, const int32_t* vertices, const int32_t* rings, const int64_t* table, int n, int h, int w,
+                        int x0, int y0, uint8_t* masks_out, const uint8_t* ref, int64_t* counts_out, void* stream) {
+    if (!e || !vertices || !rings || !table || n < 0) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_fill_polygons: bad argument");
+    if (!masks_out && !counts_out) return fail(e, SAMRS_ERR_BAD_ARG, "samrs_fill_polygons: masks_out and counts_out are both null");
+    if (!mask_boxes_shape_ok(h, w, x0, y0))
+        return fail(e, SAMRS_ERR_BAD_ARG, "samrs_fill_polygons: %d x %d masks at (%d, %d): h, w must be 1..8192 and x0 + w, y0 + h <= 32768",
+                    h, w, x0, y0);
+    if (n == 0) return SAMRS_OK;
+    ON_DEVICE(e);
+    CK(e, launch_fill_polygons(vertices, rings, (const long long*)table, n, h, w, x0, y0, masks_out, ref, (long long*)counts_out,
+                               (hipStream_t)stream));
+    return SAMRS_OK;
+}
+
 // threshold counts of n masks straight from their 256^2 logits (see samrs_hip.h)
 int samrs_score_masks(samrs_engine_t* e, const float* lowres, int n, int in_h, int in_w, int orig_h, int orig_w, float offset,
                       const float* boxes, int64_t* counts_out, void* stream) {

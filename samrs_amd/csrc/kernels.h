@@ -428,3 +428,9 @@ hipError_t launch_polygon_simplify(int32_t* vertices, int32_t* rings, long long*
 hipError_t launch_polygon_simplify_keep(const int32_t* vertices, const int32_t* rings, const long long* table, int n, int eps_q,
                                         long long vertex_capacity, long long ring_capacity, void* scratch, uint8_t* keep_out,
                                         int32_t* kept_out, hipStream_t s);
+
+// ---- polygon_fill_kernels.hip ---------------------------------------------------------------
+// Rings back to masks (definition: samrs_hip.h samrs_fill_polygons; the stages: the header comment of polygon_fill_kernels.hip).
+// One kernel per 32768 table rows and a memset of counts_out; no scratch.  The caller has checked the shape (mask_boxes_shape_ok).
+hipError_t launch_fill_polygons(const int32_t* vertices, const int32_t* rings, const long long* table, int n, int h, int w, int x0,
+                                int y0, uint8_t* masks_out, const uint8_t* ref, long long* counts_out, hipStream_t s);

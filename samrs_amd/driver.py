@@ -108,6 +108,51 @@ def reduce_statistics(class_pixels: torch.Tensor, class_instances: torch.Tensor,
     return buf[:c].clone(), buf[c:].clone()
 
 
+class PolygonIoUStat:
+    """One rank's running total of ``TileResult.polygon_counts`` (polygon_iou=True): the traced instances' count, their summed
+    intersection and union pixels, the float64 sum of their IoUs and the smallest of them.  Instances that were not traced
+    (fill = -1) are left out.  ``reduce_polygon_iou`` merges the ranks' totals."""
+
+    def __init__(self) -> None:
+        self.n, self.inter, self.union, self.total, self.low = 0, 0, 0, 0.0, float("inf")
+
+    def add(self, counts) -> None:
+        from .polygons import iou_from_counts
+        c = np.asarray(counts, dtype=np.int64).reshape(-1, 3)
+        c = c[c[:, 0] >= 0]
+        if not len(c):
+            return
+        iou = iou_from_counts(c)
+        self.n += len(c)
+        self.inter += int(c[:, 2].sum())
+        self.union += int((c[:, 0] + c[:, 1] - c[:, 2]).sum())
+        self.total += float(iou.sum(dtype=np.float64))
+        self.low = min(self.low, float(iou.min()))
+
+
+def reduce_polygon_iou(stat: PolygonIoUStat, polygon_epsilon: float, device=None, group=None) -> dict:
+    """What ``statistic/polygon_iou.json`` holds, the same on every rank: {"n": traced instances, "average": the mean of their
+    IoUs, "area": sum of intersections / sum of unions, "min": the smallest IoU, "polygon_epsilon": the effective tolerance}.
+    The integer sums go through ``reduce_statistics`` (the class statistics' all-reduce), the mean is a float64 SUM all-reduce over
+    the ranks' sums divided by n, the minimum a MIN all-reduce.  Without a traced instance average, area and min are None; a union of
+    0 pixels (every instance empty on both sides) gives area 1.0, as ``iou_from_counts`` does."""
+    import torch.distributed as dist
+    dev = torch.device("cpu") if device is None else device
+    ints, _ = reduce_statistics(torch.tensor([stat.n, stat.inter, stat.union], dtype=torch.int64, device=dev),
+                                torch.zeros(1, dtype=torch.int64, device=dev), group)
+    n, inter, union = (int(v) for v in ints.cpu().tolist())
+    total, low = stat.total, stat.low
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+        on_dev = dist.get_backend(group) == "nccl"              # gloo: through the host, as reduce_statistics
+        fsum = torch.tensor([stat.total], dtype=torch.float64, device=dev if on_dev else "cpu")
+        fmin = torch.tensor([stat.low], dtype=torch.float64, device=dev if on_dev else "cpu")
+        dist.all_reduce(fsum, op=dist.ReduceOp.SUM, group=group)
+        dist.all_reduce(fmin, op=dist.ReduceOp.MIN, group=group)
+        total, low = float(fsum.item()), float(fmin.item())
+    return {"n": n, "average": total / n if n else None, "area": (inter / union if union else 1.0) if n else None,
+            "min": low if n else None, "polygon_epsilon": float(polygon_epsilon)}
+
+
 def agree_on_list(items: List, group=None, src: int = 0) -> List:
     """Every rank gets RANK `src`'s copy of a Python list (``broadcast_object_list``; no-op outside a process group).
     Used wherever the work list is derived from something a rank could see differently from its peers -- e.g. ``generate
@@ -339,6 +384,8 @@ class TileResult:
     polygon_table: Optional[np.ndarray] = None      # int64 [n_boxes, 5] first ring, ring count, first vertex, vertex count, edge count
     polygon_rings: Optional[np.ndarray] = None      # int32 [R, 4] the batch's ring records (the table's firsts index them)
     polygon_vertices: Optional[np.ndarray] = None   # int32 [V, 2] the batch's vertices
+    # polygon_iou=True (samrs_fill_polygons on the rings as they are handed out, against the mask they were traced from):
+    polygon_counts: Optional[np.ndarray] = None     # int64 [n_boxes, 3] pixels of the rings' fill (-1: not traced), of the mask, of both
     # InstancePipeline(gt=True, ap=True) (samrs_coco_match on every prediction x every ground truth of the tile; per tile, not per box):
     ap_order: Optional[np.ndarray] = None       # int32 [100] detection index per rank (score descending, stable), -1 past n_kept
     ap_match: Optional[np.ndarray] = None       # int32 [4, 10, 100] matched ground-truth INDEX per area range, IoU threshold and rank, -1 = none
@@ -406,6 +453,15 @@ class TileResult:
         from .polygons import rings_of
         return rings_of(self.polygon_table, self.polygon_rings, self.polygon_vertices, j)
 
+    def polygon_iou(self, j: int) -> Optional[float]:
+        """IoU of instance j's mask with the even-odd fill of the rings ``polygons(j)`` hands out (what `polygon_epsilon` cost; exactly
+        1.0 without it): ``polygons.iou_from_counts(polygon_counts[j])``; None where the mask was not traced.  Only when the
+        pipeline ran with polygon_iou=True."""
+        from .polygons import iou_from_counts
+        if self.polygon_counts is None:
+            raise ValueError("no polygon counts: the pipeline ran without polygon_iou")
+        return None if int(self.polygon_counts[j, 0]) < 0 else float(iou_from_counts(self.polygon_counts[j]))
+
     def rle(self, j: int) -> dict:
         """COCO RLE of instance j exactly as the reference stores it (main_sam_hbox_semantic.py:201-202):
         ``{"size": [H, W], "counts": str}``; encoded on the device (samrs_rle_encode)."""
@@ -446,12 +502,13 @@ class OutputTable(NamedTuple):
 
 
 def output_tables(min_region_area: int = 0, mask_boxes: bool = False, quality: bool = False, gt: bool = False, rle: bool = False,
-                  instance: bool = False, overlap: str = "order", ap: bool = False, boundary: bool = False) -> List[OutputTable]:
+                  instance: bool = False, overlap: str = "order", ap: bool = False, boundary: bool = False,
+                  polygon_iou: bool = False) -> List[OutputTable]:
     """The per-box tables a pipeline with these (resolved) options allocates, copies to the host and hands out, in that order.
     Pure.  An option that is off contributes nothing: no allocation, no copy, and its TileResult fields stay None.  `instance`: an
     InstancePipeline, which always reports the predicted IoU of the mask it kept.  `ap`: the per-tile tables of the COCO matching
     (``AP_SHAPE`` = area ranges, IoU thresholds, max detections); `boundary`: a second set of them for the matching on min(mask IoU,
-    boundary IoU), and per box the diagonal band counts."""
+    boundary IoU), and per box the diagonal band counts.  `polygon_iou`: per box the three counts of ``Engine.fill_polygons``."""
     T, i64, i32 = OutputTable, torch.int64, torch.int32
     tabs = [T("areas", "area_dev", (), i64)]
     if min_region_area:
@@ -483,6 +540,8 @@ def output_tables(min_region_area: int = 0, mask_boxes: bool = False, quality: b
                  T("boundary_n_valid", "bd_nvalid_dev", (A,), i32, **tile), T("boundary_n_kept", "bd_nkept_dev", (1,), i32, **tile),
                  T("band_inter", "band_inter_dev", (), i64), T("band_area_d", "band_ad_dev", (), i64),
                  T("band_area_g", "band_ag_dev", (), i64)]
+    if polygon_iou:
+        tabs.append(T("polygon_counts", "pcnt_dev", (3,), i64))
     return tabs
 
 
@@ -532,12 +591,17 @@ def polygon_eps_q(polygon_epsilon: float = 0.0, polygons: bool = True) -> int:
 
 
 def validate_output_options(min_region_area: int = 0, region_mode: str = "both", polygons: bool = False, polygon_buffer_mb: int = 64,
-                            polygon_max_edges: int = 65536, png_lut=None, overlap: str = "order", polygon_epsilon: float = 0.0):
+                            polygon_max_edges: int = 65536, png_lut=None, overlap: str = "order", polygon_epsilon: float = 0.0,
+                            polygon_iou: bool = False):
     """The output options TilePipeline and ScenePipeline share, checked in one place -> (png_lut as contiguous uint8 [256, 3] or
     None, the vertices one polygon buffer holds or None).  `overlap` is TilePipeline's alone (ScenePipeline refuses it before it gets
-    here: ``refuse_overlap_option``).  `polygon_epsilon` is checked here and resolved by ``polygon_eps_q``.  Touches no device."""
+    here: ``refuse_overlap_option``).  `polygon_epsilon` is checked here and resolved by ``polygon_eps_q``.  `polygon_iou` (the rings filled again on the device
+    and counted against their mask) needs polygons=True; ScenePipeline and InstancePipeline refuse it (``refuse_polygon_iou_option``).
+    Touches no device."""
     from .engine import REGION_MODES
     polygon_eps_q(polygon_epsilon, bool(polygons))
+    if polygon_iou and not polygons:
+        raise ValueError("polygon_iou scores the traced polygons against their masks: it needs polygons=True")
     if overlap not in OVERLAP_OPTIONS:
         raise ValueError(f"overlap must be one of {list(OVERLAP_OPTIONS)}, got {overlap!r}")
     if int(min_region_area) < 0:
@@ -654,6 +718,13 @@ def refuse_boundary_option(who: str, why: str, **opts) -> None:
                          f"(gt=True, ap=True, boundary=True)")
 
 
+def refuse_polygon_iou_option(who: str, why: str, **opts) -> None:
+    """ValueError naming TilePipeline's `polygon_iou` option when `who` (a pipeline that does not score polygons against their masks)
+    was handed it."""
+    if opts.get("polygon_iou"):
+        raise ValueError(f"{who} does not score polygons against their masks ({why}): polygon_iou is a TilePipeline option")
+
+
 def refuse_overlap_option(who: str, why: str, **opts) -> None:
     """ValueError naming TilePipeline's `overlap` option when `who` (a pipeline that does not resolve overlapping masks) was handed
     anything but "order"."""
@@ -728,7 +799,7 @@ class TilePipeline:
                  region_mode: str = "both", mask_boxes: bool = False, quality: bool = False, min_stability: float = 0.0,
                  min_pred_iou: float = 0.0, min_inside_box: float = 0.0, polygons: bool = False, polygon_buffer_mb: int = 64,
                  polygon_max_edges: int = 65536, overlap: str = "order", vis_lut: Optional[np.ndarray] = None, vis_alpha: float = 0.4,
-                 vis_buffer_mb: Optional[int] = None, boundary: bool = False, polygon_epsilon: float = 0.0):
+                 vis_buffer_mb: Optional[int] = None, boundary: bool = False, polygon_epsilon: float = 0.0, polygon_iou: bool = False):
         """precision: the operand-split mode (engine option "split") THIS PIPELINE'S OWN CALLS run in.  The option is set around
         each of the pipeline's encode / decode calls and restored afterwards (``Engine.options``), so the mode never outlives
         them: a ``SamPredictor`` built on the same model keeps the engine's own default (round 3 changed the engine's option for
@@ -776,6 +847,13 @@ class TilePipeline:
         round(16 * polygon_epsilon) / 16 pixels, in integers): ``polygons(j)``, ``polygon_table``, ``polygon_rings`` and
         ``polygon_vertices`` then hold the simplified rings (a ring record's area stays the traced ring's), ``polygon_eps_q`` the
         tolerance in sixteenths.  Every other output is unchanged; 0.0 (default) makes no call and changes no byte.
+        polygon_iou: (needs polygons=True) what the rings that are handed out cost against the mask they were traced from, counted
+        while the mask is still on the device: after each ``mask_polygons`` call the rows it placed are simplified at once (instead
+        of the whole batch at the end; the simplified rings depend on the ring and the tolerance only, so every polygon output is
+        bit-equal to polygon_iou=False) and filled again (``Engine.fill_polygons`` without a mask output, `ref` = the chunk's
+        masks): ``TileResult.polygon_counts`` [n_boxes, 3] = pixels of the fill (-1: not traced), of the mask, of both, and
+        ``TileResult.polygon_iou(j)``.  With polygon_epsilon 0 every traced instance reports its area three times: a self-check
+        of tracing and filling.  False (default) launches and allocates nothing and leaves the call sequence as it is.
         overlap: what becomes of a pixel at which several masks of a tile are set.  "order" (default): today's behaviour -- the
         masks stay as they are and the class map follows the painting order, a later box wins; nothing is launched or allocated.
         "logit" / "smallest": the pixel is given to exactly one instance on the device, in place (``Engine.resolve_overlaps``):
@@ -790,8 +868,9 @@ class TilePipeline:
         from .transforms import ResizeLongestSide
         refuse_boundary_option("TilePipeline", "Boundary AP needs the instance pipeline's ground truth", boundary=boundary)
         lut, poly_vertices = validate_output_options(min_region_area, region_mode, polygons, polygon_buffer_mb, polygon_max_edges, png_lut,
-                                                     overlap, polygon_epsilon)
+                                                     overlap, polygon_epsilon, polygon_iou)
         self.polygon_eps_q = polygon_eps_q(polygon_epsilon, bool(polygons))
+        self.polygon_iou = bool(polygon_iou)
         vlut, self.vis_alpha = validate_vis_options(vis_lut, vis_alpha, vis_buffer_mb)
         self.vis = vlut is not None
         self.overlap = overlap
@@ -846,7 +925,7 @@ class TilePipeline:
         self.seg_dev = [torch.empty(batch, side, side, dtype=torch.uint8, device=dev) for _ in range(2)]
         # the fixed per-box outputs: one declaration each (output_tables), two device tables per entry under the entry's name
         self.tables = output_tables(self.min_region_area, self.mask_boxes, self.quality, self.gt, rle, self.INSTANCE, self.overlap,
-                                    self.ap, self.boundary)
+                                    self.ap, self.boundary, self.polygon_iou)
         for t in self.tables:
             setattr(self, t.dev, [t.alloc(batch, max_boxes, dev) for _ in range(2)])
         # the packed outputs, per input set: the payload (16-byte aligned entries) here, cursor and table in the stream
@@ -1069,6 +1148,13 @@ class TilePipeline:
             if self.polygons:                                                     # of the masks as they go out
                 eng.mask_polygons(masks[:, 0], (0, 0), self.polygon_max_edges, self.poly_vert_dev[b], self.poly_ring_dev[b],
                                   self.poly_out.cur[b], self.poly_out.tab[b][off + s:off + e])
+                if self.polygon_iou:                                              # while the chunk's masks are here: its rows, simplified now
+                    rows = self.poly_out.tab[b][off + s:off + e]
+                    if self.polygon_eps_q:
+                        eng.simplify_polygons(rows, self.poly_ring_dev[b], self.poly_vert_dev[b], self.poly_out.cur[b],
+                                              self.polygon_eps_q / 16.0)
+                    eng.fill_polygons(rows, self.poly_ring_dev[b], self.poly_vert_dev[b], (H, W), (0, 0), out=False, ref=masks[:, 0],
+                                      counts_out=self.pcnt_dev[b][i, s:e])
             eng.paint(masks[:, 0], self.dev_lab[b][off + s:off + e], seg, self.class_pixels, self.class_instances,
                       areas_out=self.area_dev[b][i, s:e])
             if self.rle:                                                          # :201-202, on the device
@@ -1118,7 +1204,7 @@ class TilePipeline:
                 for i, ((t, hw), (off, nb)) in enumerate(zip(tiles, offs)):
                     self._decode_tile(b, i, t, hw, off, nb, out, None if pre is None else pre[i])
             n_rows = sum(nb for _, nb in offs)
-            if self.polygons and self.polygon_eps_q and n_rows:                      # the batch's rings, once: its rows are 0 .. n_rows - 1
+            if self.polygons and self.polygon_eps_q and n_rows and not self.polygon_iou:   # the batch's rings, once: its rows are 0 .. n_rows - 1
                 self.eng.simplify_polygons(self.poly_out.tab[b][:n_rows], self.poly_ring_dev[b], self.poly_vert_dev[b],
                                            self.poly_out.cur[b], self.polygon_eps_q / 16.0)
             if self.png:
@@ -1319,6 +1405,7 @@ class InstancePipeline(TilePipeline):
             raise ValueError("InstancePipeline does not trace polygons: polygons is a TilePipeline / ScenePipeline option")
         if kw.get("polygon_epsilon"):
             raise ValueError("InstancePipeline does not trace polygons: polygon_epsilon is a TilePipeline / ScenePipeline option")
+        refuse_polygon_iou_option("InstancePipeline", "it traces no polygons", polygon_iou=kw.get("polygon_iou"))
         self.gt = bool(gt)             # read by TilePipeline.__init__: the ground-truth tables and stream are allocated with the rest
         super().__init__(sam, n_classes, precision=kw.pop("precision", "auto"), _multimask=bool(multimask), **kw)
         self.prompt, self.multimask = prompt, bool(multimask)

@@ -138,6 +138,8 @@ def load_library() -> C.CDLL:
     lib.samrs_k_polygon_simplify_scratch_bytes.restype = C.c_int64
     lib.samrs_k_polygon_simplify_keep.argtypes = [vp, vp, vp, ip, ip, C.c_int64, C.c_int64, vp, vp, vp, vp]
     lib.samrs_k_polygon_simplify_keep.restype = ip
+    lib.samrs_fill_polygons.argtypes = [vp, vp, vp, vp, ip, ip, ip, ip, ip, vp, vp, vp, vp]
+    lib.samrs_fill_polygons.restype = ip
     lib.samrs_score_masks.argtypes = [vp, vp, ip, ip, ip, ip, ip, fp, vp, vp, vp]
     lib.samrs_filter_masks.argtypes = [vp, vp, ip, ip, ip, vp, vp, fp, fp, fp, vp, vp]
     lib.samrs_resolve_overlaps.argtypes = [vp, vp, ip, ip, ip, ip, vp, ip, ip, vp, vp, vp, vp, vp]
@@ -925,6 +927,44 @@ class Engine:
             self._check(self.lib.samrs_k_polygon_simplify_keep(vertices.data_ptr(), rings.data_ptr(), table.data_ptr(), n, int(eps_q), V, R,
                                                                scratch.data_ptr(), keep.data_ptr(), kept.data_ptr(), _stream()))
         return keep, kept
+
+    def fill_polygons(self, table: torch.Tensor, rings: torch.Tensor, vertices: torch.Tensor, size: Sequence[int],
+                      offset: Sequence[int] = (0, 0), out=None, ref=None, counts_out=None):
+        """The rings of the n rows of `table` back to masks, on the device (samrs_fill_polygons): the even-odd fill of each row's rings,
+        sampled at the pixel centres of an (H, W) = `size` window whose origin is `offset` = (x0, y0); a centre exactly on an edge
+        counts as right of it; integers only.  `table` int64 [n, 5], `rings` int32 [R, 4], `vertices` int32 [V, 2] as
+        ``mask_polygons`` writes and ``simplify_polygons`` rewrites them, or as ``samrs_amd.polygons.pack_rings`` builds them from
+        any integer polygons (uploaded).  -> (masks uint8 [n, H, W], counts int64 [n, 3] or None).  `out`: the masks' tensor, None to
+        allocate one, False for no masks at all (only the counts are taken; nothing of size H W is written).  `ref` bool / uint8
+        [n, H, W]: masks to count against; counts[j] = (set pixels of the fill, set pixels of ref[j], set in both), the last two 0
+        without `ref`.  `counts_out`: their tensor, None to allocate one when there is something to report (`ref` given or out=False),
+        False for none.  A row that is not a set of rings (not traced / not placed, a vertex farther than 2^20 from the origin, ring
+        records that do not tile its vertices) fills as empty and has counts[j, 0] == -1.  Asynchronous on the current stream."""
+        self._polygon_buffers(table, rings, vertices)
+        n, (h, w) = int(table.shape[0]), (int(size[0]), int(size[1]))
+        if out is None:
+            out = torch.empty(n, h, w, dtype=torch.uint8, device=self.device)
+        masks = None if out is False else self._masks_u8(out)
+        if masks is not None and tuple(masks.shape) != (n, h, w):
+            raise ValueError(f"out must be [{n}, {h}, {w}], got {tuple(masks.shape)}")
+        g = None
+        if ref is not None:
+            g = self._masks_u8(ref)
+            if tuple(g.shape) != (n, h, w):
+                raise ValueError(f"ref must be [{n}, {h}, {w}], got {tuple(g.shape)}")
+        if counts_out is None:
+            counts_out = torch.empty(n, 3, dtype=torch.int64, device=self.device) if (g is not None or masks is None) else False
+        counts = None if counts_out is False else counts_out
+        if counts is not None and not (isinstance(counts, torch.Tensor) and counts.dtype == torch.int64 and counts.is_cuda
+                                       and counts.is_contiguous() and tuple(counts.shape) == (n, 3)):
+            raise ValueError(f"counts_out must be a contiguous int64 [{n}, 3] tensor on the engine's device")
+        if n or (masks is None and counts is None):               # no rows: nothing to do; no output at all: the library says so
+            with torch.cuda.device(self.device):
+                self._check(self.lib.samrs_fill_polygons(self.handle, vertices.data_ptr(), rings.data_ptr(), table.data_ptr(), n, h, w,
+                                                         int(offset[0]), int(offset[1]), None if masks is None else masks.data_ptr(),
+                                                         None if g is None else g.data_ptr(),
+                                                         None if counts is None else counts.data_ptr(), _stream()))
+        return (None if masks is None else out), counts
 
     def score_masks(self, low: torch.Tensor, input_size: Sequence[int], original_size: Sequence[int], offset: float = 1.0,
                     boxes: Optional[torch.Tensor] = None, counts_out=None) -> torch.Tensor:

@@ -62,7 +62,8 @@ def write_outputs(out_dir: str, stem: str, seg: np.ndarray, masks: Optional[np.n
                   png_files: Optional[Tuple[bytes, bytes]] = None, mask_bboxes: Optional[Sequence] = None,
                   mask_rboxes: Optional[Sequence] = None, dota_txt: bool = False, scores: Optional[dict] = None,
                   polygons: Optional[Sequence] = None, removed: Optional[Sequence[int]] = None, vis_file: Optional[bytes] = None,
-                  base_entries: Optional[Sequence[dict]] = None, polygon_epsilon: Optional[float] = None) -> None:
+                  base_entries: Optional[Sequence[dict]] = None, polygon_epsilon: Optional[float] = None,
+                  polygon_ious: Optional[Sequence] = None) -> None:
     """`rles`: the per-instance COCO RLE dicts when they were encoded on the device (driver.TileResult.rle); otherwise they are
     encoded here from `masks` (host restatement), or left out when both are None (--no-rle).  `png_files`: the complete
     (gray, color) PNG files when they were encoded on the device (--png-device: driver.TileResult.png, byte-identical with the
@@ -76,7 +77,8 @@ def write_outputs(out_dir: str, stem: str, seg: np.ndarray, masks: Optional[np.n
     (int32 [k, 2] lattice vertices, is_hole) pairs (driver.TileResult.polygons), or None for a mask over the edge cap; they become
     the pickle entries' ``"polygons"`` (the list of vertex arrays, or None) and ``"polygon_holes"`` (the list of bool, or None).
     `polygon_epsilon` (--polygon-epsilon): the effective tolerance in pixels (eps_q / 16) the rings were simplified at on the device;
-    the entries' ``"polygon_epsilon"`` beside them.
+    the entries' ``"polygon_epsilon"`` beside them.  `polygon_ious` (--polygon-iou): per instance the IoU of its mask with the fill of
+    the rings written here (driver.TileResult.polygon_iou), None where the mask was not traced; the entries' ``"polygon_iou"``.
     `removed` (--overlap logit / smallest): per instance the pixels the overlap stage gave to another instance; the entries' ``"removed"``
     (`areas` and `rles` are then those of the disjoint masks already).  `vis_file` (--vis): the complete ``vis/<stem>.png``, the
     overlay blended and encoded on the device (driver.TileResult.png("vis")); written as it is, before the pickle.
@@ -137,6 +139,8 @@ def write_outputs(out_dir: str, stem: str, seg: np.ndarray, masks: Optional[np.n
             entry["polygon_holes"] = None if pl is None else [bool(p[1]) for p in pl]
             if polygon_epsilon is not None:
                 entry["polygon_epsilon"] = float(polygon_epsilon)
+            if polygon_ious is not None:
+                entry["polygon_iou"] = None if polygon_ious[j] is None else float(polygon_ious[j])
         info.append(entry)
     if dota_txt:
         # before the pickle, whose presence says "this image is complete" (--resume)
@@ -374,6 +378,12 @@ def run(args) -> Dict[str, List[int]]:
     poly_kw = dict(polygons=True, polygon_buffer_mb=int(getattr(args, "polygon_buffer_mb", 64) or 64),
                    polygon_max_edges=int(getattr(args, "polygon_max_edges", 65536) or 65536),
                    polygon_epsilon=polygon_eps_q / 16.0) if want_polygons else {}
+    # --polygon-iou: the rings that are written filled again on the device (samrs_fill_polygons) and counted against their mask
+    want_polygon_iou = bool(getattr(args, "polygon_iou", False))
+    driver.validate_output_options(polygons=want_polygons, polygon_iou=want_polygon_iou)
+    if want_polygon_iou:
+        poly_kw["polygon_iou"] = True
+    piou = driver.PolygonIoUStat()
     # --overlap: a pixel several masks of an image are set at goes to one of them on the device (samrs_resolve_overlaps) before the masks
     # are painted, counted and RLE-encoded; "order" = the reference's painting order, nothing launched
     overlap = getattr(args, "overlap", "order") or "order"
@@ -504,7 +514,8 @@ def run(args) -> Dict[str, List[int]]:
                 polys = [r.polygons(j) for j in range(len(r.labels))] if r.polygon_table is not None else None
                 write_outputs(args.out, r.key, r.seg_mask, None, r.boxes, r.labels, r.areas, palette, names, rles, clock, png_level, files,
                               bbs, rbs, dota_txt, scores, polys, r.removed, r.png("vis") if r.vis_table is not None else None,
-                              polygon_epsilon=polygon_eps_q / 16.0 if polygon_eps_q else None)
+                              polygon_epsilon=polygon_eps_q / 16.0 if polygon_eps_q else None,
+                              polygon_ious=[r.polygon_iou(j) for j in range(len(r.labels))] if r.polygon_counts is not None else None)
             finally:
                 with lock:
                     left[0] -= 1
@@ -539,6 +550,8 @@ def run(args) -> Dict[str, List[int]]:
             if r.removed is not None:
                 resolved[0] += int(r.removed.sum())
                 resolved[1] += int((r.removed > 0).sum())
+            if r.polygon_counts is not None:
+                piou.add(r.polygon_counts)
         done[0] += len(results)
         if rank == 0 and (done[0] // batch) % 50 == 0:
             print(f"[rank 0] {done[0]} images", flush=True)
@@ -595,6 +608,9 @@ def run(args) -> Dict[str, List[int]]:
         if rank == 0:
             print(f"[rank 0] quality: {int(dn.item())} instances dropped and left unlabeled "
                   f"({', '.join(f'{k}={v:g}' for k, v in thresholds.items())})", flush=True)
+    polygon_iou_stats = None
+    if want_polygon_iou:             # over the images processed in THIS run, like region_cleanup
+        polygon_iou_stats = driver.reduce_polygon_iou(piou, polygon_eps_q / 16.0, pipe.class_pixels.device)
     if clock:
         stats["timing"] = {"images": done[0], "loop_seconds": wall, "stage_thread_seconds": dict(clock.t),   # this rank's loop
                            "readers": n_readers, "writers": n_writers, "cpu_budget": round(host_cpu_budget(), 1)}
@@ -603,6 +619,9 @@ def run(args) -> Dict[str, List[int]]:
         with open(os.path.join(args.out, "statistic", "class_stats.json"), "w") as f:       # statistic.py:28-31
             json.dump(stats, f)
         np.save(os.path.join(args.out, "statistic", "all_mask_size.npy"), np.asarray(all_sizes, dtype=np.int64))
+        if polygon_iou_stats is not None:
+            with open(os.path.join(args.out, "statistic", "polygon_iou.json"), "w") as f:
+                json.dump(polygon_iou_stats, f)
         if getattr(args, "audit_passes", 0) > 0 and sam.finish_audit() is not None:
             from . import audit
             audit.write_json(sam.audit_report, os.path.join(args.out, "statistic", "audit.json"))
@@ -737,6 +756,11 @@ def build_parser() -> argparse.ArgumentParser:
                          "tolerance of E pixels, rounded to sixteenths (1/16 .. 1024); implies --polygons.  'polygons' / 'polygon_holes' "
                          "then hold the simplified rings and the entries gain 'polygon_epsilon', the effective tolerance.  Every ring "
                          "keeps at least 3 vertices; topology is not preserved.  0 (default): off")
+    ap.add_argument("--polygon-iou", action="store_true",
+                    help="fill the rings that are written again on the GPU (even-odd, at the pixel centres, in integers) and count them "
+                         "against the mask they were traced from, while it is still on the device: the entries gain 'polygon_iou' (None "
+                         "for a mask that was not traced) and rank 0 writes OUT/statistic/polygon_iou.json (n, average, area, min, "
+                         "polygon_epsilon) -- what --polygon-epsilon costs; exactly 1.0 without it.  Needs --polygons or --polygon-epsilon")
     return ap
 
 

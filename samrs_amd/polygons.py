@@ -125,3 +125,62 @@ def rasterize_any(rings_list: Sequence, h: int, w: int, origin: Sequence[int] = 
             c = np.clip(c, 0, w)
             np.add.at(d, (np.arange(r0, r1), c), 1)
     return (np.cumsum(d, axis=1)[:, :w] & 1).astype(np.uint8)
+
+
+def pack_rings(rings_lists: Sequence) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(table int64 [n, 5], rings int32 [R, 4], vertices int32 [V, 2]) in the library's layout from one ``rings_of``-style list per
+    row -- (int [k, 2] vertices, is_hole) pairs, or bare vertex arrays -- : the inverse of ``rings_of``, what
+    ``Engine.fill_polygons`` takes once uploaded.  A None entry becomes a not-traced row (ring count = vertex count = -1, firsts -1).
+    table[j] = (first ring, ring count, first vertex, vertex count, the vertex count again where the library keeps the traced edge
+    count); a ring record = (first vertex relative to the row's, vertex count, twice the signed shoelace area, negated if it
+    disagrees with is_hole so that the sign still says hole, 0 where the library keeps a pixel index).  Empty buffers have one
+    unused row, so that they can be uploaded."""
+    table = np.zeros((len(rings_lists), 5), np.int64)
+    recs, verts = [], []
+    nv = 0
+    for j, rl in enumerate(rings_lists):
+        if rl is None:
+            table[j] = (-1, -1, -1, -1, 0)
+            continue
+        v0, r0 = nv, len(recs)
+        for ring in rl:
+            hole = None
+            if isinstance(ring, tuple) and len(ring) == 2 and np.ndim(ring[0]) == 2:
+                ring, hole = ring[0], bool(ring[1])
+            p = np.asarray(ring, dtype=np.int64).reshape(-1, 2)
+            if len(p) < 1:
+                raise ValueError(f"row {j}: a ring without vertices")
+            if np.abs(p).max() >= 1 << 31:
+                raise ValueError(f"row {j}: a vertex does not fit int32")
+            a2 = signed_area2(p)
+            if hole is not None and a2 != 0 and (a2 < 0) != hole:
+                a2 = -a2
+            recs.append((nv - v0, len(p), int(np.clip(a2, -(1 << 31) + 1, (1 << 31) - 1)), 0))
+            verts.append(p.astype(np.int32))
+            nv += len(p)
+        table[j] = (r0, len(recs) - r0, v0, nv - v0, nv - v0)
+    rings = np.asarray(recs, dtype=np.int32).reshape(-1, 4) if recs else np.zeros((1, 4), np.int32)
+    vertices = np.concatenate(verts).reshape(-1, 2) if verts else np.zeros((1, 2), np.int32)
+    return table, np.ascontiguousarray(rings), np.ascontiguousarray(vertices)
+
+
+def fill_device(engine, rings_lists: Sequence, h: int, w: int, origin: Sequence[int] = (0, 0)):
+    """uint8 [n, h, w] tensor on the engine's device: ``rasterize_any`` of every entry of `rings_lists`, on the GPU
+    (``pack_rings`` -> upload -> ``Engine.fill_polygons``).  A None entry fills as the empty mask."""
+    from . import engine as _engine            # the one function here that needs a device: this module itself stays numpy only
+    torch = _engine.torch
+    table, rings, vertices = pack_rings(rings_lists)
+    dev = engine.device
+    masks, _ = engine.fill_polygons(torch.from_numpy(table).to(dev), torch.from_numpy(rings).to(dev), torch.from_numpy(vertices).to(dev),
+                                    (h, w), origin, counts_out=False)
+    return masks
+
+
+def iou_from_counts(counts) -> np.ndarray:
+    """float64 [...]: inter / (fill + ref - inter) from ``Engine.fill_polygons``'s counts [..., 3] = (fill, ref, both).  Two empty
+    sides give 1.0; a row with fill = -1 (not rings: not traced, not placed) gives NaN."""
+    c = np.asarray(_np(counts), dtype=np.int64)
+    fill, ref, both = c[..., 0], c[..., 1], c[..., 2]
+    union = fill + ref - both
+    out = np.where(union > 0, both / np.maximum(union, 1).astype(np.float64), 1.0)
+    return np.where(fill < 0, np.nan, out)

@@ -2,7 +2,8 @@
 
     python -m samrs_amd.relabel --ins DIR --out OUT [--classes / --n-classes / --palette]
         [--min-region-area N --region-mode M] [--overlap order|smallest] [--mask-boxes] [--dota-txt]
-        [--polygons [--polygon-max-edges E] [--polygon-epsilon E]] [--png-device] [--resume] [--box-batch B]
+        [--polygons [--polygon-max-edges E] [--polygon-epsilon E] [--polygon-iou]] [--masks-from rle|polygons] [--png-device]
+        [--resume] [--box-batch B]
 
 ``DIR`` is a directory of ``*.pkl`` or a ``samrs_amd.generate`` output directory (its ``ins/`` is read): ours, a ``--resume``d run's,
 or the published SAMRS pickles, which have the same keys.  The pickle is the durable record -- COCO RLE per instance, label, box,
@@ -26,12 +27,14 @@ import numpy as np
 import torch
 
 from . import generate, rle, tile_io
-from .driver import box_chunks, check_packed, check_polygons, polygon_eps_q, validate_output_options
+from .driver import (PolygonIoUStat, box_chunks, check_packed, check_polygons, polygon_eps_q, reduce_polygon_iou,
+                     validate_output_options)
 from .engine import RLE_STATUS
-from .polygons import rings_of
+from .polygons import iou_from_counts, pack_rings, rings_of
 
 NEEDS_LOGITS = "needs the decoder's logits, which ins/*.pkl does not hold"
 NEEDS_IMAGE = "needs the image, which ins/*.pkl does not hold"
+MASK_SOURCES = ("rle", "polygons")      # --masks-from: what every entry's mask is rebuilt from
 
 
 def ins_dir_of(path: str) -> str:
@@ -56,6 +59,8 @@ def refusal(ns) -> Optional[str]:
             return f"{flag} {NEEDS_LOGITS}"
     if ns.vis:
         return f"--vis {NEEDS_IMAGE}"
+    if getattr(ns, "polygon_iou", False) and not (ns.polygons or ns.polygon_epsilon > 0):
+        return "--polygon-iou scores the traced polygons against their masks: it needs --polygons or --polygon-epsilon"
     if same_dir(os.path.join(ns.out, "ins"), ins_dir_of(ns.ins)):
         return f"--out {ns.out}: its ins/ is the input directory, and the pickles being read would be overwritten; name another --out"
     return None
@@ -100,6 +105,14 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--polygon-max-edges", type=int, default=65536, metavar="E")
     ap.add_argument("--polygon-epsilon", type=float, default=0.0, metavar="E",
                     help="simplify the traced rings on the GPU at a tolerance of E pixels, as samrs_amd.generate does; implies --polygons")
+    ap.add_argument("--polygon-iou", action="store_true",
+                    help="fill the rings that are written again on the GPU and count them against their mask, as samrs_amd.generate does: "
+                         "the entries gain 'polygon_iou', and OUT/statistic/polygon_iou.json is written; needs --polygons / --polygon-epsilon")
+    ap.add_argument("--masks-from", default="rle", choices=list(MASK_SOURCES),
+                    help="rle (default): every mask is decoded from its entry's \"mask\" RLE.  polygons: every mask is the even-odd fill, on "
+                         "the GPU, of its entry's 'polygons' (at the pixel centres; holes follow from the rule, 'polygon_holes' is not "
+                         "needed) -- a vector edit or a simplified outline becomes the class map, the statistics and the RLE again; an "
+                         "entry whose 'polygons' is None falls back to its \"mask\", one with neither is an error")
     # named so that they are refused with a reason instead of "unrecognized arguments"
     ap.add_argument("--quality", action="store_true", help="refused: " + NEEDS_LOGITS)
     ap.add_argument("--min-stability", type=float, default=0.0, help="refused: " + NEEDS_LOGITS)
@@ -109,20 +122,32 @@ def build_parser() -> argparse.ArgumentParser:
     return ap
 
 
-def load_entries(path: str, n_classes: int) -> Tuple[List[dict], Optional[Tuple[int, int]]]:
-    """(the entries of one pickle, their common mask size or None for an empty list); ValueError, naming the file, for an entry
-    without ``"mask"``, mixed sizes or a label outside 0..n_classes-1."""
+def has_rle(e) -> bool:
+    return isinstance(e, dict) and isinstance(e.get("mask"), dict) and "counts" in e["mask"] and "size" in e["mask"]
+
+
+def load_entries(path: str, n_classes: int, masks_from: str = "rle") -> Tuple[List[dict], Optional[Tuple[int, int]]]:
+    """(the entries of one pickle, their common mask size or None when no entry says it); ValueError, naming the file, for an entry
+    without ``"mask"`` (`masks_from` "polygons": with neither ``"polygons"`` nor ``"mask"``), mixed sizes or a label outside
+    0..n_classes-1."""
     with open(path, "rb") as f:
         entries = list(pickle.load(f))
     sizes = set()
+    stem = os.path.basename(path)[:-4] if path.endswith(".pkl") else os.path.basename(path)
     for j, e in enumerate(entries):
-        if not isinstance(e, dict) or not isinstance(e.get("mask"), dict) or "counts" not in e["mask"] or "size" not in e["mask"]:
+        if masks_from == "polygons" and isinstance(e, dict) and e.get("polygons") is not None:
+            if has_rle(e):
+                sizes.add((int(e["mask"]["size"][0]), int(e["mask"]["size"][1])))
+        elif masks_from == "polygons" and not has_rle(e):
+            raise ValueError(f"{path}: entry {j} of {stem} has neither \"polygons\" nor a \"mask\" RLE: nothing to rebuild it from")
+        elif not has_rle(e):
             raise ValueError(f"{path}: entry {j} has no \"mask\" RLE (written with --no-rle?): nothing to rebuild it from")
+        else:
+            sizes.add((int(e["mask"]["size"][0]), int(e["mask"]["size"][1])))
         label = int(e["label"])
         if not 0 <= label < n_classes:
             raise ValueError(f"{path}: entry {j} holds label {label}, outside 0..{n_classes - 1}: it was written with another class "
                              "list (use the same --classes / --n-classes)")
-        sizes.add((int(e["mask"]["size"][0]), int(e["mask"]["size"][1])))
     if len(sizes) > 1:
         raise ValueError(f"{path}: the entries' masks have mixed sizes {sorted(sizes)}")
     return entries, (next(iter(sizes)) if sizes else None)
@@ -142,9 +167,13 @@ class Relabeler:
         self.polygons = bool(args.polygons) or self.polygon_eps_q > 0
         self.polygon_max_edges, self.polygon_buffer_mb = int(args.polygon_max_edges), int(args.polygon_buffer_mb)
         self.rle_buffer_mb = int(args.rle_buffer_mb)
+        self.polygon_iou = bool(getattr(args, "polygon_iou", False))
+        self.masks_from = getattr(args, "masks_from", "rle") or "rle"
+        if self.masks_from not in MASK_SOURCES:
+            raise ValueError(f"masks_from must be one of {list(MASK_SOURCES)}, got {self.masks_from!r}")
         lut, poly_vertices = validate_output_options(self.min_region_area, self.region_mode, self.polygons, self.polygon_buffer_mb,
                                                      self.polygon_max_edges, tile_io.class_lut(palette) if args.png_device else None,
-                                                     "smallest" if self.resolve else "order", self.polygon_eps_q / 16.0)
+                                                     "smallest" if self.resolve else "order", self.polygon_eps_q / 16.0, self.polygon_iou)
         self.png_lut = None if lut is None else torch.from_numpy(np.ascontiguousarray(lut)).to(self.dev)
         self.class_pixels = torch.zeros(n_classes, dtype=torch.int64, device=self.dev)
         self.class_instances = torch.zeros(n_classes, dtype=torch.int64, device=self.dev)
@@ -168,18 +197,33 @@ class Relabeler:
         if self.mask_boxes:
             hbox, rbox = torch.zeros(n, 4, dtype=torch.int32, device=dev), torch.zeros(n, 4, 2, dtype=torch.float32, device=dev)
             rec = torch.zeros(n, 8, **i64)
-        ptab = pcur = None
+        ptab = pcur = pcnt = None
         if self.polygons:
             ptab, pcur = torch.zeros(n, 5, **i64), torch.zeros(2, **i64)
+            pcnt = torch.zeros(n, 3, **i64) if self.polygon_iou else None
         rtab, rcur = torch.zeros(n, 3, **i64), torch.zeros(1, **i64)
-        if n:
+        # --masks-from polygons: the entries that carry rings are filled on the device; the others (not traced) keep their RLE
+        from_rings = [self.masks_from == "polygons" and e.get("polygons") is not None for e in entries]
+        coded = [j for j in range(n) if not from_rings[j]]
+        if coded:
             # one upload: the table, then the strings
-            buf, table = rle.pack_strings([e["mask"] for e in entries])
+            buf, table = rle.pack_strings([entries[j]["mask"] for j in coded])
             both = torch.from_numpy(np.concatenate([table.reshape(-1).view(np.uint8), buf])).to(dev)
             strings, table = both[table.size * 8:], both[:table.size * 8].view(torch.int64).view(-1, 3)
+        filled = torch.zeros(n, 3, **i64)                         # --masks-from polygons: the fill's counts of the entries with rings
+        row_of = {j: k for k, j in enumerate(coded)}              # entry -> its row of the uploaded string table
         # the overlap stage needs every mask of the image at once: one chunk
         for s, e in ([(0, n)] if n else []) if self.resolve else box_chunks(n, self.box_batch):
-            masks, _, _ = eng.rle_decode(strings, table[s:e], (H, W), status_out=status[s:e])
+            if not any(from_rings[s:e]):
+                masks, _, _ = eng.rle_decode(strings, table[row_of[s]:row_of[s] + e - s], (H, W), status_out=status[s:e])
+            else:
+                t, r, v = pack_rings([[np.asarray(p) for p in entries[j]["polygons"]] if from_rings[j] else None for j in range(s, e)])
+                masks, _ = eng.fill_polygons(torch.from_numpy(t).to(dev), torch.from_numpy(r).to(dev), torch.from_numpy(v).to(dev),
+                                             (H, W), counts_out=filled[s:e])        # [:, 0] == -1: rings that cannot be filled
+                for j in range(s, e):                              # rare: a mask over the edge cap among traced ones
+                    if not from_rings[j]:
+                        eng.rle_decode(strings, table[row_of[j]:row_of[j] + 1], (H, W), out=masks[j - s:j - s + 1],
+                                       status_out=status[j:j + 1])
             if self.min_region_area:
                 eng.clean_masks(masks, self.min_region_area, self.region_mode, areas_out=False, changed_out=changed[s:e])
             if self.resolve:
@@ -188,9 +232,13 @@ class Relabeler:
                 eng.mask_boxes(masks, (0, 0), hbox[s:e], rbox[s:e], rec[s:e])
             if self.polygons:
                 eng.mask_polygons(masks, (0, 0), self.polygon_max_edges, self.poly_vert, self.poly_ring, pcur, ptab[s:e])
+                if self.polygon_iou:                                       # while the chunk's masks are here: its rows, simplified now
+                    if self.polygon_eps_q:
+                        eng.simplify_polygons(ptab[s:e], self.poly_ring, self.poly_vert, pcur, self.polygon_eps_q / 16.0)
+                    eng.fill_polygons(ptab[s:e], self.poly_ring, self.poly_vert, (H, W), out=False, ref=masks, counts_out=pcnt[s:e])
             eng.paint(masks, labels[s:e], seg, self.class_pixels, self.class_instances, areas_out=areas[s:e])
             eng.rle_encode(masks, self.rle_dev, rcur, rtab[s:e])
-        if self.polygons and self.polygon_eps_q and n:                             # the image's rings, once, after its last chunk
+        if self.polygons and self.polygon_eps_q and n and not self.polygon_iou:    # the image's rings, once, after its last chunk
             eng.simplify_polygons(ptab, self.poly_ring, self.poly_vert, pcur, self.polygon_eps_q / 16.0)
         png_tab = None
         if self.png_lut is not None:
@@ -204,11 +252,15 @@ class Relabeler:
         if bad.size:
             raise ValueError(f"{path}: the \"mask\" of entry {int(bad[0])} does not decode: {RLE_STATUS[int(status[bad[0]])]}"
                              + (f" ({bad.size - 1} more entries)" if bad.size > 1 else ""))
+        unfilled = [j for j in np.flatnonzero(filled[:, 0].cpu().numpy() < 0) if from_rings[j]]
+        if unfilled:
+            raise ValueError(f"{path}: the \"polygons\" of entry {int(unfilled[0])} cannot be filled: a vertex lies farther than 2^20 from "
+                             "the image's origin" + (f" ({len(unfilled) - 1} more entries)" if len(unfilled) > 1 else ""))
         rtab, used = rtab.cpu().numpy(), int(rcur.item())
         check_packed(rtab, used, "image", self.rle_buffer_mb)
         data = self.rle_dev[:used].cpu().numpy()
         out = {"seg": seg.cpu().numpy(), "areas": areas.cpu().numpy(), "png_files": None, "mask_bboxes": None, "mask_rboxes": None,
-               "polygons": None, "removed": None if removed is None else removed.cpu().numpy(),
+               "polygons": None, "polygon_counts": None if pcnt is None else pcnt.cpu().numpy(), "removed": None if removed is None else removed.cpu().numpy(),
                "changed": None if changed is None else changed.cpu().numpy(),
                "rles": [{"size": [int(H), int(W)], "counts": data[int(o):int(o) + int(l)].tobytes().decode("ascii")} for o, l, _ in rtab]}
         if png_tab is not None:
@@ -257,21 +309,26 @@ def run(args) -> Dict:
     dota_txt = bool(args.dota_txt)
     sizes: List[int] = []
     cleaned, resolved = [0, 0], [0, 0]
+    piou = PolygonIoUStat()
     for stem in stems:
         path = os.path.join(ins, stem + ".pkl")
-        entries, size = load_entries(path, n_classes)
+        entries, size = load_entries(path, n_classes, work.masks_from)
         if size is None:
-            # no instance, no size: a generate output directory still has the map's
+            # no instance (or none with an RLE), no size: a generate output directory still has the map's
             gray = os.path.join(os.path.dirname(os.path.abspath(ins)), "gray", stem + ".png")
             if not os.path.exists(gray):
-                raise ValueError(f"{path}: no entries, so the image's size is unknown (and there is no {gray} to take it from)")
+                raise ValueError(f"{path}: no entry says the image's size (and there is no {gray} to take it from)")
             size = tuple(int(v) for v in tile_io.png_size(gray))
         r = work.image(path, entries, size)
         labels = np.array([int(e["label"]) for e in entries], dtype=np.int64)
         generate.write_outputs(args.out, stem, r["seg"], None, [e.get("bbox") for e in entries], labels, r["areas"], palette, names,
                                r["rles"], None, args.png_level, r["png_files"], r["mask_bboxes"], r["mask_rboxes"], dota_txt, None,
                                r["polygons"], r["removed"], None, base_entries=entries,
-                               polygon_epsilon=work.polygon_eps_q / 16.0 if work.polygon_eps_q else None)
+                               polygon_epsilon=work.polygon_eps_q / 16.0 if work.polygon_eps_q else None,
+                               polygon_ious=None if r["polygon_counts"] is None else
+                               [None if c[0] < 0 else float(iou_from_counts(c)) for c in r["polygon_counts"]])
+        if r["polygon_counts"] is not None:
+            piou.add(r["polygon_counts"])
         sizes.extend(int(a) for a in r["areas"] if a > 0)                                          # statistic.py:44-49
         if r["changed"] is not None:
             cleaned[0] += int(r["changed"].sum())
@@ -293,6 +350,9 @@ def run(args) -> Dict:
     with open(os.path.join(args.out, "statistic", "class_stats.json"), "w") as f:
         json.dump(stats, f)
     np.save(os.path.join(args.out, "statistic", "all_mask_size.npy"), np.asarray(all_sizes, dtype=np.int64))
+    if work.polygon_iou:
+        with open(os.path.join(args.out, "statistic", "polygon_iou.json"), "w") as f:
+            json.dump(reduce_polygon_iou(piou, work.polygon_eps_q / 16.0), f)
     return stats
 
 

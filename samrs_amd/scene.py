@@ -121,10 +121,12 @@ class ScenePipeline:
                  region_mode: str = "both", precision="auto", rle_buffer_mb: int = 256, mask_boxes: bool = False,
                  quality: bool = False, min_stability: float = 0.0, min_pred_iou: float = 0.0, min_inside_box: float = 0.0,
                  polygons: bool = False, polygon_buffer_mb: int = 64, polygon_max_edges: int = 65536, vis_lut=None, boundary: bool = False,
-                 polygon_epsilon: float = 0.0):
+                 polygon_epsilon: float = 0.0, polygon_iou: bool = False):
         import torch
         from .driver import (TilePipeline, output_tables, polygon_eps_q, refuse_boundary_option, refuse_overlap_option,
-                             refuse_quality_options, refuse_vis_option, validate_output_options)
+                             refuse_polygon_iou_option, refuse_quality_options, refuse_vis_option, validate_output_options)
+        refuse_polygon_iou_option("ScenePipeline", "a window's masks are gone when the scene's rings are simplified; not built",
+                                  polygon_iou=polygon_iou)
         refuse_boundary_option("ScenePipeline", "scenes carry no ground truth; Boundary AP across windows is not built", boundary=boundary)
         refuse_vis_option("ScenePipeline", "the scene's composite lives in another buffer; scene overlays are not built", vis_lut=vis_lut)
         if isinstance(overlap, str):        # TilePipeline's overlap rule; the name means the windows' overlap in pixels here
